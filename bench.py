@@ -8,8 +8,12 @@ Y = B H.  Default workload is BASELINE.json configs[1] ("C2"): M=25 bins, N=4096
 256 utterances x 688 frames (the reference's corpus is 162 utterances; 256 is the next count
 whose frame tiles fill the 256 CUs in whole rounds).
 
-  python bench.py [--gpus N --steps K --warmup W] [--config C1|C2|C3|C4|C5|C5_513|STFT]
+  python bench.py [--gpus N --steps K --warmup W] [--config C1|C2|C3|C4|C5|C5_513|STFT] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times exactly K steps and prints the line; `--dump-outputs DIR` then also writes what the
+last timed step delivered (DIR/Y.npy, DIR/H.npy; see dump_outputs).  `--full` adds the legs that take runs of their
+own: `pcie`, `cpu_baseline`, `speedup_vs_cpu`, `parity` and `one_utterance` (rank 0, N=1).
 
 N>1: one process per GPU (independent shards, no data-path collective; torch.distributed is used for the barrier,
 the max-over-ranks and the ranks_seen count only).  `python bench.py --gpus N` without a launcher starts the N
@@ -21,10 +25,13 @@ shard.partition_utterances (strong scaling, BASELINE configs[3]).  Prints ONE JS
 Besides the contract's fields the line carries
   roofline       algorithmic flops of the executed algebra / HIP-event time of the iteration loop (recorded by the
                  library on the launch stream), against the dense matrix peak of the arithmetic type
+and with --full
   cpu_baseline   the oracle's restatement of the reference's scikit-learn call on this box's cores (median of 3),
                  plus the installed scikit-learn, the pymf-literal algebra and a one-thread run (rank 0, N=1 only)
   pcie           the same step with X uploaded from and Y (and H) downloaded to page-locked host memory inside the
                  wall (SURVEY.md 8d's definition of the metric for numpy callers); never the headline `value`
+  parity         the GPU path against the oracle on the CPU leg's sample and on the first frames of the timed batch
+  one_utterance  latency of one utterance's solve + synthesis
 """
 import argparse
 import json
@@ -162,6 +169,38 @@ def spawn_ranks(argv, gpus, run=None):
 
 
 # ------------------------------------------------------------------------------------------------
+DUMP_BYTES = 60_000_000     # --dump-outputs: all files together stay below 64 MB
+DUMP_SEED = 20190131
+
+
+def dump_rows(T, row_bytes, budget):
+    """Frame rows of a T-row output that --dump-outputs writes within `budget` bytes: None = all of them, else a fixed
+    seeded sample (sorted indices; the same for the same T and budget)."""
+    k = min(T, max(1, budget // row_bytes))
+    if k == T:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(T, size=k, replace=False))
+
+
+def dump_outputs(dirname, H, Y):
+    """Write what a caller of the timed path receives, Y (T x Mb) and H (T x N) in the run's I/O dtype, as DIR/Y.npy and
+    DIR/H.npy.  Y may use two thirds of DUMP_BYTES and H what Y leaves; an output larger than its share is written as
+    the sample of its frame rows that dump_rows picks.  Returns {name: shape written}."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    T = int(Y.shape[0])
+    written, left = {}, DUMP_BYTES
+    for name, t, budget in (("Y", Y, DUMP_BYTES * 2 // 3), ("H", H, None)):
+        rows = dump_rows(T, int(t.shape[1]) * t.element_size(), left if budget is None else budget)
+        if rows is not None:
+            t = t.index_select(0, torch.as_tensor(rows, device=t.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        written[name] = a.shape
+        left -= a.nbytes
+    return written
+
+
 def cpu_model():
     try:
         for line in open("/proc/cpuinfo"):
@@ -306,8 +345,12 @@ def main():
     ap.add_argument("--no-all-resident", action="store_true", help="A/B: keep k_fused_all / k_fused_xy out")
     ap.add_argument("--pair-tiles", action="store_true", help="A/B: the experimental k_fused_xy instead of k_fused_all")
     ap.add_argument("--fused-c", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the host-transfer-inclusive leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the host-transfer leg, the CPU baseline, the parity checks and the one-utterance latency")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's Y and H (a seeded sample of frame rows when large) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the host-transfer-inclusive leg")
     ap.add_argument("--cpu-frames", type=int, default=0, help="frames of the CPU sample (0: bounded automatically)")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL)")
     ap.add_argument("--same-device", action="store_true",
@@ -315,6 +358,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: start the ranks ourselves (torch is not imported yet - this process never touches the GPU)
         sys.exit(spawn_ranks(sys.argv[1:], args.gpus))
@@ -401,6 +446,8 @@ def main():
         torch.cuda.synchronize()
 
     elapsed_own = run_timed(step, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, H, Yout)
     cdev = dev if (dist is not None and args.dist_backend == "nccl") else None
     elapsed = max_over_ranks(elapsed_own, dist, cdev)
     ranks_seen, per_rank = 1, [T * args.steps / elapsed_own]
@@ -473,7 +520,7 @@ def main():
         if args.loss != "frobenius":
             res["config"]["loss"] = args.loss
             res["roofline"]["note"] = "KL update: flop count of the Frobenius update is NOT applicable; see value only"
-        if not args.no_pcie and world == 1:
+        if args.full and not args.no_pcie and world == 1:
             # wall including the upload of X and the download of Y (and of H for callers that want
             # the activations), page-locked host memory.  Reported beside the headline, never as `value`.
             Xh = torch.empty(X.shape, dtype=tdt, pin_memory=True); Xh.copy_(X)
@@ -499,7 +546,7 @@ def main():
                            "frames_per_s_upload_X_download_Y_and_H": pc["xyh"],
                            "note": "page-locked host buffers, transfers on the launch stream inside the wall; H is "
                                    f"{N * (8 if dtype == 'f64' else 4)} bytes per frame"}
-        if not args.no_cpu and args.loss == "frobenius" and world == 1:   # CPU leg: rank 0 at N=1 only
+        if args.full and not args.no_cpu and args.loss == "frobenius" and world == 1:   # CPU leg: rank 0 at N=1 only
             Tc = args.cpu_frames or cpu_sample_frames(N, Tu)
             cpu, (p, act_cpu, Y_cpu) = cpu_baseline(M, N, K, l1, dtype, 20190131, Tc)
             res["cpu_baseline"] = cpu

@@ -104,3 +104,28 @@ def test_c4_is_one_set_split_over_the_ranks():
     # strong scaling: the job's value counts the set once, whatever the number of ranks
     assert bench.job_throughput(8, 13000, 5, 2.0, total_units=109206) == pytest.approx(109206 * 5 / 2.0)
     assert bench.job_throughput(8, 1000, 5, 2.0) == pytest.approx(8 * 1000 * 5 / 2.0)
+
+
+def test_dump_outputs_stay_small_and_sample_the_same_rows(tmp_path):
+    """--dump-outputs: Y and H of the last step as DIR/<name>.npy in the I/O dtype, all files below 64 MB; an output too
+    large for its share is a seeded sample of frame rows, the same rows from run to run."""
+    import numpy as np
+    import torch
+    import bench
+    assert bench.dump_rows(100, 8, 10 ** 6) is None
+    r = bench.dump_rows(176128, 4096 * 8, 24 * 10 ** 6)
+    assert len(r) == 24 * 10 ** 6 // (4096 * 8) and np.all(np.diff(r) > 0) and r[-1] < 176128
+    assert np.array_equal(r, bench.dump_rows(176128, 4096 * 8, 24 * 10 ** 6))
+    for dt, T, N, M in ((torch.float64, 3000, 4096, 25), (torch.float32, 50, 64, 201)):
+        g = torch.Generator().manual_seed(5)
+        H, Y = torch.rand(T, N, generator=g, dtype=dt), torch.rand(T, M, generator=g, dtype=dt)
+        d = tmp_path / str(dt)
+        shapes = bench.dump_outputs(str(d), H, Y)
+        h, y = np.load(d / "H.npy"), np.load(d / "Y.npy")
+        assert h.dtype == y.dtype == (np.float64 if dt == torch.float64 else np.float32)
+        assert shapes == {"H": h.shape, "Y": y.shape} and y.shape == (T, M)
+        assert np.array_equal(y, Y.numpy())
+        assert (d / "H.npy").stat().st_size + (d / "Y.npy").stat().st_size < 64 * 10 ** 6
+        rows = bench.dump_rows(T, N * H.element_size(), bench.DUMP_BYTES - y.nbytes)
+        assert np.array_equal(h, H.numpy() if rows is None else H.numpy()[rows])
+    assert h.shape == (50, 64)                                  # small outputs are written whole

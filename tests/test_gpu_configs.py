@@ -390,6 +390,27 @@ def test_bench_gpus_flag_starts_the_ranks(tmp_path):
     assert r["value"] == pytest.approx(109206 * 2 / (r["ms_per_step"] * 2 / 1e3), rel=1e-6)
 
 
+def test_bench_dumps_the_last_step_and_full_adds_the_other_legs(tmp_path):
+    """A plain `bench.py` line times exactly --steps steps and carries none of the --full legs; --dump-outputs writes the
+    last step's Y and H, and a second run with the same arguments (here with --full) computes the same outputs."""
+    import json
+    args = ["--config", "C1", "--utterances", "2", "--steps", "3", "--warmup", "1"]
+    lines = []
+    for extra, d in (([], tmp_path / "plain"), (["--full"], tmp_path / "full")):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + args + extra + ["--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+    plain, full = lines
+    legs = {"cpu_baseline", "pcie", "parity", "one_utterance", "speedup_vs_cpu"}
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and not legs & set(plain), plain
+    assert legs <= set(full) and full["parity"]["timed_batch"]["H_max_rel_err"] < 1e-8, full
+    for name, shape in (("H", (1376, 512)), ("Y", (1376, 25))):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.shape == shape and a.dtype == np.float64 and np.isfinite(a).all() and (a >= 0).all()
+        np.testing.assert_allclose(a, b, rtol=1e-8, atol=1e-300)
+
+
 def test_non_finite_partials_cross_the_exchange_unchanged():
     """k_fused_all tags every published partial sum in its lowest mantissa bit; an infinite partial must
     come out of the exchange as the same infinity (readers clear the bit), so that results for overflowing inputs do

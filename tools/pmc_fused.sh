@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 run() { # name counters...
   local name=$1; shift
-  rocprofv3 --pmc "$@" -d "$OUT/$name" -o p --output-format csv -- python3 bench.py --steps 1 --warmup 1 --no-cpu "${EXTRA[@]}" > "$OUT/$name.json" 2> "$OUT/$name.err" || { tail -5 "$OUT/$name.err"; return 1; }
+  rocprofv3 --pmc "$@" -d "$OUT/$name" -o p --output-format csv -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu "${EXTRA[@]}" > "$OUT/$name.json" 2> "$OUT/$name.err" || { tail -5 "$OUT/$name.err"; return 1; }
 }
 EXTRA=("$@")
 run sq1 SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY
