@@ -55,8 +55,19 @@ class SolveInfo(C.Structure):
     """Mirror of `evc_solve_info` (include/evc.h): what the library actually ran."""
     _fields_ = [
         ("struct_bytes", C.c_int), ("kernel", C.c_int), ("members", C.c_int), ("launches", C.c_int),
-        ("redo", C.c_int), ("exchange", C.c_int), ("prepared", C.c_int), ("reserved", C.c_int),
+        ("redo", C.c_int), ("exchange", C.c_int), ("prepared", C.c_int), ("variant", C.c_int),
     ]
+
+
+def decode_variant(kernel: int, v: int):
+    """evc_solve_info.variant as a dict (None for the kernels that report none): schedule and template instance of the
+    task-queue kernels.  k_fused_wide: k_fused_wide<mt, w, tagged>; k_fused_wide64: k_fused_wide64<tpw>."""
+    if kernel not in (6, 7):
+        return None
+    d = {"static": bool(v & 1), "reduce": bool(v & 2), "tagged": bool(v & 4)}
+    d.update({"w": (v >> 8) & 0xff, "mt": (v >> 16) & 0xff} if kernel == 6 else {"tpw": (v >> 8) & 0xff,
+                                                                                  "tiles": (v >> 16) & 0xff})
+    return d
 
 
 KERNEL_NAMES = {0: "none", 1: "k_gemm_nt", 2: "k_gemm2", 3: "k_fused_mu", 4: "k_fused_res", 5: "k_fused_all",

@@ -630,6 +630,7 @@ int solve_wide(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
 
     inf->kernel = K::kernel;
     inf->members = fl.c;
+    inf->variant = wide_variant(fl, n_cus);
     inf->exchange = 1;               // tasks wait for tasks of other workgroups, whatever the number of ranges
     // tests only (evc_solve_opts.test_abort_at, 0 in production): k > 0 raises the abort flag in front of the k-th
     // launch of the iteration loop (-1: the call starts with it raised), as a wait that ran out would

@@ -250,6 +250,9 @@ size_t wide_ctl_words(const WideLayout& f);
 struct WideCaps { size_t aw, xw, hw, vpart, vsum, ctl; int c_cap; };
 WideCaps wide_caps(int M, int N, int T_, int n_cus);
 bool wide_fits(const WideLayout& f, const WideCaps& k);
+// evc_solve_info.variant of a solve on this layout: bit 0 static schedule, bit 1 reduce slices, bit 2 tagged hand-offs,
+// bits 8..15 wavefronts per workgroup, bits 16..23 MT (include/evc.h).  wide_iterate schedules by the same bits.
+int wide_variant(const WideLayout& f, int n_cus);
 // At1: the dictionary the numerator / denominator contraction uses (A, or A / colsum for KL), At2: A; exemplars as rows
 hipError_t wide_pack_dict(const WideLayout& f, const float* At1, const float* At2, int ld, int n_rows, float* Aw,
                           hipStream_t s);
@@ -290,6 +293,8 @@ Wide64Layout wide64_layout(int M, int N, int T_, int n_cus, int c_req, int tpw_r
 size_t wide_ctl_words(const Wide64Layout& f);
 Wide64Caps wide64_caps(int M, int N, int T_, int n_cus);
 bool wide_fits(const Wide64Layout& f, const Wide64Caps& k);
+// evc_solve_info.variant: bit 0 static schedule, bit 1 reduce slices, bits 8..15 TPW, bits 16..23 4 TPW + 1 bin tiles
+int wide_variant(const Wide64Layout& f, int n_cus);
 // (the second dictionary pointer, the KL-scaled rows of the float32 kernel, is unused: Frobenius only)
 hipError_t wide_pack_dict(const Wide64Layout& f, const double* At, const double* unused, int ld, int n_rows, double* Aw,
                           hipStream_t s);

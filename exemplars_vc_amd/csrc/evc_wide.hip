@@ -160,10 +160,18 @@ __global__ __launch_bounds__(W * 64, W / 4) void k_fused_wide(WideArgs a) {
     __syncthreads();
     // tagged hand-offs (WideArgs.tagged): the epoch bit rides in the lowest mantissa bit of every float
     // (the bit that makes room for the tag is rounded away, half to even - every dropped bit is a tie: truncation shrank
-    // every partial sum by half an ulp on average and doubled the float32 drift of a 150-iteration solve)
+    // every partial sum by half an ulp on average and doubled the float32 drift of a 150-iteration solve.  Infinities and
+    // NaNs are not rounded - 0x7FFFFFFF would carry into the sign, -0 - and a NaN gets its quiet bit, so that it is still
+    // a NaN when the reader clears bit 0: 0x7F800001 would otherwise come back as +inf)
     auto tag_set = [](f32x4 v, unsigned tg) -> f32x4 {
         u32x4 b = __builtin_bit_cast(u32x4, v);
-        b = ((b + (b & (b >> 1) & 1u)) & ~1u) | tg;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned x = b[k];
+            const bool special = (x & 0x7F800000u) == 0x7F800000u;
+            const unsigned y = special ? (x | ((x & 0x007FFFFFu) ? 0x00400000u : 0u)) : x + (x & (x >> 1) & 1u);
+            b[k] = (y & ~1u) | tg;
+        }
         return __builtin_bit_cast(f32x4, b);
     };
     auto tag_clear = [](f32x4 v) -> f32x4 {
@@ -345,7 +353,7 @@ __global__ __launch_bounds__(W * 64, W / 4) void k_fused_wide(WideArgs a) {
                 const __amdgpu_buffer_rsrc_t rsrc = make_rsrc(a.Vpart + ((((size_t)((par ^ 1u) * a.G + g) * c + e) * W + w)) * (TILE_B / 4), TILE_B);
                 const __amdgpu_buffer_rsrc_t rdst = make_rsrc(a.Vpart + ((((size_t)(par * a.G + g) * c + e) * W + w)) * (TILE_B / 4), TILE_B);
                 // (tagged: the partial of one iteration ago is this wavefront's own store - drained here - and goes out
-                // again under this iteration's epoch bit.  First the sums of iteration it - 1 must be complete, as for a
+                // again under this iteration's epoch bit: its old bit is cleared, not rounded away a second time.  First the sums of iteration it - 1 must be complete, as for a
                 // sweep: that is what says every member has read the partials of it - 1, whose slot the NEXT iteration
                 // overwrites - without it the members of a stopped group run ahead of each other's reduce slices.)
                 if (TG) {
@@ -368,7 +376,7 @@ __global__ __launch_bounds__(W * 64, W / 4) void k_fused_wide(WideArgs a) {
 #pragma unroll
                 for (int u = 0; u < MT; ++u) {
                     const f32x4 v = ld_sc1(rsrc, (u * 64 + lane) * 16u);
-                    st_sc1(rdst, (u * 64 + lane) * 16u, TG ? tag_set(v, ((unsigned)it >> 1) & 1u) : v);
+                    st_sc1(rdst, (u * 64 + lane) * 16u, TG ? tag_set(tag_clear(v), ((unsigned)it >> 1) & 1u) : v);
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the staged block of this task too)
@@ -892,6 +900,12 @@ bool wide_fits(const WideLayout& f, const WideCaps& k) {
            wide_ctl_words(f) <= k.ctl;
 }
 
+int wide_variant(const WideLayout& f, int n_cus) {
+    if (n_cus <= 0) n_cus = 256;
+    const int st = f.G * f.c <= n_cus ? 1 : 0;
+    return st | (f.rmode ? 2 : 0) | ((st && f.tagged) ? 4 : 0) | (f.W << 8) | (f.MT << 16);
+}
+
 hipError_t wide_pack_dict(const WideLayout& f, const float* At1, const float* At2, int ld, int n_rows, float* Aw,
                           hipStream_t s) {
     const long n = (long)f.aw;
@@ -990,8 +1004,9 @@ hipError_t wide_iterate(const WideLayout& f, const WideBuffers& b, const UttStat
 #endif
     // (two 4-wavefront workgroups per CU, one sweeping while the other exchanges, were tried: 90 us per iteration at one
     // utterance against 48 - twice the partial sums to exchange, and the two share the matrix pipe)
-    a.static_q = (f.G * f.c <= n_cus && !no_static) ? 1 : 0;
-    a.tagged = (a.static_q && f.tagged) ? 1 : 0;
+    const int variant = wide_variant(f, n_cus);
+    a.static_q = ((variant & 1) && !no_static) ? 1 : 0;
+    a.tagged = (a.static_q && (variant & 4)) ? 1 : 0;
     if (a.tagged && it_begin == 0) {
         // stale floats must not carry the epoch bit of the first two iterations (0): ones everywhere
         hipError_t em = hipMemsetAsync(b.Vpart, 0xFF, f.vpart * sizeof(float), s);

@@ -779,6 +779,11 @@ Wide64Layout wide64_layout(int M, int N, int T_, int n_cus, int c_req, int tpw_r
     return f;
 }
 
+int wide_variant(const Wide64Layout& f, int n_cus) {
+    if (n_cus <= 0) n_cus = 256;
+    return (f.G * f.c <= n_cus ? 1 : 0) | (f.rmode ? 2 : 0) | (f.TPW << 8) | ((4 * f.TPW + 1) << 16);
+}
+
 Wide64Caps wide64_caps(int M, int N, int T_, int n_cus) {
     const Wide64Layout a = wide64_layout(M, N, T_, n_cus, 0, 0);
     Wide64Caps k{};
@@ -872,7 +877,7 @@ hipError_t wide_iterate(const Wide64Layout& f, const Wide64Buffers& b, const Utt
 #else
     constexpr int no_static = 0;
 #endif
-    a.static_q = (f.G * f.c <= n_cus && !no_static) ? 1 : 0;
+    a.static_q = ((wide_variant(f, n_cus) & 1) && !no_static) ? 1 : 0;
     const unsigned grid = a.static_q ? (unsigned)(f.G * f.c) : (unsigned)(tasks < n_cus ? tasks : n_cus);
     hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b.ctl), (int)grid, 1, s);
     if (e != hipSuccess) return e;

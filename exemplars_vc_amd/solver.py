@@ -375,14 +375,15 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
     res = [H_out] if B is None else ([H_out] if want_h else [])
     if B is not None:
         res.append(_to_host(Y_d) if (x_np and out_y is None) else Y_d)
+    variant = _lib.decode_variant(int(sinfo.kernel), int(sinfo.variant))
     if info:
         res.append({"n_iter": n_iter, "err": err, "kernel": _lib.KERNEL_NAMES.get(sinfo.kernel, str(sinfo.kernel)),
                     "members": int(sinfo.members), "launches": int(sinfo.launches), "redo": int(sinfo.redo),
-                    "exchange": int(sinfo.exchange), "prepared": int(sinfo.prepared)})
+                    "exchange": int(sinfo.exchange), "prepared": int(sinfo.prepared), "variant": variant})
     if solve_info is not None:      # caller-supplied dict: filled without the synchronisation info=True implies
         solve_info.update(kernel=_lib.KERNEL_NAMES.get(sinfo.kernel, str(sinfo.kernel)), members=int(sinfo.members),
                           launches=int(sinfo.launches), redo=int(sinfo.redo), exchange=int(sinfo.exchange),
-                          prepared=int(sinfo.prepared))
+                          prepared=int(sinfo.prepared), variant=variant)
     return res[0] if len(res) == 1 else tuple(res)
 
 

@@ -52,9 +52,15 @@
  *   copied to the device by hipMemcpyAsync from pageable memory, which HIP stages at enqueue time; keep them valid
  *   until the call returns, not longer.
  *   k_fused_all's exchange carries its arrival flag in the lowest mantissa bit of every partial sum it publishes
- *   (readers clear it): each partial V' is truncated by at most one ulp, infinities and NaNs pass unchanged.  So does
- *   k_fused_wide on its static schedule (float32, batches of up to ~5 utterances): one float32 ulp per partial sum and
- *   per summed slice.
+ *   (readers clear it): each partial V' is truncated by at most one ulp; infinities pass unchanged, and so do NaNs (a
+ *   partial sum is a result of arithmetic, i.e. a quiet NaN, which stays a NaN without bit 0).  So does k_fused_wide on its
+ *   static schedule with reduce slices (float32, batches of up to ~5 utterances; evc_solve_info.variant bit 2): every
+ *   partial sum and summed slice is rounded to an even significand (half to even: at most one float32 ulp);
+ *   infinities and NaNs are not rounded (0x7FFFFFFF would carry into the sign bit) and stay what they are.
+ *   A NaN or infinity in a frame of X stays in that frame's column.  The other frames' results are bitwise those of the
+ *   same call without it in k_fused_wide and k_fused_wide64; in the fused float64 kernels for M <= 32 the frames that
+ *   share its frame tile of 16 may take the IEEE division instead of the shared reciprocal (<= 2 ulp apart, see
+ *   EVC_FLAG_EXACT_DIV).
  */
 #ifndef EVC_H
 #define EVC_H
@@ -194,7 +200,14 @@ typedef struct evc_solve_info {
     int redo;          /* 1: an exchange wait ran out and the solve was redone on kernels without exchange */
     int exchange;      /* 1: the delivered results come from a kernel whose workgroups exchange partial sums in a launch */
     int prepared;      /* 1: the dictionary came from an evc_dict_prepare image (no per-call import / packing) */
-    int reserved;
+    int variant;       /* the instance and schedule of the task-queue kernels (0 for every other kernel):
+                          bit 0: static schedule (workgroup b runs task b of every iteration; else a ticket queue);
+                          bit 1: reduce slices (reduce tasks sum the partial V' of a frame group);
+                          bit 2: tagged hand-offs (the epoch bit rides in the data; k_fused_wide only);
+                          bits 8..15: k_fused_wide: wavefronts per workgroup (4 | 8); k_fused_wide64: whole bin tiles per
+                                      wavefront (3 | 4 | 5 | 7 | 8);
+                          bits 16..23: bin tiles of 16 the instance holds (k_fused_wide: MT = 4 | 6 | 8 | 10 | 13;
+                                       k_fused_wide64: 4 x tiles per wavefront + 1) */
 } evc_solve_info;
 
 /* A dictionary imported once.  The reference builds A and B once per run (04_align_n_nmf.py:230-246,350-361) and the
