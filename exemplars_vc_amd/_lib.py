@@ -27,7 +27,7 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_griffin_lim_workspace_bytes", "evc_griffin_lim", "evc_griffin_lim_batch_workspace_bytes",
            "evc_griffin_lim_batch", "evc_dtw_workspace_bytes", "evc_dtw_align",
            "evc_stft_frames", "evc_stft_workspace_bytes", "evc_stft", "evc_dict_bytes", "evc_dict_prepare",
-           "evc_dtw_path_rows", "evc_dtw_gather_rows")
+           "evc_dtw_path_rows", "evc_dtw_gather_rows", "evc_cd_workspace_bytes", "evc_cd_solve")
 
 
 class SolveOpts(C.Structure):
@@ -39,6 +39,16 @@ class SolveOpts(C.Structure):
         ("loss", C.c_int), ("test_abort_at", C.c_int),
         ("eps", C.c_double), ("l1", C.c_double), ("tol", C.c_double), ("init_value", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p), ("info", C.c_void_p), ("dict", C.c_void_p),
+    ]
+
+
+class CdOpts(C.Structure):
+    """Mirror of `evc_cd_opts` (include/evc.h): options of the coordinate-descent solve."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("init_mode", C.c_int),
+        ("max_iter", C.c_int), ("reserved", C.c_int),
+        ("tol", C.c_double), ("l1", C.c_double), ("l2", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
 
@@ -161,6 +171,17 @@ def lib():
     L.evc_dtw_gather_rows.restype = C.c_int
     L.evc_dtw_gather_rows.argtypes = [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p]
+    L.evc_cd_workspace_bytes.restype = C.c_size_t
+    L.evc_cd_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_cd_solve.restype = C.c_int
+    L.evc_cd_solve.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # A, X, H
+        C.c_int, C.c_int, C.c_int,                                          # M, N, T
+        C.POINTER(C.c_int), C.c_int, C.POINTER(CdOpts),                     # utt_offsets, n_utt, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, violation_out
+        C.c_void_p,                                                         # stream
+    ]
     _lib = L
     return L
 

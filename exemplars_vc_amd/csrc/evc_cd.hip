@@ -1,0 +1,428 @@
+// evc_cd.hip - coordinate-descent activation solve: scikit-learn's solver='cd' with a fixed dictionary
+// (non_negative_factorization(..., update_H=False, solver='cd', shuffle=False), _nmf.py:376-404,496-521 and
+// _cdnmf_fast.pyx), the call of 04_align_n_nmf_pytorch.py:189-210.
+//
+// Algebra.  sklearn sweeps the components t = 0..N-1 in order and, for every frame, takes
+//   grad = G[t,:] w - P[t]   (G = A A^T + l2 I, P = A x - l1),   w_t <- max(w_t - grad / G[t,t], 0)
+// at 2N^2 flop per frame and sweep.  The same steps in the same order, reassociated: keep the residual
+// r = w A - x of every frame (M values), then grad_t = r . a_t + l2 w_t + l1 and every step adds delta_t a_t to r:
+// 4MN flop.  The components are taken in blocks of 16: the block's 16 gradients are formed from r at the block's
+// start (16 dot products of length M), the 16 steps run in order and correct the later gradients of the block with
+// the block's diagonal Gram block G_bb (a rank-1 update per step), then r += sum_j delta_j a_j.  Only the rounding
+// differs from sklearn.  The division grad / hess is the IEEE one (no reciprocal), as in sklearn.
+//
+// Kernel k_cd_sweep<T, MPL>: plain VALU arithmetic (float64 / float32), one wavefront per frame tile.  A frame
+// is served by a group of L lanes (L a power of two, from M alone: the smallest with ceil(M / L) <= 16); lane q of
+// the group holds r[m] for m = q, q + L, ... in registers (MPL >= ceil(M / L) slots), the group's partial dot products
+// are summed by an xor butterfly (bitwise the same sum in every lane of the group), and every lane of the group runs
+// the 16 sequential steps.  A tile is 64 / L frames of ONE utterance (utterances start at a tile boundary), so the
+// arithmetic of a frame never depends on the other frames of the call: a batched solve is bitwise the solo solves.
+//
+// One launch per iteration; no inter-workgroup exchange inside a launch.  Launch k first judges iteration k-1 of
+// its utterance: every workgroup sums the per-tile violation partials of the previous launch in tile order (the same
+// bits in every workgroup), applies sklearn's rule (violation_init == 0, or violation / violation_init <= tol, or
+// max_iter reached) and returns at once if the utterance has stopped; the utterance's first tile records the value,
+// violation_init and the stop iteration.  A final launch (k = max_iter + 1) only judges.  The violation is
+// accumulated in float64 for both element types; padded frames contribute nothing.
+#include "evc_internal.h"
+
+namespace evc {
+
+namespace {
+
+constexpr int CD_B = 16;        // components per block
+constexpr int CD_WAVE = 64;
+
+// the packed dictionary: blocks of 16 components, bin-major inside a block (the 16 values a lane needs for one bin
+// are contiguous)
+__device__ __forceinline__ long cd_at(int n, int m, int Mr) { return ((long)(n / CD_B) * Mr + m) * CD_B + n % CD_B; }
+
+template <typename T>
+__global__ void k_cd_pack_dict(const T* __restrict__ A, int lda, int fm, int M, int N, int Np, int Mr,
+                               T* __restrict__ Ac) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)Np * Mr) return;
+    const int n = (int)(i / Mr), m = (int)(i % Mr);
+    T v = T(0);
+    if (n < N && m < M) v = fm ? A[(long)n * lda + m] : A[(long)m * lda + n];
+    Ac[cd_at(n, m, Mr)] = v;
+}
+
+// one workgroup of 16 x 16 threads per block of 16 components: Gb[b][j][k] = a_j . a_k, hess = |a_j|^2 + l2
+template <typename T>
+__global__ void k_cd_gram_blocks(const T* __restrict__ Ac, int M, int N, int Mr, double l2, T* __restrict__ Gb,
+                                 T* __restrict__ hess) {
+    const int b = blockIdx.x, j = threadIdx.x >> 4, k = threadIdx.x & 15;
+    T s = T(0);
+    for (int m = 0; m < M; ++m) s += Ac[cd_at(b * CD_B + j, m, Mr)] * Ac[cd_at(b * CD_B + k, m, Mr)];
+    Gb[(long)b * CD_B * CD_B + j * CD_B + k] = s;
+    if (j == k) {
+        const int c = b * CD_B + j;
+        hess[c] = c < N ? s + (T)l2 : T(0);
+    }
+}
+
+// r = w A - x per frame slot (w = H on entry for EVC_INIT_GIVEN, else 0 and H is zeroed by the host); padding 0
+template <typename T>
+__global__ void k_cd_init_resid(const T* __restrict__ X, int ldx, const T* __restrict__ H, int ldh, int fm, int given,
+                                const T* __restrict__ Ac, const int4* __restrict__ tiles, int n_tiles, int F, int M,
+                                int N, int Mr, T* __restrict__ R) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)n_tiles * F * Mr) return;
+    const long slot = i / Mr;
+    const int m = (int)(i % Mr);
+    const int4 tl = tiles[slot / F];
+    const int g = (int)(slot % F);
+    T v = T(0);
+    if (g < tl.z && m < M) {
+        const long f = tl.y + g;
+        if (given)
+            for (int n = 0; n < N; ++n) v += (fm ? H[f * ldh + n] : H[(long)n * ldh + f]) * Ac[cd_at(n, m, Mr)];
+        v -= fm ? X[f * ldx + m] : X[(long)m * ldx + f];
+    }
+    R[i] = v;
+}
+
+}  // namespace
+
+template <typename T> struct CdArgs {
+    const T* Ac;            // [Np/16][Mr][16] dictionary rows, zero-padded (cd_at)
+    const T* Gb;            // [Np/16][16][16] diagonal Gram blocks
+    const T* hess;          // [Np] |a_t|^2 + l2 (0 for padding components)
+    T* R;                   // [n_tiles * F][Mr] residual w A - x of every frame slot
+    T* H;
+    long ldh;
+    int fm;                 // 1: H[t * ldh + n]; 0: H[n * ldh + t]
+    const int4* tiles;      // {utterance, first frame, frames, first tile of the utterance}
+    const int* utt_tile0;   // [n_utt + 1] first tile of every utterance
+    double* part;           // [2][n_tiles] per-tile violation of the last two launches
+    int* stop;              // [n_utt] 0: running; else the iteration the utterance stopped at (= n_iter)
+    double* vinit;          // [n_utt]
+    double* trace;          // [n_utt][CD_TRACE_CAP] violation of iteration i at slot (i - 1) % CD_TRACE_CAP
+    int n_tiles, M, N, Np, Mr, L, mpl, max_iter;
+    double tol;
+    T l1, l2;
+};
+
+template <typename T, int MPL>
+__global__ __launch_bounds__(CD_WAVE) void k_cd_sweep(CdArgs<T> a, int k) {
+    __shared__ double sv[CD_WAVE];
+    __shared__ T Gs[CD_B * CD_B + CD_B];            // the block's G_bb, then its 16 hess values
+    const int tile = blockIdx.x;
+    const int4 tl = a.tiles[tile];
+    const int u = tl.x;
+    if (a.stop[u] != 0) return;
+    if (k >= 2) {                                  // judge iteration k - 1 of utterance u
+        const int it = k - 1;
+        const double* p = a.part + (size_t)(it & 1) * a.n_tiles;
+        double s = 0.0;
+        for (int q = a.utt_tile0[u]; q < a.utt_tile0[u + 1]; ++q) s += p[q];
+        const double vi = it == 1 ? s : a.vinit[u];
+        const bool stop_now = vi == 0.0 || s / vi <= a.tol || it >= a.max_iter;
+        if (tile == tl.w && threadIdx.x == 0) {
+            a.trace[(size_t)u * CD_TRACE_CAP + (it - 1) % CD_TRACE_CAP] = s;
+            if (it == 1) a.vinit[u] = s;
+            if (stop_now) a.stop[u] = it;
+        }
+        if (stop_now) return;
+    }
+    const int L = a.L;
+    const int mpl = a.mpl;
+    const int lane = threadIdx.x;
+    const int g = lane / L;                        // frame of the tile
+    const int q = lane % L;                        // lane in the frame's group
+    const int F = CD_WAVE / L;
+    const bool valid = g < tl.z;
+    const long f = (long)tl.y + g;
+    const long slot = (long)tile * F + g;
+    T* Rs = a.R + slot * a.Mr + q;
+    T r[MPL];
+#pragma unroll
+    for (int kk = 0; kk < MPL; ++kk) r[kk] = kk < mpl ? Rs[kk * L] : T(0);
+    const long hs_t = a.fm ? a.ldh : 1, hs_n = a.fm ? 1 : a.ldh;
+    T* Hf = a.H + (valid ? f : 0) * hs_t;
+    double viol = 0.0;
+    const int nb = a.Np / CD_B;
+#pragma unroll 1
+    for (int b = 0; b < nb; ++b) {
+        const int c0 = b * CD_B;
+        T w[CD_B], gr[CD_B], d[CD_B];
+#pragma unroll
+        for (int j = 0; j < CD_B; ++j) {      // branch-free: clamped address, then select
+            const int c = c0 + j < a.N ? c0 + j : a.N - 1;
+            const T v = Hf[c * hs_n];
+            w[j] = (valid && c0 + j < a.N) ? v : T(0);
+        }
+        const T* Ab = a.Ac + ((long)b * a.Mr + q) * CD_B;     // a_{c0+j}[q + L kk] at Ab[kk * L * 16 + j]
+        {
+            const T* G = a.Gb + (long)b * CD_B * CD_B;
+#pragma unroll
+            for (int i = 0; i < CD_B * CD_B / CD_WAVE; ++i) Gs[i * CD_WAVE + lane] = G[i * CD_WAVE + lane];
+            if (lane < CD_B) Gs[CD_B * CD_B + lane] = a.hess[c0 + lane];
+        }
+        __syncthreads();
+        // 1. the block's gradients at its start: r . a_j, summed over the lane group
+#pragma unroll
+        for (int j = 0; j < CD_B; ++j) gr[j] = T(0);
+#pragma unroll
+        for (int kk = 0; kk < MPL; ++kk)
+            if (kk < mpl) {
+                const T* ap = Ab + (long)kk * L * CD_B;
+#pragma unroll
+                for (int j = 0; j < CD_B; ++j) gr[j] = fma(r[kk], ap[j], gr[j]);
+            }
+#pragma unroll 1
+        for (int o = 1; o < L; o <<= 1)
+#pragma unroll
+            for (int j = 0; j < CD_B; ++j) gr[j] += __shfl_xor(gr[j], o);
+#pragma unroll
+        for (int j = 0; j < CD_B; ++j) gr[j] = (gr[j] + a.l2 * w[j]) + a.l1;
+        // 2. the 16 coordinate steps in sklearn's order
+#pragma unroll
+        for (int j = 0; j < CD_B; ++j) {
+            // keep the compiler from hoisting every step's 15 Gram reads to the top of the block (a register per value)
+            __asm__ volatile("" ::: "memory");
+            const T grad = gr[j];
+            const T pg = w[j] == T(0) ? (grad < T(0) ? grad : T(0)) : grad;
+            if (c0 + j < a.N) viol += fabs((double)pg);
+            const T h = Gs[CD_B * CD_B + j];
+            T dj = T(0);
+            if (h != T(0)) {
+                const T v = w[j] - grad / h;
+                const T nw = v > T(0) ? v : T(0);
+                dj = nw - w[j];
+                w[j] = nw;
+            }
+            d[j] = dj;
+#pragma unroll
+            for (int kk = j + 1; kk < CD_B; ++kk) gr[kk] = fma(dj, Gs[j * CD_B + kk], gr[kk]);
+        }
+        if (valid && q == 0) {
+#pragma unroll
+            for (int j = 0; j < CD_B; ++j)
+                if (c0 + j < a.N) Hf[(c0 + j) * hs_n] = w[j];
+        }
+        // 3. r += sum_j delta_j a_j (j in order)
+#pragma unroll
+        for (int kk = 0; kk < MPL; ++kk)
+            if (kk < mpl) {
+                const T* ap = Ab + (long)kk * L * CD_B;
+                T v = r[kk];
+#pragma unroll
+                for (int j = 0; j < CD_B; ++j) v = fma(d[j], ap[j], v);
+                r[kk] = v;
+            }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int kk = 0; kk < MPL; ++kk)
+        if (kk < mpl) Rs[kk * L] = r[kk];
+    if (q == 0) sv[g] = valid ? viol : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < F; ++i) s += sv[i];
+        a.part[(size_t)(k & 1) * a.n_tiles + tile] = s;
+    }
+}
+
+CdGeometry cd_geometry(int M) {
+    CdGeometry g{};
+    if (M < 1 || M > CD_MAX_M) return g;
+    int L = 1;
+    while ((M + L - 1) / L > 16) L *= 2;
+    g.L = L;
+    g.mpl = (M + L - 1) / L;
+    g.Mr = g.mpl * L;
+    g.F = CD_WAVE / L;
+    return g;
+}
+
+namespace {
+
+template <typename T, int MPL>
+hipError_t launch_sweep_mpl(const CdArgs<T>& a, int k, hipStream_t s) {
+    hipLaunchKernelGGL((k_cd_sweep<T, MPL>), dim3(a.n_tiles), dim3(CD_WAVE), 0, s, a, k);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t launch_sweep(const CdArgs<T>& a, int k, hipStream_t s) {
+    if (a.mpl <= 1) return launch_sweep_mpl<T, 1>(a, k, s);
+    if (a.mpl <= 8) return launch_sweep_mpl<T, 8>(a, k, s);
+    return launch_sweep_mpl<T, 16>(a, k, s);
+}
+
+__global__ void k_cd_state_init(int* stop, double* vinit, double* trace, int n_utt) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_utt) {
+        stop[i] = 0;
+        vinit[i] = 0.0;
+    }
+    if (i < (long)n_utt * CD_TRACE_CAP) trace[i] = __builtin_nan("");
+}
+
+#define CD_TRY(expr)                                  \
+    do {                                              \
+        hipError_t e_ = (expr);                       \
+        if (e_ != hipSuccess) return (int)e_;         \
+    } while (0)
+
+size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+}  // namespace
+
+// The workspace: [Ac | Gb | hess | R | tiles | utt_tile0 | part | stop | vinit | trace], each 256-byte aligned.
+// n_tiles is bounded by ceil(T / F) + n_utt whatever the split into utterances.
+size_t cd_workspace_bytes(int M, int N, int T_, int n_utt, int esize) {
+    const CdGeometry g = cd_geometry(M);
+    if (g.L == 0 || N < 1 || T_ < 0 || n_utt < 1 || (esize != 4 && esize != 8)) return 0;
+    const size_t Np = (size_t)round_up(N, CD_B);
+    const size_t nt = (size_t)(T_ + g.F - 1) / g.F + n_utt;
+    size_t b = 0;
+    b += align256(Np * g.Mr * esize);
+    b += align256(Np * CD_B * esize);
+    b += align256(Np * esize);
+    b += align256(nt * g.F * g.Mr * esize);
+    b += align256(nt * sizeof(int4));
+    b += align256((n_utt + 1) * sizeof(int));
+    b += align256(2 * nt * sizeof(double));
+    b += align256(n_utt * sizeof(int));
+    b += align256(n_utt * sizeof(double));
+    b += align256((size_t)n_utt * CD_TRACE_CAP * sizeof(double));
+    return b + 256;
+}
+
+template <typename T>
+int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
+             int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
+             hipStream_t s, int* launches_out) {
+    const CdGeometry g = cd_geometry(M);
+    const bool fm = o.layout == EVC_FRAME_MAJOR;
+    const int Np = round_up(N, CD_B);
+    // tiles: each utterance starts at a tile boundary
+    int n_tiles = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        const int tu = utt_offsets ? utt_offsets[u + 1] - utt_offsets[u] : T_;
+        n_tiles += (tu + g.F - 1) / g.F;
+    }
+    const int nt_cap = (T_ + g.F - 1) / g.F + n_utt;
+    if (n_tiles > nt_cap) return -1;
+    char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = base + off; off += align256(bytes); return p; };
+    T* Ac = reinterpret_cast<T*>(take((size_t)Np * g.Mr * sizeof(T)));
+    T* Gb = reinterpret_cast<T*>(take((size_t)Np * CD_B * sizeof(T)));
+    T* hess = reinterpret_cast<T*>(take((size_t)Np * sizeof(T)));
+    T* R = reinterpret_cast<T*>(take((size_t)nt_cap * g.F * g.Mr * sizeof(T)));
+    int4* tiles = reinterpret_cast<int4*>(take((size_t)nt_cap * sizeof(int4)));
+    int* utt_tile0 = reinterpret_cast<int*>(take((size_t)(n_utt + 1) * sizeof(int)));
+    double* part = reinterpret_cast<double*>(take((size_t)2 * nt_cap * sizeof(double)));
+    int* stop = reinterpret_cast<int*>(take((size_t)n_utt * sizeof(int)));
+    double* vinit = reinterpret_cast<double*>(take((size_t)n_utt * sizeof(double)));
+    double* trace = reinterpret_cast<double*>(take((size_t)n_utt * CD_TRACE_CAP * sizeof(double)));
+    if ((size_t)(base - static_cast<char*>(ws)) + off > ws_bytes) return -2;
+
+    // the tile table (host, staged by hipMemcpyAsync from pageable memory at enqueue time)
+    int4* h_tiles = static_cast<int4*>(malloc(sizeof(int4) * (n_tiles > 0 ? n_tiles : 1) + sizeof(int) * (n_utt + 1)));
+    if (!h_tiles) return (int)hipErrorOutOfMemory;
+    int* h_t0 = reinterpret_cast<int*>(h_tiles + (n_tiles > 0 ? n_tiles : 1));
+    {
+        int t = 0;
+        for (int u = 0; u < n_utt; ++u) {
+            const int f0 = utt_offsets ? utt_offsets[u] : 0;
+            const int tu = utt_offsets ? utt_offsets[u + 1] - f0 : T_;
+            h_t0[u] = t;
+            for (int i = 0; i < tu; i += g.F) {
+                h_tiles[t] = make_int4(u, f0 + i, tu - i < g.F ? tu - i : g.F, h_t0[u]);
+                ++t;
+            }
+        }
+        h_t0[n_utt] = t;
+    }
+    hipError_t e = hipSuccess;
+    if (n_tiles > 0) e = hipMemcpyAsync(tiles, h_tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
+    free(h_tiles);      // pageable source: HIP has staged the bytes by the time hipMemcpyAsync returns
+    CD_TRY(e);
+
+    const int es = (int)sizeof(T);
+    if (o.init_mode == EVC_INIT_SKLEARN && T_ > 0) {
+        if (fm) CD_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)N * es, T_, s));
+        else CD_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)T_ * es, N, s));
+    }
+    {
+        const long n = (long)Np * g.Mr;
+        hipLaunchKernelGGL(k_cd_pack_dict<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A, lda, fm ? 1 : 0,
+                           M, N, Np, g.Mr, Ac);
+        CD_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_cd_gram_blocks<T>, dim3(Np / CD_B), dim3(CD_B * CD_B), 0, s, Ac, M, N, g.Mr, o.l2, Gb, hess);
+        CD_TRY(hipGetLastError());
+    }
+    if (n_tiles > 0) {
+        const long n = (long)n_tiles * g.F * g.Mr;
+        hipLaunchKernelGGL(k_cd_init_resid<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, X, ldx, H, ldh,
+                           fm ? 1 : 0, o.init_mode == EVC_INIT_GIVEN ? 1 : 0, Ac, tiles, n_tiles, g.F, M, N, g.Mr, R);
+        CD_TRY(hipGetLastError());
+    }
+    {
+        const long n = (long)n_utt * CD_TRACE_CAP;
+        hipLaunchKernelGGL(k_cd_state_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, stop, vinit, trace,
+                           n_utt);
+        CD_TRY(hipGetLastError());
+    }
+    CdArgs<T> a;
+    a.Ac = Ac; a.Gb = Gb; a.hess = hess; a.R = R; a.H = H; a.ldh = ldh; a.fm = fm ? 1 : 0;
+    a.tiles = tiles; a.utt_tile0 = utt_tile0; a.part = part; a.stop = stop; a.vinit = vinit; a.trace = trace;
+    a.n_tiles = n_tiles; a.M = M; a.N = N; a.Np = Np; a.Mr = g.Mr; a.L = g.L; a.mpl = g.mpl;
+    a.max_iter = o.max_iter; a.tol = o.tol; a.l1 = (T)o.l1; a.l2 = (T)o.l2;
+
+    const bool run = n_tiles > 0 && o.max_iter > 0;
+    int launches = 0;
+    int copied = 0;         // iterations whose violation has been copied to violation_out
+    if (o.ev_loop_start) CD_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
+    if (run) {
+        for (int k = 1; k <= o.max_iter + 1; ++k) {
+            CD_TRY(launch_sweep<T>(a, k, s));
+            ++launches;
+            const int judged = k - 1;
+            if (violation_out && judged > copied && (judged - copied == CD_TRACE_CAP || k == o.max_iter + 1)) {
+                const int cnt = judged - copied;
+                CD_TRY(hipMemcpy2DAsync(violation_out + copied, sizeof(double) * o.max_iter, trace,
+                                        sizeof(double) * CD_TRACE_CAP, sizeof(double) * cnt, n_utt,
+                                        hipMemcpyDeviceToHost, s));
+                copied = judged;
+            }
+        }
+    }
+    if (o.ev_loop_stop) CD_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
+    if (launches_out) *launches_out = launches;
+    if (n_iter_out || violation_out) {
+        int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
+        if (!ni_h) return (int)hipErrorOutOfMemory;
+        e = run ? hipMemcpyAsync(ni_h, stop, sizeof(int) * n_utt, hipMemcpyDeviceToHost, s) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        for (int u = 0; e == hipSuccess && u < n_utt; ++u) {
+            const int tu = utt_offsets ? utt_offsets[u + 1] - utt_offsets[u] : T_;
+            // an utterance without frames has violation 0 at its first iteration, where sklearn's rule stops it
+            const int ni = o.max_iter == 0 ? 0 : (tu == 0 || !run) ? 1 : ni_h[u];
+            if (n_iter_out) n_iter_out[u] = ni;
+            if (violation_out)
+                for (int i = 0; i < o.max_iter; ++i) {
+                    double* v = violation_out + (size_t)u * o.max_iter + i;
+                    if (i >= ni) *v = __builtin_nan("");
+                    else if (tu == 0 || !run) *v = 0.0;
+                }
+        }
+        free(ni_h);
+        CD_TRY(e);
+    }
+    return 0;
+}
+
+template int cd_solve<double>(const double*, int, const double*, int, double*, int, int, int, int, const int*, int,
+                              const evc_cd_opts&, void*, size_t, int*, double*, hipStream_t, int*);
+template int cd_solve<float>(const float*, int, const float*, int, float*, int, int, int, int, const int*, int,
+                             const evc_cd_opts&, void*, size_t, int*, double*, hipStream_t, int*);
+
+}  // namespace evc

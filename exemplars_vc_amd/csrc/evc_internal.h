@@ -331,4 +331,21 @@ hipError_t dtw_gather(const T* src, long ld_src, int elem_stride, const int* pat
                       const int* pair_off, const int* row_start, int n_pairs, int cols, int op, T* dst, long ld_dst,
                       hipStream_t s);
 
+// ----- evc_cd.hip: coordinate-descent activation solve (evc_cd_solve) -----
+constexpr int CD_MAX_M = 1024;        // 64 lanes x 16 bins per lane
+constexpr int CD_TRACE_CAP = 256;     // device ring of per-iteration violations (copied out in chunks)
+struct CdGeometry {
+    int L;      // lanes per frame (0: M unsupported)
+    int mpl;    // bins per lane, ceil(M / L)
+    int Mr;     // L * mpl: row stride of the packed dictionary and of the residual
+    int F;      // frames per tile (one wavefront): 64 / L
+};
+CdGeometry cd_geometry(int M);
+size_t cd_workspace_bytes(int M, int N, int T_, int n_utt, int esize);
+// arguments already validated by evc_cd_solve; returns 0, -1, -2 or a hipError_t
+template <typename T>
+int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
+             int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
+             hipStream_t s, int* launches_out);
+
 }  // namespace evc

@@ -387,6 +387,77 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
     return res[0] if len(res) == 1 else tuple(res)
 
 
+def solve_activations_cd(A, X, H0=None, *, layout="bin_major", max_iter=200, tol=1e-4, l1=0.0, l2=0.0,
+                         utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False,
+                         loop_events=None):
+    """scikit-learn's coordinate-descent solve with the dictionary fixed (solver='cd', update_H=False,
+    shuffle=False, Frobenius), on the GPU (evc_cd_solve).  H starts at 0 as in sklearn, or at H0 when given (a
+    warm start).  l1 / l2 are sklearn's scaled l1_reg_W / l2_reg_W.  Per utterance: stop after the iteration whose
+    violation / violation_init <= tol (or violation_init == 0), else at max_iter.
+
+    Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor
+    out); with info=True also dict(n_iter=int array per utterance, violation=[n_utt, max_iter] array (NaN after the
+    stop), kernel="k_cd_sweep", launches=int).  No CPU fallback: without a HIP device this raises RuntimeError."""
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    lay = _LAYOUTS[layout]
+    tdtype, dcode = _pick_dtype(dtype, X, A)
+    A_d, _ = _to_dev(A, tdtype, device)
+    X_d, x_np = _to_dev(X, tdtype, device)
+    if lay == _lib.BIN_MAJOR:
+        M, N = A_d.shape
+        M2, T = X_d.shape
+        hshape = (N, T)
+    else:
+        N, M = A_d.shape
+        T, M2 = X_d.shape
+        hshape = (T, N)
+    if M2 != M:
+        raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
+    if H0 is not None:
+        H_d, _ = _to_dev(H0, tdtype, device)
+        if tuple(H_d.shape) != hshape:
+            raise ValueError(f"H0 has shape {tuple(H_d.shape)}, expected {hshape}")
+        if isinstance(H0, torch.Tensor) and H_d.data_ptr() == H0.data_ptr():
+            H_d = H_d.clone()       # never clobber the caller's H0
+    else:
+        H_d = torch.empty(hshape, dtype=tdtype, device=device)
+    if utt_offsets is None:
+        n_utt, off_ptr = 1, None
+    else:
+        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
+        n_utt = len(off_arr) - 1
+        if n_utt < 1:
+            raise ValueError("utt_offsets needs at least two entries")
+        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
+    opts = _lib.CdOpts()
+    opts.struct_bytes = C.sizeof(_lib.CdOpts)
+    opts.dtype, opts.layout = dcode, lay
+    opts.init_mode = _lib.INIT_GIVEN if H0 is not None else _lib.INIT_SKLEARN
+    opts.max_iter, opts.tol, opts.l1, opts.l2 = int(max_iter), float(tol), float(l1), float(l2)
+    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
+        opts.ev_loop_start = int(loop_events[0].cuda_event)
+        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    ws_bytes = int(L.evc_cd_workspace_bytes(M, N, T, n_utt, dcode))
+    if ws_bytes == 0:
+        raise ValueError(f"unsupported coordinate-descent shape M={M}, N={N}, T={T}")
+    n_iter = np.zeros(n_utt, dtype=np.int32) if info else None
+    viol = np.full((n_utt, max(int(max_iter), 0)), np.nan) if info else None
+    ni_p = n_iter.ctypes.data_as(C.POINTER(C.c_int)) if info else None
+    vi_p = viol.ctypes.data_as(C.POINTER(C.c_double)) if info else None
+    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_cd_solve(A_d.data_ptr(), _ld(A_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, N, T,
+                            off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, vi_p, C.c_void_p(stream))
+    _lib.check(st, "evc_cd_solve")
+    H_out = _to_host(H_d) if x_np else H_d
+    if info:
+        launches = int(max_iter) + 1 if (T > 0 and max_iter > 0) else 0
+        return H_out, {"n_iter": n_iter, "violation": viol, "kernel": "k_cd_sweep", "launches": launches}
+    return H_out
+
+
 def synthesize(B, H, *, layout="bin_major", dtype=None, device=None):
     """Y = B H (bin_major, (Mb,T)) or H B (frame_major: np.matmul(H.T, B) of
     04_align_n_nmf.py:391 with H already frames-as-rows, giving (T,Mb))."""

@@ -19,6 +19,9 @@
  *   evc_dtw_path_rows, evc_dtw_gather_rows  replace align_sp_ap_f0() + the stacking  04_align_n_nmf.py:100-169,230-246
  *   evc_residual    replaces sklearn _beta_divergence(beta=2, square_root=True)
  *                   (_nmf.py:85-135) and pymf frobenius_norm (pymf/base.py:144-165)
+ *   evc_cd_solve    replaces the coordinate-descent loop behind _factorize() of 04_align_n_nmf_pytorch.py:189-210
+ *                   (sklearn solver='cd', update_H=False: _fit_coordinate_descent, _nmf.py:496-521,
+ *                    _update_coordinate_descent, :376-404, _cdnmf_fast.pyx)
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -45,7 +48,10 @@
  *         workgroups resident at once, like k_fused_all's exchange: two such solves started concurrently on two streams
  *         can starve each other until the bounded waits run out (seconds) and both are redone - give concurrent
  *         small solves EVC_FLAG_NO_EXCHANGE (the compat layer's side streams do).  Larger batches draw tasks from a
- *         queue and depend on nobody's residency.
+ *         queue and depend on nobody's residency;
+ *     (4) evc_cd_solve: n_iter_out / violation_out non-NULL (the call returns after copying them back).  Its kernels
+ *         never exchange data between workgroups inside a launch and assume nothing about residency: concurrent
+ *         coordinate-descent solves on several streams are safe.
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
  *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets) are consumed before the call returns: they are
@@ -370,6 +376,42 @@ int evc_dtw_path_rows(const int* path_len, int n_pairs, int* row_start, int* n_r
 int evc_dtw_gather_rows(const void* src, long ld_src, int elem_stride, const int* path, const int* path_len,
                         const int* src_offsets, const int* pair_offsets, const int* row_start, int n_pairs, int cols,
                         int op, void* dst, long ld_dst, int dtype, evc_stream_t stream);
+
+/* Coordinate descent - scikit-learn's solver='cd' with the dictionary fixed (update_H=False, shuffle=False), Frobenius
+ * loss: for every frame the components t = 0..N-1 are visited in order and
+ *     grad = (A^T A h)_t + l2 h_t - (A^T x)_t + l1,  h_t <- max(h_t - grad / (|a_t|^2 + l2), 0)
+ * (components with |a_t|^2 + l2 == 0 are left alone); the sum over frames and components of the projected gradient
+ * |pg| (pg = min(grad, 0) where h_t == 0, else grad) is the iteration's violation.  Per utterance, after every iteration:
+ * stop when violation_init (that of iteration 1) == 0, when violation / violation_init <= tol, or at max_iter
+ * (_nmf.py:496-521); the stopping iteration's update is kept.  float32 inputs are solved in float32 (the violation is
+ * summed in float64 for both types); the quotient is the IEEE division.  One kernel launch per iteration (k_cd_sweep)
+ * plus one that judges the last; no inter-workgroup exchange.  A frame's arithmetic does not depend on the other frames
+ * of the call: a batch of utterances gives bitwise the activations of one call per utterance.
+ *   M      : 1 .. 1024 bins (larger: -3)
+ *   layout : EVC_FRAME_MAJOR | EVC_BIN_MAJOR, as for evc_nmf_solve (A, X, H and their leading dimensions)
+ *   init   : EVC_INIT_SKLEARN - H starts at 0, what sklearn's cd starts from whatever H was passed (_nmf.py:1229-1233);
+ *            EVC_INIT_GIVEN   - H holds the start on entry (a warm start)
+ *   l1, l2 : already scaled: sklearn's l1_reg_W = M alpha_W l1_ratio and l2_reg_W = M alpha_W (1 - l1_ratio)
+ *   n_iter_out    : host, n_utt ints or NULL: iterations run per utterance (an utterance without frames: 1)
+ *   violation_out : host, n_utt x max_iter doubles ([u][i]) or NULL: violation of every iteration, NaN after the stop
+ * When both are NULL the call is fully asynchronous. */
+typedef struct evc_cd_opts {
+    int struct_bytes;  /* sizeof(evc_cd_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int init_mode;     /* EVC_INIT_SKLEARN (zeros) | EVC_INIT_GIVEN */
+    int max_iter;      /* >= 0 */
+    int reserved;      /* 0 */
+    double tol;        /* >= 0 */
+    double l1, l2;     /* >= 0 */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_cd_opts;
+/* bytes of workspace evc_cd_solve needs (0: invalid arguments) */
+size_t evc_cd_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
+int evc_cd_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
+                 const int* utt_offsets, int n_utt, const evc_cd_opts* opts, void* workspace, size_t workspace_bytes,
+                 int* n_iter_out, double* violation_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
