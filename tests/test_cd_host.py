@@ -116,11 +116,14 @@ def test_restatement_reproduces_sklearn_fixture(path):
 
 
 def test_restatement_float32_is_close_to_sklearn_float64():
-    d = np.load(os.path.join(GOLDEN, "cdnmf_m201_n128_t40_f32.npz"))
-    H, n_iter, _ = cd_solve(d["X_rows"], d["W_rows"], 200, float(d["tol"]), dtype=np.float32)
-    ref = d["H_f64"].T
-    assert np.linalg.norm(H - ref) / np.linalg.norm(ref) <= 1e-4
-    assert abs(n_iter - int(d["n_iter"])) <= 1
+    paths = [p for p in CD_FILES if p.endswith("_f32.npz")]
+    assert len(paths) >= 2
+    for path in paths:
+        d = np.load(path)
+        H, n_iter, _ = cd_solve(d["X_rows"], d["W_rows"], 200, float(d["tol"]), dtype=np.float32)
+        ref = d["H_f64"].T
+        assert np.linalg.norm(H - ref) / np.linalg.norm(ref) <= 1e-4, path
+        assert abs(n_iter - int(d["n_iter"])) <= 1, path
 
 
 def test_restatement_warm_start_continues_the_trajectory():
@@ -143,9 +146,11 @@ def test_generator_reproduces_the_fixtures():
     pytest.importorskip("sklearn")
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import make_golden_cd as g
-    specs = g.cases()
+    specs, geo = g.cases(), g.geometry_cases()
+    assert not set(specs) & set(geo)
+    specs.update(geo)
     assert sorted(specs) == sorted(os.path.basename(p)[:-4] for p in CD_FILES)
-    for name in ("cdnmf_m1_n48_t37", "cdnmf_m25_zero_utt", "cdnmf_m25_n64_t32_l1"):
+    for name in ("cdnmf_m1_n48_t37", "cdnmf_m25_zero_utt", "cdnmf_m25_n64_t32_l1", "cdnmf_m6_n17_t70"):
         out = g.make(name, specs[name])
         ref = np.load(os.path.join(GOLDEN, name + ".npz"))
         for k, v in out.items():

@@ -4,7 +4,8 @@
     non_negative_factorization(X=X, H=W, init="custom", update_H=False, n_components=W.shape[0],
                                beta_loss="frobenius", solver='cd', tol=tol, max_iter=200)
 
-run by the installed scikit-learn (1.7.2) on inputs of the existing fixtures.  Writes tests/golden/cdnmf_*.npz with
+run by the installed scikit-learn (1.7.2) on inputs of the existing fixtures, and on seeded synthetic inputs at
+the lane geometries of k_cd_sweep.  Writes tests/golden/cdnmf_*.npz with
 X_rows, W_rows, H (N x T, float64 unless noted), n_iter, tol, max_iter, alpha_W, l1_ratio, dtype and `violation`, the
 per-iteration violation trace (recorded by wrapping _update_coordinate_descent here, nowhere else).  float32 cases
 also store H_f64 / n_iter_f64 (the same call in float64).  The prefix `cdnmf_` keeps these out of the globs of the
@@ -49,6 +50,16 @@ def _load(name):
     return np.array(d["X_rows"], dtype=np.float64), np.array(d["W_rows"], dtype=np.float64)
 
 
+def _synth(M, N, T, seed):
+    """seeded synthetic inputs: squared uniform exemplars with rows 1, 8, 15 ... zero, 30 % active activations,
+    1/20 noise"""
+    rng = np.random.default_rng(seed)
+    W = rng.random((N, M)) ** 2 + 0.05
+    W[1::7] = 0.0
+    X = (rng.random((T, N)) * (rng.random((T, N)) < 0.3)) @ W + 0.05 * rng.random((T, M))
+    return X, W
+
+
 def cases():
     """name -> (X_rows, W_rows, tol, alpha_W, l1_ratio, dtype)"""
     c = {}
@@ -74,6 +85,18 @@ def cases():
     return c
 
 
+def geometry_cases():
+    """name -> (X_rows, W_rows, tol, alpha_W, l1_ratio, dtype) on seeded synthetic inputs: the lane geometries of
+    k_cd_sweep (L lanes per frame, F = 64 / L frames per tile) with N % 16 != 0"""
+    c = {}
+    c["cdnmf_m6_n17_t70"] = _synth(6, 17, 70, 6) + (1e-4, 0.0, 0.0, np.float64)             # L 1, MPL 8, 64 + 6
+    c["cdnmf_m40_n100_t50"] = _synth(40, 100, 50, 40) + (1e-4, 0.0, 0.0, np.float64)        # L 4
+    c["cdnmf_m100_n47_t20_f32"] = _synth(100, 47, 20, 100) + (1e-4, 0.0, 0.0, np.float32)   # L 8
+    c["cdnmf_m257_n33_t9_l1l2"] = _synth(257, 33, 9, 257) + (1e-4, 0.05, 0.5, np.float64)   # L 32
+    c["cdnmf_m1024_n15_t3"] = _synth(1024, 15, 3, 1024) + (1e-4, 0.0, 0.0, np.float64)      # L 64, N < 16
+    return c
+
+
 def make(name, spec):
     X, W, tol, alpha_W, l1_ratio, dt = spec
     Xd, Wd = X.astype(dt), W.astype(dt)
@@ -89,7 +112,7 @@ def make(name, spec):
 def main():
     check = "--check" in sys.argv
     bad = 0
-    for name, spec in cases().items():
+    for name, spec in {**cases(), **geometry_cases()}.items():
         out = make(name, spec)
         path = os.path.join(GOLDEN, name + ".npz")
         if check:
