@@ -65,6 +65,42 @@ constexpr unsigned ALL_POLL_LIMIT = 1u << 17;
 #define EVC_ALL_C1_ALTERNATE 0
 #endif
 
+// Round 5: the member's dictionary in LDS.  Both halves of a workgroup are the same member and read the same 32 exemplar
+// tiles in every step, for the whole launch; streamed from L2 (8 x 16-byte loads per unit and wavefront) the fragments
+// queue in the CU's memory pipe in front of the exchange's stores and polls.  Where it fits, one copy is filled once per
+// launch from A2p and both operand orders are read from it with ds_read_b64 - no vector-memory instruction in the sweep.
+//
+// Layout (doubles): slot w * AKT + k holds tile w + AW k of the member (a wavefront's 8 tiles lie within 64 KiB: the tile
+// and the k-step ride in the instruction's immediate), 16 rows of PR per tile, row rho(e) holding exemplar e of the tile,
+// bins 0 .. M-1 then zeros.  PR = 2 mod 4 and rho(4q + r) = 4 sigma(q) + r (sigma swaps 1 and 2) make both read patterns
+// conflict-free (ds_read_b64: two groups of 32 lanes, bank = dword address mod 64):
+//   D and P  (lane: exemplar 4 (l&3) + (l&15)/4 as in A1p, bin = k-step base + l/16): the 16 row starts of a tile are
+//            distinct even numbers mod 32, the two bins of a 32-lane group add 0 or 1;
+//   V'       (lane: bin l&15, exemplar 4 (l/16) + r): the rows of lane groups q and q + 1 start 16 apart mod 32.
+// Bins past M (the last k-step's upper lane groups, the last bin tile's upper lanes) read the zero slot M of their own row
+// (PR > M): same address within a row, a broadcast.  The values equal A1p's and A2p's: the MFMAs see the same operands.
+constexpr long ALL_LDS_BUDGET = 160 * 1024 - 256;      // static LDS of one workgroup, with room for alignment
+__host__ __device__ constexpr int all_dict_row(int e) { return 4 * (((e >> 2) & 1) * 2 + (e >> 3)) + (e & 3); }
+template <int MSTEPS, int C, bool KL>
+struct AllShape {
+    static constexpr int MT = MSTEPS > 4 ? 2 : 1;
+    static constexpr int E = MT * 4 * 64;          // stride of one V image (accumulator order)
+    static constexpr int NE = MSTEPS * 64;         // elements of V actually used
+    static constexpr int RSTR = NE < 256 ? 256 : NE;   // stride of a wavefront's partial V' (exchange threads read th < 256)
+    // reduce-scatter staging: whole slices hold NE words, ragged ones at most C x ceil(NE / C) <= NE + C - 1
+    static constexpr int STG = C > 0 ? 1 : (C == 0 ? NE : NE + ALL_MAX_MEMBERS - 1);
+    static constexpr long REST = 8L * 2 * (AW * RSTR + 2 * E + (KL ? E : 1) + STG) + 3 * 4;
+    static constexpr long dict_bytes(int pr) { return 8L * ATILES * 16 * pr; }
+    // M of these k-steps is 4 MSTEPS - 3 .. 4 MSTEPS; the widest row pitch that fits serves M <= PR - 1
+    static constexpr int PR_ALL = 4 * MSTEPS + 2;
+    static constexpr int PR = KL ? 0
+                              : REST + dict_bytes(PR_ALL) <= ALL_LDS_BUDGET       ? PR_ALL
+                              : REST + dict_bytes(PR_ALL - 4) <= ALL_LDS_BUDGET   ? PR_ALL - 4
+                                                                                  : 0;
+    // (one member - N = 512, no exchange, both halves sweep at once: measured 1.2 % slower from LDS, C1 A/B - it streams)
+    static constexpr bool LDS_DICT = C != 1 && PR > 0 && PR - 1 >= 4 * MSTEPS - 3;
+};
+
 #ifdef EVC_ALL_TIMING   // diagnostic build only (tools/ubench/fused_all_bench.hip); no stamp executes in the library
 #define EVC_STAMP(i)                                                                                             \
     do {                                                                                                         \
@@ -80,15 +116,20 @@ constexpr unsigned ALL_POLL_LIMIT = 1u << 17;
 // h <- h * (A~_j^T R) - no numerator tiles, no division in the sweep - and R is formed where V is combined.
 template <int MSTEPS, int C, bool KL>
 __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
-    constexpr int MT = MSTEPS > 4 ? 2 : 1;
-    constexpr int E = MT * 4 * 64;               // stride of one V image (accumulator order)
-    constexpr int NE = MSTEPS * 64;              // elements of V actually used
+    using S = AllShape<MSTEPS, C, KL>;
+    constexpr int MT = S::MT;
+    constexpr int E = S::E;
+    constexpr int NE = S::NE;
+    constexpr int RSTR = S::RSTR;
     constexpr int MSP = (MSTEPS + 1) & ~1;       // k-steps padded to pairs in A1p
-    __shared__ double s_red[2][AW * E];          // partial V' of every wavefront, per half
+    constexpr int PR = S::PR;                    // LDS dictionary: row pitch (doubles)
+    constexpr int TPD = 16 * PR;                 // LDS dictionary: doubles per tile
+    __shared__ double s_red[2][AW * RSTR];       // partial V' of every wavefront, per half
     __shared__ double s_v[2][E];                 // V, B-operand order
     __shared__ double s_x[2][E];                 // X, B-operand order
     __shared__ double s_r[2][KL ? E : 1];        // KL: X / max(V, eps), B-operand order
-    __shared__ double s_stage[2][C > 0 ? 1 : 768];   // reduce-scatter staging (more than 8 members only)
+    __shared__ double s_stage[2][S::STG];        // reduce-scatter staging (more than 8 members only)
+    __shared__ double s_dict[S::LDS_DICT ? ATILES * TPD : 1];   // the member's dictionary (see AllShape)
     __shared__ unsigned s_hb[2];                 // arrivals of a half's wavefronts at its LDS barrier
     __shared__ int s_fail;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -124,7 +165,28 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
     bool nofrag_go = false;
 #endif
     const unsigned ul16 = ul * 16u, ul8 = ul * 8u;
-    auto load_a1 = [&](double (&a1)[MSTEPS], int k) {
+    // LDS dictionary (S::LDS_DICT and M < PR): this lane's element of every fragment is one immediate away from one of
+    // four addresses - D/P order, its last k-step, V' order, its last bin tile (bins past M: the row's zero slot M)
+    constexpr int BL = 16 * ((MSTEPS - 1) >> 2) + 4 * ((MSTEPS - 1) & 3);     // first bin of the last k-step
+    const int rowA = w * AKT * TPD + all_dict_row(4 * (lane & 3) + ((lane & 15) >> 2)) * PR;
+    const int rowB = w * AKT * TPD + all_dict_row(4 * (lane >> 4)) * PR;
+    const double* const dA = s_dict + rowA + (lane >> 4);
+    const double* const dAL = s_dict + rowA + min(lane >> 4, a.M - BL);
+    const double* const dB = s_dict + rowB + (lane & 15);
+    const double* const dBL = s_dict + rowB + min(lane & 15, a.M - 16 * (MT - 1));
+    // `lds`: std::true_type - fragments from s_dict, std::false_type - buffer loads from A1p / A2p.  (The compiler would
+    // pair reads off one address into ds_read2_b64: 8 LDS cycles for 16-lane groups, where this layout is 2-way
+    // conflicted, against 2 x 2 for two ds_read_b64 - an empty asm with a memory clobber between the reads keeps them apart.)
+#define LDS_NO_PAIR() asm volatile("" ::: "memory")
+    auto load_a1 = [&](double (&a1)[MSTEPS], int k, auto lds) {
+        if constexpr (decltype(lds)::value) {
+#pragma unroll
+            for (int s = 0; s < MSTEPS; ++s) {
+                a1[s] = (s == MSTEPS - 1 ? dAL : dA)[k * TPD + 16 * (s >> 2) + 4 * (s & 3)];
+                LDS_NO_PAIR();
+            }
+            return;
+        }
 #ifdef EVC_ALL_NOFRAG    // diagnostic (tools/ubench): no fragment traffic after the numerator pass (wrong results, timing only)
         if (nofrag_go) return;
 #endif
@@ -140,7 +202,17 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
             }
         }
     };
-    auto load_a2 = [&](double (&a2)[MT][4], int k) {
+    auto load_a2 = [&](double (&a2)[MT][4], int k, auto lds) {
+        if constexpr (decltype(lds)::value) {
+#pragma unroll
+            for (int u = 0; u < MT; ++u)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    a2[u][r] = (u == MT - 1 ? dBL : dB)[k * TPD + r * PR + 16 * u];
+                    LDS_NO_PAIR();
+                }
+            return;
+        }
 #ifdef EVC_ALL_NOFRAG
         if (nofrag_go) return;
 #endif
@@ -196,6 +268,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
         while (__builtin_amdgcn_s_memtime() - t0 < a.stagger_cycles) __builtin_amdgcn_s_sleep(32);
     }
 
+    auto run = [&](auto lds) __attribute__((always_inline)) {
     for (long tt0 = g - half; tt0 < a.TT; tt0 += a.groups) {     // half 0's tile decides (it has the lower index)
         const long tt = tt0 + half;
         bool valid;
@@ -254,18 +327,18 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
             double x[MSTEPS];
 #pragma unroll
             for (int s = 0; s < MSTEPS; ++s) x[s] = xL[s * 64 + lane];
-            load_a1(a1, 0);
+            load_a1(a1, 0, lds);
 #pragma unroll
             for (int k = 0; k < AKT; ++k) {
                 f64x4 acc = {0, 0, 0, 0};
 #pragma unroll
                 for (int s = 0; s < MSTEPS; ++s) acc = Mma<double>::mma(a1[s], x[s], acc);
-                load_a1(a1, (k + 1) % AKT);
+                if (!decltype(lds)::value || k + 1 < AKT) load_a1(a1, (k + 1) % AKT, lds);
                 p[k] = acc;
             }
         }
 
-        if (valid && KL) load_a1(a1, 0);         // (the numerator pass, which otherwise leaves them, is skipped)
+        if (valid && KL) load_a1(a1, 0, lds);         // (the numerator pass, which otherwise leaves them, is skipped)
         for (int step = 0; step <= 2 * a.iters; ++step) {
 #ifdef EVC_ALL_NOFRAG
             nofrag_go = step > 2;
@@ -280,17 +353,21 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 double v[MSTEPS];
 #pragma unroll
                 for (int s = 0; s < MSTEPS; ++s) v[s] = KL ? rL[s * 64 + lane] : vL[s * 64 + lane];
+                // (from LDS the first unit's fragments come at the start of the sweep: held across the exchange step
+                // instead, they cost 14 registers there, and the compiler spilled around the sweep)
+                if constexpr (decltype(lds)::value) load_a1(a1, 0, lds);
                 f64x4 vn[MT];
 #pragma unroll
                 for (int u = 0; u < MT; ++u) vn[u] = f64x4{0, 0, 0, 0};
 #pragma unroll
                 for (int k = 0; k < AKT; ++k) {
                     __builtin_amdgcn_sched_barrier(0);
-                    load_a2(a2, k);
+                    load_a2(a2, k, lds);
                     f64x4 d = KL ? f64x4{0, 0, 0, 0} : dinit;
 #pragma unroll
                     for (int s = 0; s < MSTEPS; ++s) d = Mma<double>::mma(a1[s], v[s], d);
-                    load_a1(a1, (k + 1) % AKT);      // the next unit's (or the next sweep's first) fragments
+                    if (!decltype(lds)::value || k + 1 < AKT)
+                        load_a1(a1, (k + 1) % AKT, lds);  // the next unit's (streamed: or the next sweep's first) fragments
                     __builtin_amdgcn_sched_barrier(0);
                     if (KL) {
 #pragma unroll
@@ -307,7 +384,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 for (int u = 0; u < MT; ++u)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        if (u * 4 + r < MSTEPS) red[w * E + (u * 4 + r) * 64 + lane] = vn[u][r];
+                        if (u * 4 + r < MSTEPS) red[w * RSTR + (u * 4 + r) * 64 + lane] = vn[u][r];
             } else if (valid && !mine && step > 0) {
                 // ---------------- exchange: V' = sum over wavefronts and members, no barrier inside
                 // (run-time member counts with M <= 12: fewer elements than threads - several threads carry one element, word
@@ -324,8 +401,8 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 double s0 = 0.0, s1 = 0.0;
 #pragma unroll
                 for (int ww = 0; ww < AW; ++ww) {
-                    s0 += red[ww * E + e0];
-                    s1 += red[ww * E + (has1 ? e1 : e0)];
+                    s0 += red[ww * RSTR + e0];
+                    s1 += red[ww * RSTR + (has1 ? e1 : e0)];
                 }
                 if (C < 0) {
                     // ---- any member count without a template of its own (3, 5, 6, 7, 9 ... : N up to 32 x 512 x ...):
@@ -593,6 +670,23 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
         }
         __syncthreads();                         // xL / vL are rewritten for the next frame tile
     }
+    };
+
+    if constexpr (S::LDS_DICT) {
+        if (a.M > 0 && a.M < PR) {
+            // the member's 32 tiles from A2p (A2p[j][u][r/2][l][r&1] = A[16 u + (l&15)][16 j + 4 (l>>4) + r]), once per launch
+            for (int x = tid; x < ATILES * TPD; x += ATHREADS) {
+                const int slot = x / TPD, e = all_dict_row((x / PR) % 16), b = x % PR;   // (all_dict_row is an involution)
+                const long j = (long)member * ATILES + slot / AKT + AW * (slot % AKT);
+                const int q = e >> 2, r = e & 3;
+                s_dict[x] = b < a.M ? A2p[((j * MT + (b >> 4)) * 2 + (r >> 1)) * 128 + (16 * q + (b & 15)) * 2 + (r & 1)] : 0.0;
+            }
+            __syncthreads();
+            run(std::true_type{});
+            return;
+        }
+    }
+    run(std::false_type{});
 }
 
 template <int MSTEPS, int C, bool KL>
@@ -633,14 +727,17 @@ static hipError_t pick_c(const FusedArgs& a, int n_cus, hipStream_t s) {
         case 1: return launch_all<MSTEPS, 1, KL>(a, n_cus, s);
         case 2: return launch_all<MSTEPS, 2, KL>(a, n_cus, s);
         case 4: return launch_all<MSTEPS, 4, KL>(a, n_cus, s);
-        // 8 members: the direct exchange (every member fetches all 8 partials: 296 GB of fabric traffic per C2 launch)
-        // and the reduce-scatter (37 GB) run equally fast - 953 vs 958 k frames/s at C2, 537 vs 538 k for one
-        // utterance - so the leaner one serves.  (Below 7 members its 4 lanes per element do not cover a slice.)
-#ifdef EVC_ALL_DIRECT8   // diagnostic (tools/ubench): the direct all-to-all at 8 members (one hand-off, 8 x the fetched bytes)
-        case 8: return launch_all<MSTEPS, 8, KL>(a, n_cus, s);
-#else
+        // 8 members.  With the fragments streamed from L2 the direct exchange (every member fetches all 8 partials: 296 GB
+        // of fabric traffic per C2 launch) and the reduce-scatter (37 GB) ran equally fast - 953 vs 958 k frames/s at C2 -
+        // so the leaner one served.  With the dictionary in LDS (round 5) the sweep no longer queues fragment loads in
+        // front of the exchange's, and the direct form's single hand-off makes the shorter step: C2 1.099 M frames/s
+        // against 1.050 M for the reduce-scatter and 1.058 M before.  Shapes whose dictionary does not
+        // fit (M 26 .. 28) keep the reduce-scatter of the streamed kernel.  (Below 7 members the reduce-scatter's 4 lanes
+        // per element do not cover a slice.)
         case 8:
-#endif
+            if constexpr (AllShape<MSTEPS, 8, KL>::LDS_DICT)
+                if (a.M > 0 && a.M < AllShape<MSTEPS, 8, KL>::PR) return launch_all<MSTEPS, 8, KL>(a, n_cus, s);
+            return launch_all<MSTEPS, 0, KL>(a, n_cus, s);
         case 16:
         case 32:
         case 64: return launch_all<MSTEPS, 0, KL>(a, n_cus, s);    // run-time members, reduce-scatter, whole slices
