@@ -5,6 +5,7 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 
 using namespace evc;
 
@@ -68,14 +69,26 @@ template <typename T> struct DictArrays {
     float* Aw;
     double* Aw64;
 };
-template <typename T> DictPlan dict_plan(int M, int Mb, int N, int loss, bool prepared) {
+int algo_eff(int algo) { return algo == EVC_ALGO_AUTO ? EVC_ALGO_FACTORED : algo; }
+// Which kernels a (M, N, T) problem of one dtype can be routed to.  plan_route, the workspace and dictionary size queries
+// and the prepared images all ask these two, so that a new route family is added here and in plan_route only.
+// The float64 fused kernels (M <= 32); float32 callers ride them through a staging copy (solve_f32_on_f64).
+bool small_family(int M, int N, int T_, int algo) { return algo == EVC_ALGO_FACTORED && fused_supported(M, N, T_, EVC_F64); }
+// the task-queue kernels: k_fused_wide (float32), k_fused_wide64 (float64)
+bool wide_family(int M, int N, int T_, int dtype, int algo, int loss) {
+    return dtype == EVC_F64 ? wide64_supported(M, N, T_, dtype, algo, loss) : wide_supported(M, N, T_, dtype, algo);
+}
+
+// the plan of a prepared image (arithmetic type T): every layout a later solve of any size may be routed to
+template <typename T> DictPlan dict_plan(int M, int Mb, int N, int loss) {
+    const int dt = sizeof(T) == 8 ? EVC_F64 : EVC_F32;
     DictPlan p{};
     p.kl = loss == EVC_LOSS_KL;
-    p.fused = sizeof(T) == 8 && fused_supported(M, N, 1, EVC_F64);
+    p.fused = sizeof(T) == 8 && small_family(M, N, 1, EVC_ALGO_FACTORED);
     p.packed_b = p.fused && Mb >= 1 && Mb <= 32;
-    p.wide = sizeof(T) == 4 && wide_supported(M, N, 1, EVC_F32, EVC_ALGO_FACTORED);
-    p.wide64 = sizeof(T) == 8 && wide64_supported(M, N, 1, EVC_F64, EVC_ALGO_FACTORED, loss);
-    p.bc = prepared && Mb >= 1;
+    p.wide = sizeof(T) == 4 && wide_family(M, N, 1, dt, EVC_ALGO_FACTORED, loss);
+    p.wide64 = sizeof(T) == 8 && wide_family(M, N, 1, dt, EVC_ALGO_FACTORED, loss);
+    p.bc = Mb >= 1;
     return p;
 }
 template <typename T> DictArrays<T> take_dict(Carver& c, const Dims& d, const DictPlan& p) {
@@ -120,6 +133,20 @@ template <typename T> struct Workspace {
 
 int n_slots_for(int iters, int check_every) { return 1 + (check_every > 0 ? iters / check_every : 0); }
 
+UttState take_utt(Carver& c, const Dims& d, int n_slots) {
+    UttState u;
+    u.frame_utt = c.take<int>(d.Tp);
+    u.offsets = c.take<int>(d.n_utt + 1);
+    u.active = c.take<int>(d.n_utt + 1);
+    u.n_iter = c.take<int>(d.n_utt);
+    u.err_init = c.take<double>(d.n_utt);
+    u.err_prev = c.take<double>(d.n_utt);
+    u.h0 = c.take<double>(d.n_utt);
+    u.trace = c.take<double>((size_t)d.n_utt * n_slots);
+    u.n_slots = n_slots;
+    return u;
+}
+
 template <typename T>
 Workspace<T> carve(void* base, const Dims& d, int algo, int n_slots, bool fused, const DictArrays<T>* ext = nullptr) {
     Workspace<T> w;
@@ -127,11 +154,10 @@ Workspace<T> carve(void* base, const Dims& d, int algo, int n_slots, bool fused,
     const bool gram = (algo == EVC_ALGO_GRAM || algo == EVC_ALGO_LITERAL);
     w.fused = fused;
     // the dictionary's arrays: from the prepared image, or from this workspace (then filled on every call)
-    DictPlan plan = dict_plan<T>(d.M, d.Mb, d.N, EVC_LOSS_KL, false);
+    DictPlan plan{};
+    plan.kl = true;
     plan.fused = fused;
     plan.packed_b = fused && d.Mb >= 1 && d.Mb <= 32;
-    plan.wide = false;
-    plan.wide64 = false;
     const DictArrays<T> da = ext ? *ext : take_dict<T>(c, d, plan);
     w.At = da.At;
     w.Am = da.Am;
@@ -163,7 +189,6 @@ Workspace<T> carve(void* base, const Dims& d, int algo, int n_slots, bool fused,
         w.fb.coop_buf = c.take<double>((size_t)(ALL_SLICE_OFFSET + ALL_SLICE_ELEMS));
         w.fb.coop_cnt = c.take<int>(COOP_MAX_TILES + 1);
         w.fb.rsum = da.rsum;
-        w.fb.coop_c = 1;
     }
     w.flB = FusedLayout{};
     w.Bt = nullptr; w.B1p = w.B2p = w.Yp = nullptr;
@@ -178,27 +203,16 @@ Workspace<T> carve(void* base, const Dims& d, int algo, int n_slots, bool fused,
     w.H1 = gram ? c.take<T>((size_t)d.Tp * d.Np) : nullptr;
     w.G = gram ? c.take<T>((size_t)d.Np * d.Np) : nullptr;
     w.err2 = c.take<double>(d.Tp);
-    w.u.frame_utt = c.take<int>(d.Tp);
-    w.u.offsets = c.take<int>(d.n_utt + 1);
-    w.u.active = c.take<int>(d.n_utt + 1);
-    w.u.n_iter = c.take<int>(d.n_utt);
-    w.u.err_init = c.take<double>(d.n_utt);
-    w.u.err_prev = c.take<double>(d.n_utt);
-    w.u.h0 = c.take<double>(d.n_utt);
-    w.u.trace = c.take<double>((size_t)d.n_utt * n_slots);
-    w.u.n_slots = n_slots;
+    w.u = take_utt(c, d, n_slots);
     w.bytes = (c.off + 255) & ~size_t(255);
     return w;
 }
 
-bool use_fused(int M, int N, int T_, int dtype, int algo) {
-    return algo == EVC_ALGO_FACTORED && fused_supported(M, N, T_, dtype);
-}
-
+// (expr: a hipError_t, or a status of this file - both are 0 on success)
 #define HIP_TRY(expr)                              \
     do {                                           \
-        hipError_t e__ = (expr);                   \
-        if (e__ != hipSuccess) return (int)e__;    \
+        int e__ = (int)(expr);                     \
+        if (e__) return e__;                       \
     } while (0)
 
 // The worst-case slot count is bounded by iters+1; evc_workspace_bytes has no iters argument,
@@ -238,15 +252,15 @@ int synth_rows(const T* Hc, long ldc, const SynthArgs& y, int N, int T_, bool fm
     return ST_OK;
 }
 
-// Bring the caller's dictionary into the arrays of `a` (every layout the plan names).  B may be NULL.
+// Bring the caller's dictionary into the generic arrays of `a`
 template <typename T>
-int prepare_dict(const DictArrays<T>& a, const DictPlan& p, const T* A, int lda, const T* B, int ldb, const Dims& d,
-                 bool fm, double eps, bool want_rowsum, hipStream_t s) {
+int prepare_dict(const DictArrays<T>& a, bool kl, const T* A, int lda, const Dims& d, bool fm, double eps, hipStream_t s) {
     HIP_TRY(copy2d<T>(A, lda, d.N, d.M, fm ? 0 : 1, a.At, d.Mk, d.Np, d.Mk, 0, s));
     HIP_TRY(copy2d<T>(A, lda, d.M, d.N, fm ? 1 : 0, a.Am, d.Np, d.Mj, d.Np, 0, s));
-    if (p.kl) HIP_TRY(kl_scale_dict<T>(a.At, d.Mk, d.M, d.Np, eps, a.Akl, s));
+    if (kl) HIP_TRY(kl_scale_dict<T>(a.At, d.Mk, d.M, d.Np, eps, a.Akl, s));
     return ST_OK;
 }
+// ... and into the operand fragments of the float64 fused kernels the plan names.  B may be NULL.
 int prepare_dict_fused(const DictArrays<double>& a, const DictPlan& p, const double* B, int ldb, const Dims& d, bool fm,
                        bool want_rowsum, hipStream_t s) {
     if (p.fused) {
@@ -267,133 +281,159 @@ int prepare_dict_fused(const DictArrays<double>& a, const DictPlan& p, const dou
     }
     return ST_OK;
 }
-// the arrays of a prepared dictionary (arithmetic type T); `skip`: bytes of staging in front of them
-template <typename T> DictArrays<T> dict_arrays(const evc_dict* dk, size_t skip) {
-    const Dims dd = make_dims((int)sizeof(T), dk->M, dk->N, 1, 1, dk->Mb);
-    Carver c{static_cast<char*>(dk->mem), skip};
-    return take_dict<T>(c, dd, dict_plan<T>(dk->M, dk->Mb, dk->N, dk->loss, true));
-}
-template <typename T> DictArrays<T> dict_arrays_at(void* mem, size_t skip, int M, int Mb, int N, int loss) {
-    const Dims dd = make_dims((int)sizeof(T), M, N, 1, 1, Mb);
-    Carver c{static_cast<char*>(mem), skip};
-    return take_dict<T>(c, dd, dict_plan<T>(M, Mb, N, loss, true));
-}
 // staging of a float32 dictionary that rides the float64 fused kernels: A and B widened once
 size_t dict_f64_staging(int M, int Mb, int N) {
     return ((((size_t)N * M + (size_t)N * Mb) * sizeof(double) + 512) + 255) & ~size_t(255);
 }
 
-template <typename T> size_t dict_image_bytes(int M, int Mb, int N, int loss, size_t skip) {
-    const Dims dd = make_dims((int)sizeof(T), M, N, 1, 1, Mb);
-    Carver c{nullptr, skip};
-    take_dict<T>(c, dd, dict_plan<T>(M, Mb, N, loss, true));
-    return (c.off + 255) & ~size_t(255);
+// The image of a prepared dictionary (arithmetic type T) at `mem` (NULL: sizes only); `skip`: bytes of staging in front
+// of it.  The size query, evc_dict_prepare and the solve drivers all read the image through this one description.
+template <typename T> struct DictImage {
+    Dims d;
+    DictPlan plan;
+    DictArrays<T> a;
+    size_t bytes;
+};
+template <typename T> DictImage<T> dict_image(void* mem, size_t skip, int M, int Mb, int N, int loss) {
+    DictImage<T> im;
+    im.d = make_dims((int)sizeof(T), M, N, 1, 1, Mb);
+    im.plan = dict_plan<T>(M, Mb, N, loss);
+    Carver c{static_cast<char*>(mem), skip};
+    im.a = take_dict<T>(c, im.d, im.plan);
+    im.bytes = (c.off + 255) & ~size_t(255);
+    return im;
+}
+template <typename T> DictArrays<T> dict_arrays(const evc_dict* dk, size_t skip) {
+    return dict_image<T>(dk->mem, skip, dk->M, dk->Mb, dk->N, dk->loss).a;
 }
 
 template <typename T>
 int dict_prepare_typed(const T* A, int lda, const T* B, int ldb, int M, int Mb, int N, bool fm, int loss, double eps,
-                              void* mem, size_t skip, hipStream_t s) {
-    const Dims dd = make_dims((int)sizeof(T), M, N, 1, 1, Mb);
-    const DictPlan p = dict_plan<T>(M, Mb, N, loss, true);
-    Carver c{static_cast<char*>(mem), skip};
-    const DictArrays<T> a = take_dict<T>(c, dd, p);
-    int st = prepare_dict<T>(a, p, A, lda, B, ldb, dd, fm, eps, true, s);
-    if (st) return st;
+                       void* mem, size_t skip, hipStream_t s) {
+    const DictImage<T> im = dict_image<T>(mem, skip, M, Mb, N, loss);
+    const DictArrays<T>& a = im.a;
+    HIP_TRY(prepare_dict<T>(a, im.plan.kl, A, lda, im.d, fm, eps, s));
     if (B && a.Bc) HIP_TRY(copy2d<T>(B, ldb, N, Mb, fm ? 0 : 1, a.Bc, Mb, N, Mb, 0, s));
-    if (p.wide) {
-        const WideLayout fl = wide_layout(M, N, 1, 256, 0, 0);
-        HIP_TRY(wide_pack_dict(fl, p.kl ? reinterpret_cast<const float*>(a.Akl) : reinterpret_cast<const float*>(a.At),
-                               reinterpret_cast<const float*>(a.At), dd.Mk, dd.Np, a.Aw, s));
+    if constexpr (sizeof(T) == 4) {
+        if (im.plan.wide)
+            HIP_TRY(wide_pack_dict(wide_layout(M, N, 1, 256, 0, 0), im.plan.kl ? a.Akl : a.At, a.At, im.d.Mk, im.d.Np, a.Aw, s));
+    } else {
+        if (im.plan.wide64)
+            HIP_TRY(wide_pack_dict(wide64_layout(M, N, 1, 256, 0, 0), a.At, nullptr, im.d.Mk, im.d.Np, a.Aw64, s));
+        HIP_TRY(prepare_dict_fused(a, im.plan, B, ldb, im.d, fm, true, s));
     }
-    if (p.wide64) {
-        const Wide64Layout fl = wide64_layout(M, N, 1, 256, 0, 0);
-        HIP_TRY(wide_pack_dict(fl, reinterpret_cast<const double*>(a.At), nullptr, dd.Mk, dd.Np, a.Aw64, s));
+    return ST_OK;
+}
+
+// evc_solve_opts.reserved, decoded once per attempt (by plan_route)
+struct SolveFlags {
+    bool no_fused, exact_div, no_exchange, no_all_resident, pair_tiles;
+    int c_req;           // bits 8..15: M <= 32: 1 | 2 = the general kernel; M > 32: exemplar ranges per frame group
+    int w_req;           // bits 16..19: wavefronts per workgroup (k_fused_wide), whole bin tiles per wavefront (k_fused_wide64)
+};
+SolveFlags decode_flags(int reserved, int stop_rule) {
+    SolveFlags f;
+    f.no_fused = reserved & EVC_FLAG_NO_FUSED;
+    // pymf's stop rule compares successive errors against 2.2e-16: it only fires at the reference's
+    // iteration if the update reaches the same floating-point fixed point, i.e. with correctly rounded
+    // quotients (EVC_FLAG_EXACT_DIV asks for them explicitly)
+    f.exact_div = stop_rule == EVC_STOP_PYMF || (reserved & EVC_FLAG_EXACT_DIV);
+    f.no_exchange = reserved & EVC_FLAG_NO_EXCHANGE;
+    f.no_all_resident = reserved & EVC_FLAG_NO_ALL_RESIDENT;
+    f.pair_tiles = reserved & EVC_FLAG_PAIR_TILES;
+    f.c_req = (reserved >> 8) & 0xff;
+    f.w_req = (reserved >> 16) & 0xf;
+    return f;
+}
+
+// The route of one attempt of a solve: which driver runs it and, for M <= 32, which kernel.  plan_route (below use_wide)
+// is the one place that decides it.
+enum { ROUTE_GEMM, ROUTE_FUSED, ROUTE_WIDE };
+struct Route {
+    int family;          // ROUTE_GEMM: the two contractions; ROUTE_FUSED: float64 fused kernels (M <= 32); ROUTE_WIDE:
+                         // k_fused_wide (float32) / k_fused_wide64 (float64)
+    bool staged;         // ROUTE_FUSED for a float32 caller: through the staging copy (solve_f32_on_f64)
+    int algo;            // EVC_ALGO_AUTO resolved
+    int n_cus;
+    SolveFlags flags;
+    FusedRoute fused;    // ROUTE_FUSED only
+};
+
+// tests only (evc_solve_opts.test_abort_at, 0 in production): k > 0 raises the abort flag in front of the k-th
+// launch of the iteration loop (-1: the call starts with it raised), as a timed-out wait would; the call then
+// takes the caller's retry path after a partially completed solve
+struct AbortHook {
+    int* word;           // the abort flag of this solve's exchange (NULL: nothing is exchanged, nothing to raise)
+    int fake_at;         // 0: raised from the start, k > 0: in front of launch k, -1: never
+    int launch_no;
+    AbortHook(int* w, int test_abort_at)
+        : word(w), fake_at(test_abort_at < 0 ? 0 : (test_abort_at > 0 ? test_abort_at : -1)), launch_no(0) {}
+    // clear: the flag is not known to be 0 yet
+    int begin(bool clear, hipStream_t s) {
+        if (word && (clear || fake_at == 0)) HIP_TRY(hipMemsetAsync(word, fake_at == 0 ? 1 : 0, sizeof(int), s));
+        return ST_OK;
     }
+    int before_launch(hipStream_t s) {
+        if (word && fake_at > 0 && launch_no == fake_at) HIP_TRY(hipMemsetAsync(word, 1, sizeof(int), s));
+        ++launch_no;
+        return ST_OK;
+    }
+};
+// one host round trip: did a launch of this call give up waiting for a peer workgroup?
+int read_abort(const int* word, hipStream_t s, int* aborted) {
+    *aborted = 0;
+    HIP_TRY(hipMemcpyAsync(aborted, word, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return ST_OK;
+}
+
+// utterance bookkeeping of one attempt (a redo finds the offsets in place), then - once Xt is there - the start values
+int utt_begin(const UttState& u, const int* utt_offsets, int n_utt, const Dims& d, int iters, bool redo, hipStream_t s) {
+    if (!redo) {
+        if (utt_offsets)
+            HIP_TRY(hipMemcpyAsync(u.offsets, utt_offsets, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s));
+        else
+            HIP_TRY(utt_single(u, d.T_, s));
+    }
+    HIP_TRY(utt_setup(u, n_utt, d.T_, d.Tp, iters, s));
+    return ST_OK;
+}
+template <typename T>
+int utt_start_values(const UttState& u, const T* Xt, int n_utt, const Dims& d, const evc_solve_opts& o, hipStream_t s) {
+    if (o.init_mode == EVC_INIT_SKLEARN) HIP_TRY(utt_sklearn_h0<T>(Xt, d.Mk, d.M, d.N, u, n_utt, s));
+    else if (o.init_mode == EVC_INIT_CONST) HIP_TRY(utt_const_h0(u, n_utt, o.init_value, s));
     return ST_OK;
 }
 
 // The fused persistent path (float64, M <= 32): one launch per `check_every` iterations (or a
 // single launch when no residual is requested); V is carried between launches.
-template <typename T>
-int solve_fused(const Workspace<T>& w, const Dims& d, const evc_solve_opts& o, int n_utt, hipStream_t s,
-                int* coop_used, T* H_out, int ldh, int* exported, evc_solve_info* inf) {
-    return ST_UNSUPPORTED;
-}
-// one host round trip: did a cooperative launch of this call give up waiting for a peer workgroup?
-template <typename T>
-int coop_timed_out(const Workspace<T>& w, hipStream_t s, int* aborted) {
-    *aborted = 0;
-    HIP_TRY(hipMemcpyAsync(aborted, w.fb.coop_cnt + COOP_MAX_TILES, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return ST_OK;
-}
-template <>
-int solve_fused<double>(const Workspace<double>& w, const Dims& d, const evc_solve_opts& o, int n_utt,
-                        hipStream_t s, int* coop_used, double* H_out, int ldh, int* exported, evc_solve_info* inf) {
+int solve_fused(const Workspace<double>& w, const Dims& d, const evc_solve_opts& o, const FusedRoute& r, int n_utt,
+                hipStream_t s, double* H_out, int ldh, int* exported, evc_solve_info* inf) {
     *exported = 0;
-    const int c_override = (o.reserved >> 8) & 0xff;     // 0 = automatic, 1 / 2 = general kernel
-    // pymf's stop rule compares successive errors against 2.2e-16: it only fires at the reference's
-    // iteration if the update reaches the same floating-point fixed point, i.e. with correctly rounded
-    // quotients (reserved bit 1 asks for them explicitly)
-    const int exact_div = (o.stop_rule == EVC_STOP_PYMF || (o.reserved & 2)) ? 1 : 0;
     if (!o.dict) {     // (a prepared dictionary holds the fragments already)
         DictArrays<double> da{};
         da.At = w.At; da.Akl = w.Akl; da.A1p = w.fb.A1p; da.A2p = w.fb.A2p; da.rsum = w.fb.rsum;
         DictPlan pl{};
         pl.fused = true; pl.kl = o.loss == EVC_LOSS_KL;
-        int st = prepare_dict_fused(da, pl, nullptr, 0, d, true, false, s);
-        if (st) return st;
+        HIP_TRY(prepare_dict_fused(da, pl, nullptr, 0, d, true, false, s));
     }
     HIP_TRY(fused_pack_frames(w.fl, w.fb.Xp, w.Xt, d.Mk, s));
-    // few frame tiles (one or two utterances): several workgroups share a tile and split the exemplars
-    // (k_fused_res COOP); reserved bit 2 switches it off
     FusedBuffers fb = w.fb;
-    fb.coop_c = 1;
-    fb.all_c = 0;
-    fb.xy_c = 0;
-    int dev = 0, cus = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    fb.n_cus = cus;
-    // every activation and numerator tile register-resident, NT / 32 workgroups per frame tile (k_fused_all);
-    // reserved bit 4 switches that kernel off, bit 2 every form of inter-workgroup exchange
-    if (c_override == 0 && !(o.reserved & 16)) {
-        const int c = fused_all_members(w.fl.NT, d.N, o.eps_mode, exact_div, o.loss);
-        if (c == 1 || (c > 1 && c <= cus && !(o.reserved & 4))) fb.all_c = c;
-        // two frame tiles per member, exchange inside the sweeps (k_fused_xy, round 4): measured slower than k_fused_all
-        // (profiles/r04_xy_notes.md), so only on request - reserved bit 5, EVC_FLAG_PAIR_TILES
-        const int cx = fused_xy_members(w.fl.NT, d.N, o.eps_mode, exact_div, o.loss);
-        if (cx >= 2 && cx <= 2 * cus && !(o.reserved & 4) && (o.reserved & 32)) { fb.xy_c = cx; fb.all_c = 0; }
-    }
-    if (!fb.all_c && !fb.xy_c && !(o.reserved & 4) && c_override == 0 && fused_res_supported(d.N, o.eps_mode, exact_div))
-        fb.coop_c = fused_res_coop_factor(w.fl.NT, w.fl.TT, cus);
     // start values: caller-given ones were imported by the caller of this function; constants are either written
     // into the packed tiles here, or - first launch on k_fused_all, no residual wanted at init - formed by that kernel
-    fb.init_const = 0;
-    if (o.init_mode != EVC_INIT_GIVEN) {
-        if ((fb.all_c >= 1 || fb.xy_c >= 2) && o.iters > 0 && !(o.check_every > 0 && o.stop_rule == EVC_STOP_SKLEARN)) {
-            if (!o.dict) HIP_TRY(fused_rowsum(w.At, d.Mk, d.M, d.N, fb.rsum, s));
-            fb.init_const = 1;
-        } else {
-            HIP_TRY(fused_fill_h(w.fl, fb.Hp, d.N, d.T_, w.u, s));
-        }
+    if (r.init_const) {
+        if (!o.dict) HIP_TRY(fused_rowsum(w.At, d.Mk, d.M, d.N, fb.rsum, s));
+    } else if (o.init_mode != EVC_INIT_GIVEN) {
+        HIP_TRY(fused_fill_h(w.fl, fb.Hp, d.N, d.T_, w.u, s));
     }
-    const bool exchanges = fb.coop_c > 1 || fb.all_c > 1 || fb.xy_c > 1;
-    inf->kernel = fb.xy_c >= 2 ? EVC_KERNEL_FUSED_XY : fb.all_c >= 1 ? EVC_KERNEL_FUSED_ALL
-                  : ((c_override == 0 && fused_res_supported(d.N, o.eps_mode, exact_div)) ? EVC_KERNEL_FUSED_RES
-                                                                                          : EVC_KERNEL_FUSED_MU);
-    inf->members = fb.xy_c >= 2 ? fb.xy_c : fb.all_c >= 1 ? fb.all_c : fb.coop_c;
-    inf->exchange = exchanges ? 1 : 0;
-    int* coop_abort = fb.coop_cnt + COOP_MAX_TILES;
-    // tests only (evc_solve_opts.test_abort_at, 0 in production): k > 0 raises the abort flag in front of the k-th
-    // launch of the iteration loop (-1: the call starts with it raised), as a timed-out wait would; the call then
-    // takes the caller's retry path after a partially completed solve
-    const int fake_at = o.test_abort_at < 0 ? 0 : (o.test_abort_at > 0 ? o.test_abort_at : -1);
-    if (exchanges) HIP_TRY(hipMemsetAsync(coop_abort, fake_at == 0 ? 1 : 0, sizeof(int), s));
-    int first = 1, launch_no = 0;
+    inf->kernel = r.kernel;
+    inf->members = r.members;
+    inf->exchange = r.members > 1 ? 1 : 0;         // then the caller checks the abort flag (one host round trip)
+    AbortHook hook(r.members > 1 ? fb.coop_cnt + COOP_MAX_TILES : nullptr, o.test_abort_at);
+    HIP_TRY(hook.begin(true, s));
+    int first = 1;
     if (o.check_every > 0 && o.stop_rule == EVC_STOP_SKLEARN) {   // error_at_init
-        HIP_TRY(fused_iterate(w.fl, fb, w.u, d.N, d.T_, 0, 1, 1, w.err2, o.eps_mode, o.eps, o.l1,
-                              c_override, 1, o.loss, exact_div, s));
+        HIP_TRY(fused_iterate(w.fl, fb, r, w.u, d.N, d.T_, 0, 1, 1, w.err2, o.eps_mode, o.eps, o.l1, 1, o.loss, s));
         HIP_TRY(utt_check(w.err2, w.u, n_utt, 0, o.check_every, o.stop_rule, o.tol, s));
         first = 0;
     }
@@ -404,15 +444,14 @@ int solve_fused<double>(const Workspace<double>& w, const Dims& d, const evc_sol
         bool check = false;
         if (o.check_every > 0 && n >= o.check_every) { n = o.check_every; check = true; }
         // the last launch of a solve in which nothing can stop writes the caller's H itself (k_fused_all)
-        if (H_out && (fb.all_c >= 1 || fb.xy_c >= 2) && c_override == 0 && o.stop_rule == EVC_STOP_NONE && done + n == o.iters) {
+        if (H_out && r.direct_export && done + n == o.iters) {
             fb.Hx = H_out; fb.ldhx = ldh; fb.hx_frame_major = o.layout == EVC_FRAME_MAJOR ? 1 : 0;
             *exported = 1;
         }
-        if (exchanges && fake_at > 0 && launch_no == fake_at) HIP_TRY(hipMemsetAsync(coop_abort, 1, sizeof(int), s));
-        ++launch_no;
+        HIP_TRY(hook.before_launch(s));
         ++inf->launches;
-        HIP_TRY(fused_iterate(w.fl, fb, w.u, d.N, d.T_, n, first, check ? 1 : 0, w.err2, o.eps_mode,
-                              o.eps, o.l1, c_override, o.stop_rule == EVC_STOP_NONE ? 1 : 0, o.loss, exact_div, s));
+        HIP_TRY(fused_iterate(w.fl, fb, r, w.u, d.N, d.T_, n, first, check ? 1 : 0, w.err2, o.eps_mode, o.eps, o.l1,
+                              o.stop_rule == EVC_STOP_NONE ? 1 : 0, o.loss, s));
         first = 0;
         done += n;
         if (check)
@@ -420,19 +459,12 @@ int solve_fused<double>(const Workspace<double>& w, const Dims& d, const evc_sol
                               o.tol, s));
     }
     if (o.ev_loop_stop) HIP_TRY(hipEventRecord((hipEvent_t)o.ev_loop_stop, s));
-    *coop_used = exchanges ? 1 : 0;         // the caller checks the abort flag (one host round trip)
     return ST_OK;
 }
 
 // tail of the fused path: H out of the packed tiles, Y from them
-template <typename T>
-int finish_fused(const Workspace<T>& w, const Dims& d, const evc_solve_opts& o, T* H, int ldh,
+int finish_fused(const Workspace<double>& w, const Dims& d, const evc_solve_opts& o, double* H, int ldh,
                  const SynthArgs* y, hipStream_t s) {
-    return ST_UNSUPPORTED;
-}
-template <>
-int finish_fused<double>(const Workspace<double>& w, const Dims& d, const evc_solve_opts& o, double* H, int ldh,
-                         const SynthArgs* y, hipStream_t s) {
     const bool fm = (o.layout == EVC_FRAME_MAJOR);
     if (H) HIP_TRY(fused_export_h(w.fl, w.fb.Hp, H, ldh, fm ? 1 : 0, d.T_, d.N, s));
     if (!y) return ST_OK;
@@ -510,15 +542,7 @@ WideWs<T> carve_wide(void* base, const Dims& d, int n_slots, int n_cus, bool wit
     w.fb.Vsum = c.take<T>(w.caps.vsum);
     w.fb.ctl = c.take<unsigned>(w.caps.ctl);
     w.err2 = c.take<double>(d.Tp);
-    w.u.frame_utt = c.take<int>(d.Tp);
-    w.u.offsets = c.take<int>(d.n_utt + 1);
-    w.u.active = c.take<int>(d.n_utt + 1);
-    w.u.n_iter = c.take<int>(d.n_utt);
-    w.u.err_init = c.take<double>(d.n_utt);
-    w.u.err_prev = c.take<double>(d.n_utt);
-    w.u.h0 = c.take<double>(d.n_utt);
-    w.u.trace = c.take<double>((size_t)d.n_utt * n_slots);
-    w.u.n_slots = n_slots;
+    w.u = take_utt(c, d, n_slots);
     if constexpr (sizeof(T) == 4) {
         // k_fused_wide, several stop checks per launch: up to 4 snapshots of the activations (5 checks per launch), as
         // many as fit in 2 GiB (a 16-utterance STFT batch: 180 MB each)
@@ -551,12 +575,12 @@ WideWs<T> carve_wide(void* base, const Dims& d, int n_slots, int n_cus, bool wit
 //    (12 - 32 utterances: 0.51 - 0.52 / 0.40 - 0.47); M <= 176 pads more than a thirteenth of the tile slots and stays out
 //    (M = 160: 0.42).
 // The tuning bits (ranges, wavefronts / bin tiles) force the fused kernel at any size.
-bool use_wide(int M, int N, int T_, int dtype, int algo, int loss, int reserved) {
-    if (reserved & EVC_FLAG_NO_FUSED) return false;
+bool use_wide(int M, int N, int T_, int dtype, int algo, int loss, const SolveFlags& f) {
+    if (f.no_fused) return false;
     // the task queues hand partial sums from workgroup to workgroup inside a launch and the call reads one word back at
     // the end (a wait that ran out): exactly what EVC_FLAG_NO_EXCHANGE rules out
-    if (reserved & EVC_FLAG_NO_EXCHANGE) return false;
-    const bool forced = ((reserved >> 8) & 0xff) != 0 || ((reserved >> 16) & 0xf) != 0;
+    if (f.no_exchange) return false;
+    const bool forced = f.c_req != 0 || f.w_req != 0;
     const int tiles = (T_ + 15) / 16;
     if (dtype == EVC_F64) {
         if (!wide64_supported(M, N, T_, dtype, algo, loss)) return false;
@@ -577,30 +601,73 @@ bool use_wide(int M, int N, int T_, int dtype, int algo, int loss, int reserved)
     return tiles >= 43;
 }
 
+// The one place a route is decided (and a new one added): pure host arithmetic on the call's sizes and options.
+// The families are disjoint in M (fused: M <= 32; k_fused_wide: 32 < M <= 208, float32; k_fused_wide64: 144 < M <= 528,
+// float64), so the order of the questions does not matter.
+Route plan_route(int M, int N, int T_, int dtype, const evc_solve_opts& o, int n_cus) {
+    Route r{};
+    r.algo = algo_eff(o.algo);
+    r.n_cus = n_cus;
+    const SolveFlags& f = r.flags = decode_flags(o.reserved, o.stop_rule);
+    r.family = ROUTE_GEMM;
+    if (!f.no_fused && small_family(M, N, T_, r.algo)) r.family = ROUTE_FUSED;
+    else if (use_wide(M, N, T_, dtype, r.algo, o.loss, f)) r.family = ROUTE_WIDE;
+    if (r.family != ROUTE_FUSED) return r;
+    r.staged = dtype == EVC_F32;
+    FusedRoute& k = r.fused;
+    k.kernel = EVC_KERNEL_FUSED_MU;
+    k.members = 1;
+    k.c_req = f.c_req;
+    k.exact_div = f.exact_div ? 1 : 0;
+    k.n_cus = n_cus;
+    const FusedLayout fl = fused_layout(M, N, T_);
+    // every activation and numerator tile register-resident, NT / 32 workgroups per frame tile (k_fused_all);
+    // EVC_FLAG_NO_ALL_RESIDENT switches that kernel off, EVC_FLAG_NO_EXCHANGE every form of inter-workgroup exchange
+    if (f.c_req == 0 && !f.no_all_resident) {
+        const int c = fused_all_members(fl.NT, N, o.eps_mode, k.exact_div, o.loss);
+        if (c == 1 || (c > 1 && c <= n_cus && !f.no_exchange)) { k.kernel = EVC_KERNEL_FUSED_ALL; k.members = c; }
+        // two frame tiles per member, exchange inside the sweeps (k_fused_xy, round 4): measured slower than k_fused_all
+        // (profiles/r04_xy_notes.md), so only on request - EVC_FLAG_PAIR_TILES
+        const int cx = fused_xy_members(fl.NT, N, o.eps_mode, k.exact_div, o.loss);
+        if (cx >= 2 && cx <= 2 * n_cus && !f.no_exchange && f.pair_tiles) { k.kernel = EVC_KERNEL_FUSED_XY; k.members = cx; }
+    }
+    if (f.c_req == 0 && k.kernel == EVC_KERNEL_FUSED_MU && fused_res_supported(N, o.eps_mode, k.exact_div)) {
+        k.kernel = EVC_KERNEL_FUSED_RES;
+        // few frame tiles (one or two utterances): several workgroups share a tile and split the exemplars
+        // (k_fused_res COOP); EVC_FLAG_NO_EXCHANGE switches it off
+        if (!f.no_exchange) k.members = fused_res_coop_factor(fl.NT, fl.TT, n_cus);
+    }
+    const bool all_res = k.kernel == EVC_KERNEL_FUSED_ALL || k.kernel == EVC_KERNEL_FUSED_XY;
+    // constant start values: the first launch on k_fused_all forms them itself when no residual is wanted at init
+    k.init_const = o.init_mode != EVC_INIT_GIVEN && all_res && o.iters > 0 &&
+                   !(o.check_every > 0 && o.stop_rule == EVC_STOP_SKLEARN);
+    k.direct_export = all_res && o.stop_rule == EVC_STOP_NONE;
+    return r;
+}
+
 template <typename T>
-int solve_wide(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_,
-               const int* utt_offsets, int n_utt, const evc_solve_opts& o, void* ws, size_t ws_bytes,
+int solve_wide(const void* A_, int lda, const void* X_, int ldx, void* H_, int ldh, int M, int N, int T_,
+               const int* utt_offsets, int n_utt, const evc_solve_opts& o, const Route& r, void* ws, size_t ws_bytes,
                int* n_iter_out, double* err_out, const SynthArgs* y, hipStream_t s, evc_solve_info* inf) {
     typedef WideKind<T> K;
+    const T* A = static_cast<const T*>(A_);
+    const T* X = static_cast<const T*>(X_);
+    T* H = static_cast<T*>(H_);
     const Dims d = make_dims((int)sizeof(T), M, N, T_, n_utt, y ? y->Mb : 0);
     const int n_slots = n_slots_for(o.iters, o.check_every);
     if (n_slots > MAX_SLOTS) return ST_UNSUPPORTED;
-    const int n_cus = device_cus();
+    const int n_cus = r.n_cus;
     const bool kl = o.loss == EVC_LOSS_KL, fm = o.layout == EVC_FRAME_MAJOR;
     WideWs<T> w = carve_wide<T>(ws, d, MAX_SLOTS, n_cus, true, sizeof(T) == 4);
     if (w.bytes > ws_bytes) return ST_WORKSPACE;
     w.u.n_slots = n_slots;
-    // tuning / tests: reserved bits 8..15 = exemplar ranges per frame group, bits 16..19 = wavefronts per workgroup
-    const typename K::Layout fl = K::layout(M, N, T_, n_cus, (o.reserved >> 8) & 0xff, (o.reserved >> 16) & 0xf);
+    // tuning / tests: exemplar ranges per frame group, wavefronts per workgroup
+    const typename K::Layout fl = K::layout(M, N, T_, n_cus, r.flags.c_req, r.flags.w_req);
     // (a prepared dictionary holds the block images of the DEFAULT layout: a tuning override of the wavefront / tile
     // count does not fit it - unsupported, not a workspace problem)
-    if (!wide_fits(fl, w.caps)) return (o.dict && ((o.reserved >> 16) & 0xf)) ? ST_UNSUPPORTED : ST_WORKSPACE;
+    if (!wide_fits(fl, w.caps)) return (o.dict && r.flags.w_req) ? ST_UNSUPPORTED : ST_WORKSPACE;
 
-    if (utt_offsets)
-        HIP_TRY(hipMemcpyAsync(w.u.offsets, utt_offsets, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s));
-    else
-        HIP_TRY(utt_single(w.u, T_, s));
-    HIP_TRY(utt_setup(w.u, n_utt, T_, d.Tp, o.iters, s));
+    HIP_TRY(utt_begin(w.u, utt_offsets, n_utt, d, o.iters, false, s));
     SynthArgs ydict;
     if (o.dict) {                 // the block images (and B) come from the prepared dictionary
         const DictArrays<T> ext = dict_arrays<T>(o.dict, 0);
@@ -617,27 +684,22 @@ int solve_wide(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
         HIP_TRY(wide_pack_dict(fl, kl ? w.Akl : w.At, w.At, d.Mk, d.Np, w.fb.Aw, s));
     }
     HIP_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
-    if (o.init_mode == EVC_INIT_SKLEARN) HIP_TRY(utt_sklearn_h0<T>(w.Xt, d.Mk, M, N, w.u, n_utt, s));
-    else if (o.init_mode == EVC_INIT_CONST) HIP_TRY(utt_const_h0(w.u, n_utt, o.init_value, s));
+    HIP_TRY(utt_start_values<T>(w.u, w.Xt, n_utt, d, o, s));
     HIP_TRY(wide_pack_x(fl, w.Xt, d.Mk, d.Tp, w.fb.Xw, s));
     const int init_const = o.init_mode == EVC_INIT_GIVEN ? 0 : 1;
     if (!init_const) HIP_TRY(wide_import_h(fl, w.fb.Hw, H, ldh, fm ? 1 : 0, T_, N, s));
     HIP_TRY(wide_begin(fl, w.fb, s));
-    // (float64: pymf's stop rule compares successive errors against 2.2e-16 and reserved bit 1 asks for it explicitly -
-    // correctly rounded quotients, as in solve_fused)
-    const bool exact = sizeof(T) == 8 && (o.stop_rule == EVC_STOP_PYMF || (o.reserved & 2));
+    // (float64 only: correctly rounded quotients under pymf's stop rule or on request, as on the fused path)
+    const bool exact = sizeof(T) == 8 && r.flags.exact_div;
     const int mode = (kl ? 100 : o.eps_mode) | (exact ? 0x1000 : 0);
 
     inf->kernel = K::kernel;
     inf->members = fl.c;
     inf->variant = wide_variant(fl, n_cus);
     inf->exchange = 1;               // tasks wait for tasks of other workgroups, whatever the number of ranges
-    // tests only (evc_solve_opts.test_abort_at, 0 in production): k > 0 raises the abort flag in front of the k-th
-    // launch of the iteration loop (-1: the call starts with it raised), as a wait that ran out would
-    const int fake_at = o.test_abort_at < 0 ? 0 : (o.test_abort_at > 0 ? o.test_abort_at : -1);
     int* abort_w = reinterpret_cast<int*>(w.fb.ctl + 1);
-    if (fake_at == 0) HIP_TRY(hipMemsetAsync(abort_w, 1, sizeof(int), s));
-    int launch_no = 0;
+    AbortHook hook(abort_w, o.test_abort_at);
+    HIP_TRY(hook.begin(false, s));   // (wide_begin has cleared the flag)
     int next_it = 0;                 // first iteration not yet run (0 = the pass that forms P and V = A H0)
     auto run_to = [&](int it_end, int snap_every = 0, int snap_first = 0) -> int {      // iterations [next_it, it_end)
         if (it_end <= next_it) return 0;
@@ -664,10 +726,8 @@ int solve_wide(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
         return 0;
     };
     if (o.check_every > 0 && o.stop_rule == EVC_STOP_SKLEARN) {   // error_at_init, sklearn _nmf.py:827
-        int st = run_to(1);
-        if (st) return st;
-        st = check(0);
-        if (st) return st;
+        HIP_TRY(run_to(1));
+        HIP_TRY(check(0));
     }
     if (o.ev_loop_start) HIP_TRY(hipEventRecord((hipEvent_t)o.ev_loop_start, s));
     int done = 0;
@@ -685,10 +745,8 @@ int solve_wide(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
             n = L * o.check_every;
             chk = true;
         }
-        if (fake_at > 0 && launch_no == fake_at) HIP_TRY(hipMemsetAsync(abort_w, 1, sizeof(int), s));
-        ++launch_no;
-        int st = L > 1 ? run_to(done + n + 1, o.check_every, done + o.check_every) : run_to(done + n + 1);
-        if (st) return st;
+        HIP_TRY(hook.before_launch(s));
+        HIP_TRY(L > 1 ? run_to(done + n + 1, o.check_every, done + o.check_every) : run_to(done + n + 1));
         if constexpr (sizeof(T) == 4) {
             for (int k = 0; k + 1 < L; ++k) {      // the checks inside the launch, oldest first
                 const int cno = done / o.check_every + 1 + k;
@@ -698,32 +756,22 @@ int solve_wide(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
             }
         }
         done += n;
-        if (chk) {
-            st = check(done / o.check_every);
-            if (st) return st;
-        }
+        if (chk) HIP_TRY(check(done / o.check_every));
     }
-    {
-        int st = run_to(1);           // iters == 0: the start values still have to exist
-        if (st) return st;
-    }
+    HIP_TRY(run_to(1));               // iters == 0: the start values still have to exist
     if (o.ev_loop_stop) HIP_TRY(hipEventRecord((hipEvent_t)o.ev_loop_stop, s));
     // A bounded wait that ran out (a wedged or oversubscribed device) voids the solve: the flag is read back before
     // anything reaches the caller's H or Y - one host round trip per solve, as for the other exchanging kernels
     // (include/evc.h, Host synchronisation) - and the caller of this function redoes the solve on the two contractions
     // from the untouched inputs.  (Round 3 exported NaN under status 0.)
-    {
-        int aborted = 0;
-        HIP_TRY(hipMemcpyAsync(&aborted, abort_w, sizeof(int), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (aborted) return ST_COOP_TIMEOUT;
-    }
+    int aborted = 0;
+    HIP_TRY(read_abort(abort_w, s, &aborted));
+    if (aborted) return ST_COOP_TIMEOUT;
     const int* abort = abort_w;
     if (H) HIP_TRY(wide_export_h(fl, w.fb.Hw, H, ldh, fm ? 1 : 0, T_, N, abort, s));
     if (y) {
         HIP_TRY(wide_export_h(fl, w.fb.Hw, w.H0, d.Np, 1, T_, N, abort, s));
-        int st = synth_rows<T>(w.H0, d.Np, *y, N, T_, fm, s);
-        if (st) return st;
+        HIP_TRY(synth_rows<T>(w.H0, d.Np, *y, N, T_, fm, s));
     }
     return copy_back(w.u, n_utt, n_slots, n_iter_out, err_out, s);
 }
@@ -740,17 +788,17 @@ template <typename T> int gemm_kernel_id() {
 
 template <typename T>
 int solve_typed(const void* A_, int lda, const void* X_, int ldx, void* H_, int ldh, int M, int N,
-                int T_, const int* utt_offsets, int n_utt, const evc_solve_opts& o, void* ws,
+                int T_, const int* utt_offsets, int n_utt, const evc_solve_opts& o, const Route& r, void* ws,
                 size_t ws_bytes, int* n_iter_out, double* err_out, const SynthArgs* y, hipStream_t s,
                 evc_solve_info* inf) {
     const T* A = static_cast<const T*>(A_);
     const T* X = static_cast<const T*>(X_);
     T* H = static_cast<T*>(H_);
     const Dims d = make_dims((int)sizeof(T), M, N, T_, n_utt, y ? y->Mb : 0);
-    int algo = o.algo == EVC_ALGO_AUTO ? EVC_ALGO_FACTORED : o.algo;
+    const int algo = r.algo;
     const int n_slots = n_slots_for(o.iters, o.check_every);
     if (n_slots > MAX_SLOTS) return ST_UNSUPPORTED;
-    const bool fused = use_fused(M, N, T_, sizeof(T) == 8 ? EVC_F64 : EVC_F32, algo) && !(o.reserved & 1);
+    const bool fused = r.family == ROUTE_FUSED;
     // dictionary arrays: from the prepared image (float32 callers riding the float64 kernels: behind its staging)
     DictArrays<T> ext{};
     if (o.dict) ext = dict_arrays<T>(o.dict, (sizeof(T) == 8 && o.dict->dtype == EVC_F32) ? dict_f64_staging(M, o.dict->Mb, N) : 0);
@@ -766,12 +814,7 @@ int solve_typed(const void* A_, int lda, const void* X_, int ldx, void* H_, int 
     w.u.n_slots = n_slots;
     const bool fm = (o.layout == EVC_FRAME_MAJOR);
 
-    // ---- utterances ----
-    if (utt_offsets)
-        HIP_TRY(hipMemcpyAsync(w.u.offsets, utt_offsets, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s));
-    else
-        HIP_TRY(utt_single(w.u, T_, s));
-    HIP_TRY(utt_setup(w.u, n_utt, T_, d.Tp, o.iters, s));
+    HIP_TRY(utt_begin(w.u, utt_offsets, n_utt, d, o.iters, false, s));
 
     // ---- import the caller's matrices into zero-padded frames-as-rows workspace arrays ----
     // At[n][m], Am[m][n], Xt[t][m], Ht[t][n]
@@ -779,17 +822,14 @@ int solve_typed(const void* A_, int lda, const void* X_, int ldx, void* H_, int 
     if (!o.dict) {
         DictArrays<T> da{};
         da.At = w.At; da.Am = w.Am; da.Akl = w.Akl;
-        DictPlan pl{};
-        pl.kl = kl;
-        int st = prepare_dict<T>(da, pl, A, lda, nullptr, 0, d, fm, o.eps, false, s);
-        if (st) return st;
+        HIP_TRY(prepare_dict<T>(da, kl, A, lda, d, fm, o.eps, s));
     }
     HIP_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
-    if (o.init_mode == EVC_INIT_SKLEARN) HIP_TRY(utt_sklearn_h0<T>(w.Xt, d.Mk, M, N, w.u, n_utt, s));
-    else if (o.init_mode == EVC_INIT_CONST) HIP_TRY(utt_const_h0(w.u, n_utt, o.init_value, s));
+    HIP_TRY(utt_start_values<T>(w.u, w.Xt, n_utt, d, o, s));
 
-    if (fused) {     // activations live in the packed tile layout from start to finish
+    if constexpr (sizeof(T) == 8) if (fused) {     // activations live in the packed tile layout from start to finish
         evc_solve_opts oo = o;
+        FusedRoute fr = r.fused;
         // A cooperative launch that gave up waiting for a peer workgroup (another process or stream held the
         // CUs it needed) leaves void results, and the solve is redone with one workgroup per frame tile.  The
         // flag costs a host round trip: when the start values can be regenerated it is read after the results
@@ -798,33 +838,26 @@ int solve_typed(const void* A_, int lda, const void* X_, int ldx, void* H_, int 
         const bool check_first = (o.init_mode == EVC_INIT_GIVEN);
         for (int attempt = 0; attempt < 2; ++attempt) {
             if (o.init_mode == EVC_INIT_GIVEN)
-                HIP_TRY(fused_import_h(w.fl, w.fb.Hp, reinterpret_cast<const double*>(H), ldh, fm ? 1 : 0, T_, N, s));
-            int coop_used = 0, aborted = 0;       // (constant start values: solve_fused)
-            int exported = 0;
+                HIP_TRY(fused_import_h(w.fl, w.fb.Hp, H, ldh, fm ? 1 : 0, T_, N, s));
+            const bool coop_used = fr.members > 1;
+            const int* abort_w = w.fb.coop_cnt + COOP_MAX_TILES;
+            int aborted = 0, exported = 0;        // (constant start values: solve_fused)
             // (with caller-given start values the abort flag is read before anything goes to the caller's H: no
             // direct export then)
-            int st = solve_fused(w, d, oo, n_utt, s, &coop_used, check_first ? (T*)nullptr : H, ldh, &exported, inf);
-            if (st) return st;
-            if (coop_used && check_first) {
-                st = coop_timed_out(w, s, &aborted);
-                if (st) return st;
-            }
+            HIP_TRY(solve_fused(w, d, oo, fr, n_utt, s, check_first ? nullptr : H, ldh, &exported, inf));
+            if (coop_used && check_first) HIP_TRY(read_abort(abort_w, s, &aborted));
             if (!aborted) {
-                st = finish_fused<T>(w, d, o, exported ? (T*)nullptr : H, ldh, y, s);
-                if (st) return st;
-                if (coop_used && !check_first) {
-                    st = coop_timed_out(w, s, &aborted);
-                    if (st) return st;
-                }
+                HIP_TRY(finish_fused(w, d, o, exported ? nullptr : H, ldh, y, s));
+                if (coop_used && !check_first) HIP_TRY(read_abort(abort_w, s, &aborted));
             }
             if (!aborted) break;
             if (attempt == 1) return ST_COOP_TIMEOUT;      // cannot happen: the redo is not cooperative
-            oo.reserved |= 4;
+            oo.reserved |= EVC_FLAG_NO_EXCHANGE;
             oo.test_abort_at = 0;
+            fr = plan_route(M, N, T_, EVC_F64, oo, r.n_cus).fused;
             inf->redo = 1;
-            HIP_TRY(utt_setup(w.u, n_utt, T_, d.Tp, o.iters, s));
-            if (o.init_mode == EVC_INIT_SKLEARN) HIP_TRY(utt_sklearn_h0<T>(w.Xt, d.Mk, M, N, w.u, n_utt, s));
-            else if (o.init_mode == EVC_INIT_CONST) HIP_TRY(utt_const_h0(w.u, n_utt, o.init_value, s));
+            HIP_TRY(utt_begin(w.u, utt_offsets, n_utt, d, o.iters, true, s));
+            HIP_TRY(utt_start_values<T>(w.u, w.Xt, n_utt, d, o, s));
         }
         return copy_back(w.u, n_utt, n_slots, n_iter_out, err_out, s);
     }
@@ -853,8 +886,7 @@ int solve_typed(const void* A_, int lda, const void* X_, int ldx, void* H_, int 
     };
 
     if (o.check_every > 0 && o.stop_rule == EVC_STOP_SKLEARN) {
-        int st = residual_check(0);     // error_at_init, sklearn _nmf.py:827
-        if (st) return st;
+        HIP_TRY(residual_check(0));     // error_at_init, sklearn _nmf.py:827
     }
 
     MuEpilogue<T> ep;
@@ -889,34 +921,71 @@ int solve_typed(const void* A_, int lda, const void* X_, int ldx, void* H_, int 
             }
         }
         v_valid = false;
-        if (o.check_every > 0 && it % o.check_every == 0) {
-            int st = residual_check(it / o.check_every);
-            if (st) return st;
-        }
+        if (o.check_every > 0 && it % o.check_every == 0) HIP_TRY(residual_check(it / o.check_every));
     }
 
     if (o.ev_loop_stop) HIP_TRY(hipEventRecord((hipEvent_t)o.ev_loop_stop, s));
     if (H) HIP_TRY(copy2d<T>(Hc, d.Np, d.T_, d.N, 0, H, ldh, d.T_, d.N, fm ? 0 : 1, s));
-    if (y) {
-        int st = synth_rows<T>(Hc, d.Np, *y, d.N, d.T_, fm, s);
-        if (st) return st;
-    }
+    if (y) HIP_TRY(synth_rows<T>(Hc, d.Np, *y, d.N, d.T_, fm, s));
     return copy_back(w.u, n_utt, n_slots, n_iter_out, err_out, s);
 }
 
+// callers may disable the fused kernels per call, so the query covers the carving of every route the sizes allow
 template <typename T> size_t workspace_typed(int M, int Mb, int N, int T_, int n_utt, int algo) {
     const Dims d = make_dims((int)sizeof(T), M, N, T_, n_utt, Mb);
-    const int al = algo == EVC_ALGO_AUTO ? EVC_ALGO_FACTORED : algo;
+    const int al = algo_eff(algo);
     const int dt = sizeof(T) == 8 ? EVC_F64 : EVC_F32;
-    // callers may disable the fused path per call, so the query covers both carvings
-    const size_t a = carve<T>(nullptr, d, al, MAX_SLOTS, false).bytes;
-    const size_t b = use_fused(M, N, T_, dt, al) ? carve<T>(nullptr, d, al, MAX_SLOTS, true).bytes : 0;
-    return a > b ? a : b;
+    size_t b = carve<T>(nullptr, d, al, MAX_SLOTS, false).bytes;
+    if (dt == EVC_F64 && small_family(M, N, T_, al))
+        b = std::max(b, carve<T>(nullptr, d, al, MAX_SLOTS, true).bytes);
+    if (wide_family(M, N, T_, dt, al, EVC_LOSS_FROBENIUS))
+        b = std::max(b, carve_wide<T>(nullptr, d, MAX_SLOTS, device_cus(), true, sizeof(T) == 4).bytes);
+    return b;
+}
+
+bool utt_offsets_ok(const int* utt_offsets, int n_utt, int T) {
+    if (!utt_offsets) return n_utt == 1;
+    if (utt_offsets[0] != 0 || utt_offsets[n_utt] != T) return false;
+    for (int i = 0; i < n_utt; ++i)
+        if (utt_offsets[i + 1] < utt_offsets[i]) return false;
+    return true;
 }
 
 bool bad_ld(int layout, int ld, int rows_fm, int cols_fm) {
     // FRAME_MAJOR: rows_fm x cols_fm with ld >= cols_fm; BIN_MAJOR: the transpose
     return layout == EVC_FRAME_MAJOR ? ld < cols_fm : ld < rows_fm;
+}
+
+template <typename T>
+hipError_t synthesize_typed(const void* B_, int ldb, const void* H_, int ldh, void* Y_, int ldy, int Mb, int N, int T_,
+                            bool fm, hipStream_t s) {
+    const T* B = static_cast<const T*>(B_);
+    const T* H = static_cast<const T*>(H_);
+    T* Y = static_cast<T*>(Y_);
+    if (Mb <= 64) {     // a handful of bins: one pass over H, wavefronts split the exemplars (k_synth_skinny)
+        // FRAME_MAJOR: H[t][n], B[n][mb], Y[t][mb];  BIN_MAJOR: H[n][t], B[mb][n], Y[mb][t]
+        const long hst = fm ? ldh : 1, hsn = fm ? 1 : ldh, bsn = fm ? ldb : 1, bsm = fm ? 1 : ldb;
+        const long yst = fm ? ldy : 1, ysm = fm ? 1 : ldy;
+        return synth_skinny<T>(H, hst, hsn, B, bsn, bsm, Y, yst, ysm, T_, Mb, N, s);
+    }
+    // Y[t][mb] = sum_n H[t][n] B[n][mb]           (np.matmul(H.T, B), 04_align_n_nmf.py:391)
+    if (fm) return gemm_strided<T>(H, ldh, 1, B, 1, ldb, Y, ldy, 1, T_, Mb, N, s);
+    // Y[mb][t] = sum_n B[mb][n] H[n][t]
+    return gemm_strided<T>(B, ldb, 1, H, 1, ldh, Y, ldy, 1, Mb, T_, N, s);
+}
+
+template <typename T>
+int residual_typed(const void* A, int lda, const void* X, int ldx, const void* H, int ldh, int M, int N, int T_, bool fm,
+                   double* err2_out, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    const Dims d = make_dims((int)sizeof(T), M, N, T_, 1, 0);
+    Workspace<T> w = carve<T>(workspace, d, EVC_ALGO_FACTORED, MAX_SLOTS, false);
+    if (w.bytes > workspace_bytes) return ST_WORKSPACE;
+    HIP_TRY(copy2d<T>((const T*)A, lda, M, N, fm ? 1 : 0, w.Am, d.Np, d.Mj, d.Np, 0, s));
+    HIP_TRY(copy2d<T>((const T*)X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
+    HIP_TRY(copy2d<T>((const T*)H, ldh, T_, N, fm ? 0 : 1, w.H0, d.Np, d.Tp, d.Np, 0, s));
+    HIP_TRY(gemm_nt<T>(w.H0, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));
+    HIP_TRY(frame_err2<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, err2_out, s));
+    return ST_OK;
 }
 
 }  // namespace
@@ -948,10 +1017,6 @@ int evc_device_count(void) {
 // generic path (and exact to float32 rounding), so their matrices are widened into a staging region, solved by
 // the float64 route and narrowed on the way out.  The reference's float32 surface (nmf_tool, TF1) is compared
 // against a float64 restatement anyway: computing in float64 only moves the result towards it.
-static bool f32_rides_f64(int M, int N, int T, int algo, int reserved) {
-    return (algo == EVC_ALGO_AUTO || algo == EVC_ALGO_FACTORED) && !(reserved & 1) &&
-           fused_supported(M, N, T, EVC_F64);
-}
 static size_t f32_staging_bytes(int M, int Mb, int N, int T) {
     const size_t n = (size_t)N * M + (size_t)T * M + (size_t)T * N + (size_t)N * Mb + (size_t)T * Mb;
     return ((n * sizeof(double) + 6 * 256) + 255) & ~size_t(255);   // the inner workspace starts 256-byte aligned
@@ -960,34 +1025,17 @@ static size_t f32_staging_bytes(int M, int Mb, int N, int T) {
 size_t evc_workspace_bytes(int M, int Mb, int N, int T, int n_utt, int dtype, int algo) {
     if (M < 0 || Mb < 0 || N < 0 || T < 0 || n_utt < 1) return 0;
     if (algo < EVC_ALGO_GRAM || algo > EVC_ALGO_AUTO) return 0;
-    if (dtype == EVC_F64) {
-        size_t b = workspace_typed<double>(M, Mb, N, T, n_utt, algo);
-        if (wide64_supported(M, N, T, dtype, algo == EVC_ALGO_AUTO ? EVC_ALGO_FACTORED : algo, EVC_LOSS_FROBENIUS)) {
-            const Dims d = make_dims(8, M, N, T, n_utt, Mb);
-            const size_t wb = carve_wide<double>(nullptr, d, MAX_SLOTS, device_cus(), true, false).bytes;
-            if (wb > b) b = wb;
-        }
-        return b;
-    }
-    if (dtype == EVC_F32) {
-        size_t b = workspace_typed<float>(M, Mb, N, T, n_utt, algo);
-        if (wide_supported(M, N, T, dtype, algo == EVC_ALGO_AUTO ? EVC_ALGO_FACTORED : algo)) {
-            const Dims d = make_dims(4, M, N, T, n_utt, Mb);
-            const size_t wb = carve_wide<float>(nullptr, d, MAX_SLOTS, device_cus(), true, true).bytes;
-            if (wb > b) b = wb;
-        }
-        if (f32_rides_f64(M, N, T, algo, 0)) {
-            const size_t c = f32_staging_bytes(M, Mb, N, T) + workspace_typed<double>(M, Mb, N, T, n_utt, algo);
-            if (c > b) b = c;
-        }
-        return b;
-    }
-    return 0;
+    if (dtype == EVC_F64) return workspace_typed<double>(M, Mb, N, T, n_utt, algo);
+    if (dtype != EVC_F32) return 0;
+    size_t b = workspace_typed<float>(M, Mb, N, T, n_utt, algo);
+    if (small_family(M, N, T, algo_eff(algo)))
+        b = std::max(b, f32_staging_bytes(M, Mb, N, T) + workspace_typed<double>(M, Mb, N, T, n_utt, algo));
+    return b;
 }
 
 static int solve_f32_on_f64(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
-                            const int* utt_offsets, int n_utt, const evc_solve_opts& o, void* ws, size_t ws_bytes,
-                            int* n_iter_out, double* err_out, const SynthArgs* y, hipStream_t s,
+                            const int* utt_offsets, int n_utt, const evc_solve_opts& o, const Route& r, void* ws,
+                            size_t ws_bytes, int* n_iter_out, double* err_out, const SynthArgs* y, hipStream_t s,
                             evc_solve_info* inf) {
     const bool fm = (o.layout == EVC_FRAME_MAJOR);
     const int Mb = y ? y->Mb : 0;
@@ -1014,10 +1062,9 @@ static int solve_f32_on_f64(const void* A, int lda, const void* X, int ldx, void
     }
     evc_solve_opts o64 = o;
     o64.dtype = EVC_F64;
-    const int st = solve_typed<double>(A64, (int)aC, X64, (int)xC, H ? H64 : nullptr, (int)hC, M, N, T, utt_offsets,
-                                       n_utt, o64, static_cast<char*>(ws) + stage, ws_bytes - stage, n_iter_out,
-                                       err_out, y ? &y64 : nullptr, s, inf);
-    if (st) return st;
+    HIP_TRY(solve_typed<double>(A64, (int)aC, X64, (int)xC, H ? H64 : nullptr, (int)hC, M, N, T, utt_offsets, n_utt, o64, r,
+                                static_cast<char*>(ws) + stage, ws_bytes - stage, n_iter_out, err_out, y ? &y64 : nullptr,
+                                s, inf));
     if (H) HIP_TRY((cvt2d<double, float>(H64, hC, hR, hC, static_cast<float*>(H), ldh, s)));
     if (y) HIP_TRY((cvt2d<double, float>(Y64, yC, yR, yC, static_cast<float*>(y->Y), y->ldy, s)));
     if (n_iter_out || err_out) HIP_TRY(hipStreamSynchronize(s));    // those calls are synchronous: so are H and Y
@@ -1028,11 +1075,11 @@ static int solve_f32_on_f64(const void* A, int lda, const void* X, int ldx, void
 size_t evc_dict_bytes(int M, int Mb, int N, int dtype, int loss) {
     if (M < 1 || Mb < 0 || N < 1) return 0;
     if (loss != EVC_LOSS_FROBENIUS && loss != EVC_LOSS_KL) return 0;
-    if (dtype == EVC_F64) return dict_image_bytes<double>(M, Mb, N, loss, 0);
+    if (dtype == EVC_F64) return dict_image<double>(nullptr, 0, M, Mb, N, loss).bytes;
     if (dtype != EVC_F32) return 0;
-    if (f32_rides_f64(M, N, 1, EVC_ALGO_FACTORED, 0))     // widened once, then the float64 image
-        return dict_image_bytes<double>(M, Mb, N, loss, dict_f64_staging(M, Mb, N));
-    return dict_image_bytes<float>(M, Mb, N, loss, 0);
+    if (small_family(M, N, 1, EVC_ALGO_FACTORED))     // widened once, then the float64 image
+        return dict_image<double>(nullptr, dict_f64_staging(M, Mb, N), M, Mb, N, loss).bytes;
+    return dict_image<float>(nullptr, 0, M, Mb, N, loss).bytes;
 }
 
 int evc_dict_prepare(const void* A, int lda, const void* B, int ldb, int M, int Mb, int N, int layout, int dtype, int loss,
@@ -1046,35 +1093,23 @@ int evc_dict_prepare(const void* A, int lda, const void* B, int ldb, int M, int 
     if (mem_bytes < need || (reinterpret_cast<uintptr_t>(mem) & 255)) return ST_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool fm = layout == EVC_FRAME_MAJOR;
-    int st;
     if (dtype == EVC_F64) {
-        st = dict_prepare_typed<double>(static_cast<const double*>(A), lda, static_cast<const double*>(B), ldb, M, Mb, N, fm,
-                                        loss, eps, mem, 0, s);
-        if (!st) {
-            const Dims dd = make_dims(8, M, N, 1, 1, Mb);
-            st = prepare_dict_fused(dict_arrays_at<double>(mem, 0, M, Mb, N, loss), dict_plan<double>(M, Mb, N, loss, true),
-                                    static_cast<const double*>(B), ldb, dd, fm, true, s);
-        }
-    } else if (f32_rides_f64(M, N, 1, EVC_ALGO_FACTORED, 0)) {
+        HIP_TRY(dict_prepare_typed<double>(static_cast<const double*>(A), lda, static_cast<const double*>(B), ldb, M, Mb, N,
+                                           fm, loss, eps, mem, 0, s));
+    } else if (small_family(M, N, 1, EVC_ALGO_FACTORED)) {
         // widen A and B once (compact rows in the caller's orientation), then the float64 image behind them
-        const size_t skip = dict_f64_staging(M, Mb, N);
         Carver c{static_cast<char*>(mem), 0};
         double* A64 = c.take<double>((size_t)N * M);
         double* B64 = c.take<double>((size_t)N * Mb);
         const long aR = fm ? N : M, aC = fm ? M : N, bR = fm ? N : Mb, bC = fm ? Mb : N;
         HIP_TRY((cvt2d<float, double>(static_cast<const float*>(A), lda, aR, aC, A64, aC, s)));
         if (B) HIP_TRY((cvt2d<float, double>(static_cast<const float*>(B), ldb, bR, bC, B64, bC, s)));
-        st = dict_prepare_typed<double>(A64, (int)aC, B ? B64 : nullptr, (int)bC, M, Mb, N, fm, loss, eps, mem, skip, s);
-        if (!st) {
-            const Dims dd = make_dims(8, M, N, 1, 1, Mb);
-            st = prepare_dict_fused(dict_arrays_at<double>(mem, skip, M, Mb, N, loss), dict_plan<double>(M, Mb, N, loss, true),
-                                    B ? B64 : nullptr, (int)bC, dd, fm, true, s);
-        }
+        HIP_TRY(dict_prepare_typed<double>(A64, (int)aC, B ? B64 : nullptr, (int)bC, M, Mb, N, fm, loss, eps, mem,
+                                           dict_f64_staging(M, Mb, N), s));
     } else {
-        st = dict_prepare_typed<float>(static_cast<const float*>(A), lda, static_cast<const float*>(B), ldb, M, Mb, N, fm,
-                                       loss, eps, mem, 0, s);
+        HIP_TRY(dict_prepare_typed<float>(static_cast<const float*>(A), lda, static_cast<const float*>(B), ldb, M, Mb, N, fm,
+                                          loss, eps, mem, 0, s));
     }
-    if (st) return st;
     dict->struct_bytes = (int)sizeof(evc_dict);
     dict->magic = DICT_MAGIC;
     dict->M = M; dict->Mb = Mb; dict->N = N; dict->dtype = dtype; dict->loss = loss; dict->reserved = 0;
@@ -1111,6 +1146,7 @@ static int solve_checked(const void* A, int lda, const void* X, int ldx, void* H
         if (n_iter_out) for (int i = 0; i < n_utt; ++i) n_iter_out[i] = 0;
         return ST_OK;
     }
+    const Route route = plan_route(M, N, T, o.dtype, o, device_cus());
     const evc_dict* dk = o.dict;
     if (dk) {         // a prepared dictionary replaces the A (and B) arguments
         if (dk->struct_bytes != (int)sizeof(evc_dict) || dk->magic != DICT_MAGIC || !dk->mem) return ST_BADARG;
@@ -1119,8 +1155,7 @@ static int solve_checked(const void* A, int lda, const void* X, int ldx, void* H
         if (y && dk->Mb > 0 && dk->Mb != y->Mb) return ST_BADARG;
         if (dk->bytes < evc_dict_bytes(M, dk->Mb, N, dk->dtype, dk->loss)) return ST_BADARG;
         // a float32 dictionary with M <= 32 was widened for the float64 fused kernels: only that route is prepared
-        if (o.dtype == EVC_F32 && f32_rides_f64(M, N, T, EVC_ALGO_FACTORED, 0) && !f32_rides_f64(M, N, T, o.algo, o.reserved))
-            return ST_UNSUPPORTED;
+        if (o.dtype == EVC_F32 && small_family(M, N, T, EVC_ALGO_FACTORED) && !route.staged) return ST_UNSUPPORTED;
     }
     if ((!dk && !A) || !X || !workspace) return ST_BADARG;
     if (!H && (!y || o.init_mode == EVC_INIT_GIVEN)) return ST_BADARG;   // H may be omitted by evc_nmf_convert only
@@ -1128,59 +1163,38 @@ static int solve_checked(const void* A, int lda, const void* X, int ldx, void* H
         return ST_BADARG;
     if (y && (!y->Y || bad_ld(o.layout, y->ldy, T, y->Mb))) return ST_BADARG;
     if (y && !(dk && dk->Mb > 0) && (!y->B || bad_ld(o.layout, y->ldb, N, y->Mb))) return ST_BADARG;
-    if (utt_offsets) {
-        if (utt_offsets[0] != 0 || utt_offsets[n_utt] != T) return ST_BADARG;
-        for (int i = 0; i < n_utt; ++i)
-            if (utt_offsets[i + 1] < utt_offsets[i]) return ST_BADARG;
-    } else if (n_utt != 1) {
+    if (!utt_offsets_ok(utt_offsets, n_utt, T)) return ST_BADARG;
+    // tuning bits 16..19: wavefronts per workgroup of k_fused_wide (4 | 8), whole bin tiles per wavefront of
+    // k_fused_wide64 (4 | 5 | 7 | 8: the narrowest instance >= the request that holds M); anything else is an error
+    const int tw = route.flags.w_req;
+    if (M > 32 && tw != 0 && !(o.dtype == EVC_F32 ? (tw == 4 || tw == 8) : (tw == 3 || tw == 4 || tw == 5 || tw == 7 || tw == 8)))
         return ST_BADARG;
-    }
-    {   // tuning bits 16..19: wavefronts per workgroup of k_fused_wide (4 | 8), whole bin tiles per wavefront of
-        // k_fused_wide64 (4 | 5 | 7 | 8: the narrowest instance >= the request that holds M); anything else is an error
-        const int tw = (o.reserved >> 16) & 0xf;
-        if (M > 32 && tw != 0 && !(o.dtype == EVC_F32 ? (tw == 4 || tw == 8) : (tw == 3 || tw == 4 || tw == 5 || tw == 7 || tw == 8)))
-            return ST_BADARG;
-    }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     evc_solve_info inf{};
-    int st;
-    const int algo_eff = o.algo == EVC_ALGO_AUTO ? EVC_ALGO_FACTORED : o.algo;
-    // a task-queue solve whose bounded wait ran out is redone on the two contractions (nothing has reached H or Y)
-    evc_solve_opts redo_o = o;
-    redo_o.reserved |= EVC_FLAG_NO_FUSED;
-    redo_o.test_abort_at = 0;
-    if (o.dtype == EVC_F64 && use_wide(M, N, T, o.dtype, algo_eff, o.loss, o.reserved)) {
-        st = solve_wide<double>(static_cast<const double*>(A), lda, static_cast<const double*>(X), ldx,
-                                static_cast<double*>(H), ldh, M, N, T, utt_offsets, n_utt, o, workspace, workspace_bytes,
-                                n_iter_out, err_out, y, s, &inf);
-        if (st == ST_COOP_TIMEOUT) {
-            const int launches = inf.launches;
-            inf = evc_solve_info{};
-            st = solve_typed<double>(A, lda, X, ldx, H, ldh, M, N, T, utt_offsets, n_utt, redo_o, workspace,
-                                     workspace_bytes, n_iter_out, err_out, y, s, &inf);
-            inf.redo = 1;
-            inf.launches += launches;
+    // three drivers, one signature: the task queues, float32 staged onto the float64 fused kernels, fused / two contractions
+    auto run = [&](const Route& r, const evc_solve_opts& oo) -> int {
+        const bool f64 = o.dtype == EVC_F64;
+        auto driver = f64 ? solve_typed<double> : solve_typed<float>;
+        switch (r.family) {
+            case ROUTE_WIDE: driver = f64 ? solve_wide<double> : solve_wide<float>; break;
+            case ROUTE_FUSED: if (r.staged) driver = solve_f32_on_f64; break;
+            default: break;
         }
-    } else if (o.dtype == EVC_F64)
-        st = solve_typed<double>(A, lda, X, ldx, H, ldh, M, N, T, utt_offsets, n_utt, o, workspace,
-                                 workspace_bytes, n_iter_out, err_out, y, s, &inf);
-    else if (f32_rides_f64(M, N, T, o.algo, o.reserved))
-        st = solve_f32_on_f64(A, lda, X, ldx, H, ldh, M, N, T, utt_offsets, n_utt, o, workspace, workspace_bytes,
-                              n_iter_out, err_out, y, s, &inf);
-    else if (use_wide(M, N, T, o.dtype, algo_eff, o.loss, o.reserved)) {
-        st = solve_wide<float>(static_cast<const float*>(A), lda, static_cast<const float*>(X), ldx, static_cast<float*>(H),
-                        ldh, M, N, T, utt_offsets, n_utt, o, workspace, workspace_bytes, n_iter_out, err_out, y, s, &inf);
-        if (st == ST_COOP_TIMEOUT) {
-            const int launches = inf.launches;
-            inf = evc_solve_info{};
-            st = solve_typed<float>(A, lda, X, ldx, H, ldh, M, N, T, utt_offsets, n_utt, redo_o, workspace,
-                                    workspace_bytes, n_iter_out, err_out, y, s, &inf);
-            inf.redo = 1;
-            inf.launches += launches;
-        }
-    } else
-        st = solve_typed<float>(A, lda, X, ldx, H, ldh, M, N, T, utt_offsets, n_utt, o, workspace,
-                                workspace_bytes, n_iter_out, err_out, y, s, &inf);
+        return driver(A, lda, X, ldx, H, ldh, M, N, T, utt_offsets, n_utt, oo, r, workspace, workspace_bytes, n_iter_out,
+                      err_out, y, s, &inf);
+    };
+    int st = run(route, o);
+    if (st == ST_COOP_TIMEOUT && route.family == ROUTE_WIDE) {
+        // a task-queue solve whose bounded wait ran out is redone on the two contractions (nothing has reached H or Y)
+        evc_solve_opts redo_o = o;
+        redo_o.reserved |= EVC_FLAG_NO_FUSED;
+        redo_o.test_abort_at = 0;
+        const int launches = inf.launches;
+        inf = evc_solve_info{};
+        st = run(plan_route(M, N, T, o.dtype, redo_o, route.n_cus), redo_o);
+        inf.redo = 1;
+        inf.launches += launches;
+    }
     if (o.info && o.info->struct_bytes == (int)sizeof(evc_solve_info)) {
         inf.struct_bytes = (int)sizeof(evc_solve_info);
         *o.info = inf;
@@ -1215,30 +1229,8 @@ int evc_synthesize(const void* B, int ldb, const void* H, int ldh, void* Y, int 
     if (bad_ld(layout, ldb, N, Mb) || bad_ld(layout, ldh, T, N) || bad_ld(layout, ldy, T, Mb))
         return ST_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e;
-    if (Mb <= 64) {     // a handful of bins: one pass over H, wavefronts split the exemplars (k_synth_skinny)
-        const bool fm = layout == EVC_FRAME_MAJOR;
-        // FRAME_MAJOR: H[t][n], B[n][mb], Y[t][mb];  BIN_MAJOR: H[n][t], B[mb][n], Y[mb][t]
-        const long hst = fm ? ldh : 1, hsn = fm ? 1 : ldh, bsn = fm ? ldb : 1, bsm = fm ? 1 : ldb;
-        const long yst = fm ? ldy : 1, ysm = fm ? 1 : ldy;
-        if (dtype == EVC_F64)
-            e = synth_skinny<double>((const double*)H, hst, hsn, (const double*)B, bsn, bsm, (double*)Y, yst, ysm, T, Mb, N, s);
-        else
-            e = synth_skinny<float>((const float*)H, hst, hsn, (const float*)B, bsn, bsm, (float*)Y, yst, ysm, T, Mb, N, s);
-    } else if (layout == EVC_FRAME_MAJOR) {
-        // Y[t][mb] = sum_n H[t][n] B[n][mb]           (np.matmul(H.T, B), 04_align_n_nmf.py:391)
-        if (dtype == EVC_F64)
-            e = gemm_strided<double>((const double*)H, ldh, 1, (const double*)B, 1, ldb, (double*)Y, ldy, 1, T, Mb, N, s);
-        else
-            e = gemm_strided<float>((const float*)H, ldh, 1, (const float*)B, 1, ldb, (float*)Y, ldy, 1, T, Mb, N, s);
-    } else {
-        // Y[mb][t] = sum_n B[mb][n] H[n][t]
-        if (dtype == EVC_F64)
-            e = gemm_strided<double>((const double*)B, ldb, 1, (const double*)H, 1, ldh, (double*)Y, ldy, 1, Mb, T, N, s);
-        else
-            e = gemm_strided<float>((const float*)B, ldb, 1, (const float*)H, 1, ldh, (float*)Y, ldy, 1, Mb, T, N, s);
-    }
-    return (int)e;
+    const bool fm = layout == EVC_FRAME_MAJOR;
+    return (int)(dtype == EVC_F64 ? synthesize_typed<double> : synthesize_typed<float>)(B, ldb, H, ldh, Y, ldy, Mb, N, T, fm, s);
 }
 
 int evc_residual(const void* A, int lda, const void* X, int ldx, const void* H, int ldh, int M,
@@ -1252,21 +1244,9 @@ int evc_residual(const void* A, int lda, const void* X, int ldx, const void* H, 
     if (bad_ld(layout, lda, N, M) || bad_ld(layout, ldx, T, M) || bad_ld(layout, ldh, T, N))
         return ST_BADARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const Dims d = make_dims(dtype == EVC_F64 ? 8 : 4, M, N, T, 1, 0);
     const bool fm = (layout == EVC_FRAME_MAJOR);
-#define EVC_RESID(TT)                                                                              \
-    {                                                                                              \
-        Workspace<TT> w = carve<TT>(workspace, d, EVC_ALGO_FACTORED, MAX_SLOTS, false);             \
-        if (w.bytes > workspace_bytes) return ST_WORKSPACE;                                        \
-        HIP_TRY(copy2d<TT>((const TT*)A, lda, M, N, fm ? 1 : 0, w.Am, d.Np, d.Mj, d.Np, 0, s));     \
-        HIP_TRY(copy2d<TT>((const TT*)X, ldx, T, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));     \
-        HIP_TRY(copy2d<TT>((const TT*)H, ldh, T, N, fm ? 0 : 1, w.H0, d.Np, d.Tp, d.Np, 0, s));     \
-        HIP_TRY(gemm_nt<TT>(w.H0, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));              \
-        HIP_TRY(frame_err2<TT>(w.Xt, d.Mk, w.Vt, d.Mj, M, T, err2_out, s));                         \
-    }
-    if (dtype == EVC_F64) EVC_RESID(double) else EVC_RESID(float)
-#undef EVC_RESID
-    return ST_OK;
+    return (dtype == EVC_F64 ? residual_typed<double> : residual_typed<float>)(A, lda, X, ldx, H, ldh, M, N, T, fm, err2_out,
+                                                                               workspace, workspace_bytes, s);
 }
 
 size_t evc_griffin_lim_workspace_bytes(int T, int fft_size, int hop, int iters) {
@@ -1406,13 +1386,7 @@ int evc_cd_solve(const void* A, int lda, const void* X, int ldx, void* H, int ld
     if (!(o.tol >= 0.0) || !(o.l1 >= 0.0) || !(o.l2 >= 0.0)) return ST_BADARG;
     if (!A || !X || !H || !workspace) return ST_BADARG;
     if (bad_ld(o.layout, lda, N, M) || bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldh, T, N)) return ST_BADARG;
-    if (utt_offsets) {
-        if (utt_offsets[0] != 0 || utt_offsets[n_utt] != T) return ST_BADARG;
-        for (int i = 0; i < n_utt; ++i)
-            if (utt_offsets[i + 1] < utt_offsets[i]) return ST_BADARG;
-    } else if (n_utt != 1) {
-        return ST_BADARG;
-    }
+    if (!utt_offsets_ok(utt_offsets, n_utt, T)) return ST_BADARG;
     if (M > CD_MAX_M) return ST_UNSUPPORTED;
     if (workspace_bytes < evc_cd_workspace_bytes(M, N, T, n_utt, o.dtype)) return ST_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

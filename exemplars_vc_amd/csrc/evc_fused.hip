@@ -507,30 +507,26 @@ static hipError_t launch_general(const FusedLayout& f, const FusedArgs& a, int c
     }
 }
 
-// c_req: 0 = automatic (k_fused_res where it applies), 1 / 2 = force the general kernel with that many
-// frame tiles per workgroup (tests, A/B timing).
+// r: the kernel and the member count plan_route chose for this attempt (r.c_req: 0 = automatic, 1 / 2 = the general
+// kernel with that many frame tiles per workgroup: tests, A/B timing).
 // all_live_known: no stopping rule is in force, so every utterance is active for the whole call.
-// exact_div: correctly rounded quotients (general kernel only; see exact_div() in evc_fused_common.h).
-hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const UttState& u, int N, int T_,
-                         int iters, int first, int write_err, double* err2, int eps_mode, double eps,
-                         double l1, int c_req, int all_live_known, int loss, int exact_div, hipStream_t s) {
+hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const FusedRoute& r, const UttState& u, int N,
+                         int T_, int iters, int first, int write_err, double* err2, int eps_mode, double eps, double l1,
+                         int all_live_known, int loss, hipStream_t s) {
     FusedArgs a;
     a.A1p = b.A1p; a.A2p = b.A2p; a.Xp = b.Xp; a.Hp = reinterpret_cast<f64x2*>(b.Hp); a.Vp = b.Vp;
     a.err2 = err2; a.frame_utt = u.frame_utt; a.active = u.active;
     a.NT = f.NT; a.TT = f.TT; a.N = N; a.T_ = T_;
     a.iters = iters; a.first = first; a.write_err = write_err; a.skip_all_live = 0; a.force_live = 0;
-    a.loss = loss; a.exact_div = exact_div;
+    a.loss = loss; a.exact_div = r.exact_div;
     a.eps_mode = eps_mode; a.eps = eps; a.l1 = l1;
     a.coop_c = 1; a.coop_buf = nullptr; a.coop_cnt = nullptr; a.coop_abort = nullptr; a.groups = 0;
     a.init_const = 0; a.h0 = nullptr; a.rsum = nullptr; a.Hx = nullptr; a.ldhx = 0; a.hx_frame_major = 0;
     a.M = f.M; a.spare_q = -1; a.stagger_cycles = 0;
-    const bool xy = c_req == 0 && b.xy_c >= 2 && b.coop_buf && b.coop_cnt &&
-                    fused_xy_members(f.NT, N, eps_mode, exact_div, loss) == b.xy_c;
-    const bool all_res = xy || (c_req == 0 && b.all_c >= 1 && b.coop_buf && b.coop_cnt &&
-                                fused_all_members(f.NT, N, eps_mode, exact_div, loss) == b.all_c);
-    const bool resident = all_res || (c_req == 0 && fused_res_supported(N, eps_mode, exact_div));
-    if (!resident) return launch_general(f, a, c_req, s);
-    if (first && all_res && b.init_const && iters > 0) {
+    const bool xy = r.kernel == EVC_KERNEL_FUSED_XY;
+    const bool all_res = xy || r.kernel == EVC_KERNEL_FUSED_ALL;
+    if (r.kernel == EVC_KERNEL_FUSED_MU) return launch_general(f, a, r.c_req, s);
+    if (first && all_res && r.init_const && iters > 0) {
         // k_fused_all starts from the utterances' constants itself (every utterance is active at the first launch)
         a.init_const = 1; a.h0 = u.h0; a.rsum = b.rsum;
     } else if (first) {          // V = A H (and the residual at init) by the general kernel's pre-pass
@@ -544,15 +540,15 @@ hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const UttS
     if (iters == 0) return hipSuccess;
     hipError_t e;
     if (all_res) {
-        a.coop_c = xy ? b.xy_c : b.all_c; a.coop_buf = b.coop_buf; a.coop_cnt = b.coop_cnt;
+        a.coop_c = r.members; a.coop_buf = b.coop_buf; a.coop_cnt = b.coop_cnt;
         a.coop_abort = b.coop_cnt + COOP_MAX_TILES;
         if (all_live_known) { a.Hx = b.Hx; a.ldhx = b.ldhx; a.hx_frame_major = b.hx_frame_major; }
-        e = xy ? fused_xy_launch(f.msteps, a, b.n_cus, s) : fused_all_launch(f.msteps, a, b.n_cus, s);
+        e = xy ? fused_xy_launch(f.msteps, a, r.n_cus, s) : fused_all_launch(f.msteps, a, r.n_cus, s);
         a.coop_c = 1;            // the general kernel behind it takes no part in any exchange
         a.first = 0; a.init_const = 0; a.Hx = nullptr;
     } else {
-        if (b.coop_c > 1 && b.coop_buf && b.coop_cnt) {
-            a.coop_c = b.coop_c; a.coop_buf = b.coop_buf; a.coop_cnt = b.coop_cnt;
+        if (r.members > 1) {
+            a.coop_c = r.members; a.coop_buf = b.coop_buf; a.coop_cnt = b.coop_cnt;
             a.coop_abort = b.coop_cnt + COOP_MAX_TILES;
         }
         e = fused_res_launch(f.msteps, a, s);

@@ -177,19 +177,25 @@ int fused_all_members(int NT, int N, int eps_mode, int exact_div, int loss);
 // workgroups per PAIR of frame tiles k_fused_xy (evc_fused_xy.hip) uses for this problem; 0: it does not apply
 int fused_xy_members(int NT, int N, int eps_mode, int exact_div, int loss);
 bool fused_res_supported(int N, int eps_mode, int exact_div);
+// The M <= 32 part of a solve's route: decided once per attempt (plan_route, evc_api.hip); fused_iterate launches what it
+// says and evc_solve_info reports the same fields
+struct FusedRoute {
+    int kernel;            // EVC_KERNEL_FUSED_MU | FUSED_RES | FUSED_ALL | FUSED_XY
+    int members;           // workgroups per frame tile (k_fused_xy: per pair of frame tiles); > 1: they exchange partial sums
+    int c_req;             // k_fused_mu's frame tiles per workgroup: 0 = automatic, 1 / 2 (tests, A/B timing)
+    int exact_div;         // correctly rounded quotients (general kernel only; see exact_div() in evc_fused_common.h)
+    int init_const;        // 1: the first launch forms H = h0 and V = h0 rowsum(A) itself (no fill, no pre-pass)
+    int direct_export;     // 1: nothing can stop, so the last launch may write the caller's H itself (k_fused_all)
+    int n_cus;             // compute units of the device (sizes k_fused_all's persistent grid)
+};
 struct FusedBuffers {
     double *A1p, *A2p, *Xp, *Hp, *Vp;
     double* coop_buf;      // exchange buffers of the cooperative launch (see k_fused_res)
     int* coop_cnt;         // [COOP_MAX_TILES] arrival counters, then one abort flag
-    int coop_c;            // cooperating workgroups per frame tile chosen for this call (1 = off)
-    int all_c;             // k_fused_all: workgroups per frame tile (0 = that kernel is not used)
-    int xy_c;              // k_fused_xy: workgroups per pair of frame tiles (0 = that kernel is not used)
     double* rsum;          // [32] row sums of the dictionary (k_fused_all's in-kernel start)
-    int init_const;        // 1: the first launch forms H = h0 and V = h0 rowsum(A) itself (no fill, no pre-pass)
     double* Hx;            // k_fused_all's last launch also writes the caller's H (NULL: off); ldhx, hx_frame_major
     long ldhx;
     int hx_frame_major;
-    int n_cus;             // compute units of the device (sizes k_fused_all's persistent grid)
 };
 bool fused_supported(int M, int N, int T_, int dtype);
 FusedLayout fused_layout(int M, int N, int T_);
@@ -216,9 +222,9 @@ hipError_t fused_synthesize(const FusedLayout& fB, const double* B2p, const doub
                             hipStream_t s);
 // `iters` updates in one launch.  first: V is built from H by a pre-pass (else carried over in
 // Vp from the previous launch); write_err: per-frame squared residuals of the final H -> err2.
-hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const UttState& u, int N, int T_,
-                         int iters, int first, int write_err, double* err2, int eps_mode, double eps,
-                         double l1, int c_req, int all_live_known, int loss, int exact_div, hipStream_t s);
+hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const FusedRoute& r, const UttState& u, int N,
+                         int T_, int iters, int first, int write_err, double* err2, int eps_mode, double eps, double l1,
+                         int all_live_known, int loss, hipStream_t s);
 
 // ----- evc_wide.hip -----
 // Fused FACTORED kernel for wide spectra (32 < M <= 208 bins, float32): k_fused_wide, a task queue over
