@@ -64,6 +64,14 @@ constexpr unsigned ALL_POLL_LIMIT = 1u << 17;
 #ifndef EVC_ALL_C1_ALTERNATE
 #define EVC_ALL_C1_ALTERNATE 0
 #endif
+#ifndef EVC_ALL_X16            // the direct exchange (2, 4, 8 members) moves 16-byte words: one pair of elements per thread
+#define EVC_ALL_X16 1
+#endif
+#ifndef EVC_ALL_X16_WATCH      // ... and first watches one word per peer, like the 8-byte form
+#define EVC_ALL_X16_WATCH 1
+#endif
+typedef unsigned all_u32x4 __attribute__((ext_vector_type(4)));
+typedef long long all_i64x2 __attribute__((ext_vector_type(2)));
 
 // Round 5: the member's dictionary in LDS.  Both halves of a workgroup are the same member and read the same 32 exemplar
 // tiles in every step, for the whole launch; streamed from L2 (8 x 16-byte loads per unit and wavefront) the fragments
@@ -124,10 +132,11 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
     constexpr int MSP = (MSTEPS + 1) & ~1;       // k-steps padded to pairs in A1p
     constexpr int PR = S::PR;                    // LDS dictionary: row pitch (doubles)
     constexpr int TPD = 16 * PR;                 // LDS dictionary: doubles per tile
-    __shared__ double s_red[2][AW * RSTR];       // partial V' of every wavefront, per half
-    __shared__ double s_v[2][E];                 // V, B-operand order
-    __shared__ double s_x[2][E];                 // X, B-operand order
-    __shared__ double s_r[2][KL ? E : 1];        // KL: X / max(V, eps), B-operand order
+    // (16-byte aligned: the direct exchange reads and writes pairs of elements)
+    __shared__ __attribute__((aligned(16))) double s_red[2][AW * RSTR];   // partial V' of every wavefront, per half
+    __shared__ __attribute__((aligned(16))) double s_v[2][E];             // V, B-operand order
+    __shared__ __attribute__((aligned(16))) double s_x[2][E];             // X, B-operand order
+    __shared__ __attribute__((aligned(16))) double s_r[2][KL ? E : 1];    // KL: X / max(V, eps), B-operand order
     __shared__ double s_stage[2][S::STG];        // reduce-scatter staging (more than 8 members only)
     __shared__ double s_dict[S::LDS_DICT ? ATILES * TPD : 1];   // the member's dictionary (see AllShape)
     __shared__ unsigned s_hb[2];                 // arrivals of a half's wavefronts at its LDS barrier
@@ -161,6 +170,8 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
     // ~24 cycles beside the MFMAs; the compiler does not select the scalar-base form of global_load for it.)
     const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(A1p), 0, NT * (MSP * 512), 0x00020000);
     const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(A2p), 0, NT * (MT * 2048), 0x00020000);
+    // the direct exchange's buffers, both parities of every group: a group's base rides in the scalar offset
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(a.coop_buf, 0, C > 1 ? 2 * a.groups * (C * 4096) : 0, 0x00020000);
 #ifdef EVC_ALL_NOFRAG
     bool nofrag_go = false;
 #endif
@@ -385,6 +396,99 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (u * 4 + r < MSTEPS) red[w * RSTR + (u * 4 + r) * 64 + lane] = vn[u][r];
+            } else if (C > 1 && EVC_ALL_X16 && valid && !mine && step > 0) {
+                // ---------------- exchange, 2 / 4 / 8 members, on 16-byte words (round 7).  Thread th < NE / 2 owns the
+                // elements 2 th and 2 th + 1: one ds_read_b128 per wavefront's partial, ONE 16-byte sc1 store, and per fetch
+                // round one 16-byte sc1 load per peer (8-byte sc1 accesses run at 0.54 - 0.70 of the 16-byte rate, and a
+                // per-lane 8-byte sc1 store costs 2.7 x the fabric time per byte).  Each 8-byte half still carries its own
+                // epoch bit and is checked by itself: nothing rests on the 16 bytes arriving together.  The sums run in the
+                // same order as in the 8-byte form (wavefronts 0 .. 3, then members 0 .. C - 1): bitwise the same V'.
+                // Threads from NE / 2 on move nothing; a wavefront of such threads only counts the exchange.
+                __builtin_amdgcn_s_setprio(EVC_ALL_EXCH_PRIO);
+                const bool act = th < NE / 2;
+                const int ep = act ? 2 * th : 0;
+                f64x2 sm = {0.0, 0.0};
+                if (w * 64 < NE / 2) {
+                    f64x2 pv[AW];
+#pragma unroll
+                    for (int ww = 0; ww < AW; ++ww) pv[ww] = *reinterpret_cast<const f64x2*>(red + ww * RSTR + ep);
+                    // (the four reads in flight together: one LDS round trip, not four)
+                    static_assert(AW == 4, "the four partials are named one by one");
+                    asm volatile("" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]));
+#pragma unroll
+                    for (int ww = 0; ww < AW; ++ww) sm += pv[ww];
+                    const long long tag = (seq >> 1) & 1;        // a buffer is reused every second exchange
+                    const long long m0 = (__double_as_longlong(sm[0]) & ~1LL) | tag;
+                    const long long m1 = (__double_as_longlong(sm[1]) & ~1LL) | tag;
+                    // byte offset of this exchange's buffer (wave-uniform); member m's words follow at m * 4096
+                    const int xo = __builtin_amdgcn_readfirstlane((int)(((seq & 1) * (unsigned)a.groups + (unsigned)g) * (unsigned)(C * 4096)));
+                    if (act)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(all_u32x4, all_i64x2{m0, m1}), rx, ep * 8,
+                                                               xo + member * 4096, 16);
+                    bool ok = true;
+                    unsigned polls = 0;
+#if EVC_ALL_X16_WATCH
+                    {   // watch one word per peer (lane m <-> member m): C - 1 loads per poll and wavefront
+                        const long long* sp = reinterpret_cast<const long long*>(a.coop_buf) +
+                                              ((size_t)(seq & 1) * a.groups + g) * (size_t)(C * 512) +
+                                              (lane < C ? lane : 0) * 512 + (NE - 1);
+                        for (;;) {
+                            const long long b = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            const bool ready = lane >= C || lane == member || (b & 1) == tag;
+                            if (__all(ready)) break;
+                            if (++polls > ALL_POLL_LIMIT ||
+                                ((polls & 63) == 0 &&
+                                 __hip_atomic_load(a.coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+                                ok = false;
+                                break;
+                            }
+                            __builtin_amdgcn_s_sleep(2);
+                        }
+                    }
+#endif
+                    // every active thread fetches its pair from every peer (its own comes from registers); a half with a
+                    // stale epoch makes the thread fetch again
+                    all_i64x2 b[C > 0 ? C : 1] = {};
+                    polls = 0;
+                    while (__builtin_expect(ok && act, 1)) {        // (runs at least once: laid out in line)
+                        asm volatile("" ::: "memory");      // (the builtin load is not volatile: it stays in the loop)
+#pragma unroll
+                        for (int m = 0; m < C; ++m)
+                            if (m != member)
+                                b[m] = __builtin_bit_cast(all_i64x2, __builtin_amdgcn_raw_buffer_load_b128(rx, ep * 8, xo + m * 4096, 16));
+                        long long bad = 0;
+#pragma unroll
+                        for (int m = 0; m < C; ++m) {
+                            b[m] = (m == member) ? all_i64x2{m0, m1} : b[m];
+                            bad |= (b[m][0] ^ tag) | (b[m][1] ^ tag);
+                        }
+                        if ((bad & 1) == 0) break;
+                        if (++polls > ALL_POLL_LIMIT ||
+                            ((polls & 63) == 0 &&
+                             __hip_atomic_load(a.coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+                            ok = false;
+                            break;
+                        }
+                        __builtin_amdgcn_s_sleep(2);
+                    }
+                    f64x2 v2 = {0.0, 0.0};
+#pragma unroll
+                    for (int m = 0; m < C; ++m) {                 // member order: identical on every member
+                        v2[0] += __longlong_as_double(b[m][0] & ~1LL);
+                        v2[1] += __longlong_as_double(b[m][1] & ~1LL);
+                    }
+                    if (!ok) s_fail = 1;
+                    if (act) {
+                        *reinterpret_cast<f64x2*>(vL + ep) = v2;
+                        if (KL) {
+                            const f64x2 x2 = *reinterpret_cast<const f64x2*>(xL + ep);
+                            *reinterpret_cast<f64x2*>(rL + ep) =
+                                f64x2{x2[0] / (v2[0] < a.eps ? a.eps : v2[0]), x2[1] / (v2[1] < a.eps ? a.eps : v2[1])};
+                        }
+                    }
+                }
+                ++seq;
+                __builtin_amdgcn_s_setprio(0);
             } else if (valid && !mine && step > 0) {
                 // ---------------- exchange: V' = sum over wavefronts and members, no barrier inside
                 // (run-time member counts with M <= 12: fewer elements than threads - several threads carry one element, word
@@ -707,6 +811,8 @@ static hipError_t launch_all(FusedArgs a, int n_cus, hipStream_t s) {
     a.groups = 2 * pairs;
     // stagger (see the kernel): launches of few iterations over many rounds of frame tiles
     a.stagger_cycles = (a.iters > 0 && a.iters <= 25 && a.TT >= 4L * a.groups && pairs >= 2) ? (long long)a.iters * EVC_ALL_STAGGER_PER_ITER : 0;
+    // (the 16-byte exchange words: every group's buffer starts a multiple of 4096 bytes behind this base)
+    if (C > 1 && (reinterpret_cast<uintptr_t>(a.coop_buf) & 15)) return hipErrorInvalidValue;
     if (C != 1) {
         // stale words must not carry the epoch bit of the first two exchanges (0): fill with ones
         e = hipMemsetAsync(a.coop_buf, 0xFF, sizeof(double) * 2 * (size_t)a.groups * cr * (C < 0 ? ALL_RS_STRIDE : 512), s);

@@ -119,6 +119,16 @@ int main(int argc, char** argv) {
         printf("half %d: sweep %.0f cyc (+barrier wait %.0f)   exchange %.0f cyc (+barrier wait %.0f)\n", half,
                sw / ns, bs / ns, ex / ne, be / ne);
     }
+    // the step boundary: from behind the barrier (stamp 2) to the next step's stamp 0 (the s_fail test and the loop's branch)
+    for (int half = 0; half < 2; ++half) {
+        double bd = 0; long nb = 0;
+        for (int b = 0; b < pairs * C; ++b)
+            for (int st = 2; st < NS - 2; ++st) {
+                const long long* d = &dbg[(((size_t)b * 2 + half) * NS + st) * 4];
+                bd += d[4] - d[2]; ++nb;
+            }
+        printf("half %d: step boundary (behind the barrier to the next step) %.0f cyc\n", half, bd / nb);
+    }
     // distribution over workgroups of the exchange length (half 1)
     {
         const int st = 20; double mn = 1e30, mx = 0;
