@@ -7,7 +7,8 @@
 // tiles (512 exemplars): 4 wavefronts x 8 tiles, whose activations AND numerators stay in VGPRs (128 of
 // the 256 registers of a wavefront) for all iterations of a frame tile.  A unit is then 15 MFMAs
 // (D = A_j^T V: 7, V' += A_j H'_j: 8) instead of 20.5 on average, and the only memory traffic of the loop
-// is the dictionary fragments (L2) and the exchange of the partial V' between the members of a group.
+// is the dictionary fragments (LDS where the member's dictionary fits, see AllShape; L2 otherwise) and the
+// exchange of the partial V' between the members of a group.
 //
 // The exchange costs a memory round trip per iteration (measured 3.5 us against a 3.8 us sweep), so it has
 // to hide behind matrix work of ANOTHER frame tile.  Two free-running 4-wavefront workgroups per CU do not
@@ -26,21 +27,25 @@
 // ... (all members of a group walk the same list in lock step), so every member of every group is resident
 // for the whole launch whatever the batch size.
 //
-// Exchange: after the sweep the half's wavefronts leave their partial V' in LDS; in the exchange step every
-// thread sums its elements over the 4 wavefronts in fixed order, publishes them with agent-scope relaxed
-// atomic stores (sc1: past the non-coherent per-XCD L2s) and fetches the same elements of its peers; the
-// lowest mantissa bit of a word is the epoch of the buffer, so data and arrival travel in one word (each
-// wavefront first watches one word per peer, so that the bulk fetch normally succeeds at once).  Every
-// member sums the C words of an element in member order: all obtain the bitwise identical V'.  Two buffers
-// alternate by exchange parity (a member overwrites a buffer two exchanges later, after it has read every
-// peer's words of the exchange in between, which the peer published after reading this member's words of
-// the exchange before).  Every wait is bounded; a member that gives up raises coop_abort, everybody leaves,
-// and the host redoes the solve without inter-workgroup communication (evc_api.hip).
+// Every exchange: after the sweep the half's wavefronts leave their partial V' in LDS; the exchanging threads sum
+// their elements over the 4 wavefronts in fixed order and publish them with agent-scope stores (sc1: past the
+// non-coherent per-XCD L2s); the lowest mantissa bit of a word is the epoch of the buffer, so data and arrival travel
+// in one word.  Two buffers alternate by exchange parity (a member overwrites a buffer two exchanges later, after it
+// has read every peer's words of the exchange in between, which the peer published after reading this member's words
+// of the exchange before).  Every member sums in the same order: all obtain the bitwise identical V'.  Every wait is
+// bounded (all_polls_out); a member that gives up raises coop_abort, everybody leaves, and the host redoes the solve
+// without inter-workgroup communication (evc_api.hip).
 //
-// Other member counts (member count at run time; template C == 0: 16, 32, 64 - whole slices, the lean code of the
-// common sizes; C == -1: 3, 5, 6, 7 and 9 .. 128 - ragged slices): fetching every peer's partial would cost
-// (C - 1) x 3.5 KB per member and exchange, so the exchange becomes a reduce-scatter + all-gather (see the
-// C <= 0 branches): two memory round trips, 7 KB fetched per member whatever C is.
+// Which exchange (pick_c; template C > 0: that many members, C <= 0: member count at run time):
+//   direct (C = 2, 4, 8; 8 only where the dictionary is in LDS): every member fetches every peer's partial,
+//     16-byte words, one memory round trip.  Each wavefront first watches one word per peer, so that the bulk fetch
+//     normally succeeds at once.
+//   reduce-scatter, whole slices (C == 0: 8 members at M 26 .. 28, and 16, 32, 64): fetching every peer's partial
+//     would cost (C - 1) x 3.5 KB per member and exchange, so member m sums slice m of all partials and publishes it,
+//     and everybody fetches the summed slices: two memory round trips, 7 KB fetched per member whatever C is.  Whole
+//     slices: C divides the NE elements.
+//   reduce-scatter, ragged slices (C == -1: 3, 5, 6, 7 and 9 .. 128 members otherwise): the same with ragged slices of
+//     ceil(NE / C) elements, the last ones short or empty.
 // Measured at N = 16384 (C5): 5.8 us per step against 5.2 us at N = 4096, where the sweep is the longer half.
 //
 // Requirements (the host checks them, fused_all_members): guarded eps mode, fast quotients, Frobenius or KL loss, NT a
@@ -55,23 +60,22 @@ constexpr int AKT = 8;                 // exemplar tiles per wavefront, all regi
 constexpr int ATILES = AW * AKT;       // exemplar tiles per member
 constexpr int ATHREADS = 2 * AW * 64;  // two halves per workgroup
 constexpr unsigned ALL_POLL_LIMIT = 1u << 17;
-#ifndef EVC_ALL_STAGGER_PER_ITER
-#define EVC_ALL_STAGGER_PER_ITER 11000     // shader cycles of one iteration of one half (two steps) / 2 ... half a tile's duration = iters x one step
-#endif
-#ifndef EVC_ALL_EXCH_PRIO
-#define EVC_ALL_EXCH_PRIO 3
-#endif
-#ifndef EVC_ALL_C1_ALTERNATE
-#define EVC_ALL_C1_ALTERNATE 0
-#endif
-#ifndef EVC_ALL_X16            // the direct exchange (2, 4, 8 members) moves 16-byte words: one pair of elements per thread
-#define EVC_ALL_X16 1
-#endif
-#ifndef EVC_ALL_X16_WATCH      // ... and first watches one word per peer, like the 8-byte form
-#define EVC_ALL_X16_WATCH 1
-#endif
+constexpr int ALL_STAGGER_PER_ITER = 11000;    // shader cycles of one iteration of one half (two steps) / 2: launch_all
+// Priority of a wavefront while it exchanges.  The exchange is a chain of a few dozen dependent instructions (LDS,
+// stores, polls) on a SIMD whose other wavefront issues MFMAs and vector work back to back; at equal priority the older
+// wavefront wins the issue arbitration, so half 1's exchange (wavefronts 4-7) took 12.8 k cycles where half 0's took
+// 10.4 k (profiles/r04_fused_all_stamps_prio_and_11_tiles.txt).  The exchanging wavefront goes first: its instructions
+// are few, the sweep beside it does not notice.  Both exchanges then take 10.9 k and a C2 step 11.8 k cycles, not 12.6 k.
+constexpr int ALL_EXCH_PRIO = 3;
 typedef unsigned all_u32x4 __attribute__((ext_vector_type(4)));
 typedef long long all_i64x2 __attribute__((ext_vector_type(2)));
+
+// The one bounded wait: has this poll loop run out?  After ALL_POLL_LIMIT polls, or when somebody raised coop_abort
+// (looked at every 64th poll).
+__device__ __forceinline__ bool all_polls_out(unsigned& polls, const int* coop_abort) {
+    return ++polls > ALL_POLL_LIMIT ||
+           ((polls & 63) == 0 && __hip_atomic_load(coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0);
+}
 
 // Round 5: the member's dictionary in LDS.  Both halves of a workgroup are the same member and read the same 32 exemplar
 // tiles in every step, for the whole launch; streamed from L2 (8 x 16-byte loads per unit and wavefront) the fragments
@@ -175,7 +179,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
 #ifdef EVC_ALL_NOFRAG
     bool nofrag_go = false;
 #endif
-    const unsigned ul16 = ul * 16u, ul8 = ul * 8u;
+    const unsigned ul16 = ul * 16u;
     // LDS dictionary (S::LDS_DICT and M < PR): this lane's element of every fragment is one immediate away from one of
     // four addresses - D/P order, its last k-step, V' order, its last bin tile (bins past M: the row's zero slot M)
     constexpr int BL = 16 * ((MSTEPS - 1) >> 2) + 4 * ((MSTEPS - 1) & 3);     // first bin of the last k-step
@@ -237,7 +241,6 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 a2[u][r + 1] = v[1];
             }
     };
-    (void)ul8;
 
     const int mode = a.eps_mode;
     const double eps = a.eps;
@@ -356,7 +359,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
 #endif
             // this half's turn on the matrix pipes.  (One member per frame tile - N <= 512 - has no exchange to hide:
             // both halves then sweep in the same steps, two wavefronts per SIMD.)
-            const bool mine = (C == 1 && !EVC_ALL_C1_ALTERNATE) ? (step & 1) == 0 : (step & 1) == half;
+            const bool mine = C == 1 ? (step & 1) == 0 : (step & 1) == half;
             EVC_STAMP(0);
             if (valid && mine && step < 2 * a.iters) {
                 // ---------------- sweep: h <- h p / (A_j^T V), V' += A_j h over the 8 resident tiles
@@ -396,15 +399,15 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (u * 4 + r < MSTEPS) red[w * RSTR + (u * 4 + r) * 64 + lane] = vn[u][r];
-            } else if (C > 1 && EVC_ALL_X16 && valid && !mine && step > 0) {
+            } else if (C > 1 && valid && !mine && step > 0) {
                 // ---------------- exchange, 2 / 4 / 8 members, on 16-byte words (round 7).  Thread th < NE / 2 owns the
                 // elements 2 th and 2 th + 1: one ds_read_b128 per wavefront's partial, ONE 16-byte sc1 store, and per fetch
                 // round one 16-byte sc1 load per peer (8-byte sc1 accesses run at 0.54 - 0.70 of the 16-byte rate, and a
                 // per-lane 8-byte sc1 store costs 2.7 x the fabric time per byte).  Each 8-byte half still carries its own
                 // epoch bit and is checked by itself: nothing rests on the 16 bytes arriving together.  The sums run in the
-                // same order as in the 8-byte form (wavefronts 0 .. 3, then members 0 .. C - 1): bitwise the same V'.
+                // order wavefronts 0 .. 3, then members 0 .. C - 1 (the 8-byte form it replaced: DESIGN.md 5.1a, round 7).
                 // Threads from NE / 2 on move nothing; a wavefront of such threads only counts the exchange.
-                __builtin_amdgcn_s_setprio(EVC_ALL_EXCH_PRIO);
+                __builtin_amdgcn_s_setprio(ALL_EXCH_PRIO);
                 const bool act = th < NE / 2;
                 const int ep = act ? 2 * th : 0;
                 f64x2 sm = {0.0, 0.0};
@@ -427,8 +430,8 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                                                                xo + member * 4096, 16);
                     bool ok = true;
                     unsigned polls = 0;
-#if EVC_ALL_X16_WATCH
-                    {   // watch one word per peer (lane m <-> member m): C - 1 loads per poll and wavefront
+                    {   // watch one word per peer (lane m <-> member m): C - 1 loads per poll and wavefront.  (Without it the
+                        // exchange is shorter but its polls lengthen the sweep beside it: profiles/r07_README.md)
                         const long long* sp = reinterpret_cast<const long long*>(a.coop_buf) +
                                               ((size_t)(seq & 1) * a.groups + g) * (size_t)(C * 512) +
                                               (lane < C ? lane : 0) * 512 + (NE - 1);
@@ -436,16 +439,13 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                             const long long b = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             const bool ready = lane >= C || lane == member || (b & 1) == tag;
                             if (__all(ready)) break;
-                            if (++polls > ALL_POLL_LIMIT ||
-                                ((polls & 63) == 0 &&
-                                 __hip_atomic_load(a.coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+                            if (all_polls_out(polls, a.coop_abort)) {
                                 ok = false;
                                 break;
                             }
                             __builtin_amdgcn_s_sleep(2);
                         }
                     }
-#endif
                     // every active thread fetches its pair from every peer (its own comes from registers); a half with a
                     // stale epoch makes the thread fetch again
                     all_i64x2 b[C > 0 ? C : 1] = {};
@@ -463,9 +463,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                             bad |= (b[m][0] ^ tag) | (b[m][1] ^ tag);
                         }
                         if ((bad & 1) == 0) break;
-                        if (++polls > ALL_POLL_LIMIT ||
-                            ((polls & 63) == 0 &&
-                             __hip_atomic_load(a.coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
+                        if (all_polls_out(polls, a.coop_abort)) {
                             ok = false;
                             break;
                         }
@@ -495,13 +493,8 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 // for word; a thread beyond NE used to poll a word of the summed slices that nobody writes)
                 const int e0 = C <= 0 ? th % NE : th, e1 = th + AW * 64;
                 const bool has1 = e1 < NE;
-                // Round 4: the exchange is a chain of a few dozen dependent instructions (LDS, stores, polls) on a SIMD
-                // whose other wavefront issues MFMAs and vector work back to back; at equal priority the older wavefront
-                // wins the issue arbitration, so half 1's exchange (wavefronts 4-7) took 12.8 k cycles where half 0's
-                // took 10.4 k (profiles/r04_fused_all_stamps_prio_and_11_tiles.txt).  The exchanging wavefront goes
-                // first while it exchanges: its instructions are few, the sweep beside it does not notice.  Both
-                // exchanges then take 10.9 k and a C2 step 11.8 k cycles instead of 12.6 k.
-                __builtin_amdgcn_s_setprio(EVC_ALL_EXCH_PRIO);
+                // (the exchanging wavefront goes first: ALL_EXCH_PRIO)
+                __builtin_amdgcn_s_setprio(ALL_EXCH_PRIO);
                 double s0 = 0.0, s1 = 0.0;
 #pragma unroll
                 for (int ww = 0; ww < AW; ++ww) {
@@ -536,9 +529,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                             b1 = __hip_atomic_load(p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             b2 = __hip_atomic_load(p2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             if (__all(!ok || (((b0 ^ tag) | (b1 ^ tag) | (b2 ^ tag)) & 1) == 0)) break;
-                            if (++polls > ALL_POLL_LIMIT ||
-                                ((polls & 63) == 0 &&
-                                 __hip_atomic_load(a.coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
+                            if (all_polls_out(polls, a.coop_abort))
                                 ok = false;
                             __builtin_amdgcn_s_sleep(1);
                         }
@@ -581,11 +572,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                     if (!ok) s_fail = 1;
                 } else if (C == 0) {
                     // ---- 16, 32 or 64 members (N = 8192, 16384, 32768): the same reduce-scatter with whole slices
-                    // (CR divides NE) and two words per thread: the leaner code of the common sizes.  (original note:) reduce-scatter + all-gather.  Fetching every member's
-                    // partial (C - 1 x 3.5 KB per member and exchange: 108 KB at C = 32) would make the exchange far
-                    // longer than the sweep it hides behind.  Instead member m sums slice m (NE / C elements) of
-                    // all C partials and publishes it; everybody then fetches the C summed slices: 7 KB per member
-                    // and exchange whatever C is, for a second memory round trip - which the alternation hides.
+                    // (CR divides NE) and two words per thread: the leaner code of the common sizes.
                     const int ES = NE / CR;                          // elements per slice (CR divides 64)
                     long long* xb1 = reinterpret_cast<long long*>(a.coop_buf) +
                                      ((size_t)(seq & 1) * a.groups + g) * (size_t)CR * 512;
@@ -611,9 +598,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                             b0 = __hip_atomic_load(p0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             b1 = __hip_atomic_load(p1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             if (__all(!ok || (((b0 ^ tag) | (b1 ^ tag)) & 1) == 0)) break;
-                            if (++polls > ALL_POLL_LIMIT ||
-                                ((polls & 63) == 0 &&
-                                 __hip_atomic_load(a.coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0))
+                            if (all_polls_out(polls, a.coop_abort))
                                 ok = false;
                             __builtin_amdgcn_s_sleep(1);
                         }
@@ -653,66 +638,6 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                     fetch2(xb2 + e0, xb2 + (has1 ? e1 : e0), g0, g1);
                     s0 = __longlong_as_double(g0 & ~1LL);
                     s1 = __longlong_as_double(g1 & ~1LL);
-                    ++seq;
-                    if (!ok) s_fail = 1;
-                } else if (C > 1) {
-                    long long* xb = reinterpret_cast<long long*>(a.coop_buf) +
-                                    ((size_t)(seq & 1) * a.groups + g) * (size_t)(C * 512);
-                    const long long tag = (seq >> 1) & 1;        // a buffer is reused every second exchange
-                    const long long m0 = (__double_as_longlong(s0) & ~1LL) | tag;
-                    const long long m1 = (__double_as_longlong(s1) & ~1LL) | tag;
-                    __hip_atomic_store(xb + member * 512 + e0, m0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (has1) __hip_atomic_store(xb + member * 512 + e1, m1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    bool ok = true;
-                    unsigned polls = 0;
-                    {   // watch one word per peer (lane m <-> member m): C - 1 loads per poll and wavefront
-                        const long long* sp = xb + (lane < C ? lane : 0) * 512 + (NE - 1);
-                        for (;;) {
-                            const long long b = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            const bool ready = lane >= C || lane == member || (b & 1) == tag;
-                            if (__all(ready)) break;
-                            if (++polls > ALL_POLL_LIMIT ||
-                                ((polls & 63) == 0 &&
-                                 __hip_atomic_load(a.coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                                ok = false;
-                                break;
-                            }
-                            __builtin_amdgcn_s_sleep(2);
-                        }
-                    }
-                    // every thread fetches its elements of all members; each word carries its own epoch bit, so
-                    // a word that lags behind the watched one is simply fetched again
-                    long long b0[C > 0 ? C : 1] = {}, b1[C > 0 ? C : 1] = {};
-                    polls = 0;
-                    while (ok) {
-#pragma unroll
-                        for (int m = 0; m < C; ++m)
-                            b0[m] = __hip_atomic_load(xb + m * 512 + e0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                        for (int m = 0; m < C; ++m)     // (threads without a second element re-read their first)
-                            b1[m] = __hip_atomic_load(xb + m * 512 + (has1 ? e1 : e0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        long long bad = 0;
-#pragma unroll
-                        for (int m = 0; m < C; ++m) {
-                            b0[m] = (m == member) ? m0 : b0[m];
-                            b1[m] = (m == member) ? m1 : b1[m];
-                            bad |= (b0[m] ^ tag) | (b1[m] ^ tag);
-                        }
-                        if ((bad & 1) == 0) break;
-                        if (++polls > ALL_POLL_LIMIT ||
-                            ((polls & 63) == 0 &&
-                             __hip_atomic_load(a.coop_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) {
-                            ok = false;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(2);
-                    }
-                    s0 = 0.0; s1 = 0.0;
-#pragma unroll
-                    for (int m = 0; m < C; ++m) {                 // member order: identical on every member
-                        s0 += __longlong_as_double(b0[m] & ~1LL);
-                        s1 += __longlong_as_double(b1[m] & ~1LL);
-                    }
                     ++seq;
                     if (!ok) s_fail = 1;
                 }
@@ -810,7 +735,7 @@ static hipError_t launch_all(FusedArgs a, int n_cus, hipStream_t s) {
     if (pairs < 1) return hipErrorInvalidValue;
     a.groups = 2 * pairs;
     // stagger (see the kernel): launches of few iterations over many rounds of frame tiles
-    a.stagger_cycles = (a.iters > 0 && a.iters <= 25 && a.TT >= 4L * a.groups && pairs >= 2) ? (long long)a.iters * EVC_ALL_STAGGER_PER_ITER : 0;
+    a.stagger_cycles = (a.iters > 0 && a.iters <= 25 && a.TT >= 4L * a.groups && pairs >= 2) ? (long long)a.iters * ALL_STAGGER_PER_ITER : 0;
     // (the 16-byte exchange words: every group's buffer starts a multiple of 4096 bytes behind this base)
     if (C > 1 && (reinterpret_cast<uintptr_t>(a.coop_buf) & 15)) return hipErrorInvalidValue;
     if (C != 1) {

@@ -1,4 +1,4 @@
-"""k_fused_all's direct exchange on 16-byte words (evc_fused_all.hip, EVC_ALL_X16), without a GPU.
+"""k_fused_all's direct exchange on 16-byte words (evc_fused_all.hip), without a GPU.
 
 * A numpy mirror of the pair ownership for every k-step count 1 .. 8: thread th < NE / 2 of the exchanging half owns the
   elements 2 th and 2 th + 1; every element is published exactly once, every access is 16-byte aligned and inside the
@@ -9,6 +9,8 @@
   C - 1 execute.  The loads sit in the poll loop.  The only 8-byte agent-scope load left is the watch word (one per
   wavefront and poll), the only 4-byte one the abort word; no 8-byte agent-scope store is left.  The other instances keep
   their 8-byte words.  No kernel holds a scalar store to memory, a scalar atomic or a scalar-cache write-back.
+* Every instance of the kernel is there, and in none does a scratch access stand inside a cluster of MFMAs: whatever the
+  register allocator spills, it does not spill inside a unit of the sweep.
 """
 import os
 import re
@@ -160,6 +162,31 @@ def test_code_object_exchanges_16_byte_words(device_asm):
             if re.search(LD8, l):
                 assert loop_depth(lines, i) == 3, (ms, c, kl, i, l)
     assert seen == 8 * 2 * 2 + 7          # C = 2, 4: every k-step count, both losses; C = 8: where the dictionary fits
+
+
+def test_no_scratch_access_inside_a_cluster_of_mfmas(device_asm):
+    """A cluster is a run of MFMAs at most 60 lines apart: a unit of the sweep, or the numerator pass.  (The definition
+    is tools/spill_audit.py's, repeated here: that tool prints, it has no function to share.)  The kernel's text runs to
+    the end of the function, past every early exit."""
+    lines = device_asm.split("\n")
+    starts = [i for i, l in enumerate(lines) if re.match(r"_ZN3evc11k_fused_allILi\dELin?\d+ELb[01]EEEvNS_9FusedArgsE:", l)]
+    # k-steps 1 .. 8 x both losses x C = 1, 2, 4, 0, -1, and C = 8 where the dictionary fits in LDS (Frobenius, k-steps <= 7)
+    assert len(starts) == 8 * 2 * 5 + 7
+    for start in starts:
+        name = lines[start].split(":")[0]
+        end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
+        body = lines[start:end]
+        clusters = []
+        for i, l in enumerate(body):
+            if "v_mfma" in l:
+                if clusters and i - clusters[-1][1] <= 60:
+                    clusters[-1][1] = i
+                else:
+                    clusters.append([i, i])
+        assert clusters, name
+        inside = [body[i].strip() for i, l in enumerate(body)
+                  if "scratch_" in l and any(lo <= i <= hi for lo, hi in clusters)]
+        assert not inside, (name, inside[:4])
 
 
 def test_no_kernel_writes_memory_from_the_scalar_unit(device_asm):

@@ -1,10 +1,10 @@
-"""k_fused_all's direct exchange on 16-byte words (evc_fused_all.hip, EVC_ALL_X16: 2, 4 and 8 members) against the float64
+"""k_fused_all's direct exchange on 16-byte words (evc_fused_all.hip: 2, 4 and 8 members) against the float64
 oracle and the kernels without an exchange (`-m gpu`).
 
 Thread th of the exchanging half owns the elements 2 th and 2 th + 1 of V' (th < NE / 2 = 32 k-steps): M = 25, 21, 17, 13, 9
 and 5 have an odd k-step count, so the half's last working wavefront is half filled; M = 1 and 4 leave three of its four
 wavefronts without work, M = 12 and 24 (3 and 6 k-steps) one.  Every shape runs with 2, 4 and 8 members, with and without
-L1, from constant and from given start values.  The sums run in the order of the 8-byte exchange, so batch = solo and
+L1, from constant and from given start values.  The sums run in a fixed order (wavefronts, then members), so batch = solo and
 run = re-run hold bitwise, and a voided launch is redone to the result of a call that never exchanged.
 """
 import numpy as np

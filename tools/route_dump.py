@@ -132,6 +132,13 @@ def solve_cases():
         add("fake=%s_staged" % fake, "f32", 25, 4096, 2, **kw)
         add("fake=%s_wide" % fake, "f32", 201, 4096, 2, **kw)
         add("fake=%s_wide64" % fake, "f64", 513, 1024, 3, **kw)
+    # k_fused_all, one utterance of 90 frames: every exchange body and both fragment sources.  2 and 4 members (direct,
+    # dictionary in LDS), 3 members (ragged slices), M = 12 (ragged, fewer elements than threads), 8 members at M = 28
+    # (whole slices, dictionary streamed), 16 members; KL with one member and with 16
+    for M, N in ((25, 1024), (25, 2048), (25, 1536), (12, 1536), (28, 4096), (25, 8192)):
+        add("f64_m%d_n%d_t90" % (M, N), "f64", M, N, 1, frames=90)
+    for N in (512, 8192):
+        add("f64_m25_n%d_t90_kl" % N, "f64", 25, N, 1, frames=90, loss="kl", eps_mode="zero_replace")
     return cases
 
 
