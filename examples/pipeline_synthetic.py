@@ -8,7 +8,9 @@
                              Y = H.T @ B, Griffin-Lim                         compat.griffin_lim
 
 The DTW features of the reference are librosa MFCCs (absent here); a 25-band log-magnitude stands in.
-usage: python examples/pipeline_synthetic.py [n_pairs] [seconds per utterance]
+With --compact R the parallel dictionary is also compacted on the GPU, [A; B] ~ [Wa; Wb] G with R components
+(compact_dictionary), and the utterance converted with the compact pair (Wa, Wb) in place of every aligned frame.
+usage: python examples/pipeline_synthetic.py [n_pairs] [seconds per utterance] [--compact R]
 """
 import os
 import sys
@@ -51,7 +53,7 @@ def spectral_distance(a, b):
     return float(np.mean(np.abs(np.log(np.abs(a[:n]) + 1e-4) - np.log(np.abs(b[:n]) + 1e-4))))
 
 
-def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True):
+def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True, compact=0):
     src_f = [(700, 130), (1200, 160), (2600, 250)]
     tar_f = [(850, 130), (1500, 180), (2900, 250)]
     say = print if verbose else (lambda *a, **k: None)
@@ -100,6 +102,23 @@ def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True):
                                tol=1e-4)
         assert np.allclose(Y_d, converted, rtol=1e-3, atol=1e-6 * float(np.abs(converted).max()))
         say(f"dictionary on the device (DTW + gather + prepare, no frame leaves the GPU): {t_pd * 1e3:.1f} ms")
+        compacted = None
+        if compact:
+            # a compact parallel dictionary: R components learnt jointly from the stacked aligned frames
+            from exemplars_vc_amd import compact_dictionary, dtw_dictionary
+            A_d, B_d, _ = dtw_dictionary([band_log_mag(f["stft"]) for f in src_feat],
+                                         [band_log_mag(f["stft"]) for f in tar_feat],
+                                         [np.asarray(f["stft"]) for f in src_feat],
+                                         [np.asarray(f["stft"]) for f in tar_feat], op="abs", real_part=True)
+            t4 = time.perf_counter()
+            cpd, _, cinfo = compact_dictionary(A_d, B_d, compact, iters=100, layout="frame_major", prepared=True)
+            t_c = time.perf_counter() - t4
+            x_c = np.abs(np.asarray(tobe["real"])).astype(np.float32 if cpd.dcode else np.float64)
+            compacted = evc_convert(cpd, x_c, layout="frame_major", iters=150, eps_mode="zero_replace", init="sklearn",
+                                    want_h=False)
+            e = cinfo["err"]
+            say(f"compact dictionary: {N} exemplars -> {compact} components in {cinfo['n_iter']} iterations "
+                f"({t_c * 1e3:.1f} ms), relative error {e[0] / e[0]:.3f} -> {e[np.isfinite(e)][-1] / e[0]:.3f}")
         np.random.seed(0)
         t2 = time.perf_counter()
         wav, wav_path = griffin_lim.synthesize2(converted, FS, "converted", out_dir=os.path.join(root, "wav"),
@@ -116,9 +135,18 @@ def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True):
     say(f"conversion: {converted.shape[0]} frames x {converted.shape[1]} bins, H {H['H_stft'].shape} "
         f"{H['H_stft'].dtype} ({t_conv * 1e3:.1f} ms); Griffin-Lim {gl_iters} iterations ({t_gl * 1e3:.1f} ms)")
     say(f"log-spectral distance to the target speaker: source {d_before:.3f} -> converted {d_after:.3f}")
-    return {"N": N, "converted": converted, "wav": wav, "H": H["H_stft"], "d_before": d_before, "d_after": d_after}
+    res = {"N": N, "converted": converted, "wav": wav, "H": H["H_stft"], "d_before": d_before, "d_after": d_after}
+    if compacted is not None:
+        res.update(compacted=compacted, d_compact=spectral_distance(compacted, want))
+        say(f"  ... with the compact dictionary ({compact} components): {res['d_compact']:.3f}")
+    return res
 
 
 if __name__ == "__main__":
     a = sys.argv[1:]
-    main(int(a[0]) if a else 6, float(a[1]) if len(a) > 1 else 1.0)
+    r = 0
+    if "--compact" in a:
+        i = a.index("--compact")
+        r = int(a[i + 1])
+        del a[i:i + 2]
+    main(int(a[0]) if a else 6, float(a[1]) if len(a) > 1 else 1.0, compact=r)

@@ -20,6 +20,7 @@ INIT_GIVEN, INIT_SKLEARN, INIT_CONST = 0, 1, 2
 STOP_NONE, STOP_SKLEARN, STOP_PYMF = 0, 1, 2
 LOSS_FROBENIUS, LOSS_KL = 0, 1
 FLAG_NO_FUSED, FLAG_EXACT_DIV, FLAG_NO_EXCHANGE, FLAG_NO_ALL_RESIDENT, FLAG_PAIR_TILES = 1, 2, 4, 16, 32
+LEARN_SKLEARN, LEARN_PYMF = 0, 1
 
 # every symbol include/evc.h declares; tests check that the library exports all of them
 SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_bytes",
@@ -27,7 +28,8 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_griffin_lim_workspace_bytes", "evc_griffin_lim", "evc_griffin_lim_batch_workspace_bytes",
            "evc_griffin_lim_batch", "evc_dtw_workspace_bytes", "evc_dtw_align",
            "evc_stft_frames", "evc_stft_workspace_bytes", "evc_stft", "evc_dict_bytes", "evc_dict_prepare",
-           "evc_dtw_path_rows", "evc_dtw_gather_rows", "evc_cd_workspace_bytes", "evc_cd_solve")
+           "evc_dtw_path_rows", "evc_dtw_gather_rows", "evc_cd_workspace_bytes", "evc_cd_solve",
+           "evc_learn_workspace_bytes", "evc_learn_splits", "evc_nmf_learn")
 
 
 class SolveOpts(C.Structure):
@@ -48,6 +50,16 @@ class CdOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("init_mode", C.c_int),
         ("max_iter", C.c_int), ("reserved", C.c_int),
         ("tol", C.c_double), ("l1", C.c_double), ("l2", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class LearnOpts(C.Structure):
+    """Mirror of `evc_learn_opts` (include/evc.h): options of the solve that also learns the dictionary."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("surface", C.c_int),
+        ("iters", C.c_int), ("check_every", C.c_int), ("reserved", C.c_int),
+        ("tol", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -180,6 +192,18 @@ def lib():
         C.POINTER(C.c_int), C.c_int, C.POINTER(CdOpts),                     # utt_offsets, n_utt, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, violation_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_learn_workspace_bytes.restype = C.c_size_t
+    L.evc_learn_workspace_bytes.argtypes = [C.c_int] * 4
+    L.evc_learn_splits.restype = C.c_int
+    L.evc_learn_splits.argtypes = [C.c_int] * 3
+    L.evc_nmf_learn.restype = C.c_int
+    L.evc_nmf_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, W, H
+        C.c_int, C.c_int, C.c_int, C.POINTER(LearnOpts),                    # M, R, T, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
         C.c_void_p,                                                         # stream
     ]
     _lib = L

@@ -15,7 +15,7 @@ import warnings
 
 import numpy as np
 
-from ..solver import convert as _solve_and_synthesize, solve_activations, synthesize
+from ..solver import convert as _solve_and_synthesize, learn_dictionary, solve_activations, synthesize
 
 try:  # same warning class the reference would raise, when scikit-learn is present
     from sklearn.exceptions import ConvergenceWarning
@@ -106,6 +106,26 @@ def _factorize_impl(X, W, beta_loss, tol, device, algo, honor_beta_loss, hint, w
         _warn(f"Maximum number of iterations {MAX_ITER} reached. Increase it to improve convergence.",
               ConvergenceWarning, 3)
     return act.T, recon
+
+
+def non_negative_factorization_mu(X, W, H, update_H=True, tol=1e-4, max_iter=200, *, device=None):
+    """scikit-learn's `non_negative_factorization(X, W, H, init='custom', update_H=update_H, solver='mu',
+    beta_loss='frobenius', tol=tol, max_iter=max_iter)` on the GPU, in scikit-learn's orientation: X (n_samples,
+    n_features), W (n_samples, n_components) the activations, H (n_components, n_features) the dictionary.  Returns
+    (W, H, n_iter).  update_H=True learns the dictionary too (evc_nmf_learn); update_H=False is the fixed-dictionary
+    solve of _factorize with the given start."""
+    X = np.asarray(X)
+    if update_H:
+        # frame-major: X[t][m], the dictionary (the solver's W) as H[r][m], the activations (its H) as W[t][r]
+        Hd, Wa, info = learn_dictionary(X, np.asarray(H, dtype=X.dtype), np.asarray(W, dtype=X.dtype),
+                                        layout="frame_major", iters=int(max_iter), surface="sklearn",
+                                        check_every=10 if tol > 0 else 0, tol=float(tol), device=device, info=True)
+        return Wa, Hd, info["n_iter"]
+    act, info = solve_activations(np.asarray(H, dtype=X.dtype), X, np.asarray(W, dtype=X.dtype), layout="frame_major",
+                                  iters=int(max_iter), eps_mode="zero_replace", init="given",
+                                  check_every=10 if tol > 0 else 0, stop_rule="sklearn" if tol > 0 else "none",
+                                  tol=float(tol), device=device, info=True)
+    return act, np.asarray(H), int(info["n_iter"][0])
 
 
 def factorize_utterances(X_list, W, tol=1e-4, *, device=None, algo="auto", max_iter=MAX_ITER, hint="throughput",

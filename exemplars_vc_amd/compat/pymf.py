@@ -9,6 +9,8 @@ Only the fixed-dictionary path (`compute_w=False`) is the accelerated path.  pym
 iteration) then runs on the host in numpy, as SURVEY 8(b) S2 allows, while every activation
 update still goes through the GPU solver - a drop-in must not raise on the default arguments
 (round 3 did).  A RuntimeWarning says so once per call.
+`NMF(..., dictionary_update="device")` opts in to the accelerated loop instead: both updates run on the GPU in one
+call (evc_nmf_learn, pymf surface), W and H are updated in place and `ferr` is as pymf makes it.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import logging
 
 import numpy as np
 
-from ..solver import frame_residuals, solve_activations, synthesize
+from ..solver import frame_residuals, learn_dictionary, solve_activations, synthesize
 
 _EPS = np.finfo(float).eps
 
@@ -31,6 +33,9 @@ class NMF:
         self._data_dimension, self._num_samples = self.data.shape
         self._device = kwargs.get("device")
         self._algo = kwargs.get("algo", "auto")
+        self._dictionary_update = kwargs.get("dictionary_update", "host")
+        if self._dictionary_update not in ("host", "device"):
+            raise ValueError("dictionary_update must be 'host' or 'device'")
 
     # -- pymf/base.py:133-165 --
     def residual(self):
@@ -59,6 +64,34 @@ class NMF:
         self.W *= np.dot(self.data, self.H.T)
         self.W /= W2
         self.W /= np.sqrt(np.sum(self.W ** 2.0, axis=0))
+
+    def _factorize_on_device(self, niter, compute_err):
+        """pymf/base.py:238-270 with compute_w=True in one native call: per iteration W, then H, then the error and
+        the machine-epsilon stop test; W and H are updated in place"""
+        if not hasattr(self, "W"):
+            self._init_w()
+        if not hasattr(self, "H"):
+            self._init_h()
+        if compute_err:
+            self.ferr = np.zeros(niter)
+        if niter <= 0:
+            return
+        W, H, info = learn_dictionary(
+            np.asarray(self.data, dtype=np.float64), np.asarray(self.W, dtype=np.float64),
+            np.asarray(self.H, dtype=np.float64), layout="bin_major", iters=niter, surface="pymf",
+            check_every=1 if compute_err else 0, tol=self._EPS if compute_err else 0.0, dtype="f64",
+            device=self._device, info=True)
+        self.W[...] = W
+        self.H[...] = H
+        if compute_err:
+            n = info["n_iter"]
+            ferr = info["err"][1:1 + n]
+            if n < niter or (n >= 3 and abs(ferr[n - 1] - ferr[n - 2]) / self._num_samples < self._EPS):
+                self.ferr = ferr[:n - 1].copy()     # base.py:268: ferr = ferr[:i], i = n - 1
+            else:
+                self.ferr[:n] = ferr
+            for i, e in enumerate(self.ferr):
+                self._logger.info("FN: %s (%s/%s)" % (e, i + 1, niter))
 
     def _factorize_with_dictionary_update(self, niter, compute_h, compute_err):
         """pymf/base.py:238-270 with compute_w=True: per iteration W (host), then H (one update on the GPU), then the
@@ -96,6 +129,8 @@ class NMF:
             self._logger.setLevel(logging.INFO)
         else:
             self._logger.setLevel(logging.ERROR)
+        if compute_w and compute_h and self._dictionary_update == "device":
+            return self._factorize_on_device(niter, compute_err)
         if compute_w:
             return self._factorize_with_dictionary_update(niter, compute_h, compute_err)
         if not hasattr(self, "W"):

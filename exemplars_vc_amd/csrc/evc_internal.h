@@ -354,4 +354,28 @@ int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int
              int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
              hipStream_t s, int* launches_out);
 
+// ----- evc_learn.hip: the dictionary update of evc_nmf_learn -----
+constexpr int LEARN_MAX_M = 1056;     // 66 bin tiles of 16
+constexpr int LEARN_MAX_R = 4096;
+constexpr int LEARN_MAX_SPLITS = 64;  // frame ranges (slabs of partial sums) per launch
+constexpr int DG_MB = 4;              // bin tiles of 16 per workgroup of k_dict_grad
+constexpr int DG_RB = 2;              // component tiles of 16 per wavefront
+constexpr int DG_WAVES = 4;           // wavefronts per workgroup: DG_WAVES * DG_RB * 16 = 128 components
+// bin tiles per operand, padded to whole workgroups
+inline int learn_bin_tiles(int M) { return round_up(round_up(M, 16) / 16, DG_MB); }
+// frame ranges of the split-T contraction: a function of the sizes only (never of the device)
+int learn_splits(int M, int R, int T_);
+// part[s][which][m][r] = sum over the s-th frame range of L[t][m] Ht[t][r], L = Xt (which 0) | Vt (which 1); frames as
+// rows, Ht padded to ldh = round_up(R, 128) columns; a slab (one `which` of one s) is learn_bin_tiles(M) * 16 * ldh elements
+template <typename T>
+hipError_t dict_grad(const T* Xt, int ldx, const T* Vt, int ldv, const T* Ht, int ldh, int M, int T_, int S, T* part,
+                     hipStream_t s);
+// W <- update(W, sum_s part[s][0], sum_s part[s][1]) in the surface's literal operation order (EVC_LEARN_*), on the
+// caller's W (bin_major: W[m ldw + r], else W[r ldw + m]); pymf: then every column divided by its Euclidean norm
+template <typename T>
+hipError_t dict_apply(const T* part, int S, int ldp, T* W, long ldw, int bin_major, int M, int R, int surface,
+                      hipStream_t s);
+// *out = sqrt(sum_t err2[t]), summed in a fixed order
+hipError_t err_total(const double* err2, int T_, double* out, hipStream_t s);
+
 }  // namespace evc

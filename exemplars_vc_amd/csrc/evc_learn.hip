@@ -1,0 +1,177 @@
+// The dictionary update of evc_nmf_learn: W <- W (.) (X H^T) (/) ((W H) H^T), evaluated factored.
+//
+//   k_dict_grad   the split-T "TN" contraction C[m][r] = sum_t L[t][m] Ht[t][r] on the 16x16x4 MFMA, for the stacked left
+//                 operand L = [X; V] (V = W H comes from the existing contraction).  A workgroup owns DG_MB bin tiles of
+//                 one operand x 128 components x one contiguous frame range; its accumulators stay in registers for the
+//                 whole range and leave as one slab of partial sums.  Operands go from global memory straight into the
+//                 MFMA (frames as rows: 16 consecutive bins / components of one frame per quarter wavefront, 128-byte
+//                 rows); the wavefronts of a workgroup share the bin tiles through the vector cache.
+//   k_dict_apply  sums the slabs in the order s = 0 .. S-1 and applies the surface's update to the caller's W.
+//   k_dict_colnorm  pymf: every column divided by its Euclidean norm (sum of squares over the bins in ascending order).
+//   k_err_total   sqrt of the sum of the per-frame squared residuals, in a fixed order.
+// Nothing here exchanges data between workgroups inside a launch, uses atomics or assumes residency: the same call gives
+// bitwise the same W every time.
+#include "evc_internal.h"
+
+namespace evc {
+
+int learn_splits(int M, int R, int T_) {
+    const int blocks = (round_up(R, 128) / 128) * (2 * learn_bin_tiles(M) / DG_MB);
+    int S = (1024 + blocks - 1) / blocks;          // about four workgroups per compute unit of a 256-CU device
+    S = S < T_ / 256 ? S : T_ / 256;               // ... of at least 256 frames each
+    S = S > LEARN_MAX_SPLITS ? LEARN_MAX_SPLITS : S;
+    return S < 1 ? 1 : S;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64 * DG_WAVES) void k_dict_grad(const T* __restrict__ Xt, int ldx, const T* __restrict__ Vt,
+                                                             int ldv, const T* __restrict__ Ht, int ldh, int MT, int MTp,
+                                                             int T_, int S, T* __restrict__ part) {
+    typedef typename Mma<T>::acc_t acc_t;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int bpo = MTp / DG_MB;                   // workgroups per operand along the bins
+    const int which = blockIdx.y / bpo;
+    const int tile0 = (blockIdx.y % bpo) * DG_MB;
+    const int r0 = (blockIdx.x * DG_WAVES + wave) * DG_RB * 16;
+    const int sp = blockIdx.z;
+    const int tb = (int)((long)sp * T_ / S), te = (int)((long)(sp + 1) * T_ / S);
+    const T* __restrict__ L = which ? Vt : Xt;
+    const int ldl = which ? ldv : ldx;
+    int moff[DG_MB];
+#pragma unroll
+    for (int i = 0; i < DG_MB; ++i) {              // tiles past the last one repeat it: their sums land in padding
+        const int tile = tile0 + i < MT ? tile0 + i : MT - 1;
+        moff[i] = tile * 16 + (lane & 15);
+    }
+    acc_t acc[DG_MB][DG_RB];
+#pragma unroll
+    for (int i = 0; i < DG_MB; ++i)
+#pragma unroll
+        for (int j = 0; j < DG_RB; ++j) acc[i][j] = acc_t{0, 0, 0, 0};
+    const int hoff = r0 + (lane & 15);
+    // one step = 4 frames; the next step's operands are loaded before the current step's MFMAs are issued
+    auto load = [&](int t, T (&a)[DG_MB], T (&b)[DG_RB]) {
+        const int tt = t + (lane >> 4);
+        const bool live = tt < te;                 // a ragged range: the frames past its end contribute zeros
+        const long row = live ? tt : te - 1;
+        const T* __restrict__ lrow = L + row * ldl;
+        const T* __restrict__ hrow = Ht + row * ldh + hoff;
+#pragma unroll
+        for (int i = 0; i < DG_MB; ++i) a[i] = lrow[moff[i]];
+#pragma unroll
+        for (int j = 0; j < DG_RB; ++j) b[j] = hrow[16 * j];
+#pragma unroll
+        for (int i = 0; i < DG_MB; ++i) a[i] = live ? a[i] : T(0);
+#pragma unroll
+        for (int j = 0; j < DG_RB; ++j) b[j] = live ? b[j] : T(0);
+    };
+    T a[DG_MB], b[DG_RB];
+    if (tb < te) load(tb, a, b);
+    for (int t = tb; t < te; t += 4) {
+        T an[DG_MB], bn[DG_RB];
+        load(t + 4, an, bn);                       // past the end: the clamped row, masked to zeros, never used
+#pragma unroll
+        for (int i = 0; i < DG_MB; ++i)
+#pragma unroll
+            for (int j = 0; j < DG_RB; ++j) acc[i][j] = Mma<T>::mma(a[i], b[j], acc[i][j]);
+#pragma unroll
+        for (int i = 0; i < DG_MB; ++i) a[i] = an[i];
+#pragma unroll
+        for (int j = 0; j < DG_RB; ++j) b[j] = bn[j];
+    }
+    const long slab = (long)MTp * 16 * ldh;
+    T* __restrict__ out = part + ((long)sp * 2 + which) * slab;
+#pragma unroll
+    for (int i = 0; i < DG_MB; ++i)
+#pragma unroll
+        for (int j = 0; j < DG_RB; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                out[(long)((tile0 + i) * 16 + Mma<T>::row(lane, r)) * ldh + hoff + 16 * j] = acc[i][j][r];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_dict_apply(const T* __restrict__ part, int S, long slab, int ldp, T* __restrict__ W,
+                                                    long ldw, int bin_major, int M, int R, int surface) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)M * R) return;
+    // the caller's inner index is the fastest one here
+    const int m = bin_major ? (int)(idx / R) : (int)(idx % M);
+    const int r = bin_major ? (int)(idx % R) : (int)(idx / M);
+    const T* __restrict__ p = part + (long)m * ldp + r;
+    T num = T(0), den = T(0);
+    for (int s = 0; s < S; ++s) {
+        num += p[(long)s * 2 * slab];
+        den += p[((long)s * 2 + 1) * slab];
+    }
+    T* w = W + (bin_major ? m * ldw + r : r * ldw + m);
+    if (surface == EVC_LEARN_PYMF) {               // pymf nmf.py:72-76: W *= num; W /= (den + 1e-9)
+        *w = (*w * num) / (den + T(1e-9));
+    } else {                                       // sklearn _nmf.py:620-629 with the roles swapped
+        den = den == T(0) ? T(1.1920929e-7) : den;
+        *w = *w * (num / den);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_dict_colnorm(T* __restrict__ W, long ldw, int bin_major, int M, int R) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const long sm = bin_major ? ldw : 1;
+    T* __restrict__ col = W + (bin_major ? (long)r : r * ldw);
+    T ss = T(0);
+    for (int m = 0; m < M; ++m) {
+        const T v = col[m * sm];
+        ss += v * v;
+    }
+    const T n = sqrt(ss);                          // a zero column: 0 / 0 = NaN, as in pymf
+    for (int m = 0; m < M; ++m) col[m * sm] = col[m * sm] / n;
+}
+
+__global__ __launch_bounds__(256) void k_err_total(const double* __restrict__ err2, int T_, double* __restrict__ out) {
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int t = threadIdx.x; t < T_; t += 256) acc += err2[t];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *out = sqrt(red[0]);
+}
+
+template <typename T>
+hipError_t dict_grad(const T* Xt, int ldx, const T* Vt, int ldv, const T* Ht, int ldh, int M, int T_, int S, T* part,
+                     hipStream_t s) {
+    const int MT = round_up(M, 16) / 16, MTp = learn_bin_tiles(M);
+    const dim3 grid(ldh / (DG_WAVES * DG_RB * 16), 2 * MTp / DG_MB, S);
+    hipLaunchKernelGGL(k_dict_grad<T>, grid, dim3(64 * DG_WAVES), 0, s, Xt, ldx, Vt, ldv, Ht, ldh, MT, MTp, T_, S, part);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t dict_apply(const T* part, int S, int ldp, T* W, long ldw, int bin_major, int M, int R, int surface,
+                      hipStream_t s) {
+    const long slab = (long)learn_bin_tiles(M) * 16 * ldp;
+    const long n = (long)M * R;
+    hipLaunchKernelGGL(k_dict_apply<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, S, slab, ldp, W, ldw,
+                       bin_major, M, R, surface);
+    if (surface == EVC_LEARN_PYMF)
+        hipLaunchKernelGGL(k_dict_colnorm<T>, dim3((R + 255) / 256), dim3(256), 0, s, W, ldw, bin_major, M, R);
+    return hipGetLastError();
+}
+
+hipError_t err_total(const double* err2, int T_, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_err_total, dim3(1), dim3(256), 0, s, err2, T_, out);
+    return hipGetLastError();
+}
+
+template hipError_t dict_grad<double>(const double*, int, const double*, int, const double*, int, int, int, int, double*,
+                                      hipStream_t);
+template hipError_t dict_grad<float>(const float*, int, const float*, int, const float*, int, int, int, int, float*,
+                                     hipStream_t);
+template hipError_t dict_apply<double>(const double*, int, int, double*, long, int, int, int, int, hipStream_t);
+template hipError_t dict_apply<float>(const float*, int, int, float*, long, int, int, int, int, hipStream_t);
+
+}  // namespace evc

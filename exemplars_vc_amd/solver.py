@@ -458,6 +458,109 @@ def solve_activations_cd(A, X, H0=None, *, layout="bin_major", max_iter=200, tol
     return H_out
 
 
+_SURFACES = {"sklearn": _lib.LEARN_SKLEARN, "pymf": _lib.LEARN_PYMF}
+
+
+def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every=10, tol=0.0, dtype=None, device=None,
+                     info=False, out_w=None, out_h=None, loop_events=None, splits=0):
+    """Multiplicative updates of BOTH factors, X ~ W H (Frobenius), on the GPU (evc_nmf_learn): W is addressed like the
+    dictionary A of solve_activations, H like its activations.  surface="sklearn": scikit-learn's
+    _fit_multiplicative_update with update_H=True (per iteration H, then W; the error every `check_every` iterations and
+    its stop on `tol`); surface="pymf": pymf's factorize(compute_w=True) (W, then H; columns of W scaled to unit norm).
+
+    Returns (W, H) in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out); with
+    info=True also dict(n_iter=int, err=[1 + iters // check_every] errors (the first at the start; NaN where not
+    evaluated), splits=frame ranges of the dictionary update's sums).  out_w / out_h: device tensors updated in place
+    (they then hold the start, W0 / H0 are ignored when None).  splits: tuning and tests, 1..64 frame ranges.
+    No CPU fallback: without a HIP device this raises RuntimeError."""
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    lay = _LAYOUTS[layout]
+    tdtype, dcode = _pick_dtype(dtype, X, W0 if W0 is not None else out_w)
+    X_d, x_np = _to_dev(X, tdtype, device)
+    M, T = X_d.shape if lay == _lib.BIN_MAJOR else X_d.shape[::-1]
+
+    def start(a0, out, what):
+        if out is not None:
+            if a0 is not None:
+                out.copy_(_to_dev(a0, tdtype, device)[0])
+            if out.dtype != tdtype or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
+                raise ValueError(f"`out_{what}` must be a device matrix of the call's dtype with unit inner stride")
+            return out
+        a_d, _ = _to_dev(a0, tdtype, device)
+        if isinstance(a0, torch.Tensor) and a_d.data_ptr() == a0.data_ptr():
+            a_d = a_d.clone()       # never clobber the caller's start
+        return a_d
+
+    W_d, H_d = start(W0, out_w, "w"), start(H0, out_h, "h")
+    M2, R = W_d.shape if lay == _lib.BIN_MAJOR else W_d.shape[::-1]
+    R2, T2 = H_d.shape if lay == _lib.BIN_MAJOR else H_d.shape[::-1]
+    if M2 != M or R2 != R or T2 != T:
+        raise ValueError(f"X {tuple(X_d.shape)}, W {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
+    opts = _lib.LearnOpts()
+    opts.struct_bytes = C.sizeof(_lib.LearnOpts)
+    opts.dtype, opts.layout, opts.surface = dcode, lay, _SURFACES[surface]
+    opts.iters, opts.check_every, opts.tol = int(iters), int(check_every), float(tol)
+    opts.reserved = (int(splits) & 0xff) << 8
+    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
+        opts.ev_loop_start = int(loop_events[0].cuda_event)
+        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    ws_bytes = int(L.evc_learn_workspace_bytes(M, R, T, dcode))
+    if ws_bytes == 0:
+        raise ValueError(f"unsupported dictionary-learning shape M={M}, R={R}, T={T}")
+    n_slots = 1 + (int(iters) // int(check_every) if check_every > 0 else 0)
+    n_iter = C.c_int(0)
+    err = np.full(n_slots, np.nan) if info else None
+    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_nmf_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
+                             C.byref(opts), ws.data_ptr(), ws.numel(),
+                             C.byref(n_iter) if (info or tol > 0) else None,
+                             err.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
+    _lib.check(st, "evc_nmf_learn")
+    to_np = x_np and out_w is None and out_h is None
+    res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
+    if info:
+        res += ({"n_iter": int(n_iter.value), "err": err,
+                 "splits": int(splits) if splits else int(L.evc_learn_splits(M, R, T))},)
+    return res
+
+
+def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepared=False, dtype=None, device=None):
+    """A compact parallel dictionary: the aligned source and target exemplars are stacked, D = [A; B] ((Ma + Mb) x N),
+    and factored jointly, D ~ [Wa; Wb] G, with R << N components by learn_dictionary (scikit-learn surface, the error
+    every 10 iterations); (Wa, Wb) then stand in for (A, B) in solve_activations / convert at R / N of the cost.
+
+    The start is deterministic: W0 = R evenly spaced exemplars (columns of D) floored at 1e-6, G0 = sqrt(mean(D) / R)
+    everywhere.  Returns (Wa, Wb, G, info) in the caller's orientation; info as learn_dictionary's.  prepared=True:
+    (PreparedDictionary of (Wa, Wb), G, info) instead, ready for convert()."""
+    torch = _torch()
+    device = require_device(device)
+    lay = _LAYOUTS[layout]
+    tdtype, _ = _pick_dtype(dtype, A, B)
+    A_d, a_np = _to_dev(A, tdtype, device)
+    B_d, _ = _to_dev(B, tdtype, device)
+    bm = lay == _lib.BIN_MAJOR
+    D = torch.cat([A_d, B_d], dim=0 if bm else 1)              # bin-major: (Ma + Mb, N); frame-major: (N, Ma + Mb)
+    Ma = A_d.shape[0] if bm else A_d.shape[1]
+    N = D.shape[1] if bm else D.shape[0]
+    R = int(R)
+    if not 1 <= R <= N:
+        raise ValueError(f"R must be between 1 and the number of exemplars ({N}), got {R}")
+    pick = torch.div(torch.arange(R, device=device) * N, R, rounding_mode="floor")
+    W0 = (D[:, pick] if bm else D[pick, :]).clamp_min(1e-6).contiguous()
+    G0 = torch.full((R, N) if bm else (N, R), float(torch.sqrt(D.mean() / R)), dtype=tdtype, device=device)
+    W, G, info = learn_dictionary(D, None, None, layout=layout, iters=iters, tol=tol, check_every=10, surface="sklearn",
+                                  dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0)
+    Wa, Wb = (W[:Ma], W[Ma:]) if bm else (W[:, :Ma], W[:, Ma:])
+    if prepared:
+        return prepare_dictionary(Wa, Wb, layout=layout, dtype=tdtype, device=device), (_to_host(G) if a_np else G), info
+    if a_np:
+        return _to_host(Wa), _to_host(Wb), _to_host(G), info
+    return Wa, Wb, G, info
+
+
 def synthesize(B, H, *, layout="bin_major", dtype=None, device=None):
     """Y = B H (bin_major, (Mb,T)) or H B (frame_major: np.matmul(H.T, B) of
     04_align_n_nmf.py:391 with H already frames-as-rows, giving (T,Mb))."""

@@ -22,6 +22,10 @@
  *   evc_cd_solve    replaces the coordinate-descent loop behind _factorize() of 04_align_n_nmf_pytorch.py:189-210
  *                   (sklearn solver='cd', update_H=False: _fit_coordinate_descent, _nmf.py:496-521,
  *                    _update_coordinate_descent, :376-404, _cdnmf_fast.pyx)
+ *   evc_nmf_learn   replaces the multiplicative-update loop that also learns the dictionary: sklearn
+ *                   _fit_multiplicative_update with update_H=True (_nmf.py:731-893; beta = 2) and pymf's default
+ *                   factorize(compute_w=True) (pymf/nmf.py:66-76, pymf/base.py:238-270); evc_learn_workspace_bytes and
+ *                   evc_learn_splits size and describe it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -52,6 +56,10 @@
  *     (4) evc_cd_solve: n_iter_out / violation_out non-NULL (the call returns after copying them back).  Its kernels
  *         never exchange data between workgroups inside a launch and assume nothing about residency: concurrent
  *         coordinate-descent solves on several streams are safe.
+ *     (5) evc_nmf_learn: with check_every = 0 and NULL n_iter_out / err_out the call is fully asynchronous.  Otherwise the
+ *         host reads one double (the error) at each check that is evaluated and decides the stop there; checks are
+ *         evaluated when err_out is non-NULL or tol > 0.  Its own kernels never exchange data between workgroups inside a
+ *         launch, and its activation step runs with EVC_FLAG_NO_EXCHANGE: concurrent calls on several streams are safe.
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
  *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets) are consumed before the call returns: they are
@@ -412,6 +420,46 @@ size_t evc_cd_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
 int evc_cd_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
                  const int* utt_offsets, int n_utt, const evc_cd_opts* opts, void* workspace, size_t workspace_bytes,
                  int* n_iter_out, double* violation_out, evc_stream_t stream);
+
+/* Multiplicative updates of BOTH factors, X ~ W H (Frobenius): X is M x T, W is M x R (addressed like A of evc_nmf_solve:
+ * FRAME_MAJOR W[r*ldw+m], BIN_MAJOR W[m*ldw+r]), H is R x T (addressed like H of evc_nmf_solve).  W and H hold the start on
+ * entry and are updated in place.  The dictionary update is evaluated factored, V = W H, Num = X H^T, Den = V H^T (6MRT
+ * flop; the R x R Gram matrix of H is never formed); the activation update is one iteration of evc_nmf_solve.
+ *   SKLEARN  per iteration H first, then W:  Den[Den == 0] = 1.1920929e-7; W <- W * (Num / Den);  H by EVC_EPS_ZERO_REPLACE
+ *            (sklearn's W is H^T here, its H is W^T).  err = ||X - W H||_F at the start and after every `check_every`
+ *            iterations; stop when (err_prev - err) / err_at_start < tol (tol = 0 never stops)
+ *   PYMF     per iteration W first, then H:  W <- (W * Num) / (Den + 1e-9), then every column divided by its Euclidean
+ *            norm (a column of zeros becomes NaN, exactly as in pymf: not guarded);  H by EVC_EPS_ADD 1e-9.  From the
+ *            third evaluated error on, stop when |err - err_prev| / T < tol (pymf: check_every = 1, tol = machine epsilon;
+ *            the caller truncates its `ferr` as pymf/base.py:266-270 does)
+ * Num and Den are sums over the frames, taken in evc_learn_splits(M, R, T) contiguous frame ranges whose partial sums are
+ * added in ascending order: the count depends on the sizes only, and the same call gives bitwise the same W and H every time.
+ *   M : 1 .. 1056, R : 1 .. 4096 (larger: -3);  T >= 1
+ *   n_iter_out : host int or NULL: iterations carried out
+ *   err_out    : host, 1 + iters / check_every doubles or NULL: the error at the start, then at every check (NaN where not
+ *                evaluated)
+ * Host synchronisation: case (5) of the list at the top. */
+enum { EVC_LEARN_SKLEARN = 0, EVC_LEARN_PYMF = 1 };
+typedef struct evc_learn_opts {
+    int struct_bytes;  /* sizeof(evc_learn_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int surface;       /* EVC_LEARN_* */
+    int iters;         /* >= 0 */
+    int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
+    int reserved;      /* 0; bits 8..15, tuning and tests: that many frame ranges (1 .. 64) instead of evc_learn_splits();
+                          anything else: status -1 */
+    double tol;        /* >= 0 */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_learn_opts;
+/* bytes of workspace evc_nmf_learn needs (0: invalid arguments); room for 64 frame ranges is included */
+size_t evc_learn_workspace_bytes(int M, int R, int T, int dtype);
+/* frame ranges the dictionary update's sums over the frames are split into (0: invalid arguments) */
+int evc_learn_splits(int M, int R, int T);
+int evc_nmf_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
+                  const evc_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
+                  evc_stream_t stream);
 
 #ifdef __cplusplus
 }
