@@ -58,7 +58,7 @@ class LearnOpts(C.Structure):
     """Mirror of `evc_learn_opts` (include/evc.h): options of the solve that also learns the dictionary."""
     _fields_ = [
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("surface", C.c_int),
-        ("iters", C.c_int), ("check_every", C.c_int), ("reserved", C.c_int),
+        ("iters", C.c_int), ("check_every", C.c_int), ("reserved", C.c_int), ("loss", C.c_int),
         ("tol", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]

@@ -108,23 +108,27 @@ def _factorize_impl(X, W, beta_loss, tol, device, algo, honor_beta_loss, hint, w
     return act.T, recon
 
 
-def non_negative_factorization_mu(X, W, H, update_H=True, tol=1e-4, max_iter=200, *, device=None):
+def non_negative_factorization_mu(X, W, H, update_H=True, tol=1e-4, max_iter=200, *, device=None,
+                                  beta_loss="frobenius"):
     """scikit-learn's `non_negative_factorization(X, W, H, init='custom', update_H=update_H, solver='mu',
-    beta_loss='frobenius', tol=tol, max_iter=max_iter)` on the GPU, in scikit-learn's orientation: X (n_samples,
+    beta_loss=beta_loss, tol=tol, max_iter=max_iter)` on the GPU, in scikit-learn's orientation: X (n_samples,
     n_features), W (n_samples, n_components) the activations, H (n_components, n_features) the dictionary.  Returns
     (W, H, n_iter).  update_H=True learns the dictionary too (evc_nmf_learn); update_H=False is the fixed-dictionary
-    solve of _factorize with the given start."""
+    solve of _factorize with the given start.  beta_loss: "frobenius" or "kullback-leibler"."""
+    if beta_loss not in ("frobenius", "kullback-leibler"):
+        raise ValueError(f"Invalid beta_loss parameter: got {beta_loss!r}")
     X = np.asarray(X)
     if update_H:
         # frame-major: X[t][m], the dictionary (the solver's W) as H[r][m], the activations (its H) as W[t][r]
         Hd, Wa, info = learn_dictionary(X, np.asarray(H, dtype=X.dtype), np.asarray(W, dtype=X.dtype),
                                         layout="frame_major", iters=int(max_iter), surface="sklearn",
-                                        check_every=10 if tol > 0 else 0, tol=float(tol), device=device, info=True)
+                                        check_every=10 if tol > 0 else 0, tol=float(tol), device=device, info=True,
+                                        loss=beta_loss)
         return Wa, Hd, info["n_iter"]
     act, info = solve_activations(np.asarray(H, dtype=X.dtype), X, np.asarray(W, dtype=X.dtype), layout="frame_major",
                                   iters=int(max_iter), eps_mode="zero_replace", init="given",
                                   check_every=10 if tol > 0 else 0, stop_rule="sklearn" if tol > 0 else "none",
-                                  tol=float(tol), device=device, info=True)
+                                  tol=float(tol), device=device, info=True, loss=beta_loss)
     return act, np.asarray(H), int(info["n_iter"][0])
 
 

@@ -1026,6 +1026,8 @@ int learn_typed(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, i
     T* W = static_cast<T*>(W_);
     T* H = static_cast<T*>(H_);
     const bool pymf = o.surface == EVC_LEARN_PYMF;
+    const bool kl = o.loss == EVC_LOSS_KL;         // sklearn surface only (evc_nmf_learn rejects it with pymf)
+    const double eps_kl = 1.1920929e-7;
     const int n_checks = o.check_every > 0 ? o.iters / o.check_every : 0;
     const bool want_err = o.check_every > 0 && (err_out || o.tol > 0.0);
     if (err_out) for (int i = 0; i <= n_checks; ++i) err_out[i] = NAN;
@@ -1036,7 +1038,7 @@ int learn_typed(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, i
     so.eps_mode = pymf ? EVC_EPS_ADD : EVC_EPS_ZERO_REPLACE;
     so.eps = pymf ? 1e-9 : 1.1920929e-7;
     so.init_mode = EVC_INIT_GIVEN; so.stop_rule = EVC_STOP_NONE; so.reserved = EVC_FLAG_NO_EXCHANGE;
-    so.loss = EVC_LOSS_FROBENIUS;
+    so.loss = kl ? EVC_LOSS_KL : EVC_LOSS_FROBENIUS;
     auto update_h = [&]() -> int {
         return evc_nmf_solve(W, ldw, X, ldx, H, ldh, M, R, T_, nullptr, 1, &so, w.solve_ws, w.solve_bytes, nullptr, nullptr,
                              reinterpret_cast<evc_stream_t>(s));
@@ -1050,13 +1052,19 @@ int learn_typed(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, i
     };
     auto update_w = [&]() -> int {
         HIP_TRY(form_v());
-        HIP_TRY(dict_grad<T>(w.Xt, d.Mk, w.Vt, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
-        HIP_TRY(dict_apply<T>(w.part, S, d.Np, W, ldw, fm ? 0 : 1, M, R, o.surface, s));
+        if (kl) {                                  // nothing below reads V again: the quotient takes its place
+            HIP_TRY(dict_quot<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, eps_kl, s));
+            HIP_TRY(dict_grad_kl<T>(w.Vt, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
+        } else {
+            HIP_TRY(dict_grad<T>(w.Xt, d.Mk, w.Vt, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
+        }
+        HIP_TRY(dict_apply<T>(w.part, S, d.Np, W, ldw, fm ? 0 : 1, M, R, o.surface, o.loss, s));
         return ST_OK;
     };
     auto error_now = [&](int slot, double* host) -> int {
         HIP_TRY(form_v());
-        HIP_TRY(frame_err2<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, w.err2, s));
+        if (kl) HIP_TRY(frame_err_kl<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, eps_kl, w.err2, s));
+        else HIP_TRY(frame_err2<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, w.err2, s));
         double* dst = w.ring + slot % LEARN_RING;
         HIP_TRY(err_total(w.err2, T_, dst, s));
         HIP_TRY(hipMemcpyAsync(host, dst, sizeof(double), hipMemcpyDeviceToHost, s));
@@ -1529,12 +1537,14 @@ int evc_nmf_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, in
     if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return ST_BADARG;
     if (o.layout != EVC_FRAME_MAJOR && o.layout != EVC_BIN_MAJOR) return ST_BADARG;
     if (o.surface != EVC_LEARN_SKLEARN && o.surface != EVC_LEARN_PYMF) return ST_BADARG;
+    if (o.loss != EVC_LOSS_FROBENIUS && o.loss != EVC_LOSS_KL) return ST_BADARG;
     if (!(o.tol >= 0.0)) return ST_BADARG;
     const int forced = (o.reserved >> 8) & 0xff;
     if ((o.reserved & ~0xff00) != 0 || forced > LEARN_MAX_SPLITS) return ST_BADARG;
     if (!X || !W || !H || !workspace) return ST_BADARG;
     if (bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldw, R, M) || bad_ld(o.layout, ldh, T, R)) return ST_BADARG;
     if (M > LEARN_MAX_M || R > LEARN_MAX_R) return ST_UNSUPPORTED;
+    if (o.loss == EVC_LOSS_KL && o.surface == EVC_LEARN_PYMF) return ST_UNSUPPORTED;   // pymf has no KL update
     if (o.check_every > 0 && o.iters / o.check_every + 1 > MAX_SLOTS) return ST_BADARG;
     if (workspace_bytes < evc_learn_workspace_bytes(M, R, T, o.dtype)) return ST_WORKSPACE;
     const int S = forced ? forced : learn_splits(M, R, T);

@@ -370,12 +370,22 @@ int learn_splits(int M, int R, int T_);
 template <typename T>
 hipError_t dict_grad(const T* Xt, int ldx, const T* Vt, int ldv, const T* Ht, int ldh, int M, int T_, int S, T* part,
                      hipStream_t s);
-// W <- update(W, sum_s part[s][0], sum_s part[s][1]) in the surface's literal operation order (EVC_LEARN_*), on the
-// caller's W (bin_major: W[m ldw + r], else W[r ldw + m]); pymf: then every column divided by its Euclidean norm
+// Kullback-Leibler: Vt[t][m] <- Xt[t][m] / max(Vt[t][m], eps) in place for t < T_ (m < M; zero up to ldx columns)
 template <typename T>
-hipError_t dict_apply(const T* part, int S, int ldp, T* W, long ldw, int bin_major, int M, int R, int surface,
+hipError_t dict_quot(const T* Xt, int ldx, T* Vt, int ldv, int M, int T_, double eps, hipStream_t s);
+// ... and the one-operand contraction of that quotient: part[s][0][m][r] = sum over the s-th frame range of
+// Qt[t][m] Ht[t][r], part[s][1][0][r] = sum over the range of Ht[t][r] (the rest of the second slab is not written);
+// half the workgroups of dict_grad at the same S
+template <typename T>
+hipError_t dict_grad_kl(const T* Qt, int ldq, const T* Ht, int ldh, int M, int T_, int S, T* part, hipStream_t s);
+// W <- update(W, sum_s part[s][0], sum_s part[s][1]) in the surface's literal operation order (EVC_LEARN_*), on the
+// caller's W (bin_major: W[m ldw + r], else W[r ldw + m]); pymf: then every column divided by its Euclidean norm.
+// loss EVC_LOSS_KL (sklearn surface): W[m][r] <- W[m][r] * (sum_s part[s][0][m][r] / s_r), s_r = sum_s part[s][1][0][r],
+// s_r == 0 -> 1
+template <typename T>
+hipError_t dict_apply(const T* part, int S, int ldp, T* W, long ldw, int bin_major, int M, int R, int surface, int loss,
                       hipStream_t s);
-// *out = sqrt(sum_t err2[t]), summed in a fixed order
+// *out = sqrt(max(sum_t err2[t], 0)), summed in a fixed order
 hipError_t err_total(const double* err2, int T_, double* out, hipStream_t s);
 
 }  // namespace evc

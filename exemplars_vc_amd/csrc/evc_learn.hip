@@ -6,9 +6,13 @@
 //                 whole range and leave as one slab of partial sums.  Operands go from global memory straight into the
 //                 MFMA (frames as rows: 16 consecutive bins / components of one frame per quarter wavefront, 128-byte
 //                 rows); the wavefronts of a workgroup share the bin tiles through the vector cache.
+//                 Its one-operand form (Kullback-Leibler) contracts the quotient Q = X (/) max(V, eps) alone, with no
+//                 `which` dimension in the grid, and its first row of workgroups also sums the right operand's rows over
+//                 the range (s_r = sum_t H[r][t]) from the registers the MFMAs already read.
+//   k_dict_quot   forms Q in V's place, once per dictionary step.
 //   k_dict_apply  sums the slabs in the order s = 0 .. S-1 and applies the surface's update to the caller's W.
 //   k_dict_colnorm  pymf: every column divided by its Euclidean norm (sum of squares over the bins in ascending order).
-//   k_err_total   sqrt of the sum of the per-frame squared residuals, in a fixed order.
+//   k_err_total   sqrt of the sum of the per-frame error terms (clamped at 0), in a fixed order.
 // Nothing here exchanges data between workgroups inside a launch, uses atomics or assumes residency: the same call gives
 // bitwise the same W every time.
 #include "evc_internal.h"
@@ -23,15 +27,35 @@ int learn_splits(int M, int R, int T_) {
     return S < 1 ? 1 : S;
 }
 
+// V <- X (/) max(V, eps) in place (m < M; zero in the padding up to ldx columns), frames as rows
 template <typename T>
+__global__ __launch_bounds__(256) void k_dict_quot(const T* __restrict__ Xt, int ldx, T* __restrict__ Vt, int ldv, int M,
+                                                   long rows, T eps) {
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= rows * ldx) return;
+    const long t = gid / ldx;
+    const int m = (int)(gid % ldx);
+    T q = T(0);
+    if (m < M) {
+        T v = Vt[t * ldv + m];
+        v = (v < eps) ? eps : v;
+        q = Xt[t * ldx + m] / v;
+    }
+    Vt[t * ldv + m] = q;
+}
+
+// ONE: the left operand is Vt alone (Xt is not read), the grid has no `which` dimension, and the workgroups with
+// blockIdx.y == 0 leave the sums of Ht's columns over the range in the first row of the range's second slab
+template <typename T, bool ONE>
 __global__ __launch_bounds__(64 * DG_WAVES) void k_dict_grad(const T* __restrict__ Xt, int ldx, const T* __restrict__ Vt,
                                                              int ldv, const T* __restrict__ Ht, int ldh, int MT, int MTp,
                                                              int T_, int S, T* __restrict__ part) {
     typedef typename Mma<T>::acc_t acc_t;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int bpo = MTp / DG_MB;                   // workgroups per operand along the bins
-    const int which = blockIdx.y / bpo;
-    const int tile0 = (blockIdx.y % bpo) * DG_MB;
+    const int which = ONE ? 1 : blockIdx.y / bpo;
+    const int tile0 = (ONE ? blockIdx.y : blockIdx.y % bpo) * DG_MB;
+    const bool sums = ONE && blockIdx.y == 0;
     const int r0 = (blockIdx.x * DG_WAVES + wave) * DG_RB * 16;
     const int sp = blockIdx.z;
     const int tb = (int)((long)sp * T_ / S), te = (int)((long)(sp + 1) * T_ / S);
@@ -65,11 +89,17 @@ __global__ __launch_bounds__(64 * DG_WAVES) void k_dict_grad(const T* __restrict
 #pragma unroll
         for (int j = 0; j < DG_RB; ++j) b[j] = live ? b[j] : T(0);
     };
-    T a[DG_MB], b[DG_RB];
+    T a[DG_MB], b[DG_RB], hs[DG_RB];
+#pragma unroll
+    for (int j = 0; j < DG_RB; ++j) hs[j] = T(0);
     if (tb < te) load(tb, a, b);
     for (int t = tb; t < te; t += 4) {
         T an[DG_MB], bn[DG_RB];
         load(t + 4, an, bn);                       // past the end: the clamped row, masked to zeros, never used
+        if (sums) {                                // this lane's frames t + (lane >> 4), t + 4 + (lane >> 4), ...
+#pragma unroll
+            for (int j = 0; j < DG_RB; ++j) hs[j] += b[j];
+        }
 #pragma unroll
         for (int i = 0; i < DG_MB; ++i)
 #pragma unroll
@@ -80,7 +110,7 @@ __global__ __launch_bounds__(64 * DG_WAVES) void k_dict_grad(const T* __restrict
         for (int j = 0; j < DG_RB; ++j) b[j] = bn[j];
     }
     const long slab = (long)MTp * 16 * ldh;
-    T* __restrict__ out = part + ((long)sp * 2 + which) * slab;
+    T* __restrict__ out = part + ((long)sp * 2 + (ONE ? 0 : which)) * slab;
 #pragma unroll
     for (int i = 0; i < DG_MB; ++i)
 #pragma unroll
@@ -88,11 +118,20 @@ __global__ __launch_bounds__(64 * DG_WAVES) void k_dict_grad(const T* __restrict
 #pragma unroll
             for (int r = 0; r < 4; ++r)
                 out[(long)((tile0 + i) * 16 + Mma<T>::row(lane, r)) * ldh + hoff + 16 * j] = acc[i][j][r];
+    if (sums) {                                    // the four lane groups of a component, added in ascending order
+#pragma unroll
+        for (int j = 0; j < DG_RB; ++j) {
+            const int c = lane & 15;
+            const T s01 = __shfl(hs[j], c, 64) + __shfl(hs[j], c + 16, 64);
+            const T s = (s01 + __shfl(hs[j], c + 32, 64)) + __shfl(hs[j], c + 48, 64);
+            if (lane < 16) out[slab + hoff + 16 * j] = s;
+        }
+    }
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_dict_apply(const T* __restrict__ part, int S, long slab, int ldp, T* __restrict__ W,
-                                                    long ldw, int bin_major, int M, int R, int surface) {
+                                                    long ldw, int bin_major, int M, int R, int surface, int loss) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (long)M * R) return;
     // the caller's inner index is the fastest one here
@@ -100,6 +139,16 @@ __global__ __launch_bounds__(256) void k_dict_apply(const T* __restrict__ part, 
     const int r = bin_major ? (int)(idx % R) : (int)(idx / M);
     const T* __restrict__ p = part + (long)m * ldp + r;
     T num = T(0), den = T(0);
+    if (loss == EVC_LOSS_KL) {                     // sklearn _nmf.py:634-728 (beta 1) with the roles swapped
+        for (int s = 0; s < S; ++s) {
+            num += p[(long)s * 2 * slab];
+            den += part[((long)s * 2 + 1) * slab + r];         // s_r: the first row of the range's second slab
+        }
+        den = den == T(0) ? T(1) : den;            // _nmf.py:679-680: an absent component divides by 1, not by eps
+        T* w = W + (bin_major ? m * ldw + r : r * ldw + m);
+        *w = *w * (num / den);
+        return;
+    }
     for (int s = 0; s < S; ++s) {
         num += p[(long)s * 2 * slab];
         den += p[((long)s * 2 + 1) * slab];
@@ -138,7 +187,8 @@ __global__ __launch_bounds__(256) void k_err_total(const double* __restrict__ er
         if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
         __syncthreads();
     }
-    if (threadIdx.x == 0) *out = sqrt(red[0]);
+    // the Kullback-Leibler terms can sum to a rounding error below zero at an exact fit (k_utt_check clamps likewise)
+    if (threadIdx.x == 0) *out = sqrt(red[0] < 0.0 ? 0.0 : red[0]);
 }
 
 template <typename T>
@@ -146,17 +196,35 @@ hipError_t dict_grad(const T* Xt, int ldx, const T* Vt, int ldv, const T* Ht, in
                      hipStream_t s) {
     const int MT = round_up(M, 16) / 16, MTp = learn_bin_tiles(M);
     const dim3 grid(ldh / (DG_WAVES * DG_RB * 16), 2 * MTp / DG_MB, S);
-    hipLaunchKernelGGL(k_dict_grad<T>, grid, dim3(64 * DG_WAVES), 0, s, Xt, ldx, Vt, ldv, Ht, ldh, MT, MTp, T_, S, part);
+    hipLaunchKernelGGL((k_dict_grad<T, false>), grid, dim3(64 * DG_WAVES), 0, s, Xt, ldx, Vt, ldv, Ht, ldh, MT, MTp, T_, S,
+                       part);
     return hipGetLastError();
 }
 
 template <typename T>
-hipError_t dict_apply(const T* part, int S, int ldp, T* W, long ldw, int bin_major, int M, int R, int surface,
+hipError_t dict_quot(const T* Xt, int ldx, T* Vt, int ldv, int M, int T_, double eps, hipStream_t s) {
+    const long n = (long)T_ * ldx;
+    hipLaunchKernelGGL(k_dict_quot<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Xt, ldx, Vt, ldv, M, (long)T_,
+                       (T)eps);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t dict_grad_kl(const T* Qt, int ldq, const T* Ht, int ldh, int M, int T_, int S, T* part, hipStream_t s) {
+    const int MT = round_up(M, 16) / 16, MTp = learn_bin_tiles(M);
+    const dim3 grid(ldh / (DG_WAVES * DG_RB * 16), MTp / DG_MB, S);
+    hipLaunchKernelGGL((k_dict_grad<T, true>), grid, dim3(64 * DG_WAVES), 0, s, (const T*)nullptr, 0, Qt, ldq, Ht, ldh, MT,
+                       MTp, T_, S, part);
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t dict_apply(const T* part, int S, int ldp, T* W, long ldw, int bin_major, int M, int R, int surface, int loss,
                       hipStream_t s) {
     const long slab = (long)learn_bin_tiles(M) * 16 * ldp;
     const long n = (long)M * R;
     hipLaunchKernelGGL(k_dict_apply<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, S, slab, ldp, W, ldw,
-                       bin_major, M, R, surface);
+                       bin_major, M, R, surface, loss);
     if (surface == EVC_LEARN_PYMF)
         hipLaunchKernelGGL(k_dict_colnorm<T>, dim3((R + 255) / 256), dim3(256), 0, s, W, ldw, bin_major, M, R);
     return hipGetLastError();
@@ -171,7 +239,11 @@ template hipError_t dict_grad<double>(const double*, int, const double*, int, co
                                       hipStream_t);
 template hipError_t dict_grad<float>(const float*, int, const float*, int, const float*, int, int, int, int, float*,
                                      hipStream_t);
-template hipError_t dict_apply<double>(const double*, int, int, double*, long, int, int, int, int, hipStream_t);
-template hipError_t dict_apply<float>(const float*, int, int, float*, long, int, int, int, int, hipStream_t);
+template hipError_t dict_quot<double>(const double*, int, double*, int, int, int, double, hipStream_t);
+template hipError_t dict_quot<float>(const float*, int, float*, int, int, int, double, hipStream_t);
+template hipError_t dict_grad_kl<double>(const double*, int, const double*, int, int, int, int, double*, hipStream_t);
+template hipError_t dict_grad_kl<float>(const float*, int, const float*, int, int, int, int, float*, hipStream_t);
+template hipError_t dict_apply<double>(const double*, int, int, double*, long, int, int, int, int, int, hipStream_t);
+template hipError_t dict_apply<float>(const float*, int, int, float*, long, int, int, int, int, int, hipStream_t);
 
 }  // namespace evc

@@ -462,17 +462,23 @@ _SURFACES = {"sklearn": _lib.LEARN_SKLEARN, "pymf": _lib.LEARN_PYMF}
 
 
 def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every=10, tol=0.0, dtype=None, device=None,
-                     info=False, out_w=None, out_h=None, loop_events=None, splits=0):
-    """Multiplicative updates of BOTH factors, X ~ W H (Frobenius), on the GPU (evc_nmf_learn): W is addressed like the
+                     info=False, out_w=None, out_h=None, loop_events=None, splits=0, loss="frobenius"):
+    """Multiplicative updates of BOTH factors, X ~ W H, on the GPU (evc_nmf_learn): W is addressed like the
     dictionary A of solve_activations, H like its activations.  surface="sklearn": scikit-learn's
     _fit_multiplicative_update with update_H=True (per iteration H, then W; the error every `check_every` iterations and
     its stop on `tol`); surface="pymf": pymf's factorize(compute_w=True) (W, then H; columns of W scaled to unit norm).
+    loss: "frobenius" (default), or "kullback-leibler" / "kl" - scikit-learn's beta_loss='kullback-leibler' updates and
+    error sqrt(2 KL(X || W H)), on the sklearn surface only (pymf has no such update: ValueError).
 
     Returns (W, H) in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out); with
     info=True also dict(n_iter=int, err=[1 + iters // check_every] errors (the first at the start; NaN where not
     evaluated), splits=frame ranges of the dictionary update's sums).  out_w / out_h: device tensors updated in place
     (they then hold the start, W0 / H0 are ignored when None).  splits: tuning and tests, 1..64 frame ranges.
     No CPU fallback: without a HIP device this raises RuntimeError."""
+    if loss not in _LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_LOSSES)}, got {loss!r}")
+    if _LOSSES[loss] == _lib.LOSS_KL and surface == "pymf":
+        raise ValueError("the pymf surface has no Kullback-Leibler update; use surface='sklearn'")
     torch = _torch()
     device = require_device(device)
     L = _lib.lib()
@@ -503,6 +509,7 @@ def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every
     opts.dtype, opts.layout, opts.surface = dcode, lay, _SURFACES[surface]
     opts.iters, opts.check_every, opts.tol = int(iters), int(check_every), float(tol)
     opts.reserved = (int(splits) & 0xff) << 8
+    opts.loss = _LOSSES[loss]
     if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
         opts.ev_loop_start = int(loop_events[0].cuda_event)
         opts.ev_loop_stop = int(loop_events[1].cuda_event)
@@ -527,14 +534,18 @@ def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every
     return res
 
 
-def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepared=False, dtype=None, device=None):
+def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepared=False, dtype=None, device=None,
+                       loss="frobenius"):
     """A compact parallel dictionary: the aligned source and target exemplars are stacked, D = [A; B] ((Ma + Mb) x N),
     and factored jointly, D ~ [Wa; Wb] G, with R << N components by learn_dictionary (scikit-learn surface, the error
     every 10 iterations); (Wa, Wb) then stand in for (A, B) in solve_activations / convert at R / N of the cost.
 
     The start is deterministic: W0 = R evenly spaced exemplars (columns of D) floored at 1e-6, G0 = sqrt(mean(D) / R)
-    everywhere.  Returns (Wa, Wb, G, info) in the caller's orientation; info as learn_dictionary's.  prepared=True:
-    (PreparedDictionary of (Wa, Wb), G, info) instead, ready for convert()."""
+    everywhere, whatever the loss.  Returns (Wa, Wb, G, info) in the caller's orientation; info as learn_dictionary's.
+    prepared=True: (PreparedDictionary of (Wa, Wb), G, info) instead, ready for convert().  loss: as learn_dictionary's
+    (the prepared dictionary itself is the plain one: pass the loss to convert / prepare_dictionary to solve under it)."""
+    if loss not in _LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_LOSSES)}, got {loss!r}")
     torch = _torch()
     device = require_device(device)
     lay = _LAYOUTS[layout]
@@ -552,7 +563,7 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     W0 = (D[:, pick] if bm else D[pick, :]).clamp_min(1e-6).contiguous()
     G0 = torch.full((R, N) if bm else (N, R), float(torch.sqrt(D.mean() / R)), dtype=tdtype, device=device)
     W, G, info = learn_dictionary(D, None, None, layout=layout, iters=iters, tol=tol, check_every=10, surface="sklearn",
-                                  dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0)
+                                  dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0, loss=loss)
     Wa, Wb = (W[:Ma], W[Ma:]) if bm else (W[:, :Ma], W[:, Ma:])
     if prepared:
         return prepare_dictionary(Wa, Wb, layout=layout, dtype=tdtype, device=device), (_to_host(G) if a_np else G), info

@@ -23,7 +23,8 @@
  *                   (sklearn solver='cd', update_H=False: _fit_coordinate_descent, _nmf.py:496-521,
  *                    _update_coordinate_descent, :376-404, _cdnmf_fast.pyx)
  *   evc_nmf_learn   replaces the multiplicative-update loop that also learns the dictionary: sklearn
- *                   _fit_multiplicative_update with update_H=True (_nmf.py:731-893; beta = 2) and pymf's default
+ *                   _fit_multiplicative_update with update_H=True (_nmf.py:731-893; beta = 2, or beta = 1 with
+ *                   evc_learn_opts.loss = EVC_LOSS_KL: _nmf.py:556-606, 634-728) and pymf's default
  *                   factorize(compute_w=True) (pymf/nmf.py:66-76, pymf/base.py:238-270); evc_learn_workspace_bytes and
  *                   evc_learn_splits size and describe it
  *
@@ -421,7 +422,7 @@ int evc_cd_solve(const void* A, int lda, const void* X, int ldx, void* H, int ld
                  const int* utt_offsets, int n_utt, const evc_cd_opts* opts, void* workspace, size_t workspace_bytes,
                  int* n_iter_out, double* violation_out, evc_stream_t stream);
 
-/* Multiplicative updates of BOTH factors, X ~ W H (Frobenius): X is M x T, W is M x R (addressed like A of evc_nmf_solve:
+/* Multiplicative updates of BOTH factors, X ~ W H (Frobenius, or Kullback-Leibler on the SKLEARN surface): X is M x T, W is M x R (addressed like A of evc_nmf_solve:
  * FRAME_MAJOR W[r*ldw+m], BIN_MAJOR W[m*ldw+r]), H is R x T (addressed like H of evc_nmf_solve).  W and H hold the start on
  * entry and are updated in place.  The dictionary update is evaluated factored, V = W H, Num = X H^T, Den = V H^T (6MRT
  * flop; the R x R Gram matrix of H is never formed); the activation update is one iteration of evc_nmf_solve.
@@ -432,7 +433,15 @@ int evc_cd_solve(const void* A, int lda, const void* X, int ldx, void* H, int ld
  *            norm (a column of zeros becomes NaN, exactly as in pymf: not guarded);  H by EVC_EPS_ADD 1e-9.  From the
  *            third evaluated error on, stop when |err - err_prev| / T < tol (pymf: check_every = 1, tol = machine epsilon;
  *            the caller truncates its `ferr` as pymf/base.py:266-270 does)
- * Num and Den are sums over the frames, taken in evc_learn_splits(M, R, T) contiguous frame ranges whose partial sums are
+ *   loss = EVC_LOSS_KL (SKLEARN surface only; with PYMF: -3, pymf has no such update): scikit-learn's beta_loss =
+ *            'kullback-leibler' with update_H=True.  Per iteration H first, by one iteration of evc_nmf_solve with
+ *            EVC_LOSS_KL (EVC_EPS_ZERO_REPLACE, eps 1.1920929e-7), then W with the new H:  V = W H;
+ *            Q = X / max(V, 1.1920929e-7);  Num[m][r] = sum_t Q[m][t] H[r][t];  s_r = sum_t H[r][t], s_r == 0 -> 1.0
+ *            (_nmf.py:679-680: 1, not eps);  W <- W * (Num / s_r)  (2MRT flop for Num; Q takes V's place in the workspace).
+ *            err = sqrt(2 KL(X || W H)) as _beta_divergence(beta=1, square_root=True) computes it (a sum of per-frame terms
+ *            that rounding leaves below zero is taken as zero); the checks and the stop are those of the Frobenius loss.
+ *            evc_learn_workspace_bytes and evc_learn_splits do not depend on the loss.
+ * Num and Den (Kullback-Leibler: Num and s_r) are sums over the frames, taken in evc_learn_splits(M, R, T) contiguous frame ranges whose partial sums are
  * added in ascending order: the count depends on the sizes only, and the same call gives bitwise the same W and H every time.
  *   M : 1 .. 1056, R : 1 .. 4096 (larger: -3);  T >= 1
  *   n_iter_out : host int or NULL: iterations carried out
@@ -449,6 +458,7 @@ typedef struct evc_learn_opts {
     int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
     int reserved;      /* 0; bits 8..15, tuning and tests: that many frame ranges (1 .. 64) instead of evc_learn_splits();
                           anything else: status -1 */
+    int loss;          /* EVC_LOSS_* (0 = Frobenius: the slot was padding before it had a name); anything else: -1 */
     double tol;        /* >= 0 */
     void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
     void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */

@@ -6,13 +6,15 @@
   kernels   (--kernels) a child run of the same configuration under `rocprofv3 --kernel-trace --stats`: total time of
             k_dict_grad, of k_dict_apply (+ k_dict_colnorm) and of every other kernel of the loop; k_dict_grad's share
             of the matrix peak priced at 4 M R T flop per iteration (78.6 TF float64, 157.3 TF float32) and of 8 TB/s
-            priced at (2 M + R) T esize bytes; `bound` names the larger
+            priced at (2 M + R) T esize bytes; `bound` names the larger.  --loss kl: the one-operand contraction is
+            priced at 2 M R T flop and (M + R) T esize bytes, and the quotient pass k_dict_quot is reported on its own
+  --loss    frobenius (default) or kl: the same configurations and lines, with a `loss` field
   versus    (--versus) the pymf surface on the compaction shape, K = 5: compat.pymf.NMF(...).factorize() with the
             dictionary update in numpy on the host (the default) against dictionary_update="device", alternating, three
             runs each; ratio of the medians and whether the gain exceeds twice the run-to-run spread
 
     python tools/bench_learn.py [--configs compaction,stft_pair] [--iters K] [--repeats R] [--warmup W]
-                                [--kernels] [--versus] [--out FILE]
+                                [--loss frobenius|kl] [--kernels] [--versus] [--out FILE]
 """
 import argparse
 import csv
@@ -46,7 +48,7 @@ def problem(M, R, T, seed, dt):
     return X.astype(dt), (rng.random((M, R)) + 1e-4).astype(dt), (rng.random((R, T)) + 1e-4).astype(dt)
 
 
-def run_loop(name, iters, repeats, warmup):
+def run_loop(name, iters, repeats, warmup, loss):
     import torch
     from exemplars_vc_amd import learn_dictionary, solve_activations
     M, R, T, dt, k = CONFIGS[name]
@@ -60,7 +62,7 @@ def run_loop(name, iters, repeats, warmup):
     times = []
     for r in range(warmup + repeats):
         W, H, info = learn_dictionary(Xd, Wd, Hd, layout="bin_major", iters=iters, check_every=0, info=True,
-                                      loop_events=ev)
+                                      loop_events=ev, loss=loss)
         torch.cuda.synchronize()
         if r >= warmup:
             times.append(ev[0].elapsed_time(ev[1]) * 1e-3)
@@ -68,7 +70,7 @@ def run_loop(name, iters, repeats, warmup):
     t = float(np.median(times))
     a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     out = torch.empty_like(Hd)
-    kw = dict(layout="bin_major", iters=1, eps_mode="zero_replace", init="given", cooperative=False, out=out)
+    kw = dict(layout="bin_major", iters=1, eps_mode="zero_replace", init="given", cooperative=False, out=out, loss=loss)
     solve_activations(Wd, Xd, Hd, **kw)
     a0.record()
     for _ in range(10):
@@ -76,27 +78,28 @@ def run_loop(name, iters, repeats, warmup):
     a1.record()
     torch.cuda.synchronize()
     act_ms = a0.elapsed_time(a1) / 10
-    return {"what": "loop", "config": name, "M": M, "R": R, "T": T, "dtype": np.dtype(dt).name, "iters": iters,
+    return {"what": "loop", "config": name, "loss": loss, "M": M, "R": R, "T": T, "dtype": np.dtype(dt).name, "iters": iters,
             "splits": info["splits"], "loop_s": t, "ms_per_iter": 1e3 * t / iters, "activation_step_ms": act_ms,
             "spread_ms_per_iter": 1e3 * (max(times) - min(times)) / iters, "repeats": repeats}
 
 
-def run_kernels(name, iters):
+def run_kernels(name, iters, loss):
     M, R, T, dt, k = CONFIGS[name]
     iters = iters or k
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "learn", "--",
-               sys.executable, os.path.abspath(__file__), "--child", "--configs", name, "--iters", str(iters)]
+               sys.executable, os.path.abspath(__file__), "--child", "--configs", name, "--iters", str(iters),
+               "--loss", loss]
         p = subprocess.run(cmd, capture_output=True, text=True)
         files = glob.glob(os.path.join(tmp, "**", "*kernel_stats.csv"), recursive=True)
         if p.returncode != 0 or not files:
             found = [os.path.relpath(f, tmp) for f in glob.glob(os.path.join(tmp, "**", "*"), recursive=True)]
-            return {"what": "kernels", "config": name, "error": (p.stdout + p.stderr)[-300:], "files": found[:20]}
+            return {"what": "kernels", "config": name, "loss": loss, "error": (p.stdout + p.stderr)[-300:], "files": found[:20]}
         rows = list(csv.DictReader(open(files[0])))
     key_n = next(c for c in rows[0] if "name" in c.lower())
     key_t = next(c for c in rows[0] if "total" in c.lower() and "ns" in c.lower())
     key_c = next(c for c in rows[0] if c.lower() in ("calls", "count"))
-    tot = {"k_dict_grad": 0.0, "k_dict_apply": 0.0, "other": 0.0}
+    tot = {"k_dict_grad": 0.0, "k_dict_apply": 0.0, "k_dict_quot": 0.0, "other": 0.0}
     calls = 0
     top = []
     for r in rows:
@@ -108,19 +111,24 @@ def run_kernels(name, iters):
             calls += int(r[key_c])
         elif "k_dict_apply" in nm or "k_dict_colnorm" in nm:
             tot["k_dict_apply"] += ns
+        elif "k_dict_quot" in nm:
+            tot["k_dict_quot"] += ns
         else:
             tot["other"] += ns
     es = np.dtype(dt).itemsize
     per_call = tot["k_dict_grad"] * 1e-9 / max(calls, 1)
-    fr_f = 4.0 * M * R * T / per_call / PEAK[dt]
-    fr_b = (2.0 * M + R) * T * es / per_call / BW
-    return {"what": "kernels", "config": name, "iters": iters, "calls": calls, "k_dict_grad_ms_per_call": 1e3 * per_call,
+    kl = loss == "kl"
+    fr_f = (2.0 if kl else 4.0) * M * R * T / per_call / PEAK[dt]
+    fr_b = ((1.0 if kl else 2.0) * M + R) * T * es / per_call / BW
+    return {"what": "kernels", "config": name, "loss": loss, "iters": iters, "calls": calls,
+            "k_dict_grad_ms_per_call": 1e3 * per_call,
             "k_dict_grad_ms": tot["k_dict_grad"] * 1e-6, "k_dict_apply_ms": tot["k_dict_apply"] * 1e-6,
+            "k_dict_quot_ms_per_call": tot["k_dict_quot"] * 1e-6 / max(calls, 1),
             "other_kernels_ms": tot["other"] * 1e-6, "frac_flop": fr_f, "frac_bytes": fr_b,
             "bound": "flop" if fr_f >= fr_b else "bytes", "top": [[n, ns * 1e-6] for ns, n in sorted(top, reverse=True)[:8]]}
 
 
-def run_child(name, iters):
+def run_child(name, iters, loss):
     """what the profiled child runs: one warm-up call, nothing printed"""
     import torch
     from exemplars_vc_amd import learn_dictionary
@@ -128,7 +136,7 @@ def run_child(name, iters):
     X, W0, H0 = problem(M, R, T, 17, dt)
     dev = torch.device("cuda", 0)
     Xd, Wd, Hd = (torch.from_numpy(a).to(dev) for a in (X, W0, H0))
-    learn_dictionary(Xd, Wd, Hd, layout="bin_major", iters=iters or k, check_every=0)
+    learn_dictionary(Xd, Wd, Hd, layout="bin_major", iters=iters or k, check_every=0, loss=loss)
     torch.cuda.synchronize()
 
 
@@ -166,6 +174,7 @@ def main():
     ap.add_argument("--iters", type=int, default=0)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--loss", choices=("frobenius", "kl"), default="frobenius")
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--versus", action="store_true")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
@@ -173,11 +182,11 @@ def main():
     a = ap.parse_args()
     names = a.configs.split(",")
     if a.child:
-        return run_child(names[0], a.iters)
+        return run_child(names[0], a.iters, a.loss)
     res = []
     if a.kernels:               # first: the profiled children run before this process opens the GPU
-        res += [run_kernels(n, a.iters) for n in names]
-    res += [run_loop(n, a.iters, a.repeats, a.warmup) for n in names]
+        res += [run_kernels(n, a.iters, a.loss) for n in names]
+    res += [run_loop(n, a.iters, a.repeats, a.warmup, a.loss) for n in names]
     if a.versus:
         res.append(run_versus())
     with open(a.out, "a") as f:
