@@ -83,7 +83,11 @@ class SolveInfo(C.Structure):
 
 def decode_variant(kernel: int, v: int):
     """evc_solve_info.variant as a dict (None for the kernels that report none): schedule and template instance of the
-    task-queue kernels.  k_fused_wide: k_fused_wide<mt, w, tagged>; k_fused_wide64: k_fused_wide64<tpw>."""
+    task-queue kernels.  k_fused_wide: k_fused_wide<mt, w, tagged>; k_fused_wide64: k_fused_wide64<tpw>.  k_fused_all:
+    set when its last launch formed Y itself (evc_nmf_convert), with whether that launch still stored the packed
+    activations; None for every other solve on that kernel."""
+    if kernel == 5 and v:      # k_fused_all: what the end of a frame tile did in the last launch
+        return {"y_in_kernel": bool(v & 1), "packed_h_stored": bool(v & 2)}
     if kernel not in (6, 7):
         return None
     d = {"static": bool(v & 1), "reduce": bool(v & 2), "tagged": bool(v & 4)}

@@ -127,8 +127,12 @@ template <typename T> struct Workspace {
     FusedLayout flB;
     T* Bt;
     double *B1p, *B2p, *Yp;
+    // k_fused_all forming Y at the end of its last launch: one Yp image per member (NULL: not for these sizes); carved
+    // last, so that a workspace of bytes_min holds everything else at the same place (Yp itself serves one member)
+    double* Yslab;
+    int y_members;
     bool fused, packed_synth;
-    size_t bytes;
+    size_t bytes, bytes_min;
 };
 
 int n_slots_for(int iters, int check_every) { return 1 + (check_every > 0 ? iters / check_every : 0); }
@@ -204,7 +208,15 @@ Workspace<T> carve(void* base, const Dims& d, int algo, int n_slots, bool fused,
     w.G = gram ? c.take<T>((size_t)d.Np * d.Np) : nullptr;
     w.err2 = c.take<double>(d.Tp);
     w.u = take_utt(c, d, n_slots);
-    w.bytes = (c.off + 255) & ~size_t(255);
+    w.bytes = w.bytes_min = (c.off + 255) & ~size_t(255);
+    w.Yslab = nullptr;
+    w.y_members = 0;
+    if (w.packed_synth && w.flB.NT == w.fl.NT && w.fl.NT % 32 == 0 && w.fl.NT / 32 <= ALL_MAX_MEMBERS &&
+        d.Mb <= 16 * w.fl.mtiles) {
+        w.y_members = w.fl.NT / 32;
+        w.Yslab = w.y_members == 1 ? w.Yp : c.take<double>((size_t)w.y_members * w.flB.vp);
+        w.bytes = (c.off + 255) & ~size_t(255);
+    }
     return w;
 }
 
@@ -405,11 +417,28 @@ int utt_start_values(const UttState& u, const T* Xt, int n_utt, const Dims& d, c
     return ST_OK;
 }
 
+// B's fragments for the synthesis from the packed tiles (a prepared dictionary may hold them already)
+int pack_synth_dict(const Workspace<double>& w, const Dims& d, const evc_solve_opts& o, const SynthArgs& y, hipStream_t s) {
+    if (y.b_packed) return ST_OK;
+    const bool fm = (o.layout == EVC_FRAME_MAJOR);
+    // Bt[n][mb] (zero padded to 32 bins) -> B's V'-operand fragments
+    HIP_TRY(copy2d<double>(static_cast<const double*>(y.B), y.ldb, d.N, y.Mb, (fm || y.b_rows) ? 0 : 1, w.Bt, 32,
+                           d.Np, 32, 0, s));
+    HIP_TRY(fused_pack_dict(w.flB, w.B1p, w.B2p, w.Bt, 32, d.Np, s));
+    return ST_OK;
+}
+
 // The fused persistent path (float64, M <= 32): one launch per `check_every` iterations (or a
 // single launch when no residual is requested); V is carried between launches.
+// H_out: the caller's H when the last launch may write it (NULL: not wanted, or to be exported behind the abort check);
+// h_later: finish_fused will export H from the packed tiles whatever this function does; y: the synthesis that follows
+// (NULL: none).  *exported / *y_done: the last launch delivered H / left the members' shares of Y in w.Yslab.
 int solve_fused(const Workspace<double>& w, const Dims& d, const evc_solve_opts& o, const FusedRoute& r, int n_utt,
-                hipStream_t s, double* H_out, int ldh, int* exported, evc_solve_info* inf) {
+                hipStream_t s, double* H_out, int ldh, bool h_later, const SynthArgs* y, int* exported, int* y_done,
+                evc_solve_info* inf) {
     *exported = 0;
+    *y_done = 0;
+    if (y && w.packed_synth) HIP_TRY(pack_synth_dict(w, d, o, *y, s));
     if (!o.dict) {     // (a prepared dictionary holds the fragments already)
         DictArrays<double> da{};
         da.At = w.At; da.Akl = w.Akl; da.A1p = w.fb.A1p; da.A2p = w.fb.A2p; da.rsum = w.fb.rsum;
@@ -448,6 +477,18 @@ int solve_fused(const Workspace<double>& w, const Dims& d, const evc_solve_opts&
             fb.Hx = H_out; fb.ldhx = ldh; fb.hx_frame_major = o.layout == EVC_FRAME_MAJOR ? 1 : 0;
             *exported = 1;
         }
+        // ... and on k_fused_all forms the members' shares of Y from the activations in its registers (round 9), when
+        // B's bins fit the instance's row tiles and the workspace holds the slabs; the packed activations are then
+        // stored only if somebody reads them afterwards (finish_fused: the export of H, the two-pass synthesis)
+        if (r.kernel == EVC_KERNEL_FUSED_ALL && r.direct_export && done + n == o.iters) {
+            if (y && w.packed_synth && w.Yslab && w.y_members == r.members) {
+                fb.Yb2p = w.B2p; fb.Yslab = w.Yslab; fb.y_stride = (long)w.flB.vp; fb.y_mt = w.flB.mtiles;
+                *y_done = 1;
+            }
+            fb.skip_hp = (!h_later && (!y || *y_done)) ? 1 : 0;
+            // (reported for a synthesis formed here only: every other solve on this kernel keeps variant 0)
+            inf->variant = *y_done ? (1 | (fb.skip_hp ? 0 : 2)) : 0;
+        }
         HIP_TRY(hook.before_launch(s));
         ++inf->launches;
         HIP_TRY(fused_iterate(w.fl, fb, r, w.u, d.N, d.T_, n, first, check ? 1 : 0, w.err2, o.eps_mode, o.eps, o.l1,
@@ -463,18 +504,19 @@ int solve_fused(const Workspace<double>& w, const Dims& d, const evc_solve_opts&
 }
 
 // tail of the fused path: H out of the packed tiles, Y from them
+// (y_done: k_fused_all's last launch left the members' shares of Y in w.Yslab - they are summed; else the pre-pass over
+// the packed activations with B's fragments, which solve_fused packed, forms Y)
 int finish_fused(const Workspace<double>& w, const Dims& d, const evc_solve_opts& o, double* H, int ldh,
-                 const SynthArgs* y, hipStream_t s) {
+                 const SynthArgs* y, int y_done, int y_members, hipStream_t s) {
     const bool fm = (o.layout == EVC_FRAME_MAJOR);
     if (H) HIP_TRY(fused_export_h(w.fl, w.fb.Hp, H, ldh, fm ? 1 : 0, d.T_, d.N, s));
     if (!y) return ST_OK;
+    if (y_done) {
+        HIP_TRY(fused_unpack_y(w.flB, w.Yslab, y_members, (long)w.flB.vp, d.T_, y->Mb, static_cast<double*>(y->Y), y->ldy,
+                               fm ? 1 : 0, s));
+        return ST_OK;
+    }
     if (w.packed_synth) {
-        // Bt[n][mb] (zero padded to 32 bins) -> B's V'-operand fragments -> pre-pass -> Y
-        if (!y->b_packed) {
-            HIP_TRY(copy2d<double>(static_cast<const double*>(y->B), y->ldb, d.N, y->Mb, (fm || y->b_rows) ? 0 : 1, w.Bt, 32,
-                                   d.Np, 32, 0, s));
-            HIP_TRY(fused_pack_dict(w.flB, w.B1p, w.B2p, w.Bt, 32, d.Np, s));
-        }
         HIP_TRY(fused_synthesize(w.flB, w.B2p, w.fb.Hp, w.Yp, w.u, d.N, d.T_, y->Mb,
                                  static_cast<double*>(y->Y), y->ldy, fm ? 1 : 0, s));
         return ST_OK;
@@ -803,7 +845,8 @@ int solve_typed(const void* A_, int lda, const void* X_, int ldx, void* H_, int 
     DictArrays<T> ext{};
     if (o.dict) ext = dict_arrays<T>(o.dict, (sizeof(T) == 8 && o.dict->dtype == EVC_F32) ? dict_f64_staging(M, o.dict->Mb, N) : 0);
     Workspace<T> w = carve<T>(ws, d, algo, MAX_SLOTS, fused, o.dict ? &ext : nullptr);
-    if (w.bytes > ws_bytes) return ST_WORKSPACE;
+    if (w.bytes_min > ws_bytes) return ST_WORKSPACE;
+    if (w.bytes > ws_bytes) w.Yslab = nullptr;      // no room for the members' shares of Y: the two-pass synthesis
     inf->prepared = o.dict ? 1 : 0;
     SynthArgs ydict;              // synthesis from the prepared copy of B
     if (o.dict && y && o.dict->Mb > 0) {
@@ -841,13 +884,15 @@ int solve_typed(const void* A_, int lda, const void* X_, int ldx, void* H_, int 
                 HIP_TRY(fused_import_h(w.fl, w.fb.Hp, H, ldh, fm ? 1 : 0, T_, N, s));
             const bool coop_used = fr.members > 1;
             const int* abort_w = w.fb.coop_cnt + COOP_MAX_TILES;
-            int aborted = 0, exported = 0;        // (constant start values: solve_fused)
+            int aborted = 0, exported = 0, y_done = 0;        // (constant start values: solve_fused)
             // (with caller-given start values the abort flag is read before anything goes to the caller's H: no
             // direct export then)
-            HIP_TRY(solve_fused(w, d, oo, fr, n_utt, s, check_first ? nullptr : H, ldh, &exported, inf));
+            inf->variant = 0;
+            HIP_TRY(solve_fused(w, d, oo, fr, n_utt, s, check_first ? nullptr : H, ldh, check_first && H, y, &exported,
+                                &y_done, inf));
             if (coop_used && check_first) HIP_TRY(read_abort(abort_w, s, &aborted));
             if (!aborted) {
-                HIP_TRY(finish_fused(w, d, o, exported ? nullptr : H, ldh, y, s));
+                HIP_TRY(finish_fused(w, d, o, exported ? nullptr : H, ldh, y, y_done, fr.members, s));
                 if (coop_used && !check_first) HIP_TRY(read_abort(abort_w, s, &aborted));
             }
             if (!aborted) break;

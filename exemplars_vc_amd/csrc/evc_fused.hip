@@ -131,8 +131,11 @@ __global__ __launch_bounds__(256) void k_fill_hp(f64x2* __restrict__ Hp, long n_
 }
 
 // Y (caller layout) <- Yp[tt][s][l] = Y[bin_of(s, l>>4)][16 tt + (l&15)]   (accumulator order of B H)
+// members > 1: Yp holds one such image per member of k_fused_all's groups, `stride` doubles apart, each the share of
+// that member's exemplars; they are added in member order (fixed order, no atomics: bitwise reproducible)
 __global__ __launch_bounds__(256) void k_unpack_y(const double* __restrict__ Yp, long n_elems, int msteps, int Mb,
-                                                   int T_, double* __restrict__ Y, long ldy, int frame_major) {
+                                                   int T_, double* __restrict__ Y, long ldy, int frame_major,
+                                                   int members, long stride) {
     const long gid = (long)blockIdx.x * 256 + threadIdx.x;
     if (gid >= n_elems) return;
     const int l = gid & 63, s = (gid >> 6) % msteps;
@@ -140,7 +143,8 @@ __global__ __launch_bounds__(256) void k_unpack_y(const double* __restrict__ Yp,
     const long t = 16 * tt + (l & 15);
     const int mb = bin_of(s, l >> 4);
     if (t >= T_ || mb >= Mb) return;
-    const double v = Yp[(tt * 8 + s) * 64 + l];
+    double v = Yp[(tt * 8 + s) * 64 + l];
+    for (int m = 1; m < members; ++m) v += Yp[m * stride + (tt * 8 + s) * 64 + l];
     if (frame_major) Y[t * ldy + mb] = v; else Y[(long)mb * ldy + t] = v;
 }
 
@@ -522,6 +526,7 @@ hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const Fuse
     a.eps_mode = eps_mode; a.eps = eps; a.l1 = l1;
     a.coop_c = 1; a.coop_buf = nullptr; a.coop_cnt = nullptr; a.coop_abort = nullptr; a.groups = 0;
     a.init_const = 0; a.h0 = nullptr; a.rsum = nullptr; a.Hx = nullptr; a.ldhx = 0; a.hx_frame_major = 0;
+    a.hx_wide = 0; a.Yb2p = nullptr; a.Yslab = nullptr; a.y_stride = 0; a.y_mt = 0; a.skip_hp = 0;
     a.M = f.M; a.spare_q = -1; a.stagger_cycles = 0;
     const bool xy = r.kernel == EVC_KERNEL_FUSED_XY;
     const bool all_res = xy || r.kernel == EVC_KERNEL_FUSED_ALL;
@@ -542,10 +547,16 @@ hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const Fuse
     if (all_res) {
         a.coop_c = r.members; a.coop_buf = b.coop_buf; a.coop_cnt = b.coop_cnt;
         a.coop_abort = b.coop_cnt + COOP_MAX_TILES;
-        if (all_live_known) { a.Hx = b.Hx; a.ldhx = b.ldhx; a.hx_frame_major = b.hx_frame_major; }
+        if (all_live_known) {
+            a.Hx = b.Hx; a.ldhx = b.ldhx; a.hx_frame_major = b.hx_frame_major;
+            a.hx_wide = (a.Hx && a.hx_frame_major && !(reinterpret_cast<uintptr_t>(a.Hx) & 15) && !(a.ldhx & 1)) ? 1 : 0;
+            if (!xy) {       // the tail of k_fused_all's last launch (solve_fused decides; k_fused_xy has none)
+                a.Yb2p = b.Yb2p; a.Yslab = b.Yslab; a.y_stride = b.y_stride; a.y_mt = b.y_mt; a.skip_hp = b.skip_hp;
+            }
+        }
         e = xy ? fused_xy_launch(f.msteps, a, r.n_cus, s) : fused_all_launch(f.msteps, a, r.n_cus, s);
         a.coop_c = 1;            // the general kernel behind it takes no part in any exchange
-        a.first = 0; a.init_const = 0; a.Hx = nullptr;
+        a.first = 0; a.init_const = 0; a.Hx = nullptr; a.Yslab = nullptr; a.skip_hp = 0;
     } else {
         if (r.members > 1) {
             a.coop_c = r.members; a.coop_buf = b.coop_buf; a.coop_cnt = b.coop_cnt;
@@ -570,14 +581,21 @@ hipError_t fused_synthesize(const FusedLayout& fB, const double* B2p, const doub
     a.NT = fB.NT; a.TT = fB.TT; a.N = N; a.T_ = T_;
     a.iters = 0; a.first = 1; a.write_err = 0; a.skip_all_live = 0; a.force_live = 1; a.loss = EVC_LOSS_FROBENIUS; a.exact_div = 0;
     a.Hx = nullptr; a.ldhx = 0; a.hx_frame_major = 0;
+    a.hx_wide = 0; a.Yb2p = nullptr; a.Yslab = nullptr; a.y_stride = 0; a.y_mt = 0; a.skip_hp = 0;
     a.init_const = 0; a.h0 = nullptr; a.rsum = nullptr; a.M = fB.M; a.spare_q = -1; a.stagger_cycles = 0;
     a.coop_c = 1; a.coop_buf = nullptr; a.coop_cnt = nullptr; a.coop_abort = nullptr; a.groups = 0;
     a.eps_mode = EVC_EPS_ADD; a.eps = 0; a.l1 = 0;
     hipError_t e = dispatch_msteps<1>(fB.msteps, a, s);
     if (e != hipSuccess) return e;
+    return fused_unpack_y(fB, Yp, 1, 0, T_, Mb, Y, ldy, frame_major, s);
+}
+
+// Y from `members` images of B H in accumulator order, `stride` doubles apart, added in member order
+hipError_t fused_unpack_y(const FusedLayout& fB, const double* Yp, int members, long stride, int T_, int Mb, double* Y,
+                          long ldy, int frame_major, hipStream_t s) {
     const long n = (long)fB.TT * fB.msteps * 64;
     hipLaunchKernelGGL(k_unpack_y, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, Yp, n, fB.msteps, Mb, T_,
-                       Y, ldy, frame_major);
+                       Y, ldy, frame_major, members, stride);
     return hipGetLastError();
 }
 

@@ -658,16 +658,84 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
             }
         }
 
-        if (valid) {
+        // ---------------- the end of the frame tile
+        // Round 9, last launch with a synthesis behind it (a.Yslab): this member's share of Y = B H while the activations
+        // are still in registers - one more V'-shaped pass over the 8 resident tiles with B's fragments (streamed from
+        // B2p: the LDS dictionary holds A), the 4 wavefronts' partials summed in order through s_red (nobody exchanges
+        // any more), the sums to the member's slab.  k_unpack_y adds the slabs in member order.  Every frame tile is
+        // valid in such a launch (nothing can stop); the barriers are taken by everybody all the same.
+        // B's bin tiles of 16 (a.y_mt) are the instance's MT or, for a short B beside a tall A, 1: the tile count is a
+        // compile-time constant of each copy of the pass, so that its loads are those of the streamed load_a2.
+        auto y_tail = [&](auto ut) __attribute__((always_inline)) {
+            constexpr int UT = decltype(ut)::value;
+            f64x4 yn[UT];
 #pragma unroll
-            for (int k = 0; k < AKT; ++k) {
-                f64x2* t = Hp + (tt * NT + tile0 + AW * k) * 128;
-                t[ul] = f64x2{h[k][0], h[k][1]};
-                t[ul + 64] = f64x2{h[k][2], h[k][3]};
+            for (int u = 0; u < UT; ++u) yn[u] = f64x4{0, 0, 0, 0};
+            if (valid) {
+                const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(a.Yb2p), 0, NT * (UT * 2048), 0x00020000);
+#pragma unroll
+                for (int k = 0; k < AKT; ++k) {
+                    const int so = (int)(tile0 + AW * k) * (UT * 2048);
+                    double b2[UT][4];
+#pragma unroll
+                    for (int u = 0; u < UT; ++u)
+#pragma unroll
+                        for (int r = 0; r < 4; r += 2) {
+                            const f64x2 v = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(rb, ul16 + (u * 2 + (r >> 1)) * 1024, so, 0));
+                            b2[u][r] = v[0];
+                            b2[u][r + 1] = v[1];
+                        }
+#pragma unroll
+                    for (int u = 0; u < UT; ++u)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) yn[u] = Mma<double>::mma(b2[u][r], h[k][r], yn[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < UT; ++u) {
+                if (valid) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) red[w * RSTR + r * 64 + lane] = yn[u][r];
+                }
+                __syncthreads();
+                if (valid) {                     // thread th: k-step 4 u + th / 64, lane th % 64 of the image
+                    double y = 0.0;
+#pragma unroll
+                    for (int ww = 0; ww < AW; ++ww) y += red[ww * RSTR + th];
+                    a.Yslab[member * a.y_stride + (tt * 8 + 4 * u) * 64 + th] = y;
+                }
+                __syncthreads();
+            }
+        };
+        if (a.Yslab) {
+            if (MT > 1 && a.y_mt == 1) y_tail(std::integral_constant<int, 1>{});
+            else y_tail(std::integral_constant<int, MT>{});
+        }
+        if (valid) {
+            if (!a.skip_hp) {                    // (skipped: the last launch, when nothing reads the packed tiles after it)
+#pragma unroll
+                for (int k = 0; k < AKT; ++k) {
+                    f64x2* t = Hp + (tt * NT + tile0 + AW * k) * 128;
+                    t[ul] = f64x2{h[k][0], h[k][1]};
+                    t[ul + 64] = f64x2{h[k][2], h[k][3]};
+                }
             }
             if (a.Hx) {                          // last launch: the caller's H as well (no separate export pass)
                 const long t = 16 * tt + (lane & 15);
-                if (t < a.T_) {
+                if (t < a.T_ && a.hx_wide) {
+                    // frame-major, 16-byte aligned rows: a lane's four exemplars are 32 contiguous bytes - two 16-byte
+                    // stores; the pair that straddles or passes N goes element by element
+#pragma unroll
+                    for (int k = 0; k < AKT; ++k) {
+                        const long n0 = 16 * (tile0 + AW * k) + 4 * (lane >> 4);
+                        double* const row = a.Hx + t * a.ldhx + n0;
+#pragma unroll
+                        for (int r = 0; r < 4; r += 2) {
+                            if (n0 + r + 1 < a.N) *reinterpret_cast<f64x2*>(row + r) = f64x2{h[k][r], h[k][r + 1]};
+                            else if (n0 + r < a.N) row[r] = h[k][r];
+                        }
+                    }
+                } else if (t < a.T_) {
 #pragma unroll
                     for (int k = 0; k < AKT; ++k) {
                         const long n0 = 16 * (tile0 + AW * k) + 4 * (lane >> 4);

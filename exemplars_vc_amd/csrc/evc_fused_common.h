@@ -49,10 +49,20 @@ struct FusedArgs {
     const double* h0;        // [n_utt]
     const double* rsum;      // [32] row sums of the dictionary (bins), 0 beyond M
     // k_fused_all, last launch of a solve in which no utterance can stop: the activations also go straight to the
-    // caller's matrix (the separate export pass reads and writes all of H once more: 2.6 of 180 ms at C2)
+    // caller's matrix (the separate export pass reads and writes all of H once more: 2.6 of 180 ms at C2, round 3;
+    // the C2 step has since come down to ~159 ms, the pass it saves is the same 2 x 5.8 GB)
     double* Hx;              // NULL: off
     long ldhx;
     int hx_frame_major;      // 1: Hx[t * ldhx + n], 0: Hx[n * ldhx + t]
+    int hx_wide;             // 1: frame-major Hx, 16-byte aligned base, even ldhx: a lane's four values go as two 16-byte stores
+    // k_fused_all, the same launch, when a synthesis follows (round 9): each member forms its share of Y = B H from
+    // the activations in its registers and leaves it in its slab; k_unpack_y sums the slabs in member order.  The
+    // pre-pass over the packed activations (a second pass over all of H) does not run.
+    const double* Yb2p;      // B's V'-operand fragments, NT tiles of y_mt bin tiles (NULL: off)
+    double* Yslab;           // [member][y_stride]: a member's partial Y in the Yp image format ([tt][8][64])
+    long y_stride;           // doubles per member
+    int y_mt;                // B's bin tiles of 16: 1 or 2, at most the instance's
+    int skip_hp;             // 1: nothing reads the packed activations after this launch - they are not stored
     // k_fused_xy: bins of the dictionary (0: unknown) and the lane group of the last k-step that holds the spare bin M
     // in which the denominators' start value travels (-1: not used); see evc_fused_xy.hip
     int M, spare_q;

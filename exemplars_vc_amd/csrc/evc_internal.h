@@ -196,6 +196,12 @@ struct FusedBuffers {
     double* Hx;            // k_fused_all's last launch also writes the caller's H (NULL: off); ldhx, hx_frame_major
     long ldhx;
     int hx_frame_major;
+    // k_fused_all's last launch also forms the members' shares of Y = B H (Yslab NULL: off), see FusedArgs
+    const double* Yb2p;
+    double* Yslab;
+    long y_stride;
+    int y_mt;
+    int skip_hp;           // 1: that launch does not store the packed activations (nothing reads them after it)
 };
 bool fused_supported(int M, int N, int T_, int dtype);
 FusedLayout fused_layout(int M, int N, int T_);
@@ -220,6 +226,9 @@ hipError_t fused_fill_h(const FusedLayout& f, double* Hp, int N, int T_, const U
 hipError_t fused_synthesize(const FusedLayout& fB, const double* B2p, const double* Hp, double* Yp,
                             const UttState& u, int N, int T_, int Mb, double* Y, long ldy, int frame_major,
                             hipStream_t s);
+// Y (caller layout) from `members` images of B H in the Yp format, `stride` doubles apart, added in member order
+hipError_t fused_unpack_y(const FusedLayout& fB, const double* Yp, int members, long stride, int T_, int Mb, double* Y,
+                          long ldy, int frame_major, hipStream_t s);
 // `iters` updates in one launch.  first: V is built from H by a pre-pass (else carried over in
 // Vp from the previous launch); write_err: per-frame squared residuals of the final H -> err2.
 hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const FusedRoute& r, const UttState& u, int N,

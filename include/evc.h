@@ -215,7 +215,10 @@ typedef struct evc_solve_info {
     int redo;          /* 1: an exchange wait ran out and the solve was redone on kernels without exchange */
     int exchange;      /* 1: the delivered results come from a kernel whose workgroups exchange partial sums in a launch */
     int prepared;      /* 1: the dictionary came from an evc_dict_prepare image (no per-call import / packing) */
-    int variant;       /* the instance and schedule of the task-queue kernels (0 for every other kernel):
+    int variant;       /* k_fused_all: bit 0: its last launch formed Y = B H itself (evc_nmf_convert: no second pass over the
+                          activations); bit 1, with bit 0 only: that launch still stored the packed activations (a
+                          reader followed).  0 for every other solve on that kernel.
+                          The instance and schedule of the task-queue kernels (0 for every other kernel):
                           bit 0: static schedule (workgroup b runs task b of every iteration; else a ticket queue);
                           bit 1: reduce slices (reduce tasks sum the partial V' of a frame group);
                           bit 2: tagged hand-offs (the epoch bit rides in the data; k_fused_wide only);
