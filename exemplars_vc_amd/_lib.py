@@ -21,6 +21,7 @@ STOP_NONE, STOP_SKLEARN, STOP_PYMF = 0, 1, 2
 LOSS_FROBENIUS, LOSS_KL = 0, 1
 FLAG_NO_FUSED, FLAG_EXACT_DIV, FLAG_NO_EXCHANGE, FLAG_NO_ALL_RESIDENT, FLAG_PAIR_TILES = 1, 2, 4, 16, 32
 LEARN_SKLEARN, LEARN_PYMF = 0, 1
+CDL_BOTH, CDL_DICT_ONLY = 0, 1
 
 # every symbol include/evc.h declares; tests check that the library exports all of them
 SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_bytes",
@@ -29,7 +30,8 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_griffin_lim_batch", "evc_dtw_workspace_bytes", "evc_dtw_align",
            "evc_stft_frames", "evc_stft_workspace_bytes", "evc_stft", "evc_dict_bytes", "evc_dict_prepare",
            "evc_dtw_path_rows", "evc_dtw_gather_rows", "evc_cd_workspace_bytes", "evc_cd_solve",
-           "evc_learn_workspace_bytes", "evc_learn_splits", "evc_nmf_learn")
+           "evc_learn_workspace_bytes", "evc_learn_splits", "evc_nmf_learn",
+           "evc_cd_learn_workspace_bytes", "evc_cd_learn_splits", "evc_cd_learn")
 
 
 class SolveOpts(C.Structure):
@@ -60,6 +62,16 @@ class LearnOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("surface", C.c_int),
         ("iters", C.c_int), ("check_every", C.c_int), ("reserved", C.c_int), ("loss", C.c_int),
         ("tol", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class CdLearnOpts(C.Structure):
+    """Mirror of `evc_cd_learn_opts` (include/evc.h): options of the coordinate descent that also learns the dictionary."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("max_iter", C.c_int),
+        ("update", C.c_int), ("reserved", C.c_int),
+        ("tol", C.c_double), ("l1_h", C.c_double), ("l2_h", C.c_double), ("l1_w", C.c_double), ("l2_w", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -208,6 +220,18 @@ def lib():
         C.c_int, C.c_int, C.c_int, C.POINTER(LearnOpts),                    # M, R, T, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_cd_learn_workspace_bytes.restype = C.c_size_t
+    L.evc_cd_learn_workspace_bytes.argtypes = [C.c_int] * 4
+    L.evc_cd_learn_splits.restype = C.c_int
+    L.evc_cd_learn_splits.argtypes = [C.c_int] * 3
+    L.evc_cd_learn.restype = C.c_int
+    L.evc_cd_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, W, H
+        C.c_int, C.c_int, C.c_int, C.POINTER(CdLearnOpts),                  # M, R, T, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, violation_out
         C.c_void_p,                                                         # stream
     ]
     _lib = L

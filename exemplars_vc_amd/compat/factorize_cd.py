@@ -14,7 +14,7 @@ import warnings
 
 import numpy as np
 
-from ..solver import solve_activations_cd
+from ..solver import learn_dictionary_cd, solve_activations_cd
 from .factorize import ConvergenceWarning, _check_dictionary, _stack
 
 MAX_ITER = 200          # 04_align_n_nmf_pytorch.py:207-208
@@ -63,6 +63,42 @@ def _warn_if_capped(n_iter, max_iter, tol, warn_sink=None):
             warn_sink.append(msg)
         else:
             warnings.warn(msg, ConvergenceWarning, stacklevel=3)
+
+
+def non_negative_factorization_cd(X, W, H, update_H=True, tol=1e-4, max_iter=200, alpha_W=0.0, alpha_H="same",
+                                  l1_ratio=0.0, *, device=None):
+    """scikit-learn's non_negative_factorization(X, W, H, init="custom", solver="cd", beta_loss="frobenius",
+    shuffle=False) on the GPU, in scikit-learn's orientation: X (n_samples, n_features), W (n_samples, n_components),
+    H (n_components, n_features), X ~ W H.  update_H=True (NMF(...).fit_transform, 05_conversion.py:100-106) updates both
+    factors from the given starts (evc_cd_learn); update_H=False is the existing fixed-dictionary solve, which starts W at
+    0 as scikit-learn does.  The penalties are scaled as _compute_regularization does: l1_reg_W = n_features alpha_W
+    l1_ratio, l1_reg_H = n_samples alpha_H l1_ratio (alpha_H="same": alpha_W), likewise l2 with (1 - l1_ratio).
+    Returns (W, H, n_iter); ConvergenceWarning when max_iter is reached with tol > 0."""
+    X = _check_frames(X)
+    H = _check_dictionary(H, X.shape[1])
+    if H.dtype != X.dtype:
+        raise TypeError(f"H should have the same dtype as X. Got H.dtype = {H.dtype}.")
+    n_samples, n_features = X.shape
+    l1_h, l2_h = _reg(n_features, alpha_W, l1_ratio)
+    if not update_H:
+        act, info = solve_activations_cd(H, X, layout="frame_major", max_iter=max_iter, tol=tol, l1=l1_h, l2=l2_h,
+                                         device=device, info=True)
+        n_iter = int(info["n_iter"][0])
+        _warn_if_capped(n_iter, max_iter, tol)
+        return act, H, n_iter
+    W = np.asarray(W)
+    if W.shape != (n_samples, H.shape[0]):
+        raise ValueError(f"Array with wrong shape passed to NMF (input W). Expected {(n_samples, H.shape[0])}, "
+                         f"but got {W.shape}")
+    if W.dtype != X.dtype:
+        raise TypeError(f"W should have the same dtype as X. Got W.dtype = {W.dtype}.")
+    if not np.all(np.isfinite(W)) or (W < 0).any():
+        raise ValueError("Negative or non-finite values in data passed to NMF (input W)")
+    l1_w, l2_w = _reg(n_samples, alpha_W if isinstance(alpha_H, str) and alpha_H == "same" else alpha_H, l1_ratio)
+    Wd, act, info = learn_dictionary_cd(X, H, W, layout="frame_major", max_iter=max_iter, tol=tol, l1_h=l1_h, l2_h=l2_h,
+                                        l1_w=l1_w, l2_w=l2_w, device=device, info=True)
+    _warn_if_capped(info["n_iter"], max_iter, tol)
+    return act, Wd, info["n_iter"]
 
 
 def factorize_utterances(X_list, W, tol=1e-4, *, device=None, max_iter=MAX_ITER, alpha_W=0.0, l1_ratio=0.0,

@@ -1598,4 +1598,42 @@ int evc_nmf_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, in
                                                                             workspace_bytes, n_iter_out, err_out, s);
 }
 
+static bool cd_learn_sizes_ok(int M, int R, int T, int dtype) {
+    return M >= 1 && R >= 1 && T >= 1 && M <= CD_MAX_M && R <= CD_LEARN_MAX_R && (dtype == EVC_F64 || dtype == EVC_F32);
+}
+
+int evc_cd_learn_splits(int M, int R, int T) {
+    return cd_learn_sizes_ok(M, R, T, EVC_F64) ? learn_splits(M, R, T) : 0;
+}
+
+size_t evc_cd_learn_workspace_bytes(int M, int R, int T, int dtype) {
+    if (!cd_learn_sizes_ok(M, R, T, dtype)) return 0;
+    return cd_learn_workspace_bytes(M, R, T, learn_splits(M, R, T), dtype == EVC_F64 ? 8 : 4);
+}
+
+int evc_cd_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
+                 const evc_cd_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
+                 double* violation_out, evc_stream_t stream) {
+    if (!opts || opts->struct_bytes != (int)sizeof(evc_cd_learn_opts)) return ST_BADARG;
+    const evc_cd_learn_opts& o = *opts;
+    if (M < 1 || R < 1 || T < 1 || o.max_iter < 0) return ST_BADARG;
+    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return ST_BADARG;
+    if (o.layout != EVC_FRAME_MAJOR && o.layout != EVC_BIN_MAJOR) return ST_BADARG;
+    if (o.update != EVC_CDL_BOTH && o.update != EVC_CDL_DICT_ONLY) return ST_BADARG;
+    const int forced = (o.reserved >> 8) & 0xff;
+    if ((o.reserved & ~0xff00) != 0 || forced > LEARN_MAX_SPLITS) return ST_BADARG;
+    if (!(o.tol >= 0.0) || !(o.l1_h >= 0.0) || !(o.l2_h >= 0.0) || !(o.l1_w >= 0.0) || !(o.l2_w >= 0.0)) return ST_BADARG;
+    if (!X || !W || !H || !workspace) return ST_BADARG;
+    if (bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldw, R, M) || bad_ld(o.layout, ldh, T, R)) return ST_BADARG;
+    if (M > CD_MAX_M || R > CD_LEARN_MAX_R) return ST_UNSUPPORTED;
+    const int S = forced ? forced : learn_splits(M, R, T);
+    if (workspace_bytes < cd_learn_workspace_bytes(M, R, T, S, o.dtype == EVC_F64 ? 8 : 4)) return ST_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (o.dtype == EVC_F64)
+        return cd_learn<double>(static_cast<const double*>(X), ldx, static_cast<double*>(W), ldw, static_cast<double*>(H),
+                                ldh, M, R, T, o, S, workspace, workspace_bytes, n_iter_out, violation_out, s);
+    return cd_learn<float>(static_cast<const float*>(X), ldx, static_cast<float*>(W), ldw, static_cast<float*>(H), ldh, M, R,
+                           T, o, S, workspace, workspace_bytes, n_iter_out, violation_out, s);
+}
+
 }  // extern "C"

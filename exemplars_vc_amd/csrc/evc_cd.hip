@@ -24,6 +24,9 @@
 // max_iter reached) and returns at once if the utterance has stopped; the utterance's first tile records the value,
 // violation_init and the stop iteration.  A final launch (k = max_iter + 1) only judges.  The violation is
 // accumulated in float64 for both element types; padded frames contribute nothing.
+//
+// evc_cd_learn (the end of this file) alternates that sweep with a Gram-form sweep over the dictionary's rows
+// (k_cd_dict_sweep): sklearn's solver='cd' with update_H=True.
 #include "evc_internal.h"
 
 namespace evc {
@@ -293,12 +296,14 @@ size_t cd_workspace_bytes(int M, int N, int T_, int n_utt, int esize) {
     return b + 256;
 }
 
+namespace {
+
+// Carves the workspace, stages the tile table and clears the per-utterance state; everything of CdArgs but the
+// dictionary-dependent arrays' contents (cd_refresh) is final afterwards.  Returns 0, -1, -2 or a hipError_t.
 template <typename T>
-int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
-             int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
-             hipStream_t s, int* launches_out) {
+int cd_setup(T* H, int ldh, int M, int N, int T_, const int* utt_offsets, int n_utt, bool fm, int max_iter, double tol,
+             double l1, double l2, void* ws, size_t ws_bytes, hipStream_t s, CdArgs<T>* out) {
     const CdGeometry g = cd_geometry(M);
-    const bool fm = o.layout == EVC_FRAME_MAJOR;
     const int Np = round_up(N, CD_B);
     // tiles: each utterance starts at a tile boundary
     int n_tiles = 0;
@@ -345,37 +350,69 @@ int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int
     if (e == hipSuccess) e = hipMemcpyAsync(utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
     free(h_tiles);      // pageable source: HIP has staged the bytes by the time hipMemcpyAsync returns
     CD_TRY(e);
-
-    const int es = (int)sizeof(T);
-    if (o.init_mode == EVC_INIT_SKLEARN && T_ > 0) {
-        if (fm) CD_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)N * es, T_, s));
-        else CD_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)T_ * es, N, s));
-    }
-    {
-        const long n = (long)Np * g.Mr;
-        hipLaunchKernelGGL(k_cd_pack_dict<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A, lda, fm ? 1 : 0,
-                           M, N, Np, g.Mr, Ac);
-        CD_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_cd_gram_blocks<T>, dim3(Np / CD_B), dim3(CD_B * CD_B), 0, s, Ac, M, N, g.Mr, o.l2, Gb, hess);
-        CD_TRY(hipGetLastError());
-    }
-    if (n_tiles > 0) {
-        const long n = (long)n_tiles * g.F * g.Mr;
-        hipLaunchKernelGGL(k_cd_init_resid<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, X, ldx, H, ldh,
-                           fm ? 1 : 0, o.init_mode == EVC_INIT_GIVEN ? 1 : 0, Ac, tiles, n_tiles, g.F, M, N, g.Mr, R);
-        CD_TRY(hipGetLastError());
-    }
     {
         const long n = (long)n_utt * CD_TRACE_CAP;
         hipLaunchKernelGGL(k_cd_state_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, stop, vinit, trace,
                            n_utt);
         CD_TRY(hipGetLastError());
     }
-    CdArgs<T> a;
+    CdArgs<T>& a = *out;
     a.Ac = Ac; a.Gb = Gb; a.hess = hess; a.R = R; a.H = H; a.ldh = ldh; a.fm = fm ? 1 : 0;
     a.tiles = tiles; a.utt_tile0 = utt_tile0; a.part = part; a.stop = stop; a.vinit = vinit; a.trace = trace;
     a.n_tiles = n_tiles; a.M = M; a.N = N; a.Np = Np; a.Mr = g.Mr; a.L = g.L; a.mpl = g.mpl;
-    a.max_iter = o.max_iter; a.tol = o.tol; a.l1 = (T)o.l1; a.l2 = (T)o.l2;
+    a.max_iter = max_iter; a.tol = tol; a.l1 = (T)l1; a.l2 = (T)l2;
+    return 0;
+}
+
+// What depends on the dictionary and on the start: the packed dictionary, its diagonal Gram blocks and the residual
+// h A - x of every frame slot (given: from the activations in a.H; else from 0).
+template <typename T>
+int cd_refresh(const CdArgs<T>& a, const T* A, int lda, const T* X, int ldx, int given, double l2, hipStream_t s) {
+    const int F = CD_WAVE / a.L;
+    {
+        const long n = (long)a.Np * a.Mr;
+        hipLaunchKernelGGL(k_cd_pack_dict<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A, lda, a.fm, a.M, a.N,
+                           a.Np, a.Mr, const_cast<T*>(a.Ac));
+        CD_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_cd_gram_blocks<T>, dim3(a.Np / CD_B), dim3(CD_B * CD_B), 0, s, a.Ac, a.M, a.N, a.Mr, l2,
+                           const_cast<T*>(a.Gb), const_cast<T*>(a.hess));
+        CD_TRY(hipGetLastError());
+    }
+    if (a.n_tiles > 0) {
+        const long n = (long)a.n_tiles * F * a.Mr;
+        hipLaunchKernelGGL(k_cd_init_resid<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, X, ldx, a.H, (int)a.ldh,
+                           a.fm, given, a.Ac, a.tiles, a.n_tiles, F, a.M, a.N, a.Mr, a.R);
+        CD_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+}  // namespace
+
+template <typename T>
+int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
+             int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
+             hipStream_t s, int* launches_out) {
+    const bool fm = o.layout == EVC_FRAME_MAJOR;
+    CdArgs<T> a;
+    {
+        const int st = cd_setup<T>(H, ldh, M, N, T_, utt_offsets, n_utt, fm, o.max_iter, o.tol, o.l1, o.l2, ws, ws_bytes, s,
+                                   &a);
+        if (st != 0) return st;
+    }
+    const int n_tiles = a.n_tiles;
+    int* const stop = a.stop;
+    double* const trace = a.trace;
+    hipError_t e = hipSuccess;
+    const int es = (int)sizeof(T);
+    if (o.init_mode == EVC_INIT_SKLEARN && T_ > 0) {
+        if (fm) CD_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)N * es, T_, s));
+        else CD_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)T_ * es, N, s));
+    }
+    {
+        const int st = cd_refresh<T>(a, A, lda, X, ldx, o.init_mode == EVC_INIT_GIVEN ? 1 : 0, o.l2, s);
+        if (st != 0) return st;
+    }
 
     const bool run = n_tiles > 0 && o.max_iter > 0;
     int launches = 0;
@@ -424,5 +461,313 @@ template int cd_solve<double>(const double*, int, const double*, int, double*, i
                               const evc_cd_opts&, void*, size_t, int*, double*, hipStream_t, int*);
 template int cd_solve<float>(const float*, int, const float*, int, float*, int, int, int, int, const int*, int,
                              const evc_cd_opts&, void*, size_t, int*, double*, hipStream_t, int*);
+
+// ---- evc_cd_learn: the alternating form (sklearn solver='cd', update_H=True), DESIGN.md §5.8 ----
+//
+// Per iteration the activation half is one k_cd_sweep launch (k = 1: no judging) on the freshly packed dictionary, and
+// the dictionary half is sklearn's _update_coordinate_descent(X^T, H^T, W) in Gram form: G = H H^T + l2 I and
+// P = X H^T - l1 come from k_dict_grad's one-operand contraction (frames split into S ranges, partial sums added in
+// ascending order by k_cdl_finish), then k_cd_dict_sweep runs the M independent row sweeps.
+namespace {
+
+template <typename T> struct CdDictArgs {
+    const T* G;             // [Rp][ld] H H^T + l2 I, rows and columns past R zero
+    const T* P;             // [M][ld]  X H^T - l1
+    const T* Gb;            // [Rp/16][16][16] diagonal blocks of G
+    const T* hess;          // [Rp] G[t][t] (0 for padding components)
+    T* W;
+    long ws_m, ws_r;        // W[m * ws_m + r * ws_r]
+    double* part;           // [ceil(M / (64 / L))] per-wavefront violation
+    int ld, M, R, Rp, L, rpl;
+};
+
+// The sibling of k_cd_sweep with the Gram matrix in the dictionary's place: a dictionary row (one bin) is served by L
+// lanes (from R alone), lane q keeps w[q], w[q + L], ... in registers; per block of 16 components the gradients at the
+// block's start are 16 dot products G[c, :] . w summed by the xor butterfly, then every lane of the group runs the 16
+// in-order steps and the owning lanes store the new values.  No residual, no second pass over G; a row's arithmetic
+// does not depend on the other rows of its wavefront.  (The butterfly and the steps restate k_cd_sweep's: sharing
+// them as device functions would have meant touching that kernel.)
+template <typename T, int RPL>
+__global__ __launch_bounds__(CD_WAVE) void k_cd_dict_sweep(CdDictArgs<T> a) {
+    __shared__ double sv[CD_WAVE];
+    __shared__ T Gs[CD_B * CD_B + CD_B];            // the block's G_bb, then its 16 hess values
+    __shared__ T wn[CD_WAVE * CD_B];                // the block's new values, per row of the wavefront
+    const int L = a.L, rpl = a.rpl;
+    const int lane = threadIdx.x;
+    const int g = lane / L;                        // row of the wavefront
+    const int q = lane % L;                        // lane in the row's group
+    const int F = CD_WAVE / L;
+    const int m = blockIdx.x * F + g;
+    const bool valid = m < a.M;
+    T* Wm = a.W + (long)(valid ? m : 0) * a.ws_m;
+    const T* Pm = a.P + (long)(valid ? m : 0) * a.ld;
+    T w[RPL];
+#pragma unroll
+    for (int kk = 0; kk < RPL; ++kk) {
+        const int c = q + kk * L;
+        const T v = Wm[(long)(c < a.R ? c : a.R - 1) * a.ws_r];
+        w[kk] = (valid && kk < rpl && c < a.R) ? v : T(0);
+    }
+    double viol = 0.0;
+    const int nb = a.Rp / CD_B;
+#pragma unroll 1
+    for (int b = 0; b < nb; ++b) {
+        const int c0 = b * CD_B;
+        T wb[CD_B], gr[CD_B];
+#pragma unroll
+        for (int j = 0; j < CD_B; ++j) {
+            const int c = c0 + j < a.R ? c0 + j : a.R - 1;
+            const T v = Wm[(long)c * a.ws_r];
+            wb[j] = (valid && c0 + j < a.R) ? v : T(0);
+        }
+        {
+            const T* G = a.Gb + (long)b * CD_B * CD_B;
+#pragma unroll
+            for (int i = 0; i < CD_B * CD_B / CD_WAVE; ++i) Gs[i * CD_WAVE + lane] = G[i * CD_WAVE + lane];
+            if (lane < CD_B) Gs[CD_B * CD_B + lane] = a.hess[c0 + lane];
+        }
+        __syncthreads();
+        // 1. the block's gradients at its start: G[c0 + j, :] . w, summed over the lane group, minus P
+#pragma unroll
+        for (int j = 0; j < CD_B; ++j) gr[j] = T(0);
+#pragma unroll
+        for (int kk = 0; kk < RPL; ++kk)
+            if (kk < rpl) {
+                const T* gp = a.G + (long)c0 * a.ld + q + kk * L;
+#pragma unroll
+                for (int j = 0; j < CD_B; ++j) gr[j] = fma(gp[(long)j * a.ld], w[kk], gr[j]);
+            }
+#pragma unroll 1
+        for (int o = 1; o < L; o <<= 1)
+#pragma unroll
+            for (int j = 0; j < CD_B; ++j) gr[j] += __shfl_xor(gr[j], o);
+#pragma unroll
+        for (int j = 0; j < CD_B; ++j) gr[j] -= Pm[c0 + j];
+        // 2. the 16 coordinate steps in sklearn's order
+#pragma unroll
+        for (int j = 0; j < CD_B; ++j) {
+            __asm__ volatile("" ::: "memory");      // as in k_cd_sweep: keep the Gram reads at their steps
+            const T grad = gr[j];
+            const T pg = wb[j] == T(0) ? (grad < T(0) ? grad : T(0)) : grad;
+            if (valid && c0 + j < a.R) viol += fabs((double)pg);
+            const T h = Gs[CD_B * CD_B + j];
+            T dj = T(0);
+            if (h != T(0)) {
+                const T v = wb[j] - grad / h;
+                const T nw = v > T(0) ? v : T(0);
+                dj = nw - wb[j];
+                wb[j] = nw;
+            }
+#pragma unroll
+            for (int kk = j + 1; kk < CD_B; ++kk) gr[kk] = fma(dj, Gs[j * CD_B + kk], gr[kk]);
+        }
+        // 3. the lanes that own the block's components take the new values and store them
+        if (q == 0) {
+#pragma unroll
+            for (int j = 0; j < CD_B; ++j) wn[g * CD_B + j] = wb[j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int kk = 0; kk < RPL; ++kk) {
+            const int c = q + kk * L;
+            if (kk < rpl && c >= c0 && c < c0 + CD_B) {
+                const T v = wn[g * CD_B + (c - c0)];
+                w[kk] = v;
+                if (valid && c < a.R) Wm[(long)c * a.ws_r] = v;
+            }
+        }
+        __syncthreads();
+    }
+    if (q == 0) sv[g] = valid ? viol : 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < F; ++i) s += sv[i];
+        a.part[blockIdx.x] = s;
+    }
+}
+
+// G = sum_s partG[s] + l2 I (rows < Rp), P = sum_s partP[s] - l1 (rows < M), the slabs in the order s = 0 .. S-1; the
+// diagonal 16 x 16 blocks and hess_t = G[t][t] go out as k_cd_gram_blocks leaves them for the activation side
+template <typename T>
+__global__ __launch_bounds__(256) void k_cdl_finish(const T* __restrict__ partG, long slabG, const T* __restrict__ partP,
+                                                    long slabP, int S, int ld, int M, int R, int Rp, T l1, T l2,
+                                                    T* __restrict__ G, T* __restrict__ P, T* __restrict__ Gb,
+                                                    T* __restrict__ hess) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)(Rp + M) * ld) return;
+    const int row = (int)(idx / ld), col = (int)(idx % ld);
+    if (row < Rp) {
+        const T* __restrict__ p = partG + (long)row * ld + col;
+        T v = T(0);
+        for (int s = 0; s < S; ++s) v += p[(long)s * 2 * slabG];
+        if (row == col && row < R) v += l2;
+        G[idx] = v;
+        if (col < Rp && row / CD_B == col / CD_B) Gb[(long)(row / CD_B) * CD_B * CD_B + (row % CD_B) * CD_B + col % CD_B] = v;
+        if (row == col) hess[row] = row < R ? v : T(0);
+    } else {
+        const int m = row - Rp;
+        const T* __restrict__ p = partP + (long)m * ld + col;
+        T v = T(0);
+        for (int s = 0; s < S; ++s) v += p[(long)s * 2 * slabP];
+        P[(long)m * ld + col] = v - l1;
+    }
+}
+
+// out[0] = sum of the activation sweep's per-tile partials, out[1] = sum of the dictionary sweep's per-wavefront ones,
+// each in a fixed order (256 strided sums, then a tree)
+__global__ __launch_bounds__(256) void k_cdl_viol(const double* __restrict__ pa, int na, const double* __restrict__ pd,
+                                                  int nd, double* __restrict__ out) {
+    __shared__ double red[2][256];
+    double sa = 0.0, sd = 0.0;
+    for (int i = threadIdx.x; i < na; i += 256) sa += pa[i];
+    for (int i = threadIdx.x; i < nd; i += 256) sd += pd[i];
+    red[0][threadIdx.x] = sa;
+    red[1][threadIdx.x] = sd;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out[0] = red[0][0];
+        out[1] = red[1][0];
+    }
+}
+
+template <typename T>
+hipError_t launch_dict_sweep(const CdDictArgs<T>& a, hipStream_t s) {
+    const int F = CD_WAVE / a.L;
+    const dim3 grid((a.M + F - 1) / F), block(CD_WAVE);
+    if (a.rpl <= 1) hipLaunchKernelGGL((k_cd_dict_sweep<T, 1>), grid, block, 0, s, a);
+    else if (a.rpl <= 8) hipLaunchKernelGGL((k_cd_dict_sweep<T, 8>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_cd_dict_sweep<T, 16>), grid, block, 0, s, a);
+    return hipGetLastError();
+}
+
+constexpr int CDL_RING = 64;        // device ring of per-iteration violation pairs
+
+template <typename T> struct CdLearnWs {
+    char* cd;               // the activation half's workspace (cd_workspace_bytes)
+    size_t cd_bytes;
+    T *Xt, *Ht, *partP, *partG, *G, *P, *Gb, *hess;
+    double *dpart, *ring;
+    size_t bytes;
+};
+
+// slabs of one contraction: S ranges of two slabs each, the last range's second slab cut to the one row that is written
+size_t cdl_part_elems(int rows, int S, int ld) { return (size_t)(2 * S - 1) * learn_bin_tiles(rows) * 16 * ld + ld; }
+
+template <typename T> CdLearnWs<T> carve_cd_learn(void* ws, int M, int R, int T_, int S) {
+    CdLearnWs<T> w;
+    const uintptr_t base = (reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255);     // ws == NULL: sizes only
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = reinterpret_cast<char*>(base + off); off += align256(bytes); return p; };
+    const int Mk = round_up(M, 16), ld = round_up(R, 128), Rp = round_up(R, CD_B);
+    const CdGeometry gr = cd_geometry(R);          // the dictionary sweep's lane geometry comes from R as k_cd_sweep's from M
+    w.cd_bytes = cd_workspace_bytes(M, R, T_, 1, (int)sizeof(T));
+    w.cd = take(w.cd_bytes);
+    w.Xt = reinterpret_cast<T*>(take((size_t)T_ * Mk * sizeof(T)));
+    w.Ht = reinterpret_cast<T*>(take((size_t)T_ * ld * sizeof(T)));
+    w.partP = reinterpret_cast<T*>(take(cdl_part_elems(M, S, ld) * sizeof(T)));
+    w.partG = reinterpret_cast<T*>(take(cdl_part_elems(R, S, ld) * sizeof(T)));
+    w.G = reinterpret_cast<T*>(take((size_t)Rp * ld * sizeof(T)));
+    w.P = reinterpret_cast<T*>(take((size_t)M * ld * sizeof(T)));
+    w.Gb = reinterpret_cast<T*>(take((size_t)Rp * CD_B * sizeof(T)));
+    w.hess = reinterpret_cast<T*>(take((size_t)Rp * sizeof(T)));
+    w.dpart = reinterpret_cast<double*>(take((size_t)((M + gr.F - 1) / gr.F) * sizeof(double)));
+    w.ring = reinterpret_cast<double*>(take((size_t)CDL_RING * 2 * sizeof(double)));
+    w.bytes = (size_t)(base - reinterpret_cast<uintptr_t>(ws)) + off;
+    return w;
+}
+
+}  // namespace
+
+size_t cd_learn_workspace_bytes(int M, int R, int T_, int S, int esize) {
+    if (M < 1 || M > CD_MAX_M || R < 1 || R > CD_LEARN_MAX_R || T_ < 1 || S < 1 || S > LEARN_MAX_SPLITS) return 0;
+    if (esize == 8) return carve_cd_learn<double>(nullptr, M, R, T_, S).bytes + 256;
+    if (esize == 4) return carve_cd_learn<float>(nullptr, M, R, T_, S).bytes + 256;
+    return 0;
+}
+
+template <typename T>
+int cd_learn(const T* X, int ldx, T* W, int ldw, T* H, int ldh, int M, int R, int T_, const evc_cd_learn_opts& o, int S,
+             void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out, hipStream_t s) {
+    const CdLearnWs<T> w = carve_cd_learn<T>(ws, M, R, T_, S);
+    if (w.bytes > ws_bytes) return -2;
+    const bool fm = o.layout == EVC_FRAME_MAJOR;
+    const bool both = o.update == EVC_CDL_BOTH;
+    const int Mk = round_up(M, 16), ld = round_up(R, 128), Rp = round_up(R, CD_B);
+    const CdGeometry gr = cd_geometry(R);
+    for (int i = 0; violation_out && i < 2 * o.max_iter; ++i) violation_out[i] = __builtin_nan("");
+    if (n_iter_out) *n_iter_out = 0;
+    if (o.max_iter == 0) return 0;
+
+    CdArgs<T> a{};
+    if (both) {
+        const int st = cd_setup<T>(H, ldh, M, R, T_, nullptr, 1, fm, 1, 0.0, o.l1_h, o.l2_h, w.cd, w.cd_bytes, s, &a);
+        if (st != 0) return st;
+    }
+    CdDictArgs<T> d;
+    d.G = w.G; d.P = w.P; d.Gb = w.Gb; d.hess = w.hess; d.W = W;
+    d.ws_m = fm ? 1 : ldw; d.ws_r = fm ? ldw : 1;
+    d.part = w.dpart; d.ld = ld; d.M = M; d.R = R; d.Rp = Rp; d.L = gr.L; d.rpl = gr.mpl;
+    const int n_waves = (M + gr.F - 1) / gr.F;
+    const long slabP = (long)learn_bin_tiles(M) * 16 * ld, slabG = (long)learn_bin_tiles(R) * 16 * ld;
+
+    CD_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, Mk, T_, Mk, 0, s));
+    if (!both) CD_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, ld, T_, ld, 0, s));
+    // only a call that wants neither the stop rule nor any figure back is a pure enqueue
+    const bool sync = o.tol > 0.0 || n_iter_out || violation_out;
+    if (o.ev_loop_start) CD_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
+    int n_iter = 0;
+    double vinit = 0.0;
+    for (int it = 1; it <= o.max_iter; ++it) {
+        if (both) {
+            // activations: one sweep from the current H on the current W (the residual h W^T - x is formed afresh)
+            const int st = cd_refresh<T>(a, W, ldw, X, ldx, 1, o.l2_h, s);
+            if (st != 0) return st;
+            CD_TRY(launch_sweep<T>(a, 1, s));
+            CD_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, ld, T_, ld, 0, s));
+        }
+        // dictionary: the two contractions over the frames, their sums, the row sweeps
+        CD_TRY(dict_grad_kl<T>(w.Xt, Mk, w.Ht, ld, M, T_, S, w.partP, s));
+        CD_TRY(dict_grad_kl<T>(w.Ht, ld, w.Ht, ld, R, T_, S, w.partG, s));
+        {
+            const long n = (long)(Rp + M) * ld;
+            hipLaunchKernelGGL(k_cdl_finish<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.partG, slabG, w.partP,
+                               slabP, S, ld, M, R, Rp, (T)o.l1_w, (T)o.l2_w, w.G, w.P, w.Gb, w.hess);
+            CD_TRY(hipGetLastError());
+        }
+        CD_TRY(launch_dict_sweep<T>(d, s));
+        n_iter = it;
+        if (!sync) continue;
+        double* slot = w.ring + (size_t)(it % CDL_RING) * 2;
+        hipLaunchKernelGGL(k_cdl_viol, dim3(1), dim3(256), 0, s, both ? a.part + a.n_tiles : nullptr, both ? a.n_tiles : 0,
+                           w.dpart, n_waves, slot);
+        CD_TRY(hipGetLastError());
+        double v[2];
+        CD_TRY(hipMemcpyAsync(v, slot, sizeof(v), hipMemcpyDeviceToHost, s));
+        CD_TRY(hipStreamSynchronize(s));
+        if (violation_out) {
+            violation_out[2 * (it - 1)] = v[0];
+            violation_out[2 * (it - 1) + 1] = v[1];
+        }
+        const double viol = v[0] + v[1];
+        if (it == 1) vinit = viol;
+        if (vinit == 0.0 || viol / vinit <= o.tol) break;      // _nmf.py:513-519; the stopping iteration's updates stay
+    }
+    if (o.ev_loop_stop) CD_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
+    if (n_iter_out) *n_iter_out = n_iter;
+    return 0;
+}
+
+template int cd_learn<double>(const double*, int, double*, int, double*, int, int, int, int, const evc_cd_learn_opts&, int,
+                              void*, size_t, int*, double*, hipStream_t);
+template int cd_learn<float>(const float*, int, float*, int, float*, int, int, int, int, const evc_cd_learn_opts&, int,
+                             void*, size_t, int*, double*, hipStream_t);
 
 }  // namespace evc

@@ -363,6 +363,14 @@ int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int
              int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
              hipStream_t s, int* launches_out);
 
+// evc_cd_learn: the alternating form; S frame ranges for the two contractions over the frames (learn_splits)
+constexpr int CD_LEARN_MAX_R = 1024;  // 64 lanes x 16 components per lane; keeps learn_bin_tiles(R) within evc_nmf_learn's
+size_t cd_learn_workspace_bytes(int M, int R, int T_, int S, int esize);
+// arguments already validated by evc_cd_learn; returns 0, -2 or a hipError_t
+template <typename T>
+int cd_learn(const T* X, int ldx, T* W, int ldw, T* H, int ldh, int M, int R, int T_, const evc_cd_learn_opts& o, int S,
+             void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out, hipStream_t s);
+
 // ----- evc_learn.hip: the dictionary update of evc_nmf_learn -----
 constexpr int LEARN_MAX_M = 1056;     // 66 bin tiles of 16
 constexpr int LEARN_MAX_R = 4096;

@@ -534,8 +534,91 @@ def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every
     return res
 
 
+_CDL_UPDATES = {"both": _lib.CDL_BOTH, "dict": _lib.CDL_DICT_ONLY}
+
+
+def _cd_learn_workspace(L, M, R, T, dcode, splits):
+    """bytes evc_cd_learn needs; `splits` forced frame ranges beyond evc_cd_learn_splits() add their slabs (include/evc.h)"""
+    nbytes = int(L.evc_cd_learn_workspace_bytes(M, R, T, dcode))
+    extra = int(splits) - int(L.evc_cd_learn_splits(M, R, T)) if nbytes else 0
+    if extra > 0:
+        tiles = lambda n: (-(-n // 16) + 3) // 4 * 4
+        nbytes += extra * 2 * 16 * (tiles(M) + tiles(R)) * (-(-R // 128) * 128) * (8 if dcode == _lib.F64 else 4)
+    return nbytes
+
+
+def learn_dictionary_cd(X, W0, H0, *, layout, max_iter=200, tol=1e-4, l1_h=0.0, l2_h=0.0, l1_w=0.0, l2_w=0.0, update="both",
+                        dtype=None, device=None, info=False, out_w=None, out_h=None, loop_events=None, splits=0):
+    """scikit-learn's coordinate descent on BOTH factors, X ~ W H (solver='cd', update_H=True, shuffle=False, Frobenius), on
+    the GPU (evc_cd_learn): W is addressed like the dictionary A of solve_activations, H like its activations, both start
+    at W0 / H0.  Per iteration one activation sweep (that of solve_activations_cd), then one sweep over the dictionary's
+    rows; the loop stops after the iteration whose violation / violation_init <= tol (or violation_init == 0), else at
+    max_iter.  l1_h / l2_h are sklearn's scaled l1_reg_W / l2_reg_W (activations), l1_w / l2_w its l1_reg_H / l2_reg_H
+    (dictionary).  update="dict": the activations stay at H0 and only the dictionary half runs and counts.
+
+    Returns (W, H) in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out); with
+    info=True also dict(n_iter=int, violation=[max_iter, 2] array: the activation and the dictionary half of every
+    iteration, NaN after the stop, splits=frame ranges of the sums over the frames).  out_w / out_h: device tensors updated
+    in place (they then hold the start, W0 / H0 are ignored when None).  splits: tuning and tests, 1..64 frame ranges.
+    info=False with tol=0 enqueues max_iter iterations without waiting.  No CPU fallback: without a HIP device this raises
+    RuntimeError."""
+    if update not in _CDL_UPDATES:
+        raise ValueError(f"update must be one of {sorted(_CDL_UPDATES)}, got {update!r}")
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    lay = _LAYOUTS[layout]
+    tdtype, dcode = _pick_dtype(dtype, X, W0 if W0 is not None else out_w)
+    X_d, x_np = _to_dev(X, tdtype, device)
+    M, T = X_d.shape if lay == _lib.BIN_MAJOR else X_d.shape[::-1]
+
+    def start(a0, out, what):
+        if out is not None:
+            if a0 is not None:
+                out.copy_(_to_dev(a0, tdtype, device)[0])
+            if out.dtype != tdtype or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
+                raise ValueError(f"`out_{what}` must be a device matrix of the call's dtype with unit inner stride")
+            return out
+        a_d, _ = _to_dev(a0, tdtype, device)
+        if isinstance(a0, torch.Tensor) and a_d.data_ptr() == a0.data_ptr():
+            a_d = a_d.clone()       # never clobber the caller's start
+        return a_d
+
+    W_d, H_d = start(W0, out_w, "w"), start(H0, out_h, "h")
+    M2, R = W_d.shape if lay == _lib.BIN_MAJOR else W_d.shape[::-1]
+    R2, T2 = H_d.shape if lay == _lib.BIN_MAJOR else H_d.shape[::-1]
+    if M2 != M or R2 != R or T2 != T:
+        raise ValueError(f"X {tuple(X_d.shape)}, W {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
+    opts = _lib.CdLearnOpts()
+    opts.struct_bytes = C.sizeof(_lib.CdLearnOpts)
+    opts.dtype, opts.layout, opts.max_iter, opts.update = dcode, lay, int(max_iter), _CDL_UPDATES[update]
+    opts.reserved = (int(splits) & 0xff) << 8
+    opts.tol, opts.l1_h, opts.l2_h, opts.l1_w, opts.l2_w = float(tol), float(l1_h), float(l2_h), float(l1_w), float(l2_w)
+    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
+        opts.ev_loop_start = int(loop_events[0].cuda_event)
+        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    ws_bytes = _cd_learn_workspace(L, M, R, T, dcode, splits)
+    if ws_bytes == 0:
+        raise ValueError(f"unsupported coordinate-descent learning shape M={M}, R={R}, T={T} (M, R <= 1024)")
+    n_iter = C.c_int(0)
+    viol = np.full((max(int(max_iter), 0), 2), np.nan) if info else None
+    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_cd_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
+                            C.byref(opts), ws.data_ptr(), ws.numel(),
+                            C.byref(n_iter) if (info or tol > 0) else None,
+                            viol.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
+    _lib.check(st, "evc_cd_learn")
+    to_np = x_np and out_w is None and out_h is None
+    res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
+    if info:
+        res += ({"n_iter": int(n_iter.value), "violation": viol,
+                 "splits": int(splits) if splits else int(L.evc_cd_learn_splits(M, R, T))},)
+    return res
+
+
 def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepared=False, dtype=None, device=None,
-                       loss="frobenius"):
+                       loss="frobenius", solver="mu"):
     """A compact parallel dictionary: the aligned source and target exemplars are stacked, D = [A; B] ((Ma + Mb) x N),
     and factored jointly, D ~ [Wa; Wb] G, with R << N components by learn_dictionary (scikit-learn surface, the error
     every 10 iterations); (Wa, Wb) then stand in for (A, B) in solve_activations / convert at R / N of the cost.
@@ -543,9 +626,15 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     The start is deterministic: W0 = R evenly spaced exemplars (columns of D) floored at 1e-6, G0 = sqrt(mean(D) / R)
     everywhere, whatever the loss.  Returns (Wa, Wb, G, info) in the caller's orientation; info as learn_dictionary's.
     prepared=True: (PreparedDictionary of (Wa, Wb), G, info) instead, ready for convert().  loss: as learn_dictionary's
-    (the prepared dictionary itself is the plain one: pass the loss to convert / prepare_dictionary to solve under it)."""
+    (the prepared dictionary itself is the plain one: pass the loss to convert / prepare_dictionary to solve under it).
+    solver="cd": the same stacked compaction by learn_dictionary_cd (scikit-learn's default solver; Frobenius only, at most
+    1024 stacked bins and components; `iters` is its max_iter and `tol` its violation ratio; info as learn_dictionary_cd's)."""
     if loss not in _LOSSES:
         raise ValueError(f"loss must be one of {sorted(_LOSSES)}, got {loss!r}")
+    if solver not in ("mu", "cd"):
+        raise ValueError(f"solver must be 'mu' or 'cd', got {solver!r}")
+    if solver == "cd" and _LOSSES[loss] != _lib.LOSS_FROBENIUS:
+        raise ValueError("solver='cd' minimises the Frobenius loss only")
     torch = _torch()
     device = require_device(device)
     lay = _LAYOUTS[layout]
@@ -562,8 +651,12 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     pick = torch.div(torch.arange(R, device=device) * N, R, rounding_mode="floor")
     W0 = (D[:, pick] if bm else D[pick, :]).clamp_min(1e-6).contiguous()
     G0 = torch.full((R, N) if bm else (N, R), float(torch.sqrt(D.mean() / R)), dtype=tdtype, device=device)
-    W, G, info = learn_dictionary(D, None, None, layout=layout, iters=iters, tol=tol, check_every=10, surface="sklearn",
-                                  dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0, loss=loss)
+    if solver == "cd":
+        W, G, info = learn_dictionary_cd(D, None, None, layout=layout, max_iter=iters, tol=tol, dtype=tdtype, device=device,
+                                         info=True, out_w=W0, out_h=G0)
+    else:
+        W, G, info = learn_dictionary(D, None, None, layout=layout, iters=iters, tol=tol, check_every=10, surface="sklearn",
+                                      dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0, loss=loss)
     Wa, Wb = (W[:Ma], W[Ma:]) if bm else (W[:, :Ma], W[:, Ma:])
     if prepared:
         return prepare_dictionary(Wa, Wb, layout=layout, dtype=tdtype, device=device), (_to_host(G) if a_np else G), info

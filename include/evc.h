@@ -27,6 +27,10 @@
  *                   evc_learn_opts.loss = EVC_LOSS_KL: _nmf.py:556-606, 634-728) and pymf's default
  *                   factorize(compute_w=True) (pymf/nmf.py:66-76, pymf/base.py:238-270); evc_learn_workspace_bytes and
  *                   evc_learn_splits size and describe it
+ *   evc_cd_learn    replaces the coordinate-descent loop that also learns the dictionary: sklearn's default solver,
+ *                   NMF(n_components=...).fit_transform(...) of 05_conversion.py:100-106 (solver='cd', update_H=True:
+ *                   _fit_coordinate_descent, _nmf.py:496-521, both calls of _update_coordinate_descent, :376-404);
+ *                   evc_cd_learn_workspace_bytes and evc_cd_learn_splits size and describe it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -61,6 +65,10 @@
  *         host reads one double (the error) at each check that is evaluated and decides the stop there; checks are
  *         evaluated when err_out is non-NULL or tol > 0.  Its own kernels never exchange data between workgroups inside a
  *         launch, and its activation step runs with EVC_FLAG_NO_EXCHANGE: concurrent calls on several streams are safe.
+ *     (6) evc_cd_learn: only with tol == 0 and NULL n_iter_out / violation_out is the call a pure enqueue of max_iter
+ *         iterations.  Otherwise the host reads the iteration's two violations (two doubles) after every iteration and
+ *         decides the stop there.  None of its kernels exchanges data between workgroups inside a launch, uses atomics or
+ *         assumes residency: concurrent calls on several streams are safe.
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
  *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets) are consumed before the call returns: they are
@@ -473,6 +481,53 @@ int evc_learn_splits(int M, int R, int T);
 int evc_nmf_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
                   const evc_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
                   evc_stream_t stream);
+
+/* Coordinate descent on BOTH factors, X ~ W H: scikit-learn's solver='cd' (its default) with update_H=True, shuffle=False
+ * (_fit_coordinate_descent, _nmf.py:496-521).  X is M x T, W is M x R, H is R x T, all addressed as in evc_nmf_learn
+ * (sklearn's W is H^T here, its H is W^T); W and H hold the start on entry and are updated in place.  Per iteration:
+ *   activations  one sweep of evc_cd_solve's kernel from the current H on the current W (EVC_INIT_GIVEN; penalties l1_h,
+ *                l2_h).  With max_iter = 1 the activations are bitwise those of evc_cd_solve(max_iter = 1, EVC_INIT_GIVEN,
+ *                tol = 0) on the same inputs;
+ *   dictionary   G = H H^T with l2_w added on the diagonal, P = X H^T - l1_w; for every bin row w of W the components
+ *                t = 0 .. R-1 in order:  grad = G[t,:] . w - P[m][t];  w_t <- max(w_t - grad / G[t][t], 0)  (IEEE division;
+ *                skipped where G[t][t] == 0);  its violation is the sum of |pg|, pg = min(grad, 0) where w_t == 0, else grad.
+ *                G and P are sums over the frames, taken in evc_cd_learn_splits(M, R, T) contiguous frame ranges whose
+ *                partial sums are added in ascending order;
+ *   stop         violation = the sum of the two halves'; stop when violation_init (that of iteration 1) == 0, when
+ *                violation / violation_init <= tol, or at max_iter.  The stopping iteration's updates are kept.
+ * float32 inputs are solved in float32; every violation is summed in float64, in a fixed order.  The same call gives
+ * bitwise the same W and H every time.
+ *   M : 1 .. 1024, R : 1 .. 1024 (larger: -3);  T >= 1;  max_iter = 0 returns the start
+ *   n_iter_out    : host int or NULL: iterations carried out
+ *   violation_out : host, max_iter x 2 doubles or NULL: [i][0] the activation half's violation of iteration i + 1 (0 with
+ *                   EVC_CDL_DICT_ONLY), [i][1] the dictionary half's; NaN after the stop
+ * Host synchronisation: case (6) of the list at the top. */
+enum { EVC_CDL_BOTH = 0, EVC_CDL_DICT_ONLY = 1 };
+typedef struct evc_cd_learn_opts {
+    int struct_bytes;  /* sizeof(evc_cd_learn_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int max_iter;      /* >= 0 */
+    int update;        /* EVC_CDL_BOTH; EVC_CDL_DICT_ONLY: the activations stay fixed, only the dictionary half runs (and
+                          only its violation counts) */
+    int reserved;      /* 0; bits 8..15, tests and tuning: that many frame ranges (1 .. 64) instead of
+                          evc_cd_learn_splits(), as in evc_learn_opts; more ranges than that need more workspace (below);
+                          anything else: status -1 */
+    double tol;        /* >= 0 */
+    double l1_h, l2_h; /* >= 0; activations: sklearn's l1_reg_W, l2_reg_W (already scaled by the number of bins) */
+    double l1_w, l2_w; /* >= 0; dictionary:  sklearn's l1_reg_H, l2_reg_H (already scaled by the number of frames) */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_cd_learn_opts;
+/* bytes of workspace evc_cd_learn needs at evc_cd_learn_splits(M, R, T) frame ranges (0: invalid arguments).  Every forced
+ * range beyond that count needs 2 * 16 * (round_up(ceil(M / 16), 4) + round_up(ceil(R / 16), 4)) * round_up(R, 128) more
+ * elements (-2 otherwise). */
+size_t evc_cd_learn_workspace_bytes(int M, int R, int T, int dtype);
+/* frame ranges the sums over the frames (G and P) are split into (0: invalid arguments) */
+int evc_cd_learn_splits(int M, int R, int T);
+int evc_cd_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
+                 const evc_cd_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
+                 double* violation_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
