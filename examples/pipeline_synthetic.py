@@ -7,10 +7,11 @@
   04_align_n_nmf.py          gather aligned exemplars, H = _factorize(X, A),  compat.make_dict / compat.factorize
                              Y = H.T @ B, Griffin-Lim                         compat.griffin_lim
 
-The DTW features of the reference are librosa MFCCs (absent here); a 25-band log-magnitude stands in.
+The DTW features of the reference are librosa MFCCs: --mfcc computes them on the GPU (compat.features.extract_features,
+librosa's algorithm restated); by default a 25-band log-magnitude of the STFT stands in, as before MFCCs existed here.
 With --compact R the parallel dictionary is also compacted on the GPU, [A; B] ~ [Wa; Wb] G with R components
 (compact_dictionary), and the utterance converted with the compact pair (Wa, Wb) in place of every aligned frame.
-usage: python examples/pipeline_synthetic.py [n_pairs] [seconds per utterance] [--compact R]
+usage: python examples/pipeline_synthetic.py [n_pairs] [seconds per utterance] [--compact R] [--mfcc]
 """
 import os
 import sys
@@ -53,20 +54,35 @@ def spectral_distance(a, b):
     return float(np.mean(np.abs(np.log(np.abs(a[:n]) + 1e-4) - np.log(np.abs(b[:n]) + 1e-4))))
 
 
-def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True, compact=0):
-    src_f = [(700, 130), (1200, 160), (2600, 250)]
-    tar_f = [(850, 130), (1500, 180), (2900, 250)]
+SRC_F = [(700, 130), (1200, 160), (2600, 250)]
+TAR_F = [(850, 130), (1500, 180), (2900, 250)]
+
+
+def training_pairs(n_pairs, seconds):
+    """The parallel training utterances: (source signals, target signals), the target speaker a little slower."""
+    return ([voice(seconds, 120 + 6 * i, SRC_F, 1.0, 10 + i) for i in range(n_pairs)],
+            [voice(seconds, 210 + 9 * i, TAR_F, 1.1 + 0.02 * i, 50 + i) for i in range(n_pairs)])
+
+
+def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True, compact=0, dtw_features="band"):
+    if dtw_features not in ("band", "mfcc"):
+        raise ValueError("dtw_features must be 'band' or 'mfcc'")
+    src_f, tar_f = SRC_F, TAR_F
     say = print if verbose else (lambda *a, **k: None)
     t0 = time.perf_counter()
-    src_wavs = [voice(seconds, 120 + 6 * i, src_f, 1.0, 10 + i) for i in range(n_pairs)]
-    tar_wavs = [voice(seconds, 210 + 9 * i, tar_f, 1.1 + 0.02 * i, 50 + i) for i in range(n_pairs)]
+    src_wavs, tar_wavs = training_pairs(n_pairs, seconds)
 
     # 03_a_b_r_parallel.py: features of the training set
     src_feat = [features.conversion_features(w, FS) for w in src_wavs]
     tar_feat = [features.conversion_features(w, FS) for w in tar_wavs]
     # 01_make_dict_parallel.py: DTW paths (features transposed to (order, frames) as the reference holds them)
-    paths, _, _ = make_dict.dtw_alignment([band_log_mag(f["stft"]).T for f in src_feat],
-                                          [band_log_mag(f["stft"]).T for f in tar_feat])
+    if dtw_features == "mfcc":      # the script's own features: extract_features(..., feat='mfcc'), (20, frames) each
+        dtw_src, _ = features.extract_features(src_wavs, "SF1", sr=FS, feat="mfcc")
+        dtw_tar, _ = features.extract_features(tar_wavs, "TF1", sr=FS, feat="mfcc")
+    else:
+        dtw_src = [band_log_mag(f["stft"]).T for f in src_feat]
+        dtw_tar = [band_log_mag(f["stft"]).T for f in tar_feat]
+    paths, _, _ = make_dict.dtw_alignment(dtw_src, dtw_tar)
     W_A, W_B = make_dict.make_exemplar_dict_W(paths)
     t_dict = time.perf_counter() - t0
 
@@ -93,8 +109,7 @@ def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True, compact=0):
         # there, images prepared once): what a caller converting many utterances would hold
         from exemplars_vc_amd import convert as evc_convert
         t3 = time.perf_counter()
-        pd, rows = make_dict.aligned_dictionary([band_log_mag(f["stft"]).T for f in src_feat],
-                                                [band_log_mag(f["stft"]).T for f in tar_feat], src_feat, tar_feat)
+        pd, rows = make_dict.aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat)
         t_pd = time.perf_counter() - t3
         assert int(rows[-1]) == N
         H_d, Y_d = evc_convert(pd, np.abs(np.asarray(tobe["real"])).astype(H["H_stft"].dtype), layout="frame_major",
@@ -106,8 +121,7 @@ def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True, compact=0):
         if compact:
             # a compact parallel dictionary: R components learnt jointly from the stacked aligned frames
             from exemplars_vc_amd import compact_dictionary, dtw_dictionary
-            A_d, B_d, _ = dtw_dictionary([band_log_mag(f["stft"]) for f in src_feat],
-                                         [band_log_mag(f["stft"]) for f in tar_feat],
+            A_d, B_d, _ = dtw_dictionary([f.T for f in dtw_src], [f.T for f in dtw_tar],
                                          [np.asarray(f["stft"]) for f in src_feat],
                                          [np.asarray(f["stft"]) for f in tar_feat], op="abs", real_part=True)
             t4 = time.perf_counter()
@@ -135,7 +149,8 @@ def main(n_pairs=6, seconds=1.0, gl_iters=60, verbose=True, compact=0):
     say(f"conversion: {converted.shape[0]} frames x {converted.shape[1]} bins, H {H['H_stft'].shape} "
         f"{H['H_stft'].dtype} ({t_conv * 1e3:.1f} ms); Griffin-Lim {gl_iters} iterations ({t_gl * 1e3:.1f} ms)")
     say(f"log-spectral distance to the target speaker: source {d_before:.3f} -> converted {d_after:.3f}")
-    res = {"N": N, "converted": converted, "wav": wav, "H": H["H_stft"], "d_before": d_before, "d_after": d_after}
+    res = {"N": N, "converted": converted, "wav": wav, "H": H["H_stft"], "d_before": d_before, "d_after": d_after,
+           "paths": paths}
     if compacted is not None:
         res.update(compacted=compacted, d_compact=spectral_distance(compacted, want))
         say(f"  ... with the compact dictionary ({compact} components): {res['d_compact']:.3f}")
@@ -149,4 +164,8 @@ if __name__ == "__main__":
         i = a.index("--compact")
         r = int(a[i + 1])
         del a[i:i + 2]
-    main(int(a[0]) if a else 6, float(a[1]) if len(a) > 1 else 1.0, compact=r)
+    feats = "band"
+    if "--mfcc" in a:
+        a.remove("--mfcc")
+        feats = "mfcc"
+    main(int(a[0]) if a else 6, float(a[1]) if len(a) > 1 else 1.0, compact=r, dtw_features=feats)

@@ -31,7 +31,9 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_stft_frames", "evc_stft_workspace_bytes", "evc_stft", "evc_dict_bytes", "evc_dict_prepare",
            "evc_dtw_path_rows", "evc_dtw_gather_rows", "evc_cd_workspace_bytes", "evc_cd_solve",
            "evc_learn_workspace_bytes", "evc_learn_splits", "evc_nmf_learn",
-           "evc_cd_learn_workspace_bytes", "evc_cd_learn_splits", "evc_cd_learn")
+           "evc_cd_learn_workspace_bytes", "evc_cd_learn_splits", "evc_cd_learn",
+           "evc_mfcc_workspace_bytes", "evc_mfcc")
+MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
 
 class SolveOpts(C.Structure):
@@ -73,6 +75,15 @@ class CdLearnOpts(C.Structure):
         ("update", C.c_int), ("reserved", C.c_int),
         ("tol", C.c_double), ("l1_h", C.c_double), ("l2_h", C.c_double), ("l1_w", C.c_double), ("l2_w", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class MfccOpts(C.Structure):
+    """Mirror of `evc_mfcc_opts` (include/evc.h): options of the MFCC alignment features."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("sr", C.c_int), ("fft_size", C.c_int), ("hop", C.c_int),
+        ("n_mels", C.c_int), ("n_mfcc", C.c_int), ("center", C.c_int), ("reserved", C.c_int),
+        ("fmin", C.c_double), ("fmax", C.c_double), ("amin", C.c_double), ("top_db", C.c_double),
     ]
 
 
@@ -234,6 +245,12 @@ def lib():
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, violation_out
         C.c_void_p,                                                         # stream
     ]
+    L.evc_mfcc_workspace_bytes.restype = C.c_size_t
+    L.evc_mfcc_workspace_bytes.argtypes = [C.POINTER(C.c_long), C.c_int, C.POINTER(MfccOpts)]
+    L.evc_mfcc.restype = C.c_int
+    L.evc_mfcc.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.c_int, C.POINTER(MfccOpts), C.c_void_p, C.c_int,
+                           C.c_void_p, C.c_int, C.c_void_p, C.c_int,          # re, im
+                           C.c_void_p, C.c_size_t, C.c_void_p]
     _lib = L
     return L
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..solver import dtw_align, dtw_dictionary, prepare_dictionary
+from ..solver import _dtw_gather_device, _mfcc_device, _torch, dtw_align, dtw_dictionary, prepare_dictionary, require_device
 
 
 def _dtw_alignment(feat_A, feat_B, *, device=None):
@@ -69,3 +69,37 @@ def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, k
                                     [col(np.asarray(f[key])) for f in src_feat], [col(np.asarray(f[key])) for f in tar_feat],
                                     device=device)
     return prepare_dictionary(A, B, layout="frame_major", device=device), rows
+
+
+def aligned_frames_from_wavs(src_wavs, tar_wavs, *, sr=16000, dtype="f32", device=None):
+    """The aligned frames `dictionary_from_wavs` prepares: device tensors A, B (N x 201, |re| of the aligned source /
+    target STFT frames) and row_start (device, n_pairs + 1 ints)."""
+    torch = _torch()
+    device = require_device(device)
+    if len(src_wavs) == 0 or len(src_wavs) != len(tar_wavs):
+        raise ValueError("need the same, non-zero number of utterances on both sides")
+    if dtype not in ("f32", "f64"):
+        raise ValueError("dtype must be 'f32' or 'f64'")
+    from .features import FRAME_LENGTH, HOP_LENGTH
+    args = (sr, FRAME_LENGTH, HOP_LENGTH, 20, 128, 0.0, None, 80.0, True, True, device)
+    fa, ra, _, aoff, _ = _mfcc_device(list(src_wavs), *args)
+    fb, rb, _, boff, _ = _mfcc_device(list(tar_wavs), *args)
+    if dtype == "f32":
+        ra, rb = ra.to(torch.float32), rb.to(torch.float32)
+    cols = ra.shape[1]
+    return _dtw_gather_device(fa, fb, aoff.astype(np.int32), boff.astype(np.int32), ra, 1, cols, rb, 1, cols, 1, device)
+
+
+def dictionary_from_wavs(src_wavs, tar_wavs, *, sr=16000, dtype="f32", device=None):
+    """Decoded samples of two speakers -> prepared parallel dictionary, on the device end to end: what
+    01_make_dict_parallel.py (MFCCs, DTW), 03_a_b_r_parallel.py (STFT) and the stacking of 04_align_n_nmf.py:230-246,
+    320-324 do between them.  One evc_mfcc call per speaker yields the alignment features AND the real parts of the STFT
+    frames (n_fft = 400, hop = 80), the DTW paths are consumed on the device, the aligned |re| rows are gathered there and
+    the images prepared; no frame visits the host (only the number of rows comes back: it sizes the dictionary).
+
+      src_wavs[p], tar_wavs[p] : 1-D samples of pair p (numpy or device tensors)
+      dtype                    : "f32" casts re on the device before the gather - the script's STFT is complex64, so its
+                                 dictionary is float32; "f64" keeps the float64 of the transform
+    Returns (PreparedDictionary, row_start): row_start[p] = first dictionary row of pair p (numpy, n_pairs + 1)."""
+    A, B, rows = aligned_frames_from_wavs(src_wavs, tar_wavs, sr=sr, dtype=dtype, device=device)
+    return prepare_dictionary(A, B, layout="frame_major", device=device), rows.cpu().numpy()

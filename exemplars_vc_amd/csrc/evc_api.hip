@@ -1473,6 +1473,44 @@ int evc_stft(const void* x, long n_samples, int fft_size, int hop, int center, v
                          reinterpret_cast<hipStream_t>(stream));
 }
 
+// 0, or the status the options / offsets of an evc_mfcc call earn before anything else is looked at
+static int mfcc_check(const long* soff, int n_utt, const evc_mfcc_opts* o) {
+    if (!o || o->struct_bytes != (int)sizeof(evc_mfcc_opts) || n_utt < 0) return ST_BADARG;
+    if (o->sr < 1 || o->fft_size < 2 || (o->fft_size & 1) || o->hop < 1 || o->n_mels < 1) return ST_BADARG;
+    if (o->n_mfcc < 1 || o->n_mfcc > o->n_mels) return ST_BADARG;
+    const double fmax_ = o->fmax == 0.0 ? 0.5 * o->sr : o->fmax;
+    if (!(o->fmin >= 0.0 && o->fmin < fmax_ && fmax_ <= 0.5 * o->sr) || !(o->amin > 0.0) || o->top_db != o->top_db)
+        return ST_BADARG;
+    if (n_utt > 0) {
+        if (!soff || soff[0] < 0) return ST_BADARG;
+        for (int u = 0; u < n_utt; ++u)
+            if (soff[u + 1] < soff[u]) return ST_BADARG;
+    }
+    if (o->n_mels > EVC_MFCC_MAX_MELS || o->fft_size > EVC_MFCC_MAX_FFT) return ST_UNSUPPORTED;
+    return ST_OK;
+}
+
+size_t evc_mfcc_workspace_bytes(const long* sample_offsets, int n_utt, const evc_mfcc_opts* opts) {
+    if (mfcc_check(sample_offsets, n_utt, opts) != ST_OK || n_utt < 1) return 0;
+    return mfcc_workspace_bytes(sample_offsets, n_utt, *opts);
+}
+
+int evc_mfcc(const void* x, const long* sample_offsets, int n_utt, const evc_mfcc_opts* opts, void* mfcc, int ldc,
+             void* re, int ldre, void* im, int ldim, void* workspace, size_t workspace_bytes, evc_stream_t stream) {
+    const int st = mfcc_check(sample_offsets, n_utt, opts);
+    if (st != ST_OK) return st;
+    const int nb = opts->fft_size / 2 + 1;
+    if (ldc < opts->n_mfcc || (re && ldre < nb) || (im && ldim < nb)) return ST_BADARG;
+    if (n_utt == 0 || !mfcc_has_frames(sample_offsets, n_utt, *opts)) return ST_OK;
+    if (!x || !mfcc || !workspace) return ST_BADARG;
+    const size_t need = mfcc_workspace_bytes(sample_offsets, n_utt, *opts);
+    if (need == 0) return ST_BADARG;                            // more rows than the int indices hold
+    if (workspace_bytes < need) return ST_WORKSPACE;
+    return (int)mfcc_run(static_cast<const double*>(x), sample_offsets, n_utt, *opts, static_cast<double*>(mfcc), ldc,
+                         static_cast<double*>(re), ldre, static_cast<double*>(im), ldim, workspace,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
 static bool dtw_offsets_ok(const int* off, int n_pairs) {
     if (!off || off[0] != 0) return false;
     for (int p = 0; p < n_pairs; ++p)

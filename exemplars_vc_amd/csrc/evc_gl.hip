@@ -323,6 +323,14 @@ static GlDims stft_dims(long L, int F, int hop, bool center) {
     return d;
 }
 
+// W_f with the periodic window alone (J1 x K1, J1 = round_up(F + 2, 64), K1 = round_up(F, 16)): evc_mfcc.hip's contraction
+hipError_t stft_forward_table(int F, int hop, double* Wf, hipStream_t s) {
+    const GlDims d = gl_dims(1, F, hop);
+    const long nt = (long)d.J1 * d.K1;
+    hipLaunchKernelGGL(k_gl_tables, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, d, Wf, (double*)nullptr, true);
+    return hipGetLastError();
+}
+
 size_t stft_workspace_bytes(long L, int F, int hop, bool center) {
     const GlDims d = stft_dims(L, F, hop, center);
     return ((size_t)d.J1 * d.K1 + 9 * (size_t)d.Tp * d.J1 + (size_t)d.Lp + 128) * sizeof(double) + 4 * 256;

@@ -333,6 +333,20 @@ hipError_t stft_run(const double* x, long L, int F, int hop, bool center, double
 hipError_t gl_run(const double* mag, long ldm, const int* frame_offsets, int n_utt, int F, int hop, int iters, double* x,
                   void* ws, double* rmse_host, hipStream_t s);
 
+hipError_t stft_forward_table(int F, int hop, double* Wf, hipStream_t s);
+
+// ----- evc_mfcc.hip: MFCC alignment features (evc_mfcc) -----
+constexpr int MFCC_RB = 32;           // virtual rows per workgroup of k_mfcc_mel / k_mfcc_dct; utterances start at multiples
+constexpr int MFCC_QC = 32;           // rows of the DCT basis in LDS at a time
+constexpr int MFCC_CHUNK = 8192;      // rows of S per contraction (a multiple of 128)
+constexpr int MFCC_MAX_MELS = EVC_MFCC_MAX_MELS;   // (MFCC_QC + MFCC_RB) x (n_mels + 1) doubles of LDS: 128.5 KiB of 160
+constexpr int MFCC_MAX_FFT = EVC_MFCC_MAX_FFT;     // 4 x (fft_size / 2 + 1) doubles of LDS: 128 KiB
+// arguments already validated by evc_mfcc
+size_t mfcc_workspace_bytes(const long* sample_offsets, int n_utt, const evc_mfcc_opts& o);
+bool mfcc_has_frames(const long* sample_offsets, int n_utt, const evc_mfcc_opts& o);
+hipError_t mfcc_run(const double* x, const long* sample_offsets, int n_utt, const evc_mfcc_opts& o, double* out, long ldc,
+                    double* re, long ldre, double* im, long ldim, void* ws, hipStream_t s);
+
 // ----- evc_dtw.hip -----
 size_t dtw_workspace_bytes(const int* aoff, const int* boff, int n_pairs);
 int dtw_max_frames();

@@ -831,6 +831,83 @@ def stft(y, n_fft=400, hop_length=80, *, center=True, device=None):
     return (re.cpu().numpy(), im.cpu().numpy()) if was_np else (re, im)
 
 
+def _mfcc_device(signals, sr, n_fft, hop_length, n_mfcc, n_mels, fmin, fmax, top_db, center, want_stft, device):
+    """One evc_mfcc call on a list of 1-D signals (numpy arrays or device tensors).  Returns device tensors
+    (mfcc (T, n_mfcc), re, im (T, nb) or None) for all utterances back to back, the frame offsets (numpy, n + 1) and
+    whether every input was numpy."""
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    sr, n_fft, hop_length, n_mfcc, n_mels = int(sr), int(n_fft), int(hop_length), int(n_mfcc), int(n_mels)
+    if n_fft < 2 or n_fft % 2 or hop_length < 1:
+        raise ValueError("n_fft must be even and >= 2, hop_length >= 1")
+    all_np = True
+    xs = []
+    for y in signals:
+        if isinstance(y, torch.Tensor):
+            all_np = False
+            t = y.to(device=device, dtype=torch.float64)
+        else:
+            a = np.asarray(y, dtype=np.float64)
+            if not np.isfinite(a).all():
+                raise ValueError("Audio buffer is not finite everywhere")       # librosa.util.valid_audio
+            t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        if t.dim() != 1:
+            raise ValueError("every signal must be one-dimensional")
+        xs.append(t)
+    n = len(xs)
+    soff = np.concatenate([[0], np.cumsum([int(t.numel()) for t in xs])]).astype(np.int64)
+    foff = np.concatenate([[0], np.cumsum([int(L.evc_stft_frames(int(t.numel()), n_fft, hop_length, int(center)))
+                                           if t.numel() else 0 for t in xs])]).astype(np.int64)
+    T, nb = int(foff[-1]), n_fft // 2 + 1
+    o = _lib.MfccOpts()
+    o.struct_bytes = C.sizeof(_lib.MfccOpts)
+    o.sr, o.fft_size, o.hop, o.n_mels, o.n_mfcc, o.center = sr, n_fft, hop_length, n_mels, n_mfcc, int(bool(center))
+    o.fmin, o.fmax, o.amin = float(fmin), 0.0 if fmax is None else float(fmax), 1e-10
+    o.top_db = -1.0 if top_db is None else float(top_db)
+    with torch.cuda.device(device):
+        mf = torch.empty(T, n_mfcc, dtype=torch.float64, device=device)
+        re = torch.empty(T, nb, dtype=torch.float64, device=device) if want_stft else None
+        im = torch.empty(T, nb, dtype=torch.float64, device=device) if want_stft else None
+        if n:
+            x = torch.cat(xs) if n > 1 else xs[0].contiguous()
+            sp = soff.ctypes.data_as(C.POINTER(C.c_long))
+            ws_bytes = int(L.evc_mfcc_workspace_bytes(sp, n, C.byref(o)))
+            with _workspace(ws_bytes, device) as ws:
+                stream = torch.cuda.current_stream(device).cuda_stream
+                st = L.evc_mfcc(x.data_ptr(), sp, n, C.byref(o), mf.data_ptr(), n_mfcc,
+                                re.data_ptr() if want_stft else None, nb, im.data_ptr() if want_stft else None, nb,
+                                ws.data_ptr(), ws.numel(), C.c_void_p(stream))
+            _lib.check(st, "evc_mfcc")
+    return mf, re, im, foff, all_np
+
+
+def mfcc_batch(signals, sr=16000, n_fft=400, hop_length=80, n_mfcc=20, n_mels=128, fmin=0.0, fmax=None, top_db=80.0,
+               center=True, want_stft=False, device=None):
+    """MFCCs of a batch of utterances in one native call (float64): librosa.feature.mfcc(y, sr=sr, n_fft=n_fft,
+    hop_length=hop_length) with librosa's defaults for the rest, as 01_make_dict_parallel.py:96-104 calls it (librosa's
+    published algorithm restated; parity with the package is unpinned).  signals: 1-D arrays.  Returns a list of
+    (T_u, n_mfcc) arrays, frames as rows - what `dtw_align` takes; with want_stft=True (mfccs, re, im), re / im being
+    lists of the (T_u, n_fft/2+1) STFT parts of `stft`.  numpy in -> numpy out (non-finite samples raise ValueError, as
+    librosa does); device tensors in -> device tensors out, with no host copy.  top_db=None: no clamp."""
+    mf, re, im, foff, all_np = _mfcc_device(signals, sr, n_fft, hop_length, n_mfcc, n_mels, fmin, fmax, top_db, center,
+                                            want_stft, device)
+
+    def parts(t):
+        if all_np:
+            t = _to_host(t)
+        return [t[int(a):int(b)] for a, b in zip(foff[:-1], foff[1:])]
+
+    return (parts(mf), parts(re), parts(im)) if want_stft else parts(mf)
+
+
+def mfcc(y, sr=16000, n_fft=400, hop_length=80, n_mfcc=20, n_mels=128, fmin=0.0, fmax=None, top_db=80.0, center=True,
+         want_stft=False, device=None):
+    """`mfcc_batch` for one utterance: (T, n_mfcc) [, re, im]."""
+    out = mfcc_batch([y], sr, n_fft, hop_length, n_mfcc, n_mels, fmin, fmax, top_db, center, want_stft, device)
+    return (out[0][0], out[1][0], out[2][0]) if want_stft else out[0]
+
+
 def dtw_dictionary(dtw_a, dtw_b, src_feats, tar_feats, *, op="copy", real_part=False, dtype=None, device=None):
     """DTW alignment of parallel utterance pairs AND the gather of the aligned frames, on the GPU with no round trip of
     frames through the host (01_make_dict_parallel.py:215-249, 04_align_n_nmf.py:100-169,230-246,320-324): the paths stay
@@ -875,18 +952,32 @@ def dtw_dictionary(dtw_a, dtw_b, src_feats, tar_feats, *, op="copy", real_part=F
     sb, stride_b, cols_b = stack(tar_feats)
     if sa.dtype != sb.dtype:
         sa, sb = sa.astype(np.float64), sb.astype(np.float64)
-    tdt = torch.float64 if sa.dtype == np.float64 else torch.float32
-    dcode = _lib.F64 if sa.dtype == np.float64 else _lib.F32
     opc = {"copy": 0, "abs": 1}[op]
+    with torch.cuda.device(device):
+        FA = torch.from_numpy(np.concatenate(dtw_a, axis=0)).to(device)
+        FB = torch.from_numpy(np.concatenate(dtw_b, axis=0)).to(device)
+        SA, SB = torch.from_numpy(sa).to(device), torch.from_numpy(sb).to(device)
+    A, B, rows = _dtw_gather_device(FA, FB, aoff, boff, SA, stride_a, cols_a, SB, stride_b, cols_b, opc, device)
+    return A, B, rows.cpu().numpy()
+
+
+def _dtw_gather_device(FA, FB, aoff, boff, SA, stride_a, cols_a, SB, stride_b, cols_b, opc, device):
+    """The device part of `dtw_dictionary`: alignment features FA / FB (device, float64, frames as rows, unit inner
+    stride), the frames SA / SB the dictionary is made of (device, both float64 or both float32; element stride and
+    columns each) and the frame offsets of the pairs (host int32, n + 1).  DTW, scan of the path lengths, two gathers.
+    Returns device tensors (A, B, row_start); only N (one int) is read back."""
+    torch = _torch()
+    L = _lib.lib()
+    n = len(aoff) - 1
+    D = int(FA.shape[1])
+    tdt = SA.dtype
+    dcode = _lib.F64 if tdt == torch.float64 else _lib.F32
     ap, bp = aoff.ctypes.data_as(C.POINTER(C.c_int)), boff.ctypes.data_as(C.POINTER(C.c_int))
     ws_bytes = int(L.evc_dtw_workspace_bytes(ap, bp, n))
     if ws_bytes == 0:
         raise ValueError("utterance too long for the DTW kernel's wavefront buffers")
     cap = int(aoff[-1] + boff[-1])
     with torch.cuda.device(device):
-        FA = torch.from_numpy(np.concatenate(dtw_a, axis=0)).to(device)
-        FB = torch.from_numpy(np.concatenate(dtw_b, axis=0)).to(device)
-        SA, SB = torch.from_numpy(sa).to(device), torch.from_numpy(sb).to(device)
         pa = torch.empty(max(cap, 1), dtype=torch.int32, device=device)
         pb = torch.empty(max(cap, 1), dtype=torch.int32, device=device)
         plen = torch.empty(n, dtype=torch.int32, device=device)
@@ -896,7 +987,7 @@ def dtw_dictionary(dtw_a, dtw_b, src_feats, tar_feats, *, op="copy", real_part=F
         d_poff = torch.from_numpy((aoff[:-1] + boff[:-1]).astype(np.int32)).to(device)
         stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         with _workspace(ws_bytes, device) as ws:
-            st = L.evc_dtw_align(FA.data_ptr(), D, ap, FB.data_ptr(), D, bp, D, n, pa.data_ptr(), pb.data_ptr(),
+            st = L.evc_dtw_align(FA.data_ptr(), _ld(FA), ap, FB.data_ptr(), _ld(FB), bp, D, n, pa.data_ptr(), pb.data_ptr(),
                                  plen.data_ptr(), None, ws.data_ptr(), ws.numel(), stream)
         _lib.check(st, "evc_dtw_align")
         n_rows = C.c_int(0)
@@ -904,13 +995,13 @@ def dtw_dictionary(dtw_a, dtw_b, src_feats, tar_feats, *, op="copy", real_part=F
         N = int(n_rows.value)
         A = torch.empty((N, cols_a), dtype=tdt, device=device)
         B = torch.empty((N, cols_b), dtype=tdt, device=device)
-        _lib.check(L.evc_dtw_gather_rows(SA.data_ptr(), SA.shape[1], stride_a, pa.data_ptr(), plen.data_ptr(),
+        _lib.check(L.evc_dtw_gather_rows(SA.data_ptr(), _ld(SA), stride_a, pa.data_ptr(), plen.data_ptr(),
                                          d_aoff.data_ptr(), d_poff.data_ptr(), rows.data_ptr(), n, cols_a, opc,
                                          A.data_ptr(), cols_a, dcode, stream), "evc_dtw_gather_rows")
-        _lib.check(L.evc_dtw_gather_rows(SB.data_ptr(), SB.shape[1], stride_b, pb.data_ptr(), plen.data_ptr(),
+        _lib.check(L.evc_dtw_gather_rows(SB.data_ptr(), _ld(SB), stride_b, pb.data_ptr(), plen.data_ptr(),
                                          d_boff.data_ptr(), d_poff.data_ptr(), rows.data_ptr(), n, cols_b, opc,
                                          B.data_ptr(), cols_b, dcode, stream), "evc_dtw_gather_rows")
-    return A, B, rows.cpu().numpy()
+    return A, B, rows
 
 
 def dtw_align(feats_a, feats_b, *, device=None, want_cost=False):

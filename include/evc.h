@@ -15,6 +15,9 @@
  *   evc_nmf_convert both of the above back to back (factorize() + convert(), :452-455)
  *   evc_griffin_lim replaces reconstruct_signal_griffin_lim()  zz_audio_utilities.py:258-292
  *   evc_stft        replaces librosa.core.stft(...) of 04_align_n_nmf.py:422
+ *   evc_mfcc        replaces lbr.feature.mfcc(audiodatum, sr=sr, n_fft=frame_length, hop_length=hop_length) of
+ *                   _extract_features()  01_make_dict_parallel.py:96-104 - the features the DTW below aligns - for all
+ *                   utterances of a speaker in one call, with the STFT frames of 03_a_b_r_parallel.py:103 as a by-product
  *   evc_dtw_align   replaces _dtw_alignment() / dtw_alignment()  01_make_dict_parallel.py:215-249
  *   evc_dtw_path_rows, evc_dtw_gather_rows  replace align_sp_ap_f0() + the stacking  04_align_n_nmf.py:100-169,230-246
  *   evc_residual    replaces sklearn _beta_divergence(beta=2, square_root=True)
@@ -69,9 +72,11 @@
  *         iterations.  Otherwise the host reads the iteration's two violations (two doubles) after every iteration and
  *         decides the stop there.  None of its kernels exchanges data between workgroups inside a launch, uses atomics or
  *         assumes residency: concurrent calls on several streams are safe.
+ *     (7) evc_mfcc: never.  The call is a pure enqueue; no scalar comes back to the host (the per-utterance maximum of
+ *         the decibel clamp is formed on the device from per-workgroup partial maxima, without atomics).
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
- *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets) are consumed before the call returns: they are
+ *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets, sample_offsets) are consumed before the call returns: they are
  *   copied to the device by hipMemcpyAsync from pageable memory, which HIP stages at enqueue time; keep them valid
  *   until the call returns, not longer.
  *   k_fused_all's exchange carries its arrival flag in the lowest mantissa bit of every partial sum it publishes
@@ -332,6 +337,59 @@ int evc_stft_frames(long n_samples, int fft_size, int hop, int center);
 size_t evc_stft_workspace_bytes(long n_samples, int fft_size, int hop, int center);
 int evc_stft(const void* x, long n_samples, int fft_size, int hop, int center, void* re, int ldre,
              void* im, int ldim, void* workspace, size_t workspace_bytes, evc_stream_t stream);
+
+/* MFCC alignment features - what the dictionary build aligns by DTW: lbr.feature.mfcc(y, sr=16000, n_fft=400,
+ * hop_length=80) at 01_make_dict_parallel.py:96-104,358-359, with librosa's defaults for everything else (librosa is
+ * absent here; its published algorithm is restated, parity with the package is unpinned).  float64 throughout:
+ *   frames   the STFT exactly as evc_stft computes it; power P[t][k] = re^2 + im^2, k < nb = fft_size / 2 + 1
+ *   mel      n_mels triangular filters on the Slaney scale (mel(f) = f / (200/3) below 1000 Hz, 15 + ln(f / 1000) /
+ *            (ln(6.4) / 27) above) between fmin and fmax, each scaled by 2 / (its width in Hz); Mel = P w^T.  The
+ *            filterbank is sparse (394 non-zero weights at sr 16000, fft_size 400, n_mels 128) and is kept
+ *            row-compressed: first bin, bin count and weights per filter, summed in ascending bin order
+ *   dB       10 log10(max(amin, Mel)), then max(dB, max over the WHOLE UTTERANCE of dB - top_db)
+ *   DCT      orthonormal DCT-II over the mel axis, the first n_mfcc coefficients
+ * One call takes a batch of utterances:
+ *   x              : the samples of all utterances (device doubles); utterance u owns x[sample_offsets[u] ..
+ *                    sample_offsets[u + 1] - 1]
+ *   sample_offsets : host, n_utt + 1 longs, ascending, sample_offsets[0] >= 0
+ *   mfcc           : device, frames as rows with row stride ldc >= n_mfcc - the layout evc_dtw_align takes.  Utterance u
+ *                    owns the rows from sum over v < u of evc_stft_frames(L_v, fft_size, hop, center) on; an utterance
+ *                    without samples (or, with center = 0, shorter than fft_size) has no frames
+ *   re, im         : device or NULL (not wanted): the STFT of the same rows, row strides ldre, ldim >= nb
+ * The call is fully asynchronous (no host synchronisation, nothing read back) and deterministic: the same call gives
+ * bitwise the same output every time.  The number of kernel launches does not depend on n_utt: the utterances are laid
+ * out as one strided frame matrix (every utterance reflect-padded on its own) and S = frames W_f runs on the matrix
+ * cores in chunks of 8192 rows, so the workspace holds
+ *     8 * (J1 * K1 + 8192 * J1 + 8 * min(8192, 128 * floor(255 / (J1 / 64))) * J1     table, one chunk of S, its k-slabs
+ *          + hop * R + K1 + R * n_mels + R / 32 + 2 * nb + n_mfcc * n_mels + 3 * n_utt / 2 + 3 * n_mels / 2) bytes
+ * up to rounding, with K1 = round_up(fft_size, 16), J1 = round_up(2 * nb, 64) and R = sum over the utterances of
+ * round_up(frames_u + ceil(fft_size / hop), 32) rows: only the padded samples and the decibel values grow with the
+ * batch, the contraction's buffers do not (at most 128 MiB of k-slabs).
+ * Status -1: wrong struct_bytes, sr < 1, fft_size odd or < 2, hop < 1, n_mels < 1, n_mfcc outside 1 .. n_mels, not
+ * 0 <= fmin < fmax <= sr / 2, amin <= 0, n_utt < 0, descending or negative offsets, ldc < n_mfcc, ldre / ldim < nb, a NULL
+ * pointer that is needed; -3: n_mels > EVC_MFCC_MAX_MELS or fft_size > EVC_MFCC_MAX_FFT (what the LDS tiles of the two
+ * kernels hold); -2: workspace too small.  n_utt = 0 or a call without any frame: status 0, nothing is launched.
+ * Non-finite samples (librosa refuses them): the outputs of such an utterance are unspecified, the other utterances
+ * of the call are unaffected. */
+enum { EVC_MFCC_MAX_MELS = 256, EVC_MFCC_MAX_FFT = 8192 };
+typedef struct evc_mfcc_opts {
+    int struct_bytes;  /* sizeof(evc_mfcc_opts) */
+    int sr;            /* sampling rate in Hz (the script: 16000) */
+    int fft_size;      /* even, >= 2 (the script: 400) */
+    int hop;           /* >= 1 (the script: 80) */
+    int n_mels;        /* librosa: 128 */
+    int n_mfcc;        /* librosa: 20 */
+    int center;        /* 1: librosa's default (reflect padding), 0: frames start at sample 0 */
+    int reserved;      /* 0 */
+    double fmin;       /* librosa: 0 */
+    double fmax;       /* 0: sr / 2 (librosa's default) */
+    double amin;       /* librosa: 1e-10 */
+    double top_db;     /* librosa: 80; < 0: no clamp */
+} evc_mfcc_opts;
+/* bytes of workspace evc_mfcc needs (0: invalid arguments) */
+size_t evc_mfcc_workspace_bytes(const long* sample_offsets, int n_utt, const evc_mfcc_opts* opts);
+int evc_mfcc(const void* x, const long* sample_offsets, int n_utt, const evc_mfcc_opts* opts, void* mfcc, int ldc,
+             void* re, int ldre, void* im, int ldim, void* workspace, size_t workspace_bytes, evc_stream_t stream);
 
 /* Griffin-Lim phase reconstruction - the back end that follows the path when the scripts run on
  * STFT magnitudes: reconstruct_signal_griffin_lim(), zz_audio_utilities.py:258-292 (with its
