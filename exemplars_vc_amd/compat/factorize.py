@@ -15,7 +15,8 @@ import warnings
 
 import numpy as np
 
-from ..solver import convert as _solve_and_synthesize, learn_dictionary, solve_activations, synthesize
+from ..solver import (convert as _solve_and_synthesize, learn_dictionary, solve_activations, solve_activations_beta,
+                      synthesize)
 
 try:  # same warning class the reference would raise, when scikit-learn is present
     from sklearn.exceptions import ConvergenceWarning
@@ -25,6 +26,26 @@ except Exception:  # pragma: no cover
 
 MAX_ITER = 150          # 04_align_n_nmf.py:213
 CHECK_EVERY = 10        # sklearn _nmf.py:871
+
+
+_BETA_NAMES = {"frobenius": 2.0, "kullback-leibler": 1.0, "itakura-saito": 0.0}
+
+
+def _beta_of(beta_loss):
+    """scikit-learn's _beta_loss_to_float: one of its three names, or any finite int / float; anything else raises the
+    message the two named losses always raised here"""
+    if isinstance(beta_loss, str) and beta_loss in _BETA_NAMES:
+        return _BETA_NAMES[beta_loss]
+    if isinstance(beta_loss, (int, float, np.integer, np.floating)) and not isinstance(beta_loss, bool) \
+            and np.isfinite(beta_loss):
+        return float(beta_loss)
+    raise ValueError(f"Invalid beta_loss parameter: got {beta_loss!r}")
+
+
+def _check_beta_zeros(X, beta):
+    if beta <= 0 and X.size and X.min() == 0:      # sklearn _nmf.py:1680-1685, raised on this route too
+        raise ValueError("When beta_loss <= 0 and X contains zeros, the solver may diverge. Please add small values "
+                         "to X, or use a positive beta_loss.")
 
 
 def _check_dictionary(W, n_features):
@@ -80,9 +101,8 @@ def _factorize_impl(X, W, beta_loss, tol, device, algo, honor_beta_loss, hint, w
 
     # 04_align_n_nmf.py:210 overrides `beta_loss` with "frobenius" whatever the caller passed;
     # honor_beta_loss=True runs the loss that was asked for (sklearn's KL update)
-    loss = beta_loss if honor_beta_loss else "frobenius"
-    if loss not in ("frobenius", "kullback-leibler"):
-        raise ValueError(f"Invalid beta_loss parameter: got {loss!r}")
+    beta = _beta_of(beta_loss if honor_beta_loss else "frobenius")
+    loss = {2.0: "frobenius", 1.0: "kullback-leibler"}.get(beta)       # None: the beta-divergence solve (evc_beta_solve)
     X = np.asarray(X)
     if X.ndim != 2:
         raise ValueError(f"Expected 2D array, got {X.ndim}D array instead")
@@ -94,6 +114,17 @@ def _factorize_impl(X, W, beta_loss, tol, device, algo, honor_beta_loss, hint, w
     if (X < 0).any():
         _warn("X has negative entries; the multiplicative update is only meaningful for "
               "non-negative data (scikit-learn does not check X on this route)", RuntimeWarning, 2)
+    if loss is None:
+        if with_recon:
+            raise NotImplementedError("the reconstruction is only formed on the Frobenius / Kullback-Leibler routes")
+        _check_beta_zeros(X, beta)
+        act, info = solve_activations_beta(W, X, beta=beta, layout="frame_major", iters=MAX_ITER, init="sklearn",
+                                           check_every=CHECK_EVERY if tol > 0 else 0,
+                                           stop_rule="sklearn" if tol > 0 else "none", tol=tol, device=device, info=True)
+        if tol > 0 and int(info["n_iter"][0]) == MAX_ITER:
+            _warn(f"Maximum number of iterations {MAX_ITER} reached. Increase it to improve convergence.",
+                  ConvergenceWarning, 3)
+        return act.T, None
     kw = dict(layout="frame_major", iters=MAX_ITER, eps_mode="zero_replace", init="sklearn",
               check_every=CHECK_EVERY if tol > 0 else 0, stop_rule="sklearn" if tol > 0 else "none",
               tol=tol, algo=algo, device=device, info=True, loss=loss, cooperative=_exchange_allowed(hint))
@@ -114,10 +145,20 @@ def non_negative_factorization_mu(X, W, H, update_H=True, tol=1e-4, max_iter=200
     beta_loss=beta_loss, tol=tol, max_iter=max_iter)` on the GPU, in scikit-learn's orientation: X (n_samples,
     n_features), W (n_samples, n_components) the activations, H (n_components, n_features) the dictionary.  Returns
     (W, H, n_iter).  update_H=True learns the dictionary too (evc_nmf_learn); update_H=False is the fixed-dictionary
-    solve of _factorize with the given start.  beta_loss: "frobenius" or "kullback-leibler"."""
-    if beta_loss not in ("frobenius", "kullback-leibler"):
+    solve of _factorize with the given start.  beta_loss: "frobenius" or "kullback-leibler"; with update_H=False also
+    "itakura-saito" or any finite int / float (evc_beta_solve; beta <= 0 refuses zeros in X as scikit-learn does)."""
+    if update_H and beta_loss not in ("frobenius", "kullback-leibler"):
         raise ValueError(f"Invalid beta_loss parameter: got {beta_loss!r}")
+    beta = _beta_of(beta_loss)
     X = np.asarray(X)
+    if beta not in (1.0, 2.0):
+        _check_beta_zeros(X, beta)
+        act, info = solve_activations_beta(np.asarray(H, dtype=X.dtype), X, np.asarray(W, dtype=X.dtype), beta=beta,
+                                           layout="frame_major", iters=int(max_iter), init="given",
+                                           check_every=10 if tol > 0 else 0, stop_rule="sklearn" if tol > 0 else "none",
+                                           tol=float(tol), device=device, info=True)
+        return act, np.asarray(H), int(info["n_iter"][0])
+    beta_loss = "frobenius" if beta == 2.0 else "kullback-leibler"
     if update_H:
         # frame-major: X[t][m], the dictionary (the solver's W) as H[r][m], the activations (its H) as W[t][r]
         Hd, Wa, info = learn_dictionary(X, np.asarray(H, dtype=X.dtype), np.asarray(W, dtype=X.dtype),

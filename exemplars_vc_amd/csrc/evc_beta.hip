@@ -1,0 +1,591 @@
+// evc_beta.hip - evc_beta_solve: multiplicative updates of the activations under any beta-divergence with the dictionary
+// fixed: scikit-learn's non_negative_factorization(..., update_H=False, solver='mu', beta_loss=beta) for beta_loss =
+// 'itakura-saito' (0) or any float (_multiplicative_update_w, _nmf.py:526-631; _beta_divergence, :85-189).  DESIGN.md §5.10.
+//
+// Per iteration and frame, with EPS = 2^-23 (numpy's float32 epsilon, in both element types):
+//   V  = A h;  Vd = V, below EPS -> EPS if beta < 1;  Vn = V, below EPS -> EPS if beta < 2
+//   Q1 = x * Vn^(beta-2);  Q2 = Vd^(beta-1);  Num = A^T Q1;  Den = A^T Q2 + l1 + l2 h, 0 -> EPS
+//   h <- h * (Num / Den)^gamma,  gamma = 1/(2-beta) if beta < 1, 1/(beta-1) if beta > 2, else 1
+// beta = 1 and beta = 2 run the same generic statement (evc_nmf_solve special-cases them: not bit-compatible).
+//
+// k_beta_sweep<T>: one launch per iteration, a workgroup of four wavefronts owns a tile of 16 frames of ONE utterance
+// (utterances start at a tile boundary) for the whole iteration; the dictionary is streamed from its two packed images.
+//   phase 1  V = A H over all N on the matrix cores (16x16x4): the wavefronts split the exemplars (chunks of 16), every
+//            wavefront passes over the bin tiles in groups of 8 and the four partial sums are added in wavefront order
+//            into the LDS image V[bin][frame]
+//   phase 2  V -> Q1 | Q2 in place (two images of round_up(M, 16) x 16 elements: 135 KB at M = 528 in float64)
+//   phase 3  the wavefronts split the exemplar tiles of 16; a tile's Num and Den are one pass A_tile^T [Q1 | Q2] over the
+//            bins, then H is updated in place in the caller's memory
+// H is written once per iteration and read once in phase 3 and once per group of 8 bin tiles in phase 1 (twice in all up
+// to M = 128, 3 times at M = 201, 6 at M = 513); V, Q1, Q2, Num and Den never leave the compute unit.  The k index of
+// an MFMA is only a summation index: lane group g of chunk c takes the four consecutive elements 16 c + 4 g + s of its
+// operand row, so that every global operand read is contiguous per lane; phase 3's dictionary image is stored with the
+// bins of a chunk permuted (slot 4 g + s holds bin 16 c + 4 s + g) so that the LDS rows the four lane groups read in one
+// step are consecutive (conflict-free at the unpadded row length of 16).
+// A frame's arithmetic depends on no other frame: a batch gives bitwise the per-utterance results, and a NaN stays in
+// its frame's column.  Exponents that are multiples of 1/2 are evaluated with products, sqrt and one division (the power
+// first, then the reciprocal: beta = 0 forms Q1 = x * (1 / (V V)), not sklearn's x * (1 / V)^2); pow only serves the
+// general float beta.
+//
+// k_beta_err<T> forms V the same way and leaves every frame's share of the divergence (float64); k_beta_check sums an
+// utterance's shares in a fixed order, records sqrt(2 max(res, 0)) and applies sklearn's stop rule on the device
+// (stop[u] = the iteration the utterance stopped at; the sweeps of a stopped utterance return at once).
+#include "evc_internal.h"
+
+namespace evc {
+
+namespace {
+
+constexpr int BT_F = 16;            // frames per tile
+constexpr int BT_WAVES = 4;
+constexpr int BT_THREADS = 64 * BT_WAVES;
+constexpr int BT_GT = 8;            // bin tiles per pass of phase 1 (accumulators held at once)
+constexpr int BETA_MAX_M = 528;     // two LDS images of 528 x 16 float64: 135 168 of 163 840 bytes
+constexpr int BETA_MAX_SLOTS = 4097;
+constexpr double BETA_EPS = 1.1920928955078125e-7;
+enum { BETA_ERR_IS = 0, BETA_ERR_KL = 1, BETA_ERR_FROB = 2, BETA_ERR_GENERIC = 3 };
+
+// x^e: e = k2 / 2 without pow when `general` is 0
+struct PowSpec {
+    double e;
+    int k2;
+    int general;
+};
+
+PowSpec pow_spec(double e) {
+    PowSpec p;
+    p.e = e;
+    const double k = 2.0 * e;
+    p.general = !(k >= -16.0 && k <= 16.0 && k == (double)(long)k);      // the range first: the cast is only defined inside it
+    p.k2 = p.general ? 0 : (int)k;
+    return p;
+}
+
+__device__ __forceinline__ double pow_t(double x, double e) { return pow(x, e); }
+__device__ __forceinline__ float pow_t(float x, float e) { return powf(x, e); }
+
+template <typename T>
+__device__ __forceinline__ T pw(T x, const PowSpec& p) {
+    if (p.general) return pow_t(x, (T)p.e);
+    const int k = p.k2 < 0 ? -p.k2 : p.k2;
+    T r = T(1), b = x;
+    for (int n = k >> 1; n;) {
+        if (n & 1) r *= b;
+        n >>= 1;
+        if (n) b *= b;
+    }
+    if (k & 1) r *= sqrt(x);
+    return p.k2 < 0 ? T(1) / r : r;
+}
+
+template <typename T> struct BetaArgs {
+    const T* Ap1;           // [NP][MP] exemplars as rows, bins contiguous, zero-padded
+    const T* Ap3;           // [NP][MP] the same with the bins of every chunk of 16 permuted: slot 4 g + s = bin 4 s + g
+    const T* Xp;            // [n_tiles][MP][16] frames of a tile, zero-padded
+    T* H;
+    long hs_t, hs_n;        // H(n, t) = H[t * hs_t + n * hs_n]
+    const int4* tiles;      // {utterance, first frame, frames, -}
+    const int* stop;        // [n_utt] 0: running; else the iteration the utterance stopped at
+    double* errf;           // [n_tiles * 16] per-frame share of the divergence
+    int M, MP, N, NP;
+    int clamp_n, clamp_d;   // beta < 2, beta < 1
+    int gamma_one, err_mode;
+    PowSpec p1, p2, pg, pb; // beta - 2, beta - 1, gamma, beta
+    T l1, l2;
+    double beta;
+};
+
+template <typename T> struct Vec4;
+template <> struct Vec4<double> { typedef f64x4 type; };
+template <> struct Vec4<float> { typedef f32x4 type; };
+
+// Vs[bin][frame] = (A H)[bin][frame] for the tile's 16 frame slots (0 in the padding); ends with a barrier
+template <typename T>
+__device__ __forceinline__ void beta_form_v(const BetaArgs<T>& a, const int4 tl, T* __restrict__ Vs) {
+    typedef typename Mma<T>::acc_t acc_t;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f = lane & 15, g = lane >> 4;
+    const bool fvalid = f < tl.z;
+    const T* Hf = a.H + (long)(tl.y + (fvalid ? f : 0)) * a.hs_t;
+    const int NC = a.NP / 16, MT = a.MP / 16;
+#pragma unroll 1
+    for (int t0 = 0; t0 < MT; t0 += BT_GT) {
+        acc_t acc[BT_GT];
+#pragma unroll
+        for (int j = 0; j < BT_GT; ++j) acc[j] = acc_t{0, 0, 0, 0};
+#pragma unroll 1
+        for (int c = wave; c < NC; c += BT_WAVES) {
+            const int n0 = c * 16 + g * 4;
+            T h[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {          // clamped address, then select
+                const int n = n0 + s;
+                const T v = Hf[(long)(n < a.N ? n : a.N - 1) * a.hs_n];
+                h[s] = (fvalid && n < a.N) ? v : T(0);
+            }
+            const T* Ab = a.Ap1 + (long)n0 * a.MP + t0 * 16 + f;
+#pragma unroll
+            for (int j = 0; j < BT_GT; ++j)
+                if (t0 + j < MT) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) acc[j] = Mma<T>::mma(Ab[(long)s * a.MP + j * 16], h[s], acc[j]);
+                }
+        }
+        // the four partial sums, added in wavefront order
+#pragma unroll 1
+        for (int w = 0; w < BT_WAVES; ++w) {
+            if (wave == w) {
+#pragma unroll
+                for (int j = 0; j < BT_GT; ++j)
+                    if (t0 + j < MT) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int idx = ((t0 + j) * 16 + Mma<T>::row(lane, r)) * BT_F + f;
+                            Vs[idx] = w ? Vs[idx] + acc[j][r] : acc[j][r];
+                        }
+                    }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(BT_THREADS) void k_beta_sweep(BetaArgs<T> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char beta_lds[];
+    typedef typename Mma<T>::acc_t acc_t;
+    typedef typename Vec4<T>::type vec_t;
+    const int tile = blockIdx.x;
+    const int4 tl = a.tiles[tile];
+    if (a.stop[tl.x] != 0) return;
+    T* Q1 = reinterpret_cast<T*>(beta_lds);
+    T* Q2 = Q1 + a.MP * BT_F;
+    beta_form_v<T>(a, tl, Q1);
+    // phase 2: V -> Q1 | Q2
+    {
+        const T* Xt = a.Xp + (long)tile * a.MP * BT_F;
+        const T eps = (T)BETA_EPS;
+        for (int e = threadIdx.x; e < a.MP * BT_F; e += BT_THREADS) {
+            T q1 = T(0), q2 = T(0);
+            if ((e >> 4) < a.M) {
+                const T v = Q1[e];
+                const T vn = (a.clamp_n && v < eps) ? eps : v;
+                const T vd = (a.clamp_d && v < eps) ? eps : v;
+                q1 = pw(vn, a.p1) * Xt[e];
+                q2 = pw(vd, a.p2);
+            }
+            Q1[e] = q1;
+            Q2[e] = q2;
+        }
+    }
+    __syncthreads();
+    // phase 3: Num | Den of an exemplar tile, then the update
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f = lane & 15, g = lane >> 4;
+    const bool fvalid = f < tl.z;
+    T* Hf = a.H + (long)(tl.y + (fvalid ? f : 0)) * a.hs_t;
+    const int NT = a.NP / 16, MC = a.MP / 16;
+    const T eps = (T)BETA_EPS;
+#pragma unroll 1
+    for (int nt = wave; nt < NT; nt += BT_WAVES) {
+        acc_t num = acc_t{0, 0, 0, 0}, den = acc_t{0, 0, 0, 0};
+        const T* Ar = a.Ap3 + (long)(nt * 16 + f) * a.MP + g * 4;
+        for (int c = 0; c < MC; ++c) {
+            const vec_t av = *reinterpret_cast<const vec_t*>(Ar + c * 16);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int row = c * 16 + s * 4 + g;
+                num = Mma<T>::mma(av[s], Q1[row * BT_F + f], num);
+                den = Mma<T>::mma(av[s], Q2[row * BT_F + f], den);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int n = nt * 16 + Mma<T>::row(lane, r);
+            if (fvalid && n < a.N) {
+                T* hp = Hf + (long)n * a.hs_n;
+                const T h = *hp;
+                T d = den[r] + a.l1;
+                d = d + a.l2 * h;
+                d = d == T(0) ? eps : d;
+                T q = num[r] / d;
+                if (!a.gamma_one) q = pw(q, a.pg);
+                *hp = h * q;
+            }
+        }
+    }
+}
+
+// errf[slot] = the frame's share of _beta_divergence(X, H, A, beta): see the header comment of evc_beta_solve
+template <typename T>
+__global__ __launch_bounds__(BT_THREADS) void k_beta_err(BetaArgs<T> a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char beta_lds[];
+    const int tile = blockIdx.x;
+    const int4 tl = a.tiles[tile];
+    if (a.stop[tl.x] != 0) return;
+    T* Vs = reinterpret_cast<T*>(beta_lds);
+    double* red = reinterpret_cast<double*>(beta_lds + (size_t)a.MP * BT_F * sizeof(T));      // [3][16 parts][16 frames]
+    beta_form_v<T>(a, tl, Vs);
+    const T* Xt = a.Xp + (long)tile * a.MP * BT_F;
+    const int f = threadIdx.x & 15, part = threadIdx.x >> 4;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int m = part; m < a.M; m += 16) {
+        const double x = (double)Xt[m * BT_F + f], v = (double)Vs[m * BT_F + f];
+        const double vv = v < BETA_EPS ? BETA_EPS : v;
+        switch (a.err_mode) {
+            case BETA_ERR_IS:
+                if (x > BETA_EPS) {
+                    const double d = x / vv;
+                    s0 += d - log(d);
+                }
+                break;
+            case BETA_ERR_KL:
+                s0 += v;
+                if (x > BETA_EPS) s0 += x * log(x / vv) - x;
+                break;
+            case BETA_ERR_FROB:
+                s0 += (x - v) * (x - v);
+                break;
+            default:
+                s2 += pw(v, a.pb);
+                if (x > BETA_EPS) {
+                    s0 += pw(x, a.pb);
+                    s1 += x * pw(vv, a.p2);
+                }
+        }
+    }
+    red[part * 16 + f] = s0;
+    red[256 + part * 16 + f] = s1;
+    red[512 + part * 16 + f] = s2;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+        for (int p = 0; p < 16; ++p) {
+            t0 += red[p * 16 + f];
+            t1 += red[256 + p * 16 + f];
+            t2 += red[512 + p * 16 + f];
+        }
+        double res;
+        if (a.err_mode == BETA_ERR_IS) res = t0 - (double)a.M;
+        else if (a.err_mode == BETA_ERR_KL) res = t0;
+        else if (a.err_mode == BETA_ERR_FROB) res = 0.5 * t0;
+        else res = (t0 - a.beta * t1 + (a.beta - 1.0) * t2) / (a.beta * (a.beta - 1.0));
+        a.errf[(long)tile * BT_F + f] = f < tl.z ? res : 0.0;
+    }
+}
+
+// one block per utterance: err = sqrt(2 max(sum of the shares, 0)) in a fixed order; check c (0: the start)
+__global__ __launch_bounds__(256) void k_beta_check(const double* __restrict__ errf, const int* __restrict__ utt_tile0,
+                                                    int* stop, double* einit, double* eprev, double* trace, int n_slots,
+                                                    int c, int check_every, int stop_rule, double tol) {
+    __shared__ double red[256];
+    const int u = blockIdx.x;
+    const long i0 = (long)utt_tile0[u] * BT_F, i1 = (long)utt_tile0[u + 1] * BT_F;
+    if (stop[u] != 0 || i0 == i1) return;       // uniform per block
+    double acc = 0.0;
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) acc += errf[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double err = sqrt(2.0 * fmax(red[0], 0.0));
+    trace[(long)u * n_slots + c] = err;
+    if (c == 0) {
+        einit[u] = err;
+        eprev[u] = err;
+        return;
+    }
+    if (stop_rule == EVC_STOP_SKLEARN && (eprev[u] - err) / einit[u] < tol) stop[u] = c * check_every;
+    else eprev[u] = err;
+}
+
+__global__ void k_beta_state_init(int* stop, double* trace, int n_utt, int n_slots) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_utt) stop[i] = 0;
+    if (i < (long)n_utt * n_slots) trace[i] = __builtin_nan("");
+}
+
+template <typename T>
+__global__ void k_beta_pack_dict(const T* __restrict__ A, int lda, int fm, int M, int N, int NP, int MP,
+                                 T* __restrict__ Ap1, T* __restrict__ Ap3) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)NP * MP) return;
+    const int n = (int)(i / MP), p = (int)(i % MP);
+    const int m3 = (p & ~15) + (p & 3) * 4 + ((p >> 2) & 3);       // slot 4 g + s holds bin 4 s + g of its chunk
+    T v1 = T(0), v3 = T(0);
+    if (n < N) {
+        if (p < M) v1 = fm ? A[(long)n * lda + p] : A[(long)p * lda + n];
+        if (m3 < M) v3 = fm ? A[(long)n * lda + m3] : A[(long)m3 * lda + n];
+    }
+    Ap1[i] = v1;
+    Ap3[i] = v3;
+}
+
+template <typename T>
+__global__ void k_beta_pack_x(const T* __restrict__ X, int ldx, int fm, int M, int MP, const int4* __restrict__ tiles,
+                              int n_tiles, T* __restrict__ Xp) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)n_tiles * MP * BT_F) return;
+    const int4 tl = tiles[i / ((long)MP * BT_F)];
+    const int m = (int)((i / BT_F) % MP), f = (int)(i % BT_F);
+    T v = T(0);
+    if (m < M && f < tl.z) v = fm ? X[(long)(tl.y + f) * ldx + m] : X[(long)m * ldx + tl.y + f];
+    Xp[i] = v;
+}
+
+// h0[u] = sqrt(mean(X_u) / N) (sklearn's start, _nmf.py:1228-1231), summed in a fixed order over the packed frames
+template <typename T>
+__global__ __launch_bounds__(256) void k_beta_h0(const T* __restrict__ Xp, const int* __restrict__ utt_tile0,
+                                                 const int* __restrict__ utt_frames, int M, int MP, int N,
+                                                 double* __restrict__ h0) {
+    __shared__ double red[256];
+    const int u = blockIdx.x;
+    const long i0 = (long)utt_tile0[u] * MP * BT_F, i1 = (long)utt_tile0[u + 1] * MP * BT_F;
+    double acc = 0.0;
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) acc += (double)Xp[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const double cnt = (double)utt_frames[u] * (double)M;
+        h0[u] = cnt > 0.0 ? sqrt(red[0] / cnt / (double)N) : 0.0;
+    }
+}
+
+// every activation of utterance u starts at h0[u] (h0 == NULL: at `value`)
+template <typename T>
+__global__ void k_beta_fill(T* __restrict__ H, long hs_t, long hs_n, int N, const int4* __restrict__ tiles, int n_tiles,
+                            const double* __restrict__ h0, double value) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)n_tiles * BT_F * N) return;
+    const long slot = i / N;
+    const int n = (int)(i % N), f = (int)(slot % BT_F);
+    const int4 tl = tiles[slot / BT_F];
+    if (f < tl.z) H[(long)(tl.y + f) * hs_t + (long)n * hs_n] = (T)(h0 ? h0[tl.x] : value);
+}
+
+#define BETA_TRY(expr)                                \
+    do {                                              \
+        hipError_t e_ = (expr);                       \
+        if (e_ != hipSuccess) return (int)e_;         \
+    } while (0)
+
+size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
+
+template <typename T> struct BetaWs {
+    T *Ap1, *Ap3, *Xp;
+    double *errf, *h0, *einit, *eprev, *trace;
+    int4* tiles;
+    int *utt_tile0, *utt_frames, *stop;
+    size_t bytes;
+};
+
+// [Ap1 | Ap3 | Xp | errf | tiles | utt_tile0 | utt_frames | stop | h0 | einit | eprev | trace], each 256-byte aligned; the
+// tile count is bounded by ceil(T / 16) + n_utt whatever the split into utterances (ws == NULL: sizes only)
+template <typename T>
+BetaWs<T> carve_beta(void* ws, int M, int N, int T_, int n_utt) {
+    BetaWs<T> w;
+    const uintptr_t base = (reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char* p = reinterpret_cast<char*>(base + off); off += align256(bytes); return p; };
+    const size_t MP = (size_t)round_up(M, 16), NP = (size_t)round_up(N, 16);
+    const size_t nt = (size_t)(T_ + BT_F - 1) / BT_F + n_utt;
+    w.Ap1 = reinterpret_cast<T*>(take(NP * MP * sizeof(T)));
+    w.Ap3 = reinterpret_cast<T*>(take(NP * MP * sizeof(T)));
+    w.Xp = reinterpret_cast<T*>(take(nt * MP * BT_F * sizeof(T)));
+    w.errf = reinterpret_cast<double*>(take(nt * BT_F * sizeof(double)));
+    w.tiles = reinterpret_cast<int4*>(take(nt * sizeof(int4)));
+    w.utt_tile0 = reinterpret_cast<int*>(take((size_t)(n_utt + 1) * sizeof(int)));
+    w.utt_frames = reinterpret_cast<int*>(take((size_t)n_utt * sizeof(int)));
+    w.stop = reinterpret_cast<int*>(take((size_t)n_utt * sizeof(int)));
+    w.h0 = reinterpret_cast<double*>(take((size_t)n_utt * sizeof(double)));
+    w.einit = reinterpret_cast<double*>(take((size_t)n_utt * sizeof(double)));
+    w.eprev = reinterpret_cast<double*>(take((size_t)n_utt * sizeof(double)));
+    w.trace = reinterpret_cast<double*>(take((size_t)n_utt * BETA_MAX_SLOTS * sizeof(double)));
+    w.bytes = (size_t)(base - reinterpret_cast<uintptr_t>(ws)) + off;
+    return w;
+}
+
+size_t beta_workspace_bytes(int M, int N, int T_, int n_utt, int dtype) {
+    if (M < 1 || M > BETA_MAX_M || N < 1 || T_ < 0 || n_utt < 1) return 0;
+    if (dtype == EVC_F64) return carve_beta<double>(nullptr, M, N, T_, n_utt).bytes + 256;
+    if (dtype == EVC_F32) return carve_beta<float>(nullptr, M, N, T_, n_utt).bytes + 256;
+    return 0;
+}
+
+// arguments already validated by evc_beta_solve; returns 0, -2 or a hipError_t
+template <typename T>
+int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
+               int n_utt, const evc_beta_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* err_out,
+               hipStream_t s) {
+    const BetaWs<T> w = carve_beta<T>(ws, M, N, T_, n_utt);
+    if (w.bytes > ws_bytes) return -2;
+    const bool fm = o.layout == EVC_FRAME_MAJOR;
+    const int MP = round_up(M, 16), NP = round_up(N, 16);
+    const int n_slots = 1 + (o.check_every > 0 ? o.iters / o.check_every : 0);
+
+    // the tile table (host, staged by hipMemcpyAsync from pageable memory at enqueue time)
+    int n_tiles = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        const int tu = utt_offsets ? utt_offsets[u + 1] - utt_offsets[u] : T_;
+        n_tiles += (tu + BT_F - 1) / BT_F;
+    }
+    {
+        int4* h_tiles = static_cast<int4*>(malloc(sizeof(int4) * (n_tiles > 0 ? n_tiles : 1) + sizeof(int) * (2 * n_utt + 1)));
+        if (!h_tiles) return (int)hipErrorOutOfMemory;
+        int* h_t0 = reinterpret_cast<int*>(h_tiles + (n_tiles > 0 ? n_tiles : 1));
+        int* h_fr = h_t0 + n_utt + 1;
+        int t = 0;
+        for (int u = 0; u < n_utt; ++u) {
+            const int f0 = utt_offsets ? utt_offsets[u] : 0;
+            const int tu = utt_offsets ? utt_offsets[u + 1] - f0 : T_;
+            h_t0[u] = t;
+            h_fr[u] = tu;
+            for (int i = 0; i < tu; i += BT_F) h_tiles[t++] = make_int4(u, f0 + i, tu - i < BT_F ? tu - i : BT_F, 0);
+        }
+        h_t0[n_utt] = t;
+        hipError_t e = hipSuccess;
+        if (n_tiles > 0) e = hipMemcpyAsync(w.tiles, h_tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(w.utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(w.utt_frames, h_fr, sizeof(int) * n_utt, hipMemcpyHostToDevice, s);
+        free(h_tiles);      // pageable source: HIP has staged the bytes by the time hipMemcpyAsync returns
+        BETA_TRY(e);
+    }
+    hipLaunchKernelGGL(k_beta_state_init, dim3(blocks_of((long)n_utt * n_slots)), dim3(256), 0, s, w.stop, w.trace, n_utt,
+                       n_slots);
+    BETA_TRY(hipGetLastError());
+
+    BetaArgs<T> a;
+    a.Ap1 = w.Ap1; a.Ap3 = w.Ap3; a.Xp = w.Xp; a.H = H;
+    a.hs_t = fm ? ldh : 1; a.hs_n = fm ? 1 : ldh;
+    a.tiles = w.tiles; a.stop = w.stop; a.errf = w.errf;
+    a.M = M; a.MP = MP; a.N = N; a.NP = NP;
+    const double beta = o.beta;
+    a.beta = beta;
+    a.clamp_n = beta - 2.0 < 0 ? 1 : 0;
+    a.clamp_d = beta - 1.0 < 0 ? 1 : 0;
+    const double gamma = beta < 1.0 ? 1.0 / (2.0 - beta) : beta > 2.0 ? 1.0 / (beta - 1.0) : 1.0;
+    a.gamma_one = gamma == 1.0 ? 1 : 0;
+    a.p1 = pow_spec(beta - 2.0); a.p2 = pow_spec(beta - 1.0); a.pg = pow_spec(gamma); a.pb = pow_spec(beta);
+    a.err_mode = beta == 0.0 ? BETA_ERR_IS : beta == 1.0 ? BETA_ERR_KL : beta == 2.0 ? BETA_ERR_FROB : BETA_ERR_GENERIC;
+    a.l1 = (T)o.l1; a.l2 = (T)o.l2;
+
+    const size_t lds_sweep = (size_t)2 * MP * BT_F * sizeof(T);
+    const size_t lds_err = (size_t)MP * BT_F * sizeof(T) + 3 * 256 * sizeof(double);
+    const bool checks = o.check_every > 0;
+    if (n_tiles > 0) {
+        hipLaunchKernelGGL(k_beta_pack_dict<T>, dim3(blocks_of((long)NP * MP)), dim3(256), 0, s, A, lda, fm ? 1 : 0, M, N, NP,
+                           MP, w.Ap1, w.Ap3);
+        BETA_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_beta_pack_x<T>, dim3(blocks_of((long)n_tiles * MP * BT_F)), dim3(256), 0, s, X, ldx, fm ? 1 : 0, M,
+                           MP, w.tiles, n_tiles, w.Xp);
+        BETA_TRY(hipGetLastError());
+        if (o.init_mode != EVC_INIT_GIVEN) {
+            const bool sk = o.init_mode == EVC_INIT_SKLEARN;
+            if (sk) {
+                hipLaunchKernelGGL(k_beta_h0<T>, dim3(n_utt), dim3(256), 0, s, w.Xp, w.utt_tile0, w.utt_frames, M, MP, N, w.h0);
+                BETA_TRY(hipGetLastError());
+            }
+            hipLaunchKernelGGL(k_beta_fill<T>, dim3(blocks_of((long)n_tiles * BT_F * N)), dim3(256), 0, s, H, a.hs_t, a.hs_n, N,
+                               w.tiles, n_tiles, sk ? w.h0 : nullptr, o.init_value);
+            BETA_TRY(hipGetLastError());
+        }
+        // the attribute is per function and process-wide: always the limit of BETA_MAX_M, so that concurrent calls at
+        // different M never shrink it under one another
+        BETA_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_sweep<T>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * BETA_MAX_M * BT_F * sizeof(T))));
+        BETA_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_err<T>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)(BETA_MAX_M * BT_F * sizeof(T) + 3 * 256 * sizeof(double))));
+    }
+    auto check = [&](int c) -> int {
+        hipLaunchKernelGGL(k_beta_err<T>, dim3(n_tiles), dim3(BT_THREADS), lds_err, s, a);
+        BETA_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_beta_check, dim3(n_utt), dim3(256), 0, s, w.errf, w.utt_tile0, w.stop, w.einit, w.eprev, w.trace,
+                           n_slots, c, o.check_every, o.stop_rule, o.tol);
+        BETA_TRY(hipGetLastError());
+        return 0;
+    };
+    if (n_tiles > 0 && checks) {
+        const int st = check(0);
+        if (st != 0) return st;
+    }
+    if (o.ev_loop_start) BETA_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
+    for (int it = 1; n_tiles > 0 && it <= o.iters; ++it) {
+        hipLaunchKernelGGL(k_beta_sweep<T>, dim3(n_tiles), dim3(BT_THREADS), lds_sweep, s, a);
+        BETA_TRY(hipGetLastError());
+        if (checks && it % o.check_every == 0) {
+            const int st = check(it / o.check_every);
+            if (st != 0) return st;
+        }
+    }
+    if (o.ev_loop_stop) BETA_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
+    if (n_iter_out || err_out) {
+        int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
+        if (!ni_h) return (int)hipErrorOutOfMemory;
+        hipError_t e = hipMemcpyAsync(ni_h, w.stop, sizeof(int) * n_utt, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && err_out)
+            e = hipMemcpyAsync(err_out, w.trace, sizeof(double) * n_utt * n_slots, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        for (int u = 0; e == hipSuccess && n_iter_out && u < n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : o.iters;
+        free(ni_h);
+        BETA_TRY(e);
+    }
+    return 0;
+}
+
+bool beta_offsets_ok(const int* utt_offsets, int n_utt, int T_) {
+    if (!utt_offsets) return n_utt == 1;
+    if (utt_offsets[0] != 0 || utt_offsets[n_utt] != T_) return false;
+    for (int i = 0; i < n_utt; ++i)
+        if (utt_offsets[i + 1] < utt_offsets[i]) return false;
+    return true;
+}
+
+}  // namespace
+
+}  // namespace evc
+
+extern "C" {
+
+size_t evc_beta_workspace_bytes(int M, int N, int T, int n_utt, int dtype) {
+    return evc::beta_workspace_bytes(M, N, T, n_utt, dtype);
+}
+
+int evc_beta_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
+                   const int* utt_offsets, int n_utt, const evc_beta_opts* opts, void* workspace, size_t workspace_bytes,
+                   int* n_iter_out, double* err_out, evc_stream_t stream) {
+    using namespace evc;
+    if (!opts || opts->struct_bytes != (int)sizeof(evc_beta_opts)) return -1;
+    const evc_beta_opts& o = *opts;
+    if (M < 1 || N < 1 || T < 0 || n_utt < 1 || o.iters < 0 || o.check_every < 0 || o.reserved != 0) return -1;
+    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return -1;
+    const bool fm = o.layout == EVC_FRAME_MAJOR;
+    if (!fm && o.layout != EVC_BIN_MAJOR) return -1;
+    if (o.init_mode != EVC_INIT_GIVEN && o.init_mode != EVC_INIT_SKLEARN && o.init_mode != EVC_INIT_CONST) return -1;
+    if (o.stop_rule != EVC_STOP_NONE && o.stop_rule != EVC_STOP_SKLEARN) return -1;
+    if (!(o.beta - o.beta == 0.0)) return -1;                      // NaN or infinite
+    if (!(o.tol >= 0.0) || !(o.l1 >= 0.0) || !(o.l2 >= 0.0) || !(o.init_value - o.init_value == 0.0)) return -1;
+    if (!A || !workspace || (T > 0 && (!X || !H))) return -1;       // no frames: X and H are never touched
+    if ((fm ? lda < M : lda < N) || (fm ? ldx < M : ldx < T) || (fm ? ldh < N : ldh < T)) return -1;
+    if (!beta_offsets_ok(utt_offsets, n_utt, T)) return -1;
+    if (o.check_every > 0 && o.iters / o.check_every + 1 > BETA_MAX_SLOTS) return -1;
+    if (M > BETA_MAX_M) return -3;
+    if (workspace_bytes < beta_workspace_bytes(M, N, T, n_utt, o.dtype)) return -2;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (o.dtype == EVC_F64)
+        return beta_solve<double>(static_cast<const double*>(A), lda, static_cast<const double*>(X), ldx,
+                                  static_cast<double*>(H), ldh, M, N, T, utt_offsets, n_utt, o, workspace, workspace_bytes,
+                                  n_iter_out, err_out, s);
+    return beta_solve<float>(static_cast<const float*>(A), lda, static_cast<const float*>(X), ldx, static_cast<float*>(H),
+                             ldh, M, N, T, utt_offsets, n_utt, o, workspace, workspace_bytes, n_iter_out, err_out, s);
+}
+
+}  // extern "C"

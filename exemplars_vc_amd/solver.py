@@ -458,6 +458,96 @@ def solve_activations_cd(A, X, H0=None, *, layout="bin_major", max_iter=200, tol
     return H_out
 
 
+def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100, init=None, init_value=0.0, check_every=0,
+                           stop_rule="none", tol=0.0, l1=0.0, l2=0.0, utt_offsets: Optional[Sequence[int]] = None,
+                           dtype=None, device=None, info=False, loop_events=None):
+    """scikit-learn's multiplicative update with the dictionary fixed under any beta-divergence (solver='mu',
+    update_H=False, beta_loss=beta: 0 is Itakura-Saito, any finite float goes), on the GPU (evc_beta_solve).  beta = 1
+    and beta = 2 run the same generic statement; solve_activations serves them with kernels of their own.  init:
+    "given" (H0), "sklearn" (sqrt(mean(X_u) / N) per utterance) or "const" (init_value); default "given" with H0, else
+    "sklearn".  l1 / l2 are sklearn's scaled l1_reg_W / l2_reg_W.  stop_rule "sklearn": per utterance, every
+    `check_every` iterations, stop when (err_prev - err) / err_at_start < tol.
+
+    Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out);
+    with info=True also dict(n_iter=int array per utterance, err=[n_utt, 1 + iters // check_every] array (NaN where not
+    evaluated), kernel="k_beta_sweep", launches=int: the launches the iteration loop and its checks enqueue - one sweep per
+    iteration, two kernels per error slot, whether or not an utterance has stopped; the import and start kernels are not
+    counted).  No CPU fallback: without a HIP device this raises RuntimeError."""
+    lay = _LAYOUTS[layout]
+    beta = float(beta)
+    if not np.isfinite(beta):
+        raise ValueError(f"beta must be finite, got {beta!r}")
+    if stop_rule not in ("none", "sklearn"):
+        raise ValueError("stop_rule must be 'none' or 'sklearn'")
+    ashape = tuple(getattr(A, "shape", ()))
+    if len(ashape) == 2 and ashape[0 if lay == _lib.BIN_MAJOR else 1] > _lib.BETA_MAX_M:     # what the ABI answers with -3
+        raise ValueError(f"unsupported beta-divergence shape: M = {ashape[0 if lay == _lib.BIN_MAJOR else 1]} bins, the "
+                         f"kernel holds at most {_lib.BETA_MAX_M}")
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    tdtype, dcode = _pick_dtype(dtype, X, A)
+    A_d, _ = _to_dev(A, tdtype, device)
+    X_d, x_np = _to_dev(X, tdtype, device)
+    if lay == _lib.BIN_MAJOR:
+        M, N = A_d.shape
+        M2, T = X_d.shape
+        hshape = (N, T)
+    else:
+        N, M = A_d.shape
+        T, M2 = X_d.shape
+        hshape = (T, N)
+    if M2 != M:
+        raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
+    if M < 1 or N < 1:
+        raise ValueError(f"empty beta-divergence problem M={M}, N={N}, T={T}")
+    if init is None:
+        init = "given" if H0 is not None else "sklearn"
+    if init == "given":
+        if H0 is None:
+            raise ValueError("init='given' needs H0")
+        H_d, _ = _to_dev(H0, tdtype, device)
+        if tuple(H_d.shape) != hshape:
+            raise ValueError(f"H0 has shape {tuple(H_d.shape)}, expected {hshape}")
+        if isinstance(H0, torch.Tensor) and H_d.data_ptr() == H0.data_ptr():
+            H_d = H_d.clone()       # never clobber the caller's H0
+    else:
+        H_d = torch.empty(hshape, dtype=tdtype, device=device)
+    if utt_offsets is None:
+        n_utt, off_ptr = 1, None
+    else:
+        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
+        n_utt = len(off_arr) - 1
+        if n_utt < 1:
+            raise ValueError("utt_offsets needs at least two entries")
+        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
+    iters, check_every = int(iters), int(check_every)
+    opts = _lib.BetaOpts()
+    opts.struct_bytes = C.sizeof(_lib.BetaOpts)
+    opts.dtype, opts.layout, opts.iters, opts.init_mode = dcode, lay, iters, _INITS[init]
+    opts.check_every, opts.stop_rule = check_every, _STOPS[stop_rule]
+    opts.beta, opts.tol, opts.l1, opts.l2, opts.init_value = beta, float(tol), float(l1), float(l2), float(init_value)
+    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
+        opts.ev_loop_start = int(loop_events[0].cuda_event)
+        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    ws_bytes = int(L.evc_beta_workspace_bytes(M, N, T, n_utt, dcode))
+    n_slots = 1 + (iters // check_every if check_every > 0 else 0)
+    n_iter = np.zeros(n_utt, dtype=np.int32) if info else None
+    err = np.full((n_utt, n_slots), np.nan) if info else None
+    ni_p = n_iter.ctypes.data_as(C.POINTER(C.c_int)) if info else None
+    er_p = err.ctypes.data_as(C.POINTER(C.c_double)) if info else None
+    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_beta_solve(A_d.data_ptr(), _ld(A_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, N, T,
+                              off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p, C.c_void_p(stream))
+    _lib.check(st, "evc_beta_solve")
+    H_out = _to_host(H_d) if x_np else H_d
+    if info:
+        launches = iters + 2 * n_slots * (check_every > 0) if T > 0 else 0
+        return H_out, {"n_iter": n_iter, "err": err, "kernel": "k_beta_sweep", "launches": launches}
+    return H_out
+
+
 _SURFACES = {"sklearn": _lib.LEARN_SKLEARN, "pymf": _lib.LEARN_PYMF}
 
 

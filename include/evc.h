@@ -34,6 +34,10 @@
  *                   NMF(n_components=...).fit_transform(...) of 05_conversion.py:100-106 (solver='cd', update_H=True:
  *                   _fit_coordinate_descent, _nmf.py:496-521, both calls of _update_coordinate_descent, :376-404);
  *                   evc_cd_learn_workspace_bytes and evc_cd_learn_splits size and describe it
+ *   evc_beta_solve  replaces the multiplicative-update loop behind _factorize(X, W, beta_loss=...) of 04_align_n_nmf.py:194-215
+ *                   for the losses evc_nmf_solve does not serve: beta_loss = 'itakura-saito' or any float (sklearn
+ *                   _multiplicative_update_w, _nmf.py:556-631, and _beta_divergence, :85-189, with update_H=False);
+ *                   evc_beta_workspace_bytes sizes it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -74,6 +78,9 @@
  *         assumes residency: concurrent calls on several streams are safe.
  *     (7) evc_mfcc: never.  The call is a pure enqueue; no scalar comes back to the host (the per-utterance maximum of
  *         the decibel clamp is formed on the device from per-workgroup partial maxima, without atomics).
+ *     (8) evc_beta_solve: n_iter_out / err_out non-NULL (the call returns after copying them back); otherwise the call is
+ *         a pure enqueue: the per-utterance stop state lives on the device.  None of its kernels exchanges data between
+ *         workgroups inside a launch, uses float atomics or assumes residency: concurrent calls on several streams are safe.
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
  *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets, sample_offsets) are consumed before the call returns: they are
@@ -586,6 +593,66 @@ int evc_cd_learn_splits(int M, int R, int T);
 int evc_cd_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
                  const evc_cd_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
                  double* violation_out, evc_stream_t stream);
+
+/* Multiplicative updates of the activations under any beta-divergence, the dictionary fixed: scikit-learn's
+ * non_negative_factorization(X, H=A, init='custom', update_H=False, solver='mu', beta_loss=beta) for beta_loss =
+ * 'itakura-saito' (beta = 0) or any float.  With EPS = 1.1920929e-7 (2^-23, in both element types), per iteration and frame:
+ *     V  = A h;   Vd = V with values below EPS raised to EPS if beta < 1;   Vn = the same if beta < 2
+ *     Q1 = x * Vn^(beta-2);   Q2 = Vd^(beta-1);   Num = A^T Q1;   Den = A^T Q2 + l1 + l2 h,  Den == 0 -> EPS
+ *     h <- h * (Num / Den)^gamma,   gamma = 1/(2-beta) if beta < 1, 1/(beta-1) if beta > 2, else 1
+ * beta = 1 and beta = 2 are accepted and run this generic statement; their results agree with evc_nmf_solve's
+ * (EVC_LOSS_KL, and EVC_LOSS_FROBENIUS with EVC_EPS_ZERO_REPLACE) to rounding, not bitwise.
+ * The error of utterance u (T_u frames), at the start and after every `check_every` iterations, is sklearn's
+ * _beta_divergence(..., square_root=True) = sqrt(2 max(res, 0)): only entries with X > EPS enter the sums marked *, and
+ * there V below EPS counts as EPS:
+ *     beta = 0     res = sum* X/V - M T_u - sum* log(X/V)                       (M T_u counts every entry, as sklearn does)
+ *     beta = 1     res = sum* (X log(X/V) - X) + sum_all V
+ *     beta = 2     res = sum_all (X - V)^2 / 2
+ *     otherwise    res = (sum* X^beta - beta sum* X V^(beta-1) + (beta-1) sum_all V^beta) / (beta (beta-1))
+ * EVC_STOP_SKLEARN stops an utterance at a check when (err_prev - err) / err_at_start < tol; its frames are frozen while
+ * the others go on.  EVC_INIT_SKLEARN starts every activation of utterance u at sqrt(mean(X_u) / N).
+ * One kernel launch per iteration (k_beta_sweep): a workgroup owns 16 frames of one utterance, forms V = A H on the matrix
+ * cores, turns it into Q1 | Q2 in LDS and forms Num | Den per exemplar tile; V, Q1, Q2, Num and Den never reach memory.
+ * H is written once per iteration and read 1 + ceil(ceil(M / 16) / 8) times (twice up to M = 128, 6 times at M = 513).
+ * float32 inputs are solved in float32; the error is summed in float64 for both types, per utterance in a fixed order (no
+ * float atomics): the same call gives bitwise the same output every time.  A frame's arithmetic does not depend on the other
+ * frames of the call: a batch of utterances gives bitwise the activations of one call per utterance, and a NaN or infinity
+ * in a frame of X stays in that frame's column (the other frames are bitwise those of the call without it; only the
+ * start of EVC_INIT_SKLEARN, the utterance's mean, carries it to the utterance's other frames, as in scikit-learn).
+ * Exponents that are multiples of 1/2 (beta = 0, 0.5, 1.5, 3, ...) are evaluated with products, square roots and one
+ * division, the power first and the reciprocal last (beta = 0: Q1 = x * (1 / (V V)), one rounding away from sklearn's
+ * x * (1 / V)^2); the general float beta calls pow.
+ *   M      : 1 .. 528 bins (larger: -3);  any N >= 1, T >= 0 (an utterance may be empty: nothing is done for it, its n_iter
+ *            is `iters` and its errors stay NaN);  iters = 0 leaves the start in H
+ *   beta   : any finite value (NaN, infinity: -1)
+ *   l1, l2 : already scaled: sklearn's l1_reg_W = M alpha_W l1_ratio and l2_reg_W = M alpha_W (1 - l1_ratio)
+ *   layout, utt_offsets, n_utt : as for evc_nmf_solve
+ *   n_iter_out : host, n_utt ints or NULL: updates applied to each utterance
+ *   err_out    : host, n_utt * (1 + iters / check_every) doubles or NULL, laid out like evc_nmf_solve's: per utterance the
+ *                error at the start, then at each check that was evaluated (NaN where not; all NaN with check_every = 0);
+ *                at most 4097 slots per utterance (more: -1)
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: case (8) of the list at the top. */
+typedef struct evc_beta_opts {
+    int struct_bytes;  /* sizeof(evc_beta_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int iters;         /* maximum number of multiplicative updates (>= 0) */
+    int init_mode;     /* EVC_INIT_GIVEN | EVC_INIT_SKLEARN | EVC_INIT_CONST */
+    int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
+    int stop_rule;     /* EVC_STOP_NONE | EVC_STOP_SKLEARN */
+    int reserved;      /* 0 */
+    double beta;       /* the divergence: 0 Itakura-Saito, 1 Kullback-Leibler, 2 Frobenius, or any finite value */
+    double tol;        /* >= 0: threshold of stop_rule */
+    double l1, l2;     /* >= 0 */
+    double init_value; /* EVC_INIT_CONST */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_beta_opts;
+/* bytes of workspace evc_beta_solve needs (0: invalid arguments, M > 528 among them) */
+size_t evc_beta_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
+int evc_beta_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
+                   const int* utt_offsets, int n_utt, const evc_beta_opts* opts, void* workspace, size_t workspace_bytes,
+                   int* n_iter_out, double* err_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
