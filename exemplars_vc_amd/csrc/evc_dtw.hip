@@ -224,7 +224,12 @@ __global__ __launch_bounds__(DTW_THREADS) void k_dtw_accumulate(DtwArgs g) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             while ((i >> 6) == I && (j >> 6) == J && (i > 0 || j > 0)) {
                 const int il = i & 63, jl = j & 63;
-                const int t = *reinterpret_cast<volatile unsigned char*>(tl + (il + jl) * 64 + il);
+                int t = *reinterpret_cast<volatile unsigned char*>(tl + (il + jl) * 64 + il);
+                // on row 0 the walk can only go left, on column 0 only up.  Finite costs give those bytes anyway (the
+                // other neighbours are +inf); a NaN or +inf in D[0][j-1] or D[i-1][0] compares below nothing and leaves
+                // the byte at 0: without this the walk would step to -1 and never come back.  So every step lowers i
+                // or j, neither goes below 0, and pos stays >= 1.
+                if (i == 0) t = 2; else if (j == 0) t = 1;
                 if (t == 0) { --i; --j; } else if (t == 1) { --i; } else { --j; }
                 --pos;
                 if (lane == 0) { pa[pos] = i; pb[pos] = j; }
@@ -347,6 +352,9 @@ __global__ __launch_bounds__(1024) void k_path_scan(const int* __restrict__ path
     if (tid == 1023) row_start[n_pairs] = s_part[1023];
 }
 
+__device__ __forceinline__ double gather_abs(double v) { return fabs(v); }
+__device__ __forceinline__ float gather_abs(float v) { return fabsf(v); }
+
 // dst[row_start[p] + k][c] = op(src[src_off[p] + path[pair_off[p] + k]][c * elem_stride]), k < path_len[p].
 // One workgroup row of 256 threads walks the columns; blockIdx.y strides over the rows of pair blockIdx.z.
 template <typename T>
@@ -365,7 +373,7 @@ __global__ __launch_bounds__(256) void k_gather_pairs(const T* __restrict__ src,
         T* drow = dst + (d0 + k) * ld_dst;
         for (int c = blockIdx.x * 256 + threadIdx.x; c < cols; c += gridDim.x * 256) {
             T v = srow[(long)c * elem_stride];
-            if (op == 1) v = v < T(0) ? -v : v;          // |.|  (NaN stays NaN, -0 -> 0 like np.abs)
+            if (op == 1) v = gather_abs(v);              // |.|: the sign bit cleared like np.abs (-0 -> 0, also on NaNs)
             drow[c] = v;
         }
     }

@@ -434,7 +434,13 @@ int evc_griffin_lim_batch(const void* mag, int ldm, const int* frame_offsets, in
  *   path_a/b  : device int arrays of sum_p (Ta_p + Tb_p) entries; pair p's path starts at
  *               a_offsets[p] + b_offsets[p] and has path_len[p] (device, n_pairs) entries
  *   total     : device, n_pairs doubles or NULL: accumulated cost of the last cell
- * Frames per utterance are limited by the LDS border buffers of the tiled wavefront (7680). */
+ *   D         : 1 .. 512 features (larger: -3);  n_pairs : 1 .. 65535 (larger: -3)
+ * Frames per utterance are limited by the LDS border buffers of the tiled wavefront (7680).  A pair with an empty
+ * utterance gets path_len 0 and total 0.
+ * Non-finite features, or features whose squared differences overflow: the path of such a pair is unspecified, but it is
+ * a valid warping path - from (0, 0) to (Ta-1, Tb-1) in steps of (1,1), (1,0), (0,1), hence at most Ta + Tb - 1 entries -
+ * that stays inside the pair's part of the path buffers; its `total` is unspecified.  The other pairs of the call are
+ * bitwise unaffected. */
 size_t evc_dtw_workspace_bytes(const int* a_offsets, const int* b_offsets, int n_pairs);
 int evc_dtw_align(const void* A, int lda, const int* a_offsets, const void* B, int ldb,
                   const int* b_offsets, int D, int n_pairs, int* path_a, int* path_b, int* path_len,
@@ -452,7 +458,8 @@ int evc_dtw_align(const void* A, int lda, const int* a_offsets, const void* B, i
  * evc_dtw_gather_rows: dst[row_start[p] + k][c] = op(src[src_offsets[p] + path[pair_offsets[p] + k]][c * elem_stride])
  *   for k < path_len[p], c < cols.
  *   src          : frames as rows, row stride ld_src (elements); elem_stride = 2 picks the real parts of an interleaved
- *                  complex matrix (the script's np.abs(real(stft)), :320-324, with op = EVC_GATHER_ABS)
+ *                  complex matrix (the script's np.abs(real(stft)), :320-324, with op = EVC_GATHER_ABS: the sign bit
+ *                  cleared as np.abs does it, so -0 becomes +0 and a NaN keeps its payload)
  *   path         : device, path_a or path_b of evc_dtw_align;  pair_offsets : device, n_pairs ints, a_offsets[p] + b_offsets[p]
  *   src_offsets  : device, n_pairs ints, first row of pair p's utterance in src
  *   dst          : N x cols, row stride ld_dst;  dtype: EVC_F64 | EVC_F32 (src and dst alike) */
