@@ -32,7 +32,8 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_dtw_path_rows", "evc_dtw_gather_rows", "evc_cd_workspace_bytes", "evc_cd_solve",
            "evc_learn_workspace_bytes", "evc_learn_splits", "evc_nmf_learn",
            "evc_cd_learn_workspace_bytes", "evc_cd_learn_splits", "evc_cd_learn",
-           "evc_mfcc_workspace_bytes", "evc_mfcc", "evc_beta_workspace_bytes", "evc_beta_solve")
+           "evc_mfcc_workspace_bytes", "evc_mfcc", "evc_beta_workspace_bytes", "evc_beta_solve",
+           "evc_beta_learn_workspace_bytes", "evc_beta_learn_splits", "evc_beta_learn_route", "evc_beta_learn")
 BETA_MAX_M = 528
 MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
@@ -94,6 +95,17 @@ class BetaOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
         ("init_mode", C.c_int), ("check_every", C.c_int), ("stop_rule", C.c_int), ("reserved", C.c_int),
         ("beta", C.c_double), ("tol", C.c_double), ("l1", C.c_double), ("l2", C.c_double), ("init_value", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class BetaLearnOpts(C.Structure):
+    """Mirror of `evc_beta_learn_opts` (include/evc.h): options of the beta-divergence solve that also learns the dictionary."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
+        ("check_every", C.c_int), ("reserved", C.c_int),
+        ("beta", C.c_double), ("tol", C.c_double),
+        ("l1_h", C.c_double), ("l2_h", C.c_double), ("l1_w", C.c_double), ("l2_w", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -269,6 +281,20 @@ def lib():
         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # A, X, H
         C.c_int, C.c_int, C.c_int,                                          # M, N, T
         C.POINTER(C.c_int), C.c_int, C.POINTER(BetaOpts),                   # utt_offsets, n_utt, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_beta_learn_workspace_bytes.restype = C.c_size_t
+    L.evc_beta_learn_workspace_bytes.argtypes = [C.c_int] * 4
+    L.evc_beta_learn_splits.restype = C.c_int
+    L.evc_beta_learn_splits.argtypes = [C.c_int] * 3
+    L.evc_beta_learn_route.restype = C.c_int
+    L.evc_beta_learn_route.argtypes = [C.c_int] * 3
+    L.evc_beta_learn.restype = C.c_int
+    L.evc_beta_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, W, H
+        C.c_int, C.c_int, C.c_int, C.POINTER(BetaLearnOpts),                # M, R, T, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
         C.c_void_p,                                                         # stream

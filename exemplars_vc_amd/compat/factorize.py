@@ -15,8 +15,8 @@ import warnings
 
 import numpy as np
 
-from ..solver import (convert as _solve_and_synthesize, learn_dictionary, solve_activations, solve_activations_beta,
-                      synthesize)
+from ..solver import (convert as _solve_and_synthesize, learn_dictionary, learn_dictionary_beta, solve_activations,
+                      solve_activations_beta, synthesize)
 
 try:  # same warning class the reference would raise, when scikit-learn is present
     from sklearn.exceptions import ConvergenceWarning
@@ -171,6 +171,34 @@ def non_negative_factorization_mu(X, W, H, update_H=True, tol=1e-4, max_iter=200
                                   check_every=10 if tol > 0 else 0, stop_rule="sklearn" if tol > 0 else "none",
                                   tol=float(tol), device=device, info=True, loss=beta_loss)
     return act, np.asarray(H), int(info["n_iter"][0])
+
+
+def non_negative_factorization_beta(X, W, H, beta_loss, tol=1e-4, max_iter=200, *, alpha_W=0.0, alpha_H="same",
+                                    l1_ratio=0.0, device=None):
+    """scikit-learn's `non_negative_factorization(X, W, H, init='custom', update_H=True, solver='mu', beta_loss=beta_loss,
+    tol=tol, max_iter=max_iter, alpha_W=alpha_W, alpha_H=alpha_H, l1_ratio=l1_ratio)` on the GPU (evc_beta_learn), in
+    scikit-learn's orientation: X (n_samples, n_features), W (n_samples, n_components) the activations, H (n_components,
+    n_features) the dictionary.  Returns (W, H, n_iter).  beta_loss: one of scikit-learn's three names or any finite int /
+    float; beta <= 0 refuses zeros in X as scikit-learn does.  The penalties are scaled as scikit-learn scales them
+    (_nmf.py:1254-1265): those of W by n_features, those of H by n_samples.  At most 528 features."""
+    beta = _beta_of(beta_loss)
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError(f"Expected 2D array, got {X.ndim}D array instead")
+    _check_beta_zeros(X, beta)
+    if X.dtype not in (np.float64, np.float32):
+        X = X.astype(np.float64)
+    n_samples, n_features = X.shape
+    alpha_W = float(alpha_W)
+    alpha_H = alpha_W if isinstance(alpha_H, str) and alpha_H == "same" else float(alpha_H)
+    l1_ratio = float(l1_ratio)
+    # frame-major: X[t][m], the dictionary (the solver's W) as H[r][m], the activations (its H) as W[t][r]
+    Hd, Wa, info = learn_dictionary_beta(X, np.asarray(H, dtype=X.dtype), np.asarray(W, dtype=X.dtype), beta=beta,
+                                         layout="frame_major", iters=int(max_iter), check_every=10 if tol > 0 else 0,
+                                         tol=float(tol), l1_h=n_features * alpha_W * l1_ratio,
+                                         l2_h=n_features * alpha_W * (1.0 - l1_ratio), l1_w=n_samples * alpha_H * l1_ratio,
+                                         l2_w=n_samples * alpha_H * (1.0 - l1_ratio), device=device, info=True)
+    return Wa, Hd, info["n_iter"]
 
 
 def factorize_utterances(X_list, W, tol=1e-4, *, device=None, algo="auto", max_iter=MAX_ITER, hint="throughput",

@@ -30,70 +30,15 @@
 // k_beta_err<T> forms V the same way and leaves every frame's share of the divergence (float64); k_beta_check sums an
 // utterance's shares in a fixed order, records sqrt(2 max(res, 0)) and applies sklearn's stop rule on the device
 // (stop[u] = the iteration the utterance stopped at; the sweeps of a stopped utterance return at once).
-#include "evc_internal.h"
+//
+// The host steps (beta_begin, beta_pack_dict, beta_sweep, beta_check; evc_beta_common.h) also serve evc_beta_learn, which
+// repacks the dictionary every iteration and sets BetaArgs.flush (an updated activation below it is stored as 0);
+// evc_beta_solve passes 0 and its results are bitwise what they were without the field.
+#include "evc_beta_common.h"
 
 namespace evc {
 
 namespace {
-
-constexpr int BT_F = 16;            // frames per tile
-constexpr int BT_WAVES = 4;
-constexpr int BT_THREADS = 64 * BT_WAVES;
-constexpr int BT_GT = 8;            // bin tiles per pass of phase 1 (accumulators held at once)
-constexpr int BETA_MAX_M = 528;     // two LDS images of 528 x 16 float64: 135 168 of 163 840 bytes
-constexpr int BETA_MAX_SLOTS = 4097;
-constexpr double BETA_EPS = 1.1920928955078125e-7;
-enum { BETA_ERR_IS = 0, BETA_ERR_KL = 1, BETA_ERR_FROB = 2, BETA_ERR_GENERIC = 3 };
-
-// x^e: e = k2 / 2 without pow when `general` is 0
-struct PowSpec {
-    double e;
-    int k2;
-    int general;
-};
-
-PowSpec pow_spec(double e) {
-    PowSpec p;
-    p.e = e;
-    const double k = 2.0 * e;
-    p.general = !(k >= -16.0 && k <= 16.0 && k == (double)(long)k);      // the range first: the cast is only defined inside it
-    p.k2 = p.general ? 0 : (int)k;
-    return p;
-}
-
-__device__ __forceinline__ double pow_t(double x, double e) { return pow(x, e); }
-__device__ __forceinline__ float pow_t(float x, float e) { return powf(x, e); }
-
-template <typename T>
-__device__ __forceinline__ T pw(T x, const PowSpec& p) {
-    if (p.general) return pow_t(x, (T)p.e);
-    const int k = p.k2 < 0 ? -p.k2 : p.k2;
-    T r = T(1), b = x;
-    for (int n = k >> 1; n;) {
-        if (n & 1) r *= b;
-        n >>= 1;
-        if (n) b *= b;
-    }
-    if (k & 1) r *= sqrt(x);
-    return p.k2 < 0 ? T(1) / r : r;
-}
-
-template <typename T> struct BetaArgs {
-    const T* Ap1;           // [NP][MP] exemplars as rows, bins contiguous, zero-padded
-    const T* Ap3;           // [NP][MP] the same with the bins of every chunk of 16 permuted: slot 4 g + s = bin 4 s + g
-    const T* Xp;            // [n_tiles][MP][16] frames of a tile, zero-padded
-    T* H;
-    long hs_t, hs_n;        // H(n, t) = H[t * hs_t + n * hs_n]
-    const int4* tiles;      // {utterance, first frame, frames, -}
-    const int* stop;        // [n_utt] 0: running; else the iteration the utterance stopped at
-    double* errf;           // [n_tiles * 16] per-frame share of the divergence
-    int M, MP, N, NP;
-    int clamp_n, clamp_d;   // beta < 2, beta < 1
-    int gamma_one, err_mode;
-    PowSpec p1, p2, pg, pb; // beta - 2, beta - 1, gamma, beta
-    T l1, l2;
-    double beta;
-};
 
 template <typename T> struct Vec4;
 template <> struct Vec4<double> { typedef f64x4 type; };
@@ -210,7 +155,9 @@ __global__ __launch_bounds__(BT_THREADS) void k_beta_sweep(BetaArgs<T> a) {
                 d = d == T(0) ? eps : d;
                 T q = num[r] / d;
                 if (!a.gamma_one) q = pw(q, a.pg);
-                *hp = h * q;
+                T hn = h * q;
+                if (a.flush > T(0) && hn < a.flush) hn = T(0);
+                *hp = hn;
             }
         }
     }
@@ -379,14 +326,6 @@ __global__ void k_beta_fill(T* __restrict__ H, long hs_t, long hs_n, int N, cons
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 
-template <typename T> struct BetaWs {
-    T *Ap1, *Ap3, *Xp;
-    double *errf, *h0, *einit, *eprev, *trace;
-    int4* tiles;
-    int *utt_tile0, *utt_frames, *stop;
-    size_t bytes;
-};
-
 // [Ap1 | Ap3 | Xp | errf | tiles | utt_tile0 | utt_frames | stop | h0 | einit | eprev | trace], each 256-byte aligned; the
 // tile count is bounded by ceil(T / 16) + n_utt whatever the split into utterances (ws == NULL: sizes only)
 template <typename T>
@@ -413,6 +352,8 @@ BetaWs<T> carve_beta(void* ws, int M, int N, int T_, int n_utt) {
     return w;
 }
 
+}  // namespace
+
 size_t beta_workspace_bytes(int M, int N, int T_, int n_utt, int dtype) {
     if (M < 1 || M > BETA_MAX_M || N < 1 || T_ < 0 || n_utt < 1) return 0;
     if (dtype == EVC_F64) return carve_beta<double>(nullptr, M, N, T_, n_utt).bytes + 256;
@@ -420,16 +361,18 @@ size_t beta_workspace_bytes(int M, int N, int T_, int n_utt, int dtype) {
     return 0;
 }
 
-// arguments already validated by evc_beta_solve; returns 0, -2 or a hipError_t
 template <typename T>
-int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
-               int n_utt, const evc_beta_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* err_out,
+int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets, int n_utt,
+               int layout, double beta, double l1, double l2, double flush, int n_slots, void* ws, size_t ws_bytes,
                hipStream_t s) {
-    const BetaWs<T> w = carve_beta<T>(ws, M, N, T_, n_utt);
+    c.w = carve_beta<T>(ws, M, N, T_, n_utt);
+    const BetaWs<T>& w = c.w;
     if (w.bytes > ws_bytes) return -2;
-    const bool fm = o.layout == EVC_FRAME_MAJOR;
+    const bool fm = layout == EVC_FRAME_MAJOR;
     const int MP = round_up(M, 16), NP = round_up(N, 16);
-    const int n_slots = 1 + (o.check_every > 0 ? o.iters / o.check_every : 0);
+    c.n_utt = n_utt;
+    c.n_slots = n_slots;
+    c.fm = fm ? 1 : 0;
 
     // the tile table (host, staged by hipMemcpyAsync from pageable memory at enqueue time)
     int n_tiles = 0;
@@ -437,6 +380,7 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
         const int tu = utt_offsets ? utt_offsets[u + 1] - utt_offsets[u] : T_;
         n_tiles += (tu + BT_F - 1) / BT_F;
     }
+    c.n_tiles = n_tiles;
     {
         int4* h_tiles = static_cast<int4*>(malloc(sizeof(int4) * (n_tiles > 0 ? n_tiles : 1) + sizeof(int) * (2 * n_utt + 1)));
         if (!h_tiles) return (int)hipErrorOutOfMemory;
@@ -462,41 +406,24 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
                        n_slots);
     BETA_TRY(hipGetLastError());
 
-    BetaArgs<T> a;
+    BetaArgs<T>& a = c.a;
     a.Ap1 = w.Ap1; a.Ap3 = w.Ap3; a.Xp = w.Xp; a.H = H;
     a.hs_t = fm ? ldh : 1; a.hs_n = fm ? 1 : ldh;
     a.tiles = w.tiles; a.stop = w.stop; a.errf = w.errf;
     a.M = M; a.MP = MP; a.N = N; a.NP = NP;
-    const double beta = o.beta;
     a.beta = beta;
     a.clamp_n = beta - 2.0 < 0 ? 1 : 0;
     a.clamp_d = beta - 1.0 < 0 ? 1 : 0;
-    const double gamma = beta < 1.0 ? 1.0 / (2.0 - beta) : beta > 2.0 ? 1.0 / (beta - 1.0) : 1.0;
+    const double gamma = beta_gamma(beta);
     a.gamma_one = gamma == 1.0 ? 1 : 0;
     a.p1 = pow_spec(beta - 2.0); a.p2 = pow_spec(beta - 1.0); a.pg = pow_spec(gamma); a.pb = pow_spec(beta);
     a.err_mode = beta == 0.0 ? BETA_ERR_IS : beta == 1.0 ? BETA_ERR_KL : beta == 2.0 ? BETA_ERR_FROB : BETA_ERR_GENERIC;
-    a.l1 = (T)o.l1; a.l2 = (T)o.l2;
-
-    const size_t lds_sweep = (size_t)2 * MP * BT_F * sizeof(T);
-    const size_t lds_err = (size_t)MP * BT_F * sizeof(T) + 3 * 256 * sizeof(double);
-    const bool checks = o.check_every > 0;
+    a.l1 = (T)l1; a.l2 = (T)l2;
+    a.flush = (T)flush;
     if (n_tiles > 0) {
-        hipLaunchKernelGGL(k_beta_pack_dict<T>, dim3(blocks_of((long)NP * MP)), dim3(256), 0, s, A, lda, fm ? 1 : 0, M, N, NP,
-                           MP, w.Ap1, w.Ap3);
-        BETA_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_beta_pack_x<T>, dim3(blocks_of((long)n_tiles * MP * BT_F)), dim3(256), 0, s, X, ldx, fm ? 1 : 0, M,
                            MP, w.tiles, n_tiles, w.Xp);
         BETA_TRY(hipGetLastError());
-        if (o.init_mode != EVC_INIT_GIVEN) {
-            const bool sk = o.init_mode == EVC_INIT_SKLEARN;
-            if (sk) {
-                hipLaunchKernelGGL(k_beta_h0<T>, dim3(n_utt), dim3(256), 0, s, w.Xp, w.utt_tile0, w.utt_frames, M, MP, N, w.h0);
-                BETA_TRY(hipGetLastError());
-            }
-            hipLaunchKernelGGL(k_beta_fill<T>, dim3(blocks_of((long)n_tiles * BT_F * N)), dim3(256), 0, s, H, a.hs_t, a.hs_n, N,
-                               w.tiles, n_tiles, sk ? w.h0 : nullptr, o.init_value);
-            BETA_TRY(hipGetLastError());
-        }
         // the attribute is per function and process-wide: always the limit of BETA_MAX_M, so that concurrent calls at
         // different M never shrink it under one another
         BETA_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_sweep<T>),
@@ -505,26 +432,78 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
                                      hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)(BETA_MAX_M * BT_F * sizeof(T) + 3 * 256 * sizeof(double))));
     }
-    auto check = [&](int c) -> int {
-        hipLaunchKernelGGL(k_beta_err<T>, dim3(n_tiles), dim3(BT_THREADS), lds_err, s, a);
+    return 0;
+}
+
+template <typename T> int beta_pack_dict(const BetaCtx<T>& c, const T* A, int lda, hipStream_t s) {
+    if (c.n_tiles == 0) return 0;
+    const BetaArgs<T>& a = c.a;
+    hipLaunchKernelGGL(k_beta_pack_dict<T>, dim3(blocks_of((long)a.NP * a.MP)), dim3(256), 0, s, A, lda, c.fm,
+                       a.M, a.N, a.NP, a.MP, c.w.Ap1, c.w.Ap3);
+    BETA_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T> int beta_sweep(const BetaCtx<T>& c, hipStream_t s) {
+    if (c.n_tiles == 0) return 0;
+    hipLaunchKernelGGL(k_beta_sweep<T>, dim3(c.n_tiles), dim3(BT_THREADS), (size_t)2 * c.a.MP * BT_F * sizeof(T), s, c.a);
+    BETA_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, double tol, hipStream_t s) {
+    if (c.n_tiles == 0) return 0;
+    const size_t lds_err = (size_t)c.a.MP * BT_F * sizeof(T) + 3 * 256 * sizeof(double);
+    hipLaunchKernelGGL(k_beta_err<T>, dim3(c.n_tiles), dim3(BT_THREADS), lds_err, s, c.a);
+    BETA_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_beta_check, dim3(c.n_utt), dim3(256), 0, s, c.w.errf, c.w.utt_tile0, c.w.stop, c.w.einit, c.w.eprev,
+                       c.w.trace, c.n_slots, chk, check_every, stop_rule, tol);
+    BETA_TRY(hipGetLastError());
+    return 0;
+}
+
+#define BETA_INSTANTIATE(T)                                                                                              \
+    template int beta_begin<T>(BetaCtx<T>&, const T*, int, T*, int, int, int, int, const int*, int, int, double, double, \
+                               double, double, int, void*, size_t, hipStream_t);                                        \
+    template int beta_pack_dict<T>(const BetaCtx<T>&, const T*, int, hipStream_t);                                       \
+    template int beta_sweep<T>(const BetaCtx<T>&, hipStream_t);                                                          \
+    template int beta_check<T>(const BetaCtx<T>&, int, int, int, double, hipStream_t);
+BETA_INSTANTIATE(double)
+BETA_INSTANTIATE(float)
+
+namespace {
+
+// arguments already validated by evc_beta_solve; returns 0, -2 or a hipError_t
+template <typename T>
+int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
+               int n_utt, const evc_beta_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* err_out,
+               hipStream_t s) {
+    const int n_slots = 1 + (o.check_every > 0 ? o.iters / o.check_every : 0);
+    BetaCtx<T> c;
+    int st = beta_begin<T>(c, X, ldx, H, ldh, M, N, T_, utt_offsets, n_utt, o.layout, o.beta, o.l1, o.l2, 0.0, n_slots, ws,
+                           ws_bytes, s);
+    if (st != 0) return st;
+    if ((st = beta_pack_dict<T>(c, A, lda, s)) != 0) return st;
+    const BetaWs<T>& w = c.w;
+    const int n_tiles = c.n_tiles;
+    if (n_tiles > 0 && o.init_mode != EVC_INIT_GIVEN) {
+        const bool sk = o.init_mode == EVC_INIT_SKLEARN;
+        if (sk) {
+            hipLaunchKernelGGL(k_beta_h0<T>, dim3(n_utt), dim3(256), 0, s, w.Xp, w.utt_tile0, w.utt_frames, M, c.a.MP, N, w.h0);
+            BETA_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_beta_fill<T>, dim3(blocks_of((long)n_tiles * BT_F * N)), dim3(256), 0, s, H, c.a.hs_t, c.a.hs_n, N,
+                           w.tiles, n_tiles, sk ? w.h0 : nullptr, o.init_value);
         BETA_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_beta_check, dim3(n_utt), dim3(256), 0, s, w.errf, w.utt_tile0, w.stop, w.einit, w.eprev, w.trace,
-                           n_slots, c, o.check_every, o.stop_rule, o.tol);
-        BETA_TRY(hipGetLastError());
-        return 0;
-    };
-    if (n_tiles > 0 && checks) {
-        const int st = check(0);
-        if (st != 0) return st;
     }
+    const bool checks = o.check_every > 0;
+    if (checks && (st = beta_check<T>(c, 0, o.check_every, o.stop_rule, o.tol, s)) != 0) return st;
     if (o.ev_loop_start) BETA_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
     for (int it = 1; n_tiles > 0 && it <= o.iters; ++it) {
-        hipLaunchKernelGGL(k_beta_sweep<T>, dim3(n_tiles), dim3(BT_THREADS), lds_sweep, s, a);
-        BETA_TRY(hipGetLastError());
-        if (checks && it % o.check_every == 0) {
-            const int st = check(it / o.check_every);
-            if (st != 0) return st;
-        }
+        if ((st = beta_sweep<T>(c, s)) != 0) return st;
+        if (checks && it % o.check_every == 0 && (st = beta_check<T>(c, it / o.check_every, o.check_every, o.stop_rule, o.tol, s)) != 0)
+            return st;
     }
     if (o.ev_loop_stop) BETA_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
     if (n_iter_out || err_out) {

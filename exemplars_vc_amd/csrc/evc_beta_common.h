@@ -1,0 +1,103 @@
+// Declarations shared by evc_beta.hip (evc_beta_solve) and evc_beta_learn.hip (evc_beta_learn): the tile geometry, the
+// power evaluation and the host steps of the activation half.
+#pragma once
+#include "evc_internal.h"
+
+namespace evc {
+
+constexpr int BT_F = 16;            // frames per tile
+constexpr int BT_WAVES = 4;
+constexpr int BT_THREADS = 64 * BT_WAVES;
+constexpr int BT_GT = 8;            // bin tiles per pass of phase 1 (accumulators held at once)
+constexpr int BETA_MAX_M = 528;     // two LDS images of 528 x 16 float64: 135 168 of 163 840 bytes
+constexpr int BETA_MAX_SLOTS = 4097;
+constexpr double BETA_EPS = 1.1920928955078125e-7;
+enum { BETA_ERR_IS = 0, BETA_ERR_KL = 1, BETA_ERR_FROB = 2, BETA_ERR_GENERIC = 3 };
+
+// x^e: e = k2 / 2 without pow when `general` is 0
+struct PowSpec {
+    double e;
+    int k2;
+    int general;
+};
+
+inline PowSpec pow_spec(double e) {
+    PowSpec p;
+    p.e = e;
+    const double k = 2.0 * e;
+    p.general = !(k >= -16.0 && k <= 16.0 && k == (double)(long)k);      // the range first: the cast is only defined inside it
+    p.k2 = p.general ? 0 : (int)k;
+    return p;
+}
+
+__device__ __forceinline__ double pow_t(double x, double e) { return pow(x, e); }
+__device__ __forceinline__ float pow_t(float x, float e) { return powf(x, e); }
+
+template <typename T>
+__device__ __forceinline__ T pw(T x, const PowSpec& p) {
+    if (p.general) return pow_t(x, (T)p.e);
+    const int k = p.k2 < 0 ? -p.k2 : p.k2;
+    T r = T(1), b = x;
+    for (int n = k >> 1; n;) {
+        if (n & 1) r *= b;
+        n >>= 1;
+        if (n) b *= b;
+    }
+    if (k & 1) r *= sqrt(x);
+    return p.k2 < 0 ? T(1) / r : r;
+}
+
+template <typename T> struct BetaArgs {
+    const T* Ap1;           // [NP][MP] exemplars as rows, bins contiguous, zero-padded
+    const T* Ap3;           // [NP][MP] the same with the bins of every chunk of 16 permuted: slot 4 g + s = bin 4 s + g
+    const T* Xp;            // [n_tiles][MP][16] frames of a tile, zero-padded
+    T* H;
+    long hs_t, hs_n;        // H(n, t) = H[t * hs_t + n * hs_n]
+    const int4* tiles;      // {utterance, first frame, frames, -}
+    const int* stop;        // [n_utt] 0: running; else the iteration the utterance stopped at
+    double* errf;           // [n_tiles * 16] per-frame share of the divergence
+    int M, MP, N, NP;
+    int clamp_n, clamp_d;   // beta < 2, beta < 1
+    int gamma_one, err_mode;
+    PowSpec p1, p2, pg, pb; // beta - 2, beta - 1, gamma, beta
+    T l1, l2;
+    T flush;                // > 0: an updated activation below it is stored as 0 (evc_beta_learn, beta < 1); 0: off
+    double beta;
+};
+
+
+template <typename T> struct BetaWs {
+    T *Ap1, *Ap3, *Xp;
+    double *errf, *h0, *einit, *eprev, *trace;
+    int4* tiles;
+    int *utt_tile0, *utt_frames, *stop;
+    size_t bytes;
+};
+
+// one call's activation half: the kernel arguments, the carved workspace and the tile count
+template <typename T> struct BetaCtx {
+    BetaArgs<T> a;
+    BetaWs<T> w;
+    int n_tiles, n_utt, n_slots, fm;
+};
+
+// gamma of the multiplicative update (sklearn _nmf.py:780-785)
+inline double beta_gamma(double beta) { return beta < 1.0 ? 1.0 / (2.0 - beta) : beta > 2.0 ? 1.0 / (beta - 1.0) : 1.0; }
+
+// ----- evc_beta.hip: the host steps of evc_beta_solve, in the order it takes them -----
+size_t beta_workspace_bytes(int M, int N, int T_, int n_utt, int dtype);
+// carves the workspace, stages the tile table, clears the stop state and the trace, packs X and fills the kernel
+// arguments; returns 0, -2 or a hipError_t
+template <typename T>
+int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets, int n_utt,
+               int layout, double beta, double l1, double l2, double flush, int n_slots, void* ws, size_t ws_bytes,
+               hipStream_t s);
+// the two packed images of the dictionary the sweeps stream (A addressed as in evc_beta_solve)
+template <typename T> int beta_pack_dict(const BetaCtx<T>& c, const T* A, int lda, hipStream_t s);
+// one multiplicative update of every running utterance's activations, in place
+template <typename T> int beta_sweep(const BetaCtx<T>& c, hipStream_t s);
+// check number `chk` (0: the start): every utterance's error into its trace slot, then the stop rule on the device
+template <typename T>
+int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, double tol, hipStream_t s);
+
+}  // namespace evc

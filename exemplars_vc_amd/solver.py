@@ -624,6 +624,89 @@ def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every
     return res
 
 
+_BETA_ROUTES = {None: 0, "fused": 1, "unfused": 2}
+
+
+def learn_dictionary_beta(X, W0, H0, *, beta, layout, iters, check_every=10, tol=0.0, l1_h=0.0, l2_h=0.0, l1_w=0.0,
+                          l2_w=0.0, dtype=None, device=None, info=False, out_w=None, out_h=None, loop_events=None,
+                          splits=0, route=None):
+    """scikit-learn's multiplicative updates of BOTH factors under any beta-divergence, X ~ W H (solver='mu',
+    update_H=True, beta_loss=beta: 0 is Itakura-Saito, any finite float goes), on the GPU (evc_beta_learn).  W is
+    addressed like the dictionary A of solve_activations, H like its activations, both start at W0 / H0.  Per iteration
+    H by one update of solve_activations_beta's kernel, then W; the error every `check_every` iterations and the stop when
+    (err_prev - err) / err_at_start < tol.  beta = 1 and beta = 2 run the same generic statement (learn_dictionary serves
+    them with kernels of their own).  l1_h / l2_h are sklearn's scaled l1_reg_W / l2_reg_W (activations), l1_w / l2_w its
+    l1_reg_H / l2_reg_H (dictionary).  At most 528 bins.
+
+    Returns (W, H) as learn_dictionary does; with info=True also dict(n_iter=int, err=[1 + iters // check_every] errors,
+    splits=frame ranges of the dictionary half's sums, route="fused" | "unfused": the kernels that formed those sums).
+    out_w / out_h, loop_events, splits: as learn_dictionary's.  route: tests and tuning, "fused" or "unfused" instead of
+    the library's choice.  No CPU fallback: without a HIP device this raises RuntimeError."""
+    lay = _LAYOUTS[layout]
+    beta = float(beta)
+    if not np.isfinite(beta):
+        raise ValueError(f"beta must be finite, got {beta!r}")
+    if route not in _BETA_ROUTES:
+        raise ValueError(f"route must be None, 'fused' or 'unfused', got {route!r}")
+    xshape = tuple(getattr(X, "shape", ()))
+    if len(xshape) == 2 and xshape[0 if lay == _lib.BIN_MAJOR else 1] > _lib.BETA_MAX_M:     # what the ABI answers with -3
+        raise ValueError(f"unsupported beta-divergence shape: M = {xshape[0 if lay == _lib.BIN_MAJOR else 1]} bins, the "
+                         f"kernel holds at most {_lib.BETA_MAX_M}")
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    tdtype, dcode = _pick_dtype(dtype, X, W0 if W0 is not None else out_w)
+    X_d, x_np = _to_dev(X, tdtype, device)
+    M, T = X_d.shape if lay == _lib.BIN_MAJOR else X_d.shape[::-1]
+
+    def start(a0, out, what):
+        if out is not None:
+            if a0 is not None:
+                out.copy_(_to_dev(a0, tdtype, device)[0])
+            if out.dtype != tdtype or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
+                raise ValueError(f"`out_{what}` must be a device matrix of the call's dtype with unit inner stride")
+            return out
+        a_d, _ = _to_dev(a0, tdtype, device)
+        if isinstance(a0, torch.Tensor) and a_d.data_ptr() == a0.data_ptr():
+            a_d = a_d.clone()       # never clobber the caller's start
+        return a_d
+
+    W_d, H_d = start(W0, out_w, "w"), start(H0, out_h, "h")
+    M2, R = W_d.shape if lay == _lib.BIN_MAJOR else W_d.shape[::-1]
+    R2, T2 = H_d.shape if lay == _lib.BIN_MAJOR else H_d.shape[::-1]
+    if M2 != M or R2 != R or T2 != T:
+        raise ValueError(f"X {tuple(X_d.shape)}, W {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
+    opts = _lib.BetaLearnOpts()
+    opts.struct_bytes = C.sizeof(_lib.BetaLearnOpts)
+    opts.dtype, opts.layout, opts.iters, opts.check_every = dcode, lay, int(iters), int(check_every)
+    opts.reserved = ((int(splits) & 0xff) << 8) | (_BETA_ROUTES[route] << 16)
+    opts.beta, opts.tol = beta, float(tol)
+    opts.l1_h, opts.l2_h, opts.l1_w, opts.l2_w = float(l1_h), float(l2_h), float(l1_w), float(l2_w)
+    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
+        opts.ev_loop_start = int(loop_events[0].cuda_event)
+        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    ws_bytes = int(L.evc_beta_learn_workspace_bytes(M, R, T, dcode))
+    if ws_bytes == 0:
+        raise ValueError(f"unsupported beta-divergence learning shape M={M}, R={R}, T={T} (M <= {_lib.BETA_MAX_M}, R <= 4096)")
+    n_slots = 1 + (int(iters) // int(check_every) if check_every > 0 else 0)
+    n_iter = C.c_int(0)
+    err = np.full(n_slots, np.nan) if info else None
+    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_beta_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
+                              C.byref(opts), ws.data_ptr(), ws.numel(),
+                              C.byref(n_iter) if (info or tol > 0) else None,
+                              err.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
+    _lib.check(st, "evc_beta_learn")
+    to_np = x_np and out_w is None and out_h is None
+    res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
+    if info:
+        res += ({"n_iter": int(n_iter.value), "err": err,
+                 "splits": int(splits) if splits else int(L.evc_beta_learn_splits(M, R, T)),
+                 "route": route or ("fused", "unfused")[int(L.evc_beta_learn_route(M, R, T)) - 1]},)
+    return res
+
+
 _CDL_UPDATES = {"both": _lib.CDL_BOTH, "dict": _lib.CDL_DICT_ONLY}
 
 
@@ -708,7 +791,7 @@ def learn_dictionary_cd(X, W0, H0, *, layout, max_iter=200, tol=1e-4, l1_h=0.0, 
 
 
 def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepared=False, dtype=None, device=None,
-                       loss="frobenius", solver="mu"):
+                       loss="frobenius", solver="mu", beta=None):
     """A compact parallel dictionary: the aligned source and target exemplars are stacked, D = [A; B] ((Ma + Mb) x N),
     and factored jointly, D ~ [Wa; Wb] G, with R << N components by learn_dictionary (scikit-learn surface, the error
     every 10 iterations); (Wa, Wb) then stand in for (A, B) in solve_activations / convert at R / N of the cost.
@@ -718,7 +801,12 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     prepared=True: (PreparedDictionary of (Wa, Wb), G, info) instead, ready for convert().  loss: as learn_dictionary's
     (the prepared dictionary itself is the plain one: pass the loss to convert / prepare_dictionary to solve under it).
     solver="cd": the same stacked compaction by learn_dictionary_cd (scikit-learn's default solver; Frobenius only, at most
-    1024 stacked bins and components; `iters` is its max_iter and `tol` its violation ratio; info as learn_dictionary_cd's)."""
+    1024 stacked bins and components; `iters` is its max_iter and `tol` its violation ratio; info as learn_dictionary_cd's).
+    beta: when given, the compaction minimises that beta-divergence by learn_dictionary_beta from the same start (0 is
+    Itakura-Saito, the usual loss for power spectra; at most 528 stacked bins; info as learn_dictionary_beta's); `loss`
+    must then be left at its default and solver at "mu"."""
+    if beta is not None and (loss != "frobenius" or solver != "mu"):
+        raise ValueError("beta names the loss itself: leave `loss` and `solver` at their defaults")
     if loss not in _LOSSES:
         raise ValueError(f"loss must be one of {sorted(_LOSSES)}, got {loss!r}")
     if solver not in ("mu", "cd"):
@@ -741,7 +829,10 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     pick = torch.div(torch.arange(R, device=device) * N, R, rounding_mode="floor")
     W0 = (D[:, pick] if bm else D[pick, :]).clamp_min(1e-6).contiguous()
     G0 = torch.full((R, N) if bm else (N, R), float(torch.sqrt(D.mean() / R)), dtype=tdtype, device=device)
-    if solver == "cd":
+    if beta is not None:
+        W, G, info = learn_dictionary_beta(D, None, None, beta=beta, layout=layout, iters=iters, tol=tol, check_every=10,
+                                           dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0)
+    elif solver == "cd":
         W, G, info = learn_dictionary_cd(D, None, None, layout=layout, max_iter=iters, tol=tol, dtype=tdtype, device=device,
                                          info=True, out_w=W0, out_h=G0)
     else:

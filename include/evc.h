@@ -38,6 +38,10 @@
  *                   for the losses evc_nmf_solve does not serve: beta_loss = 'itakura-saito' or any float (sklearn
  *                   _multiplicative_update_w, _nmf.py:556-631, and _beta_divergence, :85-189, with update_H=False);
  *                   evc_beta_workspace_bytes sizes it
+ *   evc_beta_learn  replaces the multiplicative-update loop that also learns the dictionary under the losses evc_nmf_learn
+ *                   does not serve: sklearn _fit_multiplicative_update with update_H=True and beta_loss = 'itakura-saito'
+ *                   or any float (_nmf.py:526-893); evc_beta_learn_workspace_bytes, evc_beta_learn_splits and
+ *                   evc_beta_learn_route size and describe it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -81,6 +85,11 @@
  *     (8) evc_beta_solve: n_iter_out / err_out non-NULL (the call returns after copying them back); otherwise the call is
  *         a pure enqueue: the per-utterance stop state lives on the device.  None of its kernels exchanges data between
  *         workgroups inside a launch, uses float atomics or assumes residency: concurrent calls on several streams are safe.
+ *     (9) evc_beta_learn: with check_every = 0 and NULL n_iter_out / err_out the call is a pure enqueue.  Otherwise the
+ *         host reads one double (the error) at each check that is evaluated and decides the stop there, as in case (5);
+ *         checks are evaluated when err_out is non-NULL or tol > 0.  None of its kernels exchanges data between workgroups
+ *         inside a launch, uses float atomics or assumes residency: concurrent calls on several streams are safe, and the
+ *         same call gives the same bits every time.
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
  *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets, sample_offsets) are consumed before the call returns: they are
@@ -660,6 +669,60 @@ size_t evc_beta_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
 int evc_beta_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
                    const int* utt_offsets, int n_utt, const evc_beta_opts* opts, void* workspace, size_t workspace_bytes,
                    int* n_iter_out, double* err_out, evc_stream_t stream);
+
+/* Multiplicative updates of BOTH factors under any beta-divergence, X ~ W H: scikit-learn's
+ * non_negative_factorization(init='custom', update_H=True, solver='mu', beta_loss=beta) for beta_loss = 'itakura-saito'
+ * (beta = 0) or any float (_fit_multiplicative_update, _nmf.py:731-893).  X is M x T, W is M x R, H is R x T, all addressed
+ * as in evc_nmf_learn (sklearn's W is H^T here, its H is W^T); W and H hold the start on entry and are updated in place.
+ * With EPS = 1.1920929e-7 (2^-23) and E64 = 2.220446e-16 (2^-52), both in both element types, per iteration:
+ *   activations  one iteration of evc_beta_solve's statement on the current W with l1_h and l2_h (the same kernel; its
+ *                packed dictionary images are rebuilt from W every iteration); then, if beta < 1, H[H < E64] = 0.  With
+ *                iters = 1 and beta >= 1 the activations are bitwise those of evc_beta_solve(iters = 1, EVC_INIT_GIVEN);
+ *   dictionary   with the new H:  V = W H;  Vn = V with values below EPS raised to EPS if beta < 2;  Vd = the same if
+ *                beta < 1;  Q1 = X * Vn^(beta-2);  Q2 = Vd^(beta-1);  Num = Q1 H^T;  Den = Q2 H^T + l1_w + l2_w W,
+ *                Den == 0 -> EPS;  W <- W * (Num / Den)^gamma;  then, if beta <= 1, W[W < E64] = 0
+ *                (gamma and the evaluation of the powers as in evc_beta_solve);
+ *   error        evc_beta_solve's formulas with one utterance, over the whole matrix, at the start and after every
+ *                `check_every` iterations; stop when (err_prev - err) / err_at_start < tol (tol = 0 never stops).
+ * beta = 1 and beta = 2 are accepted and run this generic statement: they agree with evc_nmf_learn to rounding, not bitwise
+ * (at beta = 1 the two flushes above are scikit-learn's, which evc_nmf_learn omits).
+ * Num and Den are sums over the frames, taken in evc_beta_learn_splits(M, R, T) contiguous frame ranges whose partial sums
+ * are added in ascending order: the count depends on the sizes only.  Two routes form them (evc_beta_learn_route): a fused
+ * kernel for small R that forms V, Q1 and Q2 in registers and never writes them (k_beta_dict_grad), and for any R the
+ * generic contraction for V, an element-wise kernel for Q1 and Q2 and evc_nmf_learn's split-T contraction.  float32 inputs
+ * are solved in float32; the error is summed in float64 in a fixed order.
+ *   M : 1 .. 528 (k_beta_sweep's limit; larger: -3 - stacked WORLD spectra at 1026 bins are not served), R : 1 .. 4096
+ *       (larger: -3);  T >= 1;  iters = 0 returns the start, and its error if asked for
+ *   beta : any finite value (NaN, infinity: -1);  tol and the four penalties >= 0 (negative or NaN: -1)
+ *   l1_h, l2_h, l1_w, l2_w : already scaled, as in evc_cd_learn_opts
+ *   n_iter_out : host int or NULL: iterations carried out
+ *   err_out    : host, 1 + iters / check_every doubles or NULL, laid out like evc_nmf_learn's; at most 4097 slots (more: -1)
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: case (9) of the list at the top. */
+typedef struct evc_beta_learn_opts {
+    int struct_bytes;  /* sizeof(evc_beta_learn_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int iters;         /* >= 0 */
+    int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
+    int reserved;      /* 0; tests and tuning: bits 8..15 that many frame ranges (1 .. 64) instead of evc_beta_learn_splits(),
+                          bits 16..17 the dictionary route, 1 = fused (R > 256, which it does not hold: -3), 2 = unfused;
+                          anything else: status -1 */
+    double beta;       /* the divergence: 0 Itakura-Saito, 1 Kullback-Leibler, 2 Frobenius, or any finite value */
+    double tol;        /* >= 0 */
+    double l1_h, l2_h; /* >= 0; activations: sklearn's l1_reg_W, l2_reg_W (already scaled by the number of bins) */
+    double l1_w, l2_w; /* >= 0; dictionary:  sklearn's l1_reg_H, l2_reg_H (already scaled by the number of frames) */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_beta_learn_opts;
+/* bytes of workspace evc_beta_learn needs (0: invalid arguments, M > 528 among them); room for 64 frame ranges is included */
+size_t evc_beta_learn_workspace_bytes(int M, int R, int T, int dtype);
+/* frame ranges the dictionary half's sums over the frames are split into (0: invalid arguments) */
+int evc_beta_learn_splits(int M, int R, int T);
+/* the dictionary route a call with reserved = 0 takes: 1 = fused, 2 = unfused (0: invalid arguments); sizes only */
+int evc_beta_learn_route(int M, int R, int T);
+int evc_beta_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
+                   const evc_beta_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
+                   evc_stream_t stream);
 
 #ifdef __cplusplus
 }
