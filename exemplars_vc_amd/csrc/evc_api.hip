@@ -1,5 +1,6 @@
 // C ABI of libevc_hip.so (see include/evc.h): argument checking, workspace carving and the
 // launch sequence of one activation solve.  No allocation, no global state, no exceptions.
+// (The entries that learn the dictionary too sit with their kernels: evc_learn.hip, evc_cd.hip, evc_beta_learn.hip.)
 #include "evc_internal.h"
 
 #include <math.h>
@@ -10,43 +11,6 @@
 using namespace evc;
 
 namespace {
-
-enum { ST_OK = 0, ST_BADARG = -1, ST_WORKSPACE = -2, ST_UNSUPPORTED = -3, ST_COOP_TIMEOUT = -4 };
-
-struct Carver {
-    char* base;
-    size_t off;
-    template <typename U> U* take(size_t count) {
-        off = (off + 255) & ~size_t(255);
-        U* p = base ? reinterpret_cast<U*>(base + off) : nullptr;
-        off += count * sizeof(U);
-        return p;
-    }
-};
-
-struct Dims {
-    int M, N, T_, n_utt, Mb;
-    int Mk, Mj, Np, Tp;
-};
-
-Dims make_dims(int esize, int M, int N, int T_, int n_utt, int Mb = 0) {
-    Dims d;
-    d.M = M; d.N = N; d.T_ = T_; d.n_utt = n_utt; d.Mb = Mb;
-    d.Mk = round_up(M, 16);
-    d.Mj = round_up(M, 64);
-    d.Np = round_up(N, 128);
-    // frames are padded to the contraction kernels' frame tile: 64 where k_gemm2 is in charge (float32) and for short
-    // float64 batches (<= 2048 frames: k_gemm_nt then runs 64-row blocks anyway, and one 688-frame utterance is 704
-    // rows instead of 768), 128 otherwise (diagnostic builds: see use_gemm2 in evc_gemm.hip)
-#if defined(EVC_DIAG_GEMM_V1)
-    d.Tp = round_up(T_, 128);
-#elif defined(EVC_DIAG_GEMM2_F64)
-    d.Tp = round_up(T_, 64);
-#else
-    d.Tp = round_up(T_, (esize == 4 || T_ <= 2048) ? 64 : 128);
-#endif
-    return d;
-}
 
 constexpr int DICT_MAGIC = 0x45564344;      // "EVCD"
 
@@ -135,8 +99,6 @@ template <typename T> struct Workspace {
     size_t bytes, bytes_min;
 };
 
-int n_slots_for(int iters, int check_every) { return 1 + (check_every > 0 ? iters / check_every : 0); }
-
 UttState take_utt(Carver& c, const Dims& d, int n_slots) {
     UttState u;
     u.frame_utt = c.take<int>(d.Tp);
@@ -219,17 +181,6 @@ Workspace<T> carve(void* base, const Dims& d, int algo, int n_slots, bool fused,
     }
     return w;
 }
-
-// (expr: a hipError_t, or a status of this file - both are 0 on success)
-#define HIP_TRY(expr)                              \
-    do {                                           \
-        int e__ = (int)(expr);                     \
-        if (e__) return e__;                       \
-    } while (0)
-
-// The worst-case slot count is bounded by iters+1; evc_workspace_bytes has no iters argument,
-// so the trace region is sized for MAX_SLOTS checks and evc_nmf_solve rejects more.
-constexpr int MAX_SLOTS = 4097;
 
 struct SynthArgs {          // optional Y = B H appended to a solve (evc_nmf_convert)
     const void* B; int ldb; void* Y; int ldy; int Mb;
@@ -996,11 +947,6 @@ bool utt_offsets_ok(const int* utt_offsets, int n_utt, int T) {
     return true;
 }
 
-bool bad_ld(int layout, int ld, int rows_fm, int cols_fm) {
-    // FRAME_MAJOR: rows_fm x cols_fm with ld >= cols_fm; BIN_MAJOR: the transpose
-    return layout == EVC_FRAME_MAJOR ? ld < cols_fm : ld < rows_fm;
-}
-
 template <typename T>
 hipError_t synthesize_typed(const void* B_, int ldb, const void* H_, int ldh, void* Y_, int ldy, int Mb, int N, int T_,
                             bool fm, hipStream_t s) {
@@ -1030,121 +976,6 @@ int residual_typed(const void* A, int lda, const void* X, int ldx, const void* H
     HIP_TRY(copy2d<T>((const T*)H, ldh, T_, N, fm ? 0 : 1, w.H0, d.Np, d.Tp, d.Np, 0, s));
     HIP_TRY(gemm_nt<T>(w.H0, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));
     HIP_TRY(frame_err2<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, err2_out, s));
-    return ST_OK;
-}
-
-
-// ---- evc_nmf_learn: both factors updated (evc_learn.hip holds the dictionary update's kernels) ----
-template <typename T> struct LearnWs {
-    T *Xt, *Am, *Ht, *Vt, *part;
-    double *err2, *ring;
-    char* solve_ws;
-    size_t solve_bytes, bytes;
-};
-constexpr int LEARN_RING = 64;
-
-template <typename T> LearnWs<T> carve_learn(void* base, const Dims& d) {
-    LearnWs<T> w;
-    Carver c{static_cast<char*>(base), 0};
-    w.Xt = c.take<T>((size_t)d.Tp * d.Mk);
-    w.Am = c.take<T>((size_t)d.Mj * d.Np);
-    w.Ht = c.take<T>((size_t)d.Tp * d.Np);
-    w.Vt = c.take<T>((size_t)d.Tp * d.Mj);
-    w.part = c.take<T>((size_t)LEARN_MAX_SPLITS * 2 * learn_bin_tiles(d.M) * 16 * d.Np);
-    w.err2 = c.take<double>(d.Tp);
-    w.ring = c.take<double>(LEARN_RING);
-    w.solve_bytes = evc_workspace_bytes(d.M, 0, d.N, d.T_, 1, sizeof(T) == 8 ? EVC_F64 : EVC_F32, EVC_ALGO_AUTO);
-    w.solve_ws = c.take<char>(w.solve_bytes);
-    w.bytes = (c.off + 255) & ~size_t(255);
-    return w;
-}
-
-template <typename T>
-int learn_typed(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, int M, int R, int T_,
-                const evc_learn_opts& o, int S, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
-                hipStream_t s) {
-    const Dims d = make_dims((int)sizeof(T), M, R, T_, 1, 0);
-    const LearnWs<T> w = carve_learn<T>(workspace, d);
-    if (w.bytes > workspace_bytes) return ST_WORKSPACE;
-    const bool fm = o.layout == EVC_FRAME_MAJOR;
-    const T* X = static_cast<const T*>(X_);
-    T* W = static_cast<T*>(W_);
-    T* H = static_cast<T*>(H_);
-    const bool pymf = o.surface == EVC_LEARN_PYMF;
-    const bool kl = o.loss == EVC_LOSS_KL;         // sklearn surface only (evc_nmf_learn rejects it with pymf)
-    const double eps_kl = 1.1920929e-7;
-    const int n_checks = o.check_every > 0 ? o.iters / o.check_every : 0;
-    const bool want_err = o.check_every > 0 && (err_out || o.tol > 0.0);
-    if (err_out) for (int i = 0; i <= n_checks; ++i) err_out[i] = NAN;
-
-    evc_solve_opts so{};                           // the activation step: one update of the existing solve, a pure enqueue
-    so.struct_bytes = (int)sizeof(evc_solve_opts);
-    so.dtype = o.dtype; so.layout = o.layout; so.algo = EVC_ALGO_AUTO; so.iters = 1;
-    so.eps_mode = pymf ? EVC_EPS_ADD : EVC_EPS_ZERO_REPLACE;
-    so.eps = pymf ? 1e-9 : 1.1920929e-7;
-    so.init_mode = EVC_INIT_GIVEN; so.stop_rule = EVC_STOP_NONE; so.reserved = EVC_FLAG_NO_EXCHANGE;
-    so.loss = kl ? EVC_LOSS_KL : EVC_LOSS_FROBENIUS;
-    auto update_h = [&]() -> int {
-        return evc_nmf_solve(W, ldw, X, ldx, H, ldh, M, R, T_, nullptr, 1, &so, w.solve_ws, w.solve_bytes, nullptr, nullptr,
-                             reinterpret_cast<evc_stream_t>(s));
-    };
-    // V = W H on frames-as-rows copies of the current factors (Ht is the dictionary update's right operand too)
-    auto form_v = [&]() -> int {
-        HIP_TRY(copy2d<T>(W, ldw, M, R, fm ? 1 : 0, w.Am, d.Np, d.Mj, d.Np, 0, s));
-        HIP_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, d.Np, d.Tp, d.Np, 0, s));
-        HIP_TRY(gemm_nt<T>(w.Ht, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));
-        return ST_OK;
-    };
-    auto update_w = [&]() -> int {
-        HIP_TRY(form_v());
-        if (kl) {                                  // nothing below reads V again: the quotient takes its place
-            HIP_TRY(dict_quot<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, eps_kl, s));
-            HIP_TRY(dict_grad_kl<T>(w.Vt, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
-        } else {
-            HIP_TRY(dict_grad<T>(w.Xt, d.Mk, w.Vt, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
-        }
-        HIP_TRY(dict_apply<T>(w.part, S, d.Np, W, ldw, fm ? 0 : 1, M, R, o.surface, o.loss, s));
-        return ST_OK;
-    };
-    auto error_now = [&](int slot, double* host) -> int {
-        HIP_TRY(form_v());
-        if (kl) HIP_TRY(frame_err_kl<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, eps_kl, w.err2, s));
-        else HIP_TRY(frame_err2<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, w.err2, s));
-        double* dst = w.ring + slot % LEARN_RING;
-        HIP_TRY(err_total(w.err2, T_, dst, s));
-        HIP_TRY(hipMemcpyAsync(host, dst, sizeof(double), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return ST_OK;
-    };
-
-    HIP_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
-    double err_init = 0.0, err_prev = 0.0, err = 0.0;
-    if (want_err) {
-        HIP_TRY(error_now(0, &err_init));
-        err_prev = err_init;
-        if (err_out) err_out[0] = err_init;
-    }
-    if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
-    int n_iter = 0;
-    for (int it = 1; it <= o.iters; ++it) {
-        if (pymf) {
-            HIP_TRY(update_w());
-            HIP_TRY(update_h());
-        } else {
-            HIP_TRY(update_h());
-            HIP_TRY(update_w());
-        }
-        n_iter = it;
-        if (!want_err || it % o.check_every != 0) continue;
-        const int c = it / o.check_every;
-        HIP_TRY(error_now(c, &err));
-        if (err_out) err_out[c] = err;
-        // (tol = 0 never stops, as in scikit-learn; a NaN error compares false and never stops, as in both references)
-        if (o.tol > 0.0 && (pymf ? (c >= 3 && fabs(err - err_prev) / T_ < o.tol) : ((err_prev - err) / err_init < o.tol))) break;
-        err_prev = err;
-    }
-    if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    if (n_iter_out) *n_iter_out = n_iter;
     return ST_OK;
 }
 
@@ -1595,83 +1426,6 @@ int evc_cd_solve(const void* A, int lda, const void* X, int ldx, void* H, int ld
     return cd_solve<float>(static_cast<const float*>(A), lda, static_cast<const float*>(X), ldx, static_cast<float*>(H),
                            ldh, M, N, T, utt_offsets, n_utt, o, workspace, workspace_bytes, n_iter_out, violation_out, s,
                            nullptr);
-}
-
-static bool learn_sizes_ok(int M, int R, int T, int dtype) {
-    return M >= 1 && R >= 1 && T >= 1 && M <= LEARN_MAX_M && R <= LEARN_MAX_R && (dtype == EVC_F64 || dtype == EVC_F32);
-}
-
-size_t evc_learn_workspace_bytes(int M, int R, int T, int dtype) {
-    if (!learn_sizes_ok(M, R, T, dtype)) return 0;
-    if (dtype == EVC_F64) return carve_learn<double>(nullptr, make_dims(8, M, R, T, 1, 0)).bytes;
-    return carve_learn<float>(nullptr, make_dims(4, M, R, T, 1, 0)).bytes;
-}
-
-int evc_learn_splits(int M, int R, int T) {
-    return learn_sizes_ok(M, R, T, EVC_F64) ? learn_splits(M, R, T) : 0;
-}
-
-int evc_nmf_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
-                  const evc_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
-                  evc_stream_t stream) {
-    if (!opts || opts->struct_bytes != (int)sizeof(evc_learn_opts)) return ST_BADARG;
-    const evc_learn_opts& o = *opts;
-    if (M < 1 || R < 1 || T < 1 || o.iters < 0 || o.check_every < 0) return ST_BADARG;
-    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return ST_BADARG;
-    if (o.layout != EVC_FRAME_MAJOR && o.layout != EVC_BIN_MAJOR) return ST_BADARG;
-    if (o.surface != EVC_LEARN_SKLEARN && o.surface != EVC_LEARN_PYMF) return ST_BADARG;
-    if (o.loss != EVC_LOSS_FROBENIUS && o.loss != EVC_LOSS_KL) return ST_BADARG;
-    if (!(o.tol >= 0.0)) return ST_BADARG;
-    const int forced = (o.reserved >> 8) & 0xff;
-    if ((o.reserved & ~0xff00) != 0 || forced > LEARN_MAX_SPLITS) return ST_BADARG;
-    if (!X || !W || !H || !workspace) return ST_BADARG;
-    if (bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldw, R, M) || bad_ld(o.layout, ldh, T, R)) return ST_BADARG;
-    if (M > LEARN_MAX_M || R > LEARN_MAX_R) return ST_UNSUPPORTED;
-    if (o.loss == EVC_LOSS_KL && o.surface == EVC_LEARN_PYMF) return ST_UNSUPPORTED;   // pymf has no KL update
-    if (o.check_every > 0 && o.iters / o.check_every + 1 > MAX_SLOTS) return ST_BADARG;
-    if (workspace_bytes < evc_learn_workspace_bytes(M, R, T, o.dtype)) return ST_WORKSPACE;
-    const int S = forced ? forced : learn_splits(M, R, T);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    return (o.dtype == EVC_F64 ? learn_typed<double> : learn_typed<float>)(X, ldx, W, ldw, H, ldh, M, R, T, o, S, workspace,
-                                                                            workspace_bytes, n_iter_out, err_out, s);
-}
-
-static bool cd_learn_sizes_ok(int M, int R, int T, int dtype) {
-    return M >= 1 && R >= 1 && T >= 1 && M <= CD_MAX_M && R <= CD_LEARN_MAX_R && (dtype == EVC_F64 || dtype == EVC_F32);
-}
-
-int evc_cd_learn_splits(int M, int R, int T) {
-    return cd_learn_sizes_ok(M, R, T, EVC_F64) ? learn_splits(M, R, T) : 0;
-}
-
-size_t evc_cd_learn_workspace_bytes(int M, int R, int T, int dtype) {
-    if (!cd_learn_sizes_ok(M, R, T, dtype)) return 0;
-    return cd_learn_workspace_bytes(M, R, T, learn_splits(M, R, T), dtype == EVC_F64 ? 8 : 4);
-}
-
-int evc_cd_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
-                 const evc_cd_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
-                 double* violation_out, evc_stream_t stream) {
-    if (!opts || opts->struct_bytes != (int)sizeof(evc_cd_learn_opts)) return ST_BADARG;
-    const evc_cd_learn_opts& o = *opts;
-    if (M < 1 || R < 1 || T < 1 || o.max_iter < 0) return ST_BADARG;
-    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return ST_BADARG;
-    if (o.layout != EVC_FRAME_MAJOR && o.layout != EVC_BIN_MAJOR) return ST_BADARG;
-    if (o.update != EVC_CDL_BOTH && o.update != EVC_CDL_DICT_ONLY) return ST_BADARG;
-    const int forced = (o.reserved >> 8) & 0xff;
-    if ((o.reserved & ~0xff00) != 0 || forced > LEARN_MAX_SPLITS) return ST_BADARG;
-    if (!(o.tol >= 0.0) || !(o.l1_h >= 0.0) || !(o.l2_h >= 0.0) || !(o.l1_w >= 0.0) || !(o.l2_w >= 0.0)) return ST_BADARG;
-    if (!X || !W || !H || !workspace) return ST_BADARG;
-    if (bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldw, R, M) || bad_ld(o.layout, ldh, T, R)) return ST_BADARG;
-    if (M > CD_MAX_M || R > CD_LEARN_MAX_R) return ST_UNSUPPORTED;
-    const int S = forced ? forced : learn_splits(M, R, T);
-    if (workspace_bytes < cd_learn_workspace_bytes(M, R, T, S, o.dtype == EVC_F64 ? 8 : 4)) return ST_WORKSPACE;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (o.dtype == EVC_F64)
-        return cd_learn<double>(static_cast<const double*>(X), ldx, static_cast<double*>(W), ldw, static_cast<double*>(H),
-                                ldh, M, R, T, o, S, workspace, workspace_bytes, n_iter_out, violation_out, s);
-    return cd_learn<float>(static_cast<const float*>(X), ldx, static_cast<float*>(W), ldw, static_cast<float*>(H), ldh, M, R,
-                           T, o, S, workspace, workspace_bytes, n_iter_out, violation_out, s);
 }
 
 }  // extern "C"

@@ -317,13 +317,6 @@ __global__ void k_beta_fill(T* __restrict__ H, long hs_t, long hs_n, int N, cons
     if (f < tl.z) H[(long)(tl.y + f) * hs_t + (long)n * hs_n] = (T)(h0 ? h0[tl.x] : value);
 }
 
-#define BETA_TRY(expr)                                \
-    do {                                              \
-        hipError_t e_ = (expr);                       \
-        if (e_ != hipSuccess) return (int)e_;         \
-    } while (0)
-
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 
 // [Ap1 | Ap3 | Xp | errf | tiles | utt_tile0 | utt_frames | stop | h0 | einit | eprev | trace], each 256-byte aligned; the
@@ -331,24 +324,22 @@ unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 template <typename T>
 BetaWs<T> carve_beta(void* ws, int M, int N, int T_, int n_utt) {
     BetaWs<T> w;
-    const uintptr_t base = (reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = reinterpret_cast<char*>(base + off); off += align256(bytes); return p; };
+    Carver c = Carver::rounded(ws);
     const size_t MP = (size_t)round_up(M, 16), NP = (size_t)round_up(N, 16);
     const size_t nt = (size_t)(T_ + BT_F - 1) / BT_F + n_utt;
-    w.Ap1 = reinterpret_cast<T*>(take(NP * MP * sizeof(T)));
-    w.Ap3 = reinterpret_cast<T*>(take(NP * MP * sizeof(T)));
-    w.Xp = reinterpret_cast<T*>(take(nt * MP * BT_F * sizeof(T)));
-    w.errf = reinterpret_cast<double*>(take(nt * BT_F * sizeof(double)));
-    w.tiles = reinterpret_cast<int4*>(take(nt * sizeof(int4)));
-    w.utt_tile0 = reinterpret_cast<int*>(take((size_t)(n_utt + 1) * sizeof(int)));
-    w.utt_frames = reinterpret_cast<int*>(take((size_t)n_utt * sizeof(int)));
-    w.stop = reinterpret_cast<int*>(take((size_t)n_utt * sizeof(int)));
-    w.h0 = reinterpret_cast<double*>(take((size_t)n_utt * sizeof(double)));
-    w.einit = reinterpret_cast<double*>(take((size_t)n_utt * sizeof(double)));
-    w.eprev = reinterpret_cast<double*>(take((size_t)n_utt * sizeof(double)));
-    w.trace = reinterpret_cast<double*>(take((size_t)n_utt * BETA_MAX_SLOTS * sizeof(double)));
-    w.bytes = (size_t)(base - reinterpret_cast<uintptr_t>(ws)) + off;
+    w.Ap1 = c.take<T>(NP * MP);
+    w.Ap3 = c.take<T>(NP * MP);
+    w.Xp = c.take<T>(nt * MP * BT_F);
+    w.errf = c.take<double>(nt * BT_F);
+    w.tiles = c.take<int4>(nt);
+    w.utt_tile0 = c.take<int>((size_t)n_utt + 1);
+    w.utt_frames = c.take<int>(n_utt);
+    w.stop = c.take<int>(n_utt);
+    w.h0 = c.take<double>(n_utt);
+    w.einit = c.take<double>(n_utt);
+    w.eprev = c.take<double>(n_utt);
+    w.trace = c.take<double>((size_t)n_utt * BETA_MAX_SLOTS);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -367,7 +358,7 @@ int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, 
                hipStream_t s) {
     c.w = carve_beta<T>(ws, M, N, T_, n_utt);
     const BetaWs<T>& w = c.w;
-    if (w.bytes > ws_bytes) return -2;
+    if (w.bytes > ws_bytes) return ST_WORKSPACE;
     const bool fm = layout == EVC_FRAME_MAJOR;
     const int MP = round_up(M, 16), NP = round_up(N, 16);
     c.n_utt = n_utt;
@@ -400,11 +391,11 @@ int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, 
         if (e == hipSuccess) e = hipMemcpyAsync(w.utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(w.utt_frames, h_fr, sizeof(int) * n_utt, hipMemcpyHostToDevice, s);
         free(h_tiles);      // pageable source: HIP has staged the bytes by the time hipMemcpyAsync returns
-        BETA_TRY(e);
+        HIP_TRY(e);
     }
     hipLaunchKernelGGL(k_beta_state_init, dim3(blocks_of((long)n_utt * n_slots)), dim3(256), 0, s, w.stop, w.trace, n_utt,
                        n_slots);
-    BETA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
 
     BetaArgs<T>& a = c.a;
     a.Ap1 = w.Ap1; a.Ap3 = w.Ap3; a.Xp = w.Xp; a.H = H;
@@ -423,14 +414,14 @@ int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, 
     if (n_tiles > 0) {
         hipLaunchKernelGGL(k_beta_pack_x<T>, dim3(blocks_of((long)n_tiles * MP * BT_F)), dim3(256), 0, s, X, ldx, fm ? 1 : 0, M,
                            MP, w.tiles, n_tiles, w.Xp);
-        BETA_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         // the attribute is per function and process-wide: always the limit of BETA_MAX_M, so that concurrent calls at
         // different M never shrink it under one another
-        BETA_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_sweep<T>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * BETA_MAX_M * BT_F * sizeof(T))));
-        BETA_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_err<T>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)(BETA_MAX_M * BT_F * sizeof(T) + 3 * 256 * sizeof(double))));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_sweep<T>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * BETA_MAX_M * BT_F * sizeof(T))));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_err<T>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(BETA_MAX_M * BT_F * sizeof(T) + 3 * 256 * sizeof(double))));
     }
     return 0;
 }
@@ -440,14 +431,14 @@ template <typename T> int beta_pack_dict(const BetaCtx<T>& c, const T* A, int ld
     const BetaArgs<T>& a = c.a;
     hipLaunchKernelGGL(k_beta_pack_dict<T>, dim3(blocks_of((long)a.NP * a.MP)), dim3(256), 0, s, A, lda, c.fm,
                        a.M, a.N, a.NP, a.MP, c.w.Ap1, c.w.Ap3);
-    BETA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
 template <typename T> int beta_sweep(const BetaCtx<T>& c, hipStream_t s) {
     if (c.n_tiles == 0) return 0;
     hipLaunchKernelGGL(k_beta_sweep<T>, dim3(c.n_tiles), dim3(BT_THREADS), (size_t)2 * c.a.MP * BT_F * sizeof(T), s, c.a);
-    BETA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -456,10 +447,10 @@ int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, dou
     if (c.n_tiles == 0) return 0;
     const size_t lds_err = (size_t)c.a.MP * BT_F * sizeof(T) + 3 * 256 * sizeof(double);
     hipLaunchKernelGGL(k_beta_err<T>, dim3(c.n_tiles), dim3(BT_THREADS), lds_err, s, c.a);
-    BETA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_beta_check, dim3(c.n_utt), dim3(256), 0, s, c.w.errf, c.w.utt_tile0, c.w.stop, c.w.einit, c.w.eprev,
                        c.w.trace, c.n_slots, chk, check_every, stop_rule, tol);
-    BETA_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -491,21 +482,21 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
         const bool sk = o.init_mode == EVC_INIT_SKLEARN;
         if (sk) {
             hipLaunchKernelGGL(k_beta_h0<T>, dim3(n_utt), dim3(256), 0, s, w.Xp, w.utt_tile0, w.utt_frames, M, c.a.MP, N, w.h0);
-            BETA_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(k_beta_fill<T>, dim3(blocks_of((long)n_tiles * BT_F * N)), dim3(256), 0, s, H, c.a.hs_t, c.a.hs_n, N,
                            w.tiles, n_tiles, sk ? w.h0 : nullptr, o.init_value);
-        BETA_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     const bool checks = o.check_every > 0;
     if (checks && (st = beta_check<T>(c, 0, o.check_every, o.stop_rule, o.tol, s)) != 0) return st;
-    if (o.ev_loop_start) BETA_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
+    if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
     for (int it = 1; n_tiles > 0 && it <= o.iters; ++it) {
         if ((st = beta_sweep<T>(c, s)) != 0) return st;
         if (checks && it % o.check_every == 0 && (st = beta_check<T>(c, it / o.check_every, o.check_every, o.stop_rule, o.tol, s)) != 0)
             return st;
     }
-    if (o.ev_loop_stop) BETA_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
+    if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
     if (n_iter_out || err_out) {
         int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
         if (!ni_h) return (int)hipErrorOutOfMemory;
@@ -515,7 +506,7 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         for (int u = 0; e == hipSuccess && n_iter_out && u < n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : o.iters;
         free(ni_h);
-        BETA_TRY(e);
+        HIP_TRY(e);
     }
     return 0;
 }
@@ -542,22 +533,22 @@ int evc_beta_solve(const void* A, int lda, const void* X, int ldx, void* H, int 
                    const int* utt_offsets, int n_utt, const evc_beta_opts* opts, void* workspace, size_t workspace_bytes,
                    int* n_iter_out, double* err_out, evc_stream_t stream) {
     using namespace evc;
-    if (!opts || opts->struct_bytes != (int)sizeof(evc_beta_opts)) return -1;
+    if (!opts || opts->struct_bytes != (int)sizeof(evc_beta_opts)) return ST_BADARG;
     const evc_beta_opts& o = *opts;
-    if (M < 1 || N < 1 || T < 0 || n_utt < 1 || o.iters < 0 || o.check_every < 0 || o.reserved != 0) return -1;
-    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return -1;
+    if (M < 1 || N < 1 || T < 0 || n_utt < 1 || o.iters < 0 || o.check_every < 0 || o.reserved != 0) return ST_BADARG;
+    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return ST_BADARG;
     const bool fm = o.layout == EVC_FRAME_MAJOR;
-    if (!fm && o.layout != EVC_BIN_MAJOR) return -1;
-    if (o.init_mode != EVC_INIT_GIVEN && o.init_mode != EVC_INIT_SKLEARN && o.init_mode != EVC_INIT_CONST) return -1;
-    if (o.stop_rule != EVC_STOP_NONE && o.stop_rule != EVC_STOP_SKLEARN) return -1;
-    if (!(o.beta - o.beta == 0.0)) return -1;                      // NaN or infinite
-    if (!(o.tol >= 0.0) || !(o.l1 >= 0.0) || !(o.l2 >= 0.0) || !(o.init_value - o.init_value == 0.0)) return -1;
-    if (!A || !workspace || (T > 0 && (!X || !H))) return -1;       // no frames: X and H are never touched
-    if ((fm ? lda < M : lda < N) || (fm ? ldx < M : ldx < T) || (fm ? ldh < N : ldh < T)) return -1;
-    if (!beta_offsets_ok(utt_offsets, n_utt, T)) return -1;
-    if (o.check_every > 0 && o.iters / o.check_every + 1 > BETA_MAX_SLOTS) return -1;
-    if (M > BETA_MAX_M) return -3;
-    if (workspace_bytes < beta_workspace_bytes(M, N, T, n_utt, o.dtype)) return -2;
+    if (!fm && o.layout != EVC_BIN_MAJOR) return ST_BADARG;
+    if (o.init_mode != EVC_INIT_GIVEN && o.init_mode != EVC_INIT_SKLEARN && o.init_mode != EVC_INIT_CONST) return ST_BADARG;
+    if (o.stop_rule != EVC_STOP_NONE && o.stop_rule != EVC_STOP_SKLEARN) return ST_BADARG;
+    if (!(o.beta - o.beta == 0.0)) return ST_BADARG;                      // NaN or infinite
+    if (!(o.tol >= 0.0) || !(o.l1 >= 0.0) || !(o.l2 >= 0.0) || !(o.init_value - o.init_value == 0.0)) return ST_BADARG;
+    if (!A || !workspace || (T > 0 && (!X || !H))) return ST_BADARG;       // no frames: X and H are never touched
+    if (bad_ld(o.layout, lda, N, M) || bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldh, T, N)) return ST_BADARG;
+    if (!beta_offsets_ok(utt_offsets, n_utt, T)) return ST_BADARG;
+    if (o.check_every > 0 && o.iters / o.check_every + 1 > BETA_MAX_SLOTS) return ST_BADARG;
+    if (M > BETA_MAX_M) return ST_UNSUPPORTED;
+    if (workspace_bytes < beta_workspace_bytes(M, N, T, n_utt, o.dtype)) return ST_WORKSPACE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (o.dtype == EVC_F64)
         return beta_solve<double>(static_cast<const double*>(A), lda, static_cast<const double*>(X), ldx,

@@ -38,12 +38,6 @@ constexpr int BDG_ROUTE_R = 64;       // the fused route is taken up to this R: 
 constexpr double BETA_E64 = 2.220446049250313e-16;      // 2^-52, numpy's float64 epsilon (in both element types)
 enum { ROUTE_AUTO = 0, ROUTE_FUSED = 1, ROUTE_UNFUSED = 2 };
 
-#define BL_TRY(expr)                          \
-    do {                                      \
-        int e_ = (int)(expr);                 \
-        if (e_ != 0) return e_;               \
-    } while (0)
-
 template <typename T> struct Vec4;
 template <> struct Vec4<double> { typedef f64x4 type; };
 template <> struct Vec4<float> { typedef f32x4 type; };
@@ -221,27 +215,6 @@ template <typename T> size_t bdg_lds_bytes(int RP16) {
     return ((size_t)RP16 * BDG_LD + (size_t)(BDG_WAVES - 1) * 2 * BDG_RB * 4 * 64) * sizeof(T);
 }
 
-struct BlDims {
-    int Mk, Mj, Np, Tp, MTp;
-};
-
-BlDims bl_dims(int esize, int M, int R, int T_) {
-    BlDims d;
-    d.Mk = round_up(M, 16);
-    d.Mj = round_up(M, 64);
-    d.Np = round_up(R, 128);
-    // the frame padding of the generic contraction (make_dims, evc_api.hip)
-#if defined(EVC_DIAG_GEMM_V1)
-    d.Tp = round_up(T_, 128);
-#elif defined(EVC_DIAG_GEMM2_F64)
-    d.Tp = round_up(T_, 64);
-#else
-    d.Tp = round_up(T_, (esize == 4 || T_ <= 2048) ? 64 : 128);
-#endif
-    d.MTp = learn_bin_tiles(M);
-    return d;
-}
-
 template <typename T> struct BlWs {
     T *Xt, *Am, *Ht, *Vt, *Q2t, *part;
     char* beta_ws;
@@ -249,25 +222,18 @@ template <typename T> struct BlWs {
 };
 
 // [Xt | Am | Ht | Vt | Q2t | part | the activation half's workspace], each 256-byte aligned (ws == NULL: sizes only)
-template <typename T> BlWs<T> carve_bl(void* ws, int M, int R, int T_) {
+template <typename T> BlWs<T> carve_bl(void* ws, const Dims& d) {
     BlWs<T> w;
-    const BlDims d = bl_dims((int)sizeof(T), M, R, T_);
-    const uintptr_t base = (reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* p = reinterpret_cast<char*>(base + off);
-        off += (bytes + 255) & ~size_t(255);
-        return p;
-    };
-    w.Xt = reinterpret_cast<T*>(take((size_t)d.Tp * d.Mk * sizeof(T)));
-    w.Am = reinterpret_cast<T*>(take((size_t)d.Mj * d.Np * sizeof(T)));
-    w.Ht = reinterpret_cast<T*>(take((size_t)d.Tp * d.Np * sizeof(T)));
-    w.Vt = reinterpret_cast<T*>(take((size_t)d.Tp * d.Mj * sizeof(T)));
-    w.Q2t = reinterpret_cast<T*>(take((size_t)d.Tp * d.Mj * sizeof(T)));
-    w.part = reinterpret_cast<T*>(take((size_t)LEARN_MAX_SPLITS * 2 * d.MTp * 16 * d.Np * sizeof(T)));
-    w.beta_bytes = beta_workspace_bytes(M, R, T_, 1, sizeof(T) == 8 ? EVC_F64 : EVC_F32);
-    w.beta_ws = take(w.beta_bytes);
-    w.bytes = (size_t)(base - reinterpret_cast<uintptr_t>(ws)) + off;
+    Carver c = Carver::rounded(ws);
+    w.Xt = c.take<T>((size_t)d.Tp * d.Mk);
+    w.Am = c.take<T>((size_t)d.Mj * d.Np);
+    w.Ht = c.take<T>((size_t)d.Tp * d.Np);
+    w.Vt = c.take<T>((size_t)d.Tp * d.Mj);
+    w.Q2t = c.take<T>((size_t)d.Tp * d.Mj);
+    w.part = c.take<T>((size_t)LEARN_MAX_SPLITS * 2 * learn_bin_tiles(d.M) * 16 * d.Np);
+    w.beta_bytes = beta_workspace_bytes(d.M, d.N, d.T_, 1, sizeof(T) == 8 ? EVC_F64 : EVC_F32);
+    w.beta_ws = c.take<char>(w.beta_bytes);
+    w.bytes = c.bytes();
     return w;
 }
 
@@ -277,98 +243,81 @@ bool bl_sizes_ok(int M, int R, int T_, int dtype) {
 
 size_t bl_workspace_bytes(int M, int R, int T_, int dtype) {
     if (!bl_sizes_ok(M, R, T_, dtype)) return 0;
-    return (dtype == EVC_F64 ? carve_bl<double>(nullptr, M, R, T_).bytes : carve_bl<float>(nullptr, M, R, T_).bytes) + 256;
+    return (dtype == EVC_F64 ? carve_bl<double>(nullptr, make_dims(8, M, R, T_, 1)).bytes
+                             : carve_bl<float>(nullptr, make_dims(4, M, R, T_, 1)).bytes) + 256;
 }
 
-// arguments already validated by evc_beta_learn; returns 0, -2 or a hipError_t
+// arguments already validated by evc_beta_learn; returns ST_OK, ST_WORKSPACE or a hipError_t
 template <typename T>
 int beta_learn(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, int M, int R, int T_,
                const evc_beta_learn_opts& o, int S, bool fused, void* ws, size_t ws_bytes, int* n_iter_out, double* err_out,
                hipStream_t s) {
-    const BlWs<T> w = carve_bl<T>(ws, M, R, T_);
-    if (w.bytes > ws_bytes) return -2;
-    const BlDims d = bl_dims((int)sizeof(T), M, R, T_);
+    const Dims d = make_dims((int)sizeof(T), M, R, T_, 1);
+    const BlWs<T> w = carve_bl<T>(ws, d);
+    if (w.bytes > ws_bytes) return ST_WORKSPACE;
+    const int MTp = learn_bin_tiles(M);
     const bool fm = o.layout == EVC_FRAME_MAJOR;
     const T* X = static_cast<const T*>(X_);
     T* W = static_cast<T*>(W_);
     T* H = static_cast<T*>(H_);
     const double beta = o.beta;
-    const int n_checks = o.check_every > 0 ? o.iters / o.check_every : 0;
-    const bool want_err = o.check_every > 0 && (err_out || o.tol > 0.0);
-    if (err_out) for (int i = 0; i <= n_checks; ++i) err_out[i] = NAN;
 
     BetaCtx<T> c;
-    BL_TRY(beta_begin<T>(c, X, ldx, H, ldh, M, R, T_, nullptr, 1, o.layout, beta, o.l1_h, o.l2_h, beta < 1.0 ? BETA_E64 : 0.0,
-                         1 + n_checks, w.beta_ws, w.beta_bytes, s));
+    HIP_TRY(beta_begin<T>(c, X, ldx, H, ldh, M, R, T_, nullptr, 1, o.layout, beta, o.l1_h, o.l2_h, beta < 1.0 ? BETA_E64 : 0.0,
+                          n_slots_for(o.iters, o.check_every), w.beta_ws, w.beta_bytes, s));
     const double gamma = beta_gamma(beta);
     const PowSpec p1 = pow_spec(beta - 2.0), p2 = pow_spec(beta - 1.0), pg = pow_spec(gamma);
     const int clamp_n = beta - 2.0 < 0 ? 1 : 0, clamp_d = beta - 1.0 < 0 ? 1 : 0;
 
     auto update_w = [&]() -> int {
         // frames-as-rows copies of the current factors (Ht is the right operand of the sums over the frames)
-        BL_TRY(copy2d<T>(W, ldw, M, R, fm ? 1 : 0, w.Am, d.Np, d.Mj, d.Np, 0, s));
-        BL_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, d.Np, d.Tp, d.Np, 0, s));
+        HIP_TRY(copy2d<T>(W, ldw, M, R, fm ? 1 : 0, w.Am, d.Np, d.Mj, d.Np, 0, s));
+        HIP_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, d.Np, d.Tp, d.Np, 0, s));
         if (fused) {
             BetaDictArgs<T> a;
             a.Xt = w.Xt; a.Ht = w.Ht; a.Am = w.Am; a.part = w.part;
             a.ldx = d.Mk; a.ldh = d.Np;
-            a.M = M; a.R = R; a.RP16 = round_up(R, 16); a.MTp = d.MTp; a.T_ = T_; a.S = S;
+            a.M = M; a.R = R; a.RP16 = round_up(R, 16); a.MTp = MTp; a.T_ = T_; a.S = S;
             a.clamp_n = clamp_n; a.clamp_d = clamp_d; a.p1 = p1; a.p2 = p2;
             const dim3 grid(round_up(R, BDG_RB * 16) / (BDG_RB * 16), d.Mk / 16, S);
             hipLaunchKernelGGL(k_beta_dict_grad<T>, grid, dim3(64 * BDG_WAVES), bdg_lds_bytes<T>(a.RP16), s, a);
-            BL_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         } else {
-            BL_TRY(gemm_nt<T>(w.Ht, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));
+            HIP_TRY(gemm_nt<T>(w.Ht, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));
             const long n = (long)T_ * d.Mk;
             hipLaunchKernelGGL(k_beta_dict_q<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.Xt, d.Mk, w.Vt, w.Q2t,
                                d.Mj, M, d.Mk, (long)T_, clamp_n, clamp_d, p1, p2);
-            BL_TRY(hipGetLastError());
-            BL_TRY(dict_grad<T>(w.Vt, d.Mj, w.Q2t, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(dict_grad<T>(w.Vt, d.Mj, w.Q2t, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
         }
         const long n = (long)M * R;
         hipLaunchKernelGGL(k_beta_dict_apply<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.part, S,
-                           (long)d.MTp * 16 * d.Np, d.Np, W, (long)ldw, fm ? 0 : 1, M, R, (T)o.l1_w, (T)o.l2_w,
+                           (long)MTp * 16 * d.Np, d.Np, W, (long)ldw, fm ? 0 : 1, M, R, (T)o.l1_w, (T)o.l2_w,
                            gamma == 1.0 ? 1 : 0, pg, (T)(beta <= 1.0 ? BETA_E64 : 0.0));
-        BL_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         return 0;
     };
     // the error of the current factors: the activation half's error kernels on freshly packed dictionary images
     auto error_now = [&](int slot, double* host) -> int {
-        BL_TRY(beta_pack_dict<T>(c, W, ldw, s));
-        BL_TRY(beta_check<T>(c, slot, o.check_every, EVC_STOP_NONE, 0.0, s));
-        BL_TRY(hipMemcpyAsync(host, c.w.trace + slot, sizeof(double), hipMemcpyDeviceToHost, s));
-        BL_TRY(hipStreamSynchronize(s));
+        HIP_TRY(beta_pack_dict<T>(c, W, ldw, s));
+        HIP_TRY(beta_check<T>(c, slot, o.check_every, EVC_STOP_NONE, 0.0, s));
+        HIP_TRY(hipMemcpyAsync(host, c.w.trace + slot, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         return 0;
     };
 
-    BL_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
+    HIP_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
     if (fused)
-        BL_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_dict_grad<T>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)bdg_lds_bytes<T>(BDG_MAX_R)));
-    double err_init = 0.0, err_prev = 0.0, err = 0.0;
-    if (want_err) {
-        BL_TRY(error_now(0, &err_init));
-        err_prev = err_init;
-        if (err_out) err_out[0] = err_init;
-    }
-    if (o.ev_loop_start) BL_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
-    int n_iter = 0;
-    for (int it = 1; it <= o.iters; ++it) {
-        BL_TRY(beta_pack_dict<T>(c, W, ldw, s));
-        BL_TRY(beta_sweep<T>(c, s));
-        BL_TRY(update_w());
-        n_iter = it;
-        if (!want_err || it % o.check_every != 0) continue;
-        const int chk = it / o.check_every;
-        BL_TRY(error_now(chk, &err));
-        if (err_out) err_out[chk] = err;
-        // tol = 0 never stops, as in scikit-learn; a NaN error compares false and never stops either
-        if (o.tol > 0.0 && (err_prev - err) / err_init < o.tol) break;
-        err_prev = err;
-    }
-    if (o.ev_loop_stop) BL_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    if (n_iter_out) *n_iter_out = n_iter;
-    return 0;
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_dict_grad<T>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)bdg_lds_bytes<T>(BDG_MAX_R)));
+    auto step = [&]() -> int {
+        HIP_TRY(beta_pack_dict<T>(c, W, ldw, s));
+        HIP_TRY(beta_sweep<T>(c, s));
+        return update_w();
+    };
+    auto stop = [&](int, double err, double err_prev, double err_init) { return (err_prev - err) / err_init < o.tol; };
+    return learn_loop(o.iters, o.check_every, o.tol, err_out, n_iter_out, o.ev_loop_start, o.ev_loop_stop, s, step, error_now,
+                      stop);
 }
 
 }  // namespace
@@ -392,22 +341,18 @@ int evc_beta_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, i
                    const evc_beta_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
                    evc_stream_t stream) {
     using namespace evc;
-    if (!opts || opts->struct_bytes != (int)sizeof(evc_beta_learn_opts)) return -1;
+    if (!opts || opts->struct_bytes != (int)sizeof(evc_beta_learn_opts)) return ST_BADARG;
     const evc_beta_learn_opts& o = *opts;
-    if (M < 1 || R < 1 || T < 1 || o.iters < 0 || o.check_every < 0) return -1;
-    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return -1;
-    const bool fm = o.layout == EVC_FRAME_MAJOR;
-    if (!fm && o.layout != EVC_BIN_MAJOR) return -1;
-    if (!(o.beta - o.beta == 0.0)) return -1;                      // NaN or infinite
-    if (!(o.tol >= 0.0) || !(o.l1_h >= 0.0) || !(o.l2_h >= 0.0) || !(o.l1_w >= 0.0) || !(o.l2_w >= 0.0)) return -1;
-    const int forced = (o.reserved >> 8) & 0xff, route = (o.reserved >> 16) & 3;
-    if ((o.reserved & ~0x3ff00) != 0 || forced > LEARN_MAX_SPLITS || route == 3) return -1;
-    if (!X || !W || !H || !workspace) return -1;
-    if ((fm ? ldx < M : ldx < T) || (fm ? ldw < M : ldw < R) || (fm ? ldh < R : ldh < T)) return -1;
-    if (o.check_every > 0 && o.iters / o.check_every + 1 > BETA_MAX_SLOTS) return -1;
-    if (M > BETA_MAX_M || R > LEARN_MAX_R) return -3;
-    if (route == ROUTE_FUSED && R > BDG_MAX_R) return -3;
-    if (workspace_bytes < bl_workspace_bytes(M, R, T, o.dtype)) return -2;
+    int forced;
+    HIP_TRY(learn_args_ok(M, R, T, o.dtype, o.layout, X, W, H, workspace, ldx, ldw, ldh, o.reserved, 0x3ff00, &forced));
+    const int route = (o.reserved >> 16) & 3;
+    if (o.iters < 0 || o.check_every < 0 || route == 3) return ST_BADARG;
+    if (!(o.beta - o.beta == 0.0)) return ST_BADARG;               // NaN or infinite
+    if (!(o.tol >= 0.0) || !(o.l1_h >= 0.0) || !(o.l2_h >= 0.0) || !(o.l1_w >= 0.0) || !(o.l2_w >= 0.0)) return ST_BADARG;
+    if (o.check_every > 0 && o.iters / o.check_every + 1 > BETA_MAX_SLOTS) return ST_BADARG;
+    if (M > BETA_MAX_M || R > LEARN_MAX_R) return ST_UNSUPPORTED;
+    if (route == ROUTE_FUSED && R > BDG_MAX_R) return ST_UNSUPPORTED;
+    if (workspace_bytes < bl_workspace_bytes(M, R, T, o.dtype)) return ST_WORKSPACE;
     const int S = forced ? forced : learn_splits(M, R, T);
     const bool fused = route == ROUTE_FUSED || (route == ROUTE_AUTO && R <= BDG_ROUTE_R);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);

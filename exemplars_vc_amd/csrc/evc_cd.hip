@@ -265,41 +265,49 @@ __global__ void k_cd_state_init(int* stop, double* vinit, double* trace, int n_u
     if (i < (long)n_utt * CD_TRACE_CAP) trace[i] = __builtin_nan("");
 }
 
-#define CD_TRY(expr)                                  \
-    do {                                              \
-        hipError_t e_ = (expr);                       \
-        if (e_ != hipSuccess) return (int)e_;         \
-    } while (0)
+template <typename T> struct CdWs {
+    T *Ac, *Gb, *hess, *R;
+    int4* tiles;
+    int* utt_tile0;
+    double* part;
+    int* stop;
+    double *vinit, *trace;
+    size_t bytes;
+};
 
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+// The workspace: [Ac | Gb | hess | R | tiles | utt_tile0 | part | stop | vinit | trace], each 256-byte aligned (ws == NULL:
+// sizes only).  The tile count is bounded by ceil(T / F) + n_utt whatever the split into utterances.
+template <typename T> CdWs<T> carve_cd(void* ws, const CdGeometry& g, int N, int T_, int n_utt) {
+    CdWs<T> w;
+    Carver c = Carver::rounded(ws);
+    const size_t Np = (size_t)round_up(N, CD_B);
+    const size_t nt = (size_t)(T_ + g.F - 1) / g.F + n_utt;
+    w.Ac = c.take<T>(Np * g.Mr);
+    w.Gb = c.take<T>(Np * CD_B);
+    w.hess = c.take<T>(Np);
+    w.R = c.take<T>(nt * g.F * g.Mr);
+    w.tiles = c.take<int4>(nt);
+    w.utt_tile0 = c.take<int>((size_t)n_utt + 1);
+    w.part = c.take<double>(2 * nt);
+    w.stop = c.take<int>(n_utt);
+    w.vinit = c.take<double>(n_utt);
+    w.trace = c.take<double>((size_t)n_utt * CD_TRACE_CAP);
+    w.bytes = c.bytes();
+    return w;
+}
 
 }  // namespace
 
-// The workspace: [Ac | Gb | hess | R | tiles | utt_tile0 | part | stop | vinit | trace], each 256-byte aligned.
-// n_tiles is bounded by ceil(T / F) + n_utt whatever the split into utterances.
 size_t cd_workspace_bytes(int M, int N, int T_, int n_utt, int esize) {
     const CdGeometry g = cd_geometry(M);
     if (g.L == 0 || N < 1 || T_ < 0 || n_utt < 1 || (esize != 4 && esize != 8)) return 0;
-    const size_t Np = (size_t)round_up(N, CD_B);
-    const size_t nt = (size_t)(T_ + g.F - 1) / g.F + n_utt;
-    size_t b = 0;
-    b += align256(Np * g.Mr * esize);
-    b += align256(Np * CD_B * esize);
-    b += align256(Np * esize);
-    b += align256(nt * g.F * g.Mr * esize);
-    b += align256(nt * sizeof(int4));
-    b += align256((n_utt + 1) * sizeof(int));
-    b += align256(2 * nt * sizeof(double));
-    b += align256(n_utt * sizeof(int));
-    b += align256(n_utt * sizeof(double));
-    b += align256((size_t)n_utt * CD_TRACE_CAP * sizeof(double));
-    return b + 256;
+    return (esize == 8 ? carve_cd<double>(nullptr, g, N, T_, n_utt).bytes : carve_cd<float>(nullptr, g, N, T_, n_utt).bytes) + 256;
 }
 
 namespace {
 
 // Carves the workspace, stages the tile table and clears the per-utterance state; everything of CdArgs but the
-// dictionary-dependent arrays' contents (cd_refresh) is final afterwards.  Returns 0, -1, -2 or a hipError_t.
+// dictionary-dependent arrays' contents (cd_refresh) is final afterwards.  Returns ST_OK, ST_BADARG, ST_WORKSPACE or a hipError_t.
 template <typename T>
 int cd_setup(T* H, int ldh, int M, int N, int T_, const int* utt_offsets, int n_utt, bool fm, int max_iter, double tol,
              double l1, double l2, void* ws, size_t ws_bytes, hipStream_t s, CdArgs<T>* out) {
@@ -312,21 +320,9 @@ int cd_setup(T* H, int ldh, int M, int N, int T_, const int* utt_offsets, int n_
         n_tiles += (tu + g.F - 1) / g.F;
     }
     const int nt_cap = (T_ + g.F - 1) / g.F + n_utt;
-    if (n_tiles > nt_cap) return -1;
-    char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = base + off; off += align256(bytes); return p; };
-    T* Ac = reinterpret_cast<T*>(take((size_t)Np * g.Mr * sizeof(T)));
-    T* Gb = reinterpret_cast<T*>(take((size_t)Np * CD_B * sizeof(T)));
-    T* hess = reinterpret_cast<T*>(take((size_t)Np * sizeof(T)));
-    T* R = reinterpret_cast<T*>(take((size_t)nt_cap * g.F * g.Mr * sizeof(T)));
-    int4* tiles = reinterpret_cast<int4*>(take((size_t)nt_cap * sizeof(int4)));
-    int* utt_tile0 = reinterpret_cast<int*>(take((size_t)(n_utt + 1) * sizeof(int)));
-    double* part = reinterpret_cast<double*>(take((size_t)2 * nt_cap * sizeof(double)));
-    int* stop = reinterpret_cast<int*>(take((size_t)n_utt * sizeof(int)));
-    double* vinit = reinterpret_cast<double*>(take((size_t)n_utt * sizeof(double)));
-    double* trace = reinterpret_cast<double*>(take((size_t)n_utt * CD_TRACE_CAP * sizeof(double)));
-    if ((size_t)(base - static_cast<char*>(ws)) + off > ws_bytes) return -2;
+    if (n_tiles > nt_cap) return ST_BADARG;
+    const CdWs<T> w = carve_cd<T>(ws, g, N, T_, n_utt);
+    if (w.bytes > ws_bytes) return ST_WORKSPACE;
 
     // the tile table (host, staged by hipMemcpyAsync from pageable memory at enqueue time)
     int4* h_tiles = static_cast<int4*>(malloc(sizeof(int4) * (n_tiles > 0 ? n_tiles : 1) + sizeof(int) * (n_utt + 1)));
@@ -346,19 +342,19 @@ int cd_setup(T* H, int ldh, int M, int N, int T_, const int* utt_offsets, int n_
         h_t0[n_utt] = t;
     }
     hipError_t e = hipSuccess;
-    if (n_tiles > 0) e = hipMemcpyAsync(tiles, h_tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
+    if (n_tiles > 0) e = hipMemcpyAsync(w.tiles, h_tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(w.utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
     free(h_tiles);      // pageable source: HIP has staged the bytes by the time hipMemcpyAsync returns
-    CD_TRY(e);
+    HIP_TRY(e);
     {
         const long n = (long)n_utt * CD_TRACE_CAP;
-        hipLaunchKernelGGL(k_cd_state_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, stop, vinit, trace,
+        hipLaunchKernelGGL(k_cd_state_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.stop, w.vinit, w.trace,
                            n_utt);
-        CD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     CdArgs<T>& a = *out;
-    a.Ac = Ac; a.Gb = Gb; a.hess = hess; a.R = R; a.H = H; a.ldh = ldh; a.fm = fm ? 1 : 0;
-    a.tiles = tiles; a.utt_tile0 = utt_tile0; a.part = part; a.stop = stop; a.vinit = vinit; a.trace = trace;
+    a.Ac = w.Ac; a.Gb = w.Gb; a.hess = w.hess; a.R = w.R; a.H = H; a.ldh = ldh; a.fm = fm ? 1 : 0;
+    a.tiles = w.tiles; a.utt_tile0 = w.utt_tile0; a.part = w.part; a.stop = w.stop; a.vinit = w.vinit; a.trace = w.trace;
     a.n_tiles = n_tiles; a.M = M; a.N = N; a.Np = Np; a.Mr = g.Mr; a.L = g.L; a.mpl = g.mpl;
     a.max_iter = max_iter; a.tol = tol; a.l1 = (T)l1; a.l2 = (T)l2;
     return 0;
@@ -373,16 +369,16 @@ int cd_refresh(const CdArgs<T>& a, const T* A, int lda, const T* X, int ldx, int
         const long n = (long)a.Np * a.Mr;
         hipLaunchKernelGGL(k_cd_pack_dict<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, A, lda, a.fm, a.M, a.N,
                            a.Np, a.Mr, const_cast<T*>(a.Ac));
-        CD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_cd_gram_blocks<T>, dim3(a.Np / CD_B), dim3(CD_B * CD_B), 0, s, a.Ac, a.M, a.N, a.Mr, l2,
                            const_cast<T*>(a.Gb), const_cast<T*>(a.hess));
-        CD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (a.n_tiles > 0) {
         const long n = (long)a.n_tiles * F * a.Mr;
         hipLaunchKernelGGL(k_cd_init_resid<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, X, ldx, a.H, (int)a.ldh,
                            a.fm, given, a.Ac, a.tiles, a.n_tiles, F, a.M, a.N, a.Mr, a.R);
-        CD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     return 0;
 }
@@ -406,8 +402,8 @@ int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int
     hipError_t e = hipSuccess;
     const int es = (int)sizeof(T);
     if (o.init_mode == EVC_INIT_SKLEARN && T_ > 0) {
-        if (fm) CD_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)N * es, T_, s));
-        else CD_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)T_ * es, N, s));
+        if (fm) HIP_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)N * es, T_, s));
+        else HIP_TRY(hipMemset2DAsync(H, (size_t)ldh * es, 0, (size_t)T_ * es, N, s));
     }
     {
         const int st = cd_refresh<T>(a, A, lda, X, ldx, o.init_mode == EVC_INIT_GIVEN ? 1 : 0, o.l2, s);
@@ -417,22 +413,22 @@ int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int
     const bool run = n_tiles > 0 && o.max_iter > 0;
     int launches = 0;
     int copied = 0;         // iterations whose violation has been copied to violation_out
-    if (o.ev_loop_start) CD_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
+    if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
     if (run) {
         for (int k = 1; k <= o.max_iter + 1; ++k) {
-            CD_TRY(launch_sweep<T>(a, k, s));
+            HIP_TRY(launch_sweep<T>(a, k, s));
             ++launches;
             const int judged = k - 1;
             if (violation_out && judged > copied && (judged - copied == CD_TRACE_CAP || k == o.max_iter + 1)) {
                 const int cnt = judged - copied;
-                CD_TRY(hipMemcpy2DAsync(violation_out + copied, sizeof(double) * o.max_iter, trace,
-                                        sizeof(double) * CD_TRACE_CAP, sizeof(double) * cnt, n_utt,
-                                        hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpy2DAsync(violation_out + copied, sizeof(double) * o.max_iter, trace,
+                                         sizeof(double) * CD_TRACE_CAP, sizeof(double) * cnt, n_utt,
+                                         hipMemcpyDeviceToHost, s));
                 copied = judged;
             }
         }
     }
-    if (o.ev_loop_stop) CD_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
+    if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
     if (launches_out) *launches_out = launches;
     if (n_iter_out || violation_out) {
         int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
@@ -452,7 +448,7 @@ int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int
                 }
         }
         free(ni_h);
-        CD_TRY(e);
+        HIP_TRY(e);
     }
     return 0;
 }
@@ -663,29 +659,26 @@ size_t cdl_part_elems(int rows, int S, int ld) { return (size_t)(2 * S - 1) * le
 
 template <typename T> CdLearnWs<T> carve_cd_learn(void* ws, int M, int R, int T_, int S) {
     CdLearnWs<T> w;
-    const uintptr_t base = (reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255);     // ws == NULL: sizes only
-    size_t off = 0;
-    auto take = [&](size_t bytes) { char* p = reinterpret_cast<char*>(base + off); off += align256(bytes); return p; };
+    Carver c = Carver::rounded(ws);                // ws == NULL: sizes only
     const int Mk = round_up(M, 16), ld = round_up(R, 128), Rp = round_up(R, CD_B);
     const CdGeometry gr = cd_geometry(R);          // the dictionary sweep's lane geometry comes from R as k_cd_sweep's from M
     w.cd_bytes = cd_workspace_bytes(M, R, T_, 1, (int)sizeof(T));
-    w.cd = take(w.cd_bytes);
-    w.Xt = reinterpret_cast<T*>(take((size_t)T_ * Mk * sizeof(T)));
-    w.Ht = reinterpret_cast<T*>(take((size_t)T_ * ld * sizeof(T)));
-    w.partP = reinterpret_cast<T*>(take(cdl_part_elems(M, S, ld) * sizeof(T)));
-    w.partG = reinterpret_cast<T*>(take(cdl_part_elems(R, S, ld) * sizeof(T)));
-    w.G = reinterpret_cast<T*>(take((size_t)Rp * ld * sizeof(T)));
-    w.P = reinterpret_cast<T*>(take((size_t)M * ld * sizeof(T)));
-    w.Gb = reinterpret_cast<T*>(take((size_t)Rp * CD_B * sizeof(T)));
-    w.hess = reinterpret_cast<T*>(take((size_t)Rp * sizeof(T)));
-    w.dpart = reinterpret_cast<double*>(take((size_t)((M + gr.F - 1) / gr.F) * sizeof(double)));
-    w.ring = reinterpret_cast<double*>(take((size_t)CDL_RING * 2 * sizeof(double)));
-    w.bytes = (size_t)(base - reinterpret_cast<uintptr_t>(ws)) + off;
+    w.cd = c.take<char>(w.cd_bytes);
+    w.Xt = c.take<T>((size_t)T_ * Mk);
+    w.Ht = c.take<T>((size_t)T_ * ld);
+    w.partP = c.take<T>(cdl_part_elems(M, S, ld));
+    w.partG = c.take<T>(cdl_part_elems(R, S, ld));
+    w.G = c.take<T>((size_t)Rp * ld);
+    w.P = c.take<T>((size_t)M * ld);
+    w.Gb = c.take<T>((size_t)Rp * CD_B);
+    w.hess = c.take<T>(Rp);
+    w.dpart = c.take<double>((M + gr.F - 1) / gr.F);
+    w.ring = c.take<double>(CDL_RING * 2);
+    w.bytes = c.bytes();
     return w;
 }
 
-}  // namespace
-
+// S frame ranges for the two contractions over the frames (learn_splits, or what the caller forces)
 size_t cd_learn_workspace_bytes(int M, int R, int T_, int S, int esize) {
     if (M < 1 || M > CD_MAX_M || R < 1 || R > CD_LEARN_MAX_R || T_ < 1 || S < 1 || S > LEARN_MAX_SPLITS) return 0;
     if (esize == 8) return carve_cd_learn<double>(nullptr, M, R, T_, S).bytes + 256;
@@ -693,11 +686,12 @@ size_t cd_learn_workspace_bytes(int M, int R, int T_, int S, int esize) {
     return 0;
 }
 
+// arguments already validated by evc_cd_learn; returns ST_OK, ST_WORKSPACE or a hipError_t
 template <typename T>
 int cd_learn(const T* X, int ldx, T* W, int ldw, T* H, int ldh, int M, int R, int T_, const evc_cd_learn_opts& o, int S,
              void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out, hipStream_t s) {
     const CdLearnWs<T> w = carve_cd_learn<T>(ws, M, R, T_, S);
-    if (w.bytes > ws_bytes) return -2;
+    if (w.bytes > ws_bytes) return ST_WORKSPACE;
     const bool fm = o.layout == EVC_FRAME_MAJOR;
     const bool both = o.update == EVC_CDL_BOTH;
     const int Mk = round_up(M, 16), ld = round_up(R, 128), Rp = round_up(R, CD_B);
@@ -718,11 +712,11 @@ int cd_learn(const T* X, int ldx, T* W, int ldw, T* H, int ldh, int M, int R, in
     const int n_waves = (M + gr.F - 1) / gr.F;
     const long slabP = (long)learn_bin_tiles(M) * 16 * ld, slabG = (long)learn_bin_tiles(R) * 16 * ld;
 
-    CD_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, Mk, T_, Mk, 0, s));
-    if (!both) CD_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, ld, T_, ld, 0, s));
+    HIP_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, Mk, T_, Mk, 0, s));
+    if (!both) HIP_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, ld, T_, ld, 0, s));
     // only a call that wants neither the stop rule nor any figure back is a pure enqueue
     const bool sync = o.tol > 0.0 || n_iter_out || violation_out;
-    if (o.ev_loop_start) CD_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
+    if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
     int n_iter = 0;
     double vinit = 0.0;
     for (int it = 1; it <= o.max_iter; ++it) {
@@ -730,28 +724,28 @@ int cd_learn(const T* X, int ldx, T* W, int ldw, T* H, int ldh, int M, int R, in
             // activations: one sweep from the current H on the current W (the residual h W^T - x is formed afresh)
             const int st = cd_refresh<T>(a, W, ldw, X, ldx, 1, o.l2_h, s);
             if (st != 0) return st;
-            CD_TRY(launch_sweep<T>(a, 1, s));
-            CD_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, ld, T_, ld, 0, s));
+            HIP_TRY(launch_sweep<T>(a, 1, s));
+            HIP_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, ld, T_, ld, 0, s));
         }
         // dictionary: the two contractions over the frames, their sums, the row sweeps
-        CD_TRY(dict_grad_kl<T>(w.Xt, Mk, w.Ht, ld, M, T_, S, w.partP, s));
-        CD_TRY(dict_grad_kl<T>(w.Ht, ld, w.Ht, ld, R, T_, S, w.partG, s));
+        HIP_TRY(dict_grad_kl<T>(w.Xt, Mk, w.Ht, ld, M, T_, S, w.partP, s));
+        HIP_TRY(dict_grad_kl<T>(w.Ht, ld, w.Ht, ld, R, T_, S, w.partG, s));
         {
             const long n = (long)(Rp + M) * ld;
             hipLaunchKernelGGL(k_cdl_finish<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.partG, slabG, w.partP,
                                slabP, S, ld, M, R, Rp, (T)o.l1_w, (T)o.l2_w, w.G, w.P, w.Gb, w.hess);
-            CD_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
-        CD_TRY(launch_dict_sweep<T>(d, s));
+        HIP_TRY(launch_dict_sweep<T>(d, s));
         n_iter = it;
         if (!sync) continue;
         double* slot = w.ring + (size_t)(it % CDL_RING) * 2;
         hipLaunchKernelGGL(k_cdl_viol, dim3(1), dim3(256), 0, s, both ? a.part + a.n_tiles : nullptr, both ? a.n_tiles : 0,
                            w.dpart, n_waves, slot);
-        CD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         double v[2];
-        CD_TRY(hipMemcpyAsync(v, slot, sizeof(v), hipMemcpyDeviceToHost, s));
-        CD_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(v, slot, sizeof(v), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         if (violation_out) {
             violation_out[2 * (it - 1)] = v[0];
             violation_out[2 * (it - 1) + 1] = v[1];
@@ -760,14 +754,50 @@ int cd_learn(const T* X, int ldx, T* W, int ldw, T* H, int ldh, int M, int R, in
         if (it == 1) vinit = viol;
         if (vinit == 0.0 || viol / vinit <= o.tol) break;      // _nmf.py:513-519; the stopping iteration's updates stay
     }
-    if (o.ev_loop_stop) CD_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
+    if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
     if (n_iter_out) *n_iter_out = n_iter;
     return 0;
 }
 
-template int cd_learn<double>(const double*, int, double*, int, double*, int, int, int, int, const evc_cd_learn_opts&, int,
-                              void*, size_t, int*, double*, hipStream_t);
-template int cd_learn<float>(const float*, int, float*, int, float*, int, int, int, int, const evc_cd_learn_opts&, int,
-                             void*, size_t, int*, double*, hipStream_t);
+bool cd_learn_sizes_ok(int M, int R, int T, int dtype) {
+    return M >= 1 && R >= 1 && T >= 1 && M <= CD_MAX_M && R <= CD_LEARN_MAX_R && (dtype == EVC_F64 || dtype == EVC_F32);
+}
+
+}  // namespace
 
 }  // namespace evc
+
+using namespace evc;
+
+extern "C" {
+
+int evc_cd_learn_splits(int M, int R, int T) {
+    return cd_learn_sizes_ok(M, R, T, EVC_F64) ? learn_splits(M, R, T) : 0;
+}
+
+size_t evc_cd_learn_workspace_bytes(int M, int R, int T, int dtype) {
+    if (!cd_learn_sizes_ok(M, R, T, dtype)) return 0;
+    return cd_learn_workspace_bytes(M, R, T, learn_splits(M, R, T), dtype == EVC_F64 ? 8 : 4);
+}
+
+int evc_cd_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
+                 const evc_cd_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
+                 double* violation_out, evc_stream_t stream) {
+    if (!opts || opts->struct_bytes != (int)sizeof(evc_cd_learn_opts)) return ST_BADARG;
+    const evc_cd_learn_opts& o = *opts;
+    int forced;
+    HIP_TRY(learn_args_ok(M, R, T, o.dtype, o.layout, X, W, H, workspace, ldx, ldw, ldh, o.reserved, 0xff00, &forced));
+    if (o.max_iter < 0 || (o.update != EVC_CDL_BOTH && o.update != EVC_CDL_DICT_ONLY)) return ST_BADARG;
+    if (!(o.tol >= 0.0) || !(o.l1_h >= 0.0) || !(o.l2_h >= 0.0) || !(o.l1_w >= 0.0) || !(o.l2_w >= 0.0)) return ST_BADARG;
+    if (M > CD_MAX_M || R > CD_LEARN_MAX_R) return ST_UNSUPPORTED;
+    const int S = forced ? forced : learn_splits(M, R, T);
+    if (workspace_bytes < cd_learn_workspace_bytes(M, R, T, S, o.dtype == EVC_F64 ? 8 : 4)) return ST_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (o.dtype == EVC_F64)
+        return cd_learn<double>(static_cast<const double*>(X), ldx, static_cast<double*>(W), ldw, static_cast<double*>(H),
+                                ldh, M, R, T, o, S, workspace, workspace_bytes, n_iter_out, violation_out, s);
+    return cd_learn<float>(static_cast<const float*>(X), ldx, static_cast<float*>(W), ldw, static_cast<float*>(H), ldh, M, R,
+                           T, o, S, workspace, workspace_bytes, n_iter_out, violation_out, s);
+}
+
+}  // extern "C"

@@ -81,6 +81,82 @@ template <typename T> struct MuEpilogue {
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// ------------------------------------------------------------------------------------------
+// Host pieces every entry's translation unit shares: statuses, padded sizes, workspace carving.
+// ------------------------------------------------------------------------------------------
+enum { ST_OK = 0, ST_BADARG = -1, ST_WORKSPACE = -2, ST_UNSUPPORTED = -3, ST_COOP_TIMEOUT = -4 };
+
+// (expr: a hipError_t or one of the statuses above - both are 0 on success)
+#define HIP_TRY(expr)                              \
+    do {                                           \
+        int e__ = (int)(expr);                     \
+        if (e__) return e__;                       \
+    } while (0)
+
+// FRAME_MAJOR: rows_fm x cols_fm with ld >= cols_fm; BIN_MAJOR: the transpose
+inline bool bad_ld(int layout, int ld, int rows_fm, int cols_fm) {
+    return layout == EVC_FRAME_MAJOR ? ld < cols_fm : ld < rows_fm;
+}
+
+// The worst-case slot count is bounded by iters+1; evc_workspace_bytes has no iters argument,
+// so the trace region is sized for MAX_SLOTS checks and evc_nmf_solve rejects more.
+constexpr int MAX_SLOTS = 4097;
+inline int n_slots_for(int iters, int check_every) { return 1 + (check_every > 0 ? iters / check_every : 0); }
+
+// frames are padded to the contraction kernels' frame tile: 64 where k_gemm2 is in charge (float32) and for short
+// float64 batches (<= 2048 frames: k_gemm_nt then runs 64-row blocks anyway, and one 688-frame utterance is 704
+// rows instead of 768), 128 otherwise (diagnostic builds: see use_gemm2 in evc_gemm.hip)
+inline int frame_pad(int esize, int T_) {
+#if defined(EVC_DIAG_GEMM_V1)
+    return round_up(T_, 128);
+#elif defined(EVC_DIAG_GEMM2_F64)
+    return round_up(T_, 64);
+#else
+    return round_up(T_, (esize == 4 || T_ <= 2048) ? 64 : 128);
+#endif
+}
+
+// the padded sizes of the frames-as-rows arrays gemm_nt and dict_grad work on
+struct Dims {
+    int M, N, T_, n_utt, Mb;
+    int Mk, Mj, Np, Tp;
+};
+inline Dims make_dims(int esize, int M, int N, int T_, int n_utt, int Mb = 0) {
+    Dims d;
+    d.M = M; d.N = N; d.T_ = T_; d.n_utt = n_utt; d.Mb = Mb;
+    d.Mk = round_up(M, 16);
+    d.Mj = round_up(M, 64);
+    d.Np = round_up(N, 128);
+    d.Tp = frame_pad(esize, T_);
+    return d;
+}
+
+// Workspace carving.  take() first rounds `off` up to 256 bytes, so every array starts at a multiple of 256 bytes from
+// `base`, `off` is the end of the last array, and bytes() is what the carving needs of the caller's pointer.  The base is
+// one of two:
+//   Carver{ws, skip}       the caller's pointer as given: the caller aligns it (evc_workspace_bytes, evc_dict_bytes and the
+//                          entries built on them: the solves, the prepared images, evc_nmf_learn)
+//   Carver::rounded(ws)    the caller's pointer rounded up to 256 bytes; bytes() counts the shift, and the size query -
+//                          which carves from NULL, where there is none - adds 256 for it (evc_cd_solve, evc_beta_solve,
+//                          evc_cd_learn, evc_beta_learn)
+// base == NULL: sizes only, every take() gives NULL.
+struct Carver {
+    char* base;
+    size_t off;
+    size_t shift = 0;
+    static Carver rounded(void* ws) {
+        const uintptr_t p = reinterpret_cast<uintptr_t>(ws), up = (p + 255) & ~uintptr_t(255);
+        return Carver{reinterpret_cast<char*>(up), 0, (size_t)(up - p)};
+    }
+    template <typename U> U* take(size_t count) {
+        off = (off + 255) & ~size_t(255);
+        U* p = base ? reinterpret_cast<U*>(base + off) : nullptr;
+        off += count * sizeof(U);
+        return p;
+    }
+    size_t bytes() const { return shift + ((off + 255) & ~size_t(255)); }
+};
+
 // ----- evc_gemm.hip -----
 // C[I x J] = L[I x Kd] * R[J x Kd]^T, all row-major, I % 128 == 0, J % 64 == 0, Kd % 16 == 0.
 // scratch (optional, scratch_elems elements): lets a small-grid, long-K product be split over K.
@@ -377,13 +453,8 @@ int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int
              int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
              hipStream_t s, int* launches_out);
 
-// evc_cd_learn: the alternating form; S frame ranges for the two contractions over the frames (learn_splits)
+// evc_cd_learn (entry and driver in evc_cd.hip): the alternating form
 constexpr int CD_LEARN_MAX_R = 1024;  // 64 lanes x 16 components per lane; keeps learn_bin_tiles(R) within evc_nmf_learn's
-size_t cd_learn_workspace_bytes(int M, int R, int T_, int S, int esize);
-// arguments already validated by evc_cd_learn; returns 0, -2 or a hipError_t
-template <typename T>
-int cd_learn(const T* X, int ldx, T* W, int ldw, T* H, int ldh, int M, int R, int T_, const evc_cd_learn_opts& o, int S,
-             void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out, hipStream_t s);
 
 // ----- evc_learn.hip: the dictionary update of evc_nmf_learn -----
 constexpr int LEARN_MAX_M = 1056;     // 66 bin tiles of 16
@@ -418,5 +489,53 @@ hipError_t dict_apply(const T* part, int S, int ldp, T* W, long ldw, int bin_maj
                       hipStream_t s);
 // *out = sqrt(max(sum_t err2[t], 0)), summed in a fixed order
 hipError_t err_total(const double* err2, int T_, double* out, hipStream_t s);
+
+// ----- the host skeleton of the entries that learn both factors (evc_nmf_learn in evc_learn.hip, evc_cd_learn in
+// evc_cd.hip, evc_beta_learn in evc_beta_learn.hip) -----
+// What the three entries check alike, after their own look at `opts`: ST_OK or ST_BADARG.  reserved: bits 8..15 force the
+// frame ranges (*forced; 0: learn_splits decides), no bit outside `allowed` may be set.
+inline int learn_args_ok(int M, int R, int T_, int dtype, int layout, const void* X, const void* W, const void* H,
+                         const void* ws, int ldx, int ldw, int ldh, int reserved, int allowed, int* forced) {
+    *forced = (reserved >> 8) & 0xff;
+    if (M < 1 || R < 1 || T_ < 1 || (dtype != EVC_F64 && dtype != EVC_F32)) return ST_BADARG;
+    if (layout != EVC_FRAME_MAJOR && layout != EVC_BIN_MAJOR) return ST_BADARG;
+    if ((reserved & ~allowed) != 0 || *forced > LEARN_MAX_SPLITS) return ST_BADARG;
+    if (!X || !W || !H || !ws) return ST_BADARG;
+    if (bad_ld(layout, ldx, T_, M) || bad_ld(layout, ldw, R, M) || bad_ld(layout, ldh, T_, R)) return ST_BADARG;
+    return ST_OK;
+}
+
+// The check-and-stop loop of the two multiplicative-update drivers.  step() runs one iteration; error_now(slot, &err)
+// evaluates the error of the current factors and waits for it (slot 0: the start, before ev_start; slot c: after
+// iteration c * check_every); stop(c, err, err_prev, err_init) is the surface's rule, asked only when tol > 0 (tol = 0
+// never stops, as in scikit-learn; a NaN error compares false in both rules and never stops, as in both references).
+// The errors are evaluated at all only when somebody reads them: err_out (NaN where not evaluated) or the rule.
+template <typename Step, typename ErrorNow, typename Stop>
+int learn_loop(int iters, int check_every, double tol, double* err_out, int* n_iter_out, void* ev_start, void* ev_stop,
+               hipStream_t s, Step step, ErrorNow error_now, Stop stop) {
+    const bool want_err = check_every > 0 && (err_out || tol > 0.0);
+    if (err_out) for (int i = 0; i < n_slots_for(iters, check_every); ++i) err_out[i] = __builtin_nan("");
+    double err_init = 0.0, err_prev = 0.0, err = 0.0;
+    if (want_err) {
+        HIP_TRY(error_now(0, &err_init));
+        err_prev = err_init;
+        if (err_out) err_out[0] = err_init;
+    }
+    if (ev_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(ev_start), s));
+    int n_iter = 0;
+    for (int it = 1; it <= iters; ++it) {
+        HIP_TRY(step());
+        n_iter = it;
+        if (!want_err || it % check_every != 0) continue;
+        const int c = it / check_every;
+        HIP_TRY(error_now(c, &err));
+        if (err_out) err_out[c] = err;
+        if (tol > 0.0 && stop(c, err, err_prev, err_init)) break;
+        err_prev = err;
+    }
+    if (ev_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(ev_stop), s));
+    if (n_iter_out) *n_iter_out = n_iter;
+    return ST_OK;
+}
 
 }  // namespace evc

@@ -1,4 +1,4 @@
-// The dictionary update of evc_nmf_learn: W <- W (.) (X H^T) (/) ((W H) H^T), evaluated factored.
+// evc_nmf_learn.  Its dictionary update: W <- W (.) (X H^T) (/) ((W H) H^T), evaluated factored.
 //
 //   k_dict_grad   the split-T "TN" contraction C[m][r] = sum_t L[t][m] Ht[t][r] on the 16x16x4 MFMA, for the stacked left
 //                 operand L = [X; V] (V = W H comes from the existing contraction).  A workgroup owns DG_MB bin tiles of
@@ -15,7 +15,10 @@
 //   k_err_total   sqrt of the sum of the per-frame error terms (clamped at 0), in a fixed order.
 // Nothing here exchanges data between workgroups inside a launch, uses atomics or assumes residency: the same call gives
 // bitwise the same W every time.
+// Below the kernels: evc_nmf_learn itself - its workspace, its steps for learn_loop (evc_internal.h) and its C entries.
 #include "evc_internal.h"
+
+#include <math.h>
 
 namespace evc {
 
@@ -246,4 +249,141 @@ template hipError_t dict_grad_kl<float>(const float*, int, const float*, int, in
 template hipError_t dict_apply<double>(const double*, int, int, double*, long, int, int, int, int, int, hipStream_t);
 template hipError_t dict_apply<float>(const float*, int, int, float*, long, int, int, int, int, int, hipStream_t);
 
+// ---- evc_nmf_learn: the host driver.  The activation step is one update of evc_nmf_solve, the dictionary step the
+// kernels above; learn_loop (evc_internal.h) alternates them and applies the surface's stop rule ----
+namespace {
+
+template <typename T> struct LearnWs {
+    T *Xt, *Am, *Ht, *Vt, *part;
+    double *err2, *ring;
+    char* solve_ws;
+    size_t solve_bytes, bytes;
+};
+constexpr int LEARN_RING = 64;
+
+template <typename T> LearnWs<T> carve_learn(void* base, const Dims& d) {
+    LearnWs<T> w;
+    Carver c{static_cast<char*>(base), 0};
+    w.Xt = c.take<T>((size_t)d.Tp * d.Mk);
+    w.Am = c.take<T>((size_t)d.Mj * d.Np);
+    w.Ht = c.take<T>((size_t)d.Tp * d.Np);
+    w.Vt = c.take<T>((size_t)d.Tp * d.Mj);
+    w.part = c.take<T>((size_t)LEARN_MAX_SPLITS * 2 * learn_bin_tiles(d.M) * 16 * d.Np);
+    w.err2 = c.take<double>(d.Tp);
+    w.ring = c.take<double>(LEARN_RING);
+    w.solve_bytes = evc_workspace_bytes(d.M, 0, d.N, d.T_, 1, sizeof(T) == 8 ? EVC_F64 : EVC_F32, EVC_ALGO_AUTO);
+    w.solve_ws = c.take<char>(w.solve_bytes);
+    w.bytes = c.bytes();
+    return w;
+}
+
+template <typename T>
+int learn_typed(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, int M, int R, int T_,
+                const evc_learn_opts& o, int S, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
+                hipStream_t s) {
+    const Dims d = make_dims((int)sizeof(T), M, R, T_, 1, 0);
+    const LearnWs<T> w = carve_learn<T>(workspace, d);
+    if (w.bytes > workspace_bytes) return ST_WORKSPACE;
+    const bool fm = o.layout == EVC_FRAME_MAJOR;
+    const T* X = static_cast<const T*>(X_);
+    T* W = static_cast<T*>(W_);
+    T* H = static_cast<T*>(H_);
+    const bool pymf = o.surface == EVC_LEARN_PYMF;
+    const bool kl = o.loss == EVC_LOSS_KL;         // sklearn surface only (evc_nmf_learn rejects it with pymf)
+    const double eps_kl = 1.1920929e-7;
+
+    evc_solve_opts so{};                           // the activation step: one update of the existing solve, a pure enqueue
+    so.struct_bytes = (int)sizeof(evc_solve_opts);
+    so.dtype = o.dtype; so.layout = o.layout; so.algo = EVC_ALGO_AUTO; so.iters = 1;
+    so.eps_mode = pymf ? EVC_EPS_ADD : EVC_EPS_ZERO_REPLACE;
+    so.eps = pymf ? 1e-9 : 1.1920929e-7;
+    so.init_mode = EVC_INIT_GIVEN; so.stop_rule = EVC_STOP_NONE; so.reserved = EVC_FLAG_NO_EXCHANGE;
+    so.loss = kl ? EVC_LOSS_KL : EVC_LOSS_FROBENIUS;
+    auto update_h = [&]() -> int {
+        return evc_nmf_solve(W, ldw, X, ldx, H, ldh, M, R, T_, nullptr, 1, &so, w.solve_ws, w.solve_bytes, nullptr, nullptr,
+                             reinterpret_cast<evc_stream_t>(s));
+    };
+    // V = W H on frames-as-rows copies of the current factors (Ht is the dictionary update's right operand too)
+    auto form_v = [&]() -> int {
+        HIP_TRY(copy2d<T>(W, ldw, M, R, fm ? 1 : 0, w.Am, d.Np, d.Mj, d.Np, 0, s));
+        HIP_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, d.Np, d.Tp, d.Np, 0, s));
+        HIP_TRY(gemm_nt<T>(w.Ht, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));
+        return ST_OK;
+    };
+    auto update_w = [&]() -> int {
+        HIP_TRY(form_v());
+        if (kl) {                                  // nothing below reads V again: the quotient takes its place
+            HIP_TRY(dict_quot<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, eps_kl, s));
+            HIP_TRY(dict_grad_kl<T>(w.Vt, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
+        } else {
+            HIP_TRY(dict_grad<T>(w.Xt, d.Mk, w.Vt, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
+        }
+        HIP_TRY(dict_apply<T>(w.part, S, d.Np, W, ldw, fm ? 0 : 1, M, R, o.surface, o.loss, s));
+        return ST_OK;
+    };
+    auto step = [&]() -> int {                     // pymf: W, then H; scikit-learn: H, then W
+        HIP_TRY(pymf ? update_w() : update_h());
+        return pymf ? update_h() : update_w();
+    };
+    auto error_now = [&](int slot, double* host) -> int {
+        HIP_TRY(form_v());
+        if (kl) HIP_TRY(frame_err_kl<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, eps_kl, w.err2, s));
+        else HIP_TRY(frame_err2<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, w.err2, s));
+        double* dst = w.ring + slot % LEARN_RING;
+        HIP_TRY(err_total(w.err2, T_, dst, s));
+        HIP_TRY(hipMemcpyAsync(host, dst, sizeof(double), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return ST_OK;
+    };
+    auto stop = [&](int c, double err, double err_prev, double err_init) {
+        return pymf ? (c >= 3 && fabs(err - err_prev) / T_ < o.tol) : ((err_prev - err) / err_init < o.tol);
+    };
+
+    HIP_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
+    return learn_loop(o.iters, o.check_every, o.tol, err_out, n_iter_out, o.ev_loop_start, o.ev_loop_stop, s, step, error_now,
+                      stop);
+}
+
+bool learn_sizes_ok(int M, int R, int T, int dtype) {
+    return M >= 1 && R >= 1 && T >= 1 && M <= LEARN_MAX_M && R <= LEARN_MAX_R && (dtype == EVC_F64 || dtype == EVC_F32);
+}
+
+}  // namespace
+
 }  // namespace evc
+
+using namespace evc;
+
+extern "C" {
+
+size_t evc_learn_workspace_bytes(int M, int R, int T, int dtype) {
+    if (!learn_sizes_ok(M, R, T, dtype)) return 0;
+    if (dtype == EVC_F64) return carve_learn<double>(nullptr, make_dims(8, M, R, T, 1, 0)).bytes;
+    return carve_learn<float>(nullptr, make_dims(4, M, R, T, 1, 0)).bytes;
+}
+
+int evc_learn_splits(int M, int R, int T) {
+    return learn_sizes_ok(M, R, T, EVC_F64) ? learn_splits(M, R, T) : 0;
+}
+
+int evc_nmf_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
+                  const evc_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
+                  evc_stream_t stream) {
+    if (!opts || opts->struct_bytes != (int)sizeof(evc_learn_opts)) return ST_BADARG;
+    const evc_learn_opts& o = *opts;
+    int forced;
+    HIP_TRY(learn_args_ok(M, R, T, o.dtype, o.layout, X, W, H, workspace, ldx, ldw, ldh, o.reserved, 0xff00, &forced));
+    if (o.iters < 0 || o.check_every < 0 || !(o.tol >= 0.0)) return ST_BADARG;
+    if (o.surface != EVC_LEARN_SKLEARN && o.surface != EVC_LEARN_PYMF) return ST_BADARG;
+    if (o.loss != EVC_LOSS_FROBENIUS && o.loss != EVC_LOSS_KL) return ST_BADARG;
+    if (M > LEARN_MAX_M || R > LEARN_MAX_R) return ST_UNSUPPORTED;
+    if (o.loss == EVC_LOSS_KL && o.surface == EVC_LEARN_PYMF) return ST_UNSUPPORTED;   // pymf has no KL update
+    if (o.check_every > 0 && o.iters / o.check_every + 1 > MAX_SLOTS) return ST_BADARG;
+    if (workspace_bytes < evc_learn_workspace_bytes(M, R, T, o.dtype)) return ST_WORKSPACE;
+    const int S = forced ? forced : learn_splits(M, R, T);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return (o.dtype == EVC_F64 ? learn_typed<double> : learn_typed<float>)(X, ldx, W, ldw, H, ldh, M, R, T, o, S, workspace,
+                                                                            workspace_bytes, n_iter_out, err_out, s);
+}
+
+}  // extern "C"

@@ -548,27 +548,13 @@ def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100
     return H_out
 
 
-_SURFACES = {"sklearn": _lib.LEARN_SKLEARN, "pymf": _lib.LEARN_PYMF}
-
-
-def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every=10, tol=0.0, dtype=None, device=None,
-                     info=False, out_w=None, out_h=None, loop_events=None, splits=0, loss="frobenius"):
-    """Multiplicative updates of BOTH factors, X ~ W H, on the GPU (evc_nmf_learn): W is addressed like the
-    dictionary A of solve_activations, H like its activations.  surface="sklearn": scikit-learn's
-    _fit_multiplicative_update with update_H=True (per iteration H, then W; the error every `check_every` iterations and
-    its stop on `tol`); surface="pymf": pymf's factorize(compute_w=True) (W, then H; columns of W scaled to unit norm).
-    loss: "frobenius" (default), or "kullback-leibler" / "kl" - scikit-learn's beta_loss='kullback-leibler' updates and
-    error sqrt(2 KL(X || W H)), on the sklearn surface only (pymf has no such update: ValueError).
-
-    Returns (W, H) in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out); with
-    info=True also dict(n_iter=int, err=[1 + iters // check_every] errors (the first at the start; NaN where not
-    evaluated), splits=frame ranges of the dictionary update's sums).  out_w / out_h: device tensors updated in place
-    (they then hold the start, W0 / H0 are ignored when None).  splits: tuning and tests, 1..64 frame ranges.
-    No CPU fallback: without a HIP device this raises RuntimeError."""
-    if loss not in _LOSSES:
-        raise ValueError(f"loss must be one of {sorted(_LOSSES)}, got {loss!r}")
-    if _LOSSES[loss] == _lib.LOSS_KL and surface == "pymf":
-        raise ValueError("the pymf surface has no Kullback-Leibler update; use surface='sklearn'")
+def _learn(entry, opts, X, W0, H0, *, layout, ws_bytes, unsupported, trace, extra_info, tol, dtype, device, info, out_w,
+           out_h, loop_events, splits):
+    """What learn_dictionary, learn_dictionary_beta and learn_dictionary_cd share around their C entry `entry`: the
+    operands on the device (out_w / out_h in place, a caller's start never clobbered), the shape check, the common fields
+    of `opts` (the entry's own are already set), the workspace lease, the call and the return rule.
+    ws_bytes(L, M, R, T, dcode): the entry's workspace, 0 -> ValueError(unsupported(M, R, T)); trace = (name, shape) of the
+    float64 array the entry fills when info is asked for; extra_info(L, M, R, T): the entry's own info fields."""
     torch = _torch()
     device = require_device(device)
     L = _lib.lib()
@@ -594,34 +580,67 @@ def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every
     R2, T2 = H_d.shape if lay == _lib.BIN_MAJOR else H_d.shape[::-1]
     if M2 != M or R2 != R or T2 != T:
         raise ValueError(f"X {tuple(X_d.shape)}, W {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
-    opts = _lib.LearnOpts()
-    opts.struct_bytes = C.sizeof(_lib.LearnOpts)
-    opts.dtype, opts.layout, opts.surface = dcode, lay, _SURFACES[surface]
-    opts.iters, opts.check_every, opts.tol = int(iters), int(check_every), float(tol)
-    opts.reserved = (int(splits) & 0xff) << 8
-    opts.loss = _LOSSES[loss]
+    opts.struct_bytes = C.sizeof(opts)
+    opts.dtype, opts.layout = dcode, lay
+    opts.reserved |= (int(splits) & 0xff) << 8
     if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
         opts.ev_loop_start = int(loop_events[0].cuda_event)
         opts.ev_loop_stop = int(loop_events[1].cuda_event)
-    ws_bytes = int(L.evc_learn_workspace_bytes(M, R, T, dcode))
-    if ws_bytes == 0:
-        raise ValueError(f"unsupported dictionary-learning shape M={M}, R={R}, T={T}")
-    n_slots = 1 + (int(iters) // int(check_every) if check_every > 0 else 0)
+    nbytes = ws_bytes(L, M, R, T, dcode)
+    if nbytes == 0:
+        raise ValueError(unsupported(M, R, T))
     n_iter = C.c_int(0)
-    err = np.full(n_slots, np.nan) if info else None
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
+    trace_name, trace_shape = trace
+    tr = np.full(trace_shape, np.nan) if info else None
+    with torch.cuda.device(device), _workspace(nbytes, device) as ws:
         stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_nmf_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
-                             C.byref(opts), ws.data_ptr(), ws.numel(),
-                             C.byref(n_iter) if (info or tol > 0) else None,
-                             err.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
-    _lib.check(st, "evc_nmf_learn")
+        st = getattr(L, entry)(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
+                               C.byref(opts), ws.data_ptr(), ws.numel(),
+                               C.byref(n_iter) if (info or tol > 0) else None,
+                               tr.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
+    _lib.check(st, entry)
     to_np = x_np and out_w is None and out_h is None
     res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
     if info:
-        res += ({"n_iter": int(n_iter.value), "err": err,
-                 "splits": int(splits) if splits else int(L.evc_learn_splits(M, R, T))},)
+        res += ({"n_iter": int(n_iter.value), trace_name: tr, **extra_info(L, M, R, T)},)
     return res
+
+
+def _splits_info(query, splits):
+    """the `splits` field of info: what the caller forced, else the library's own choice"""
+    return lambda L, M, R, T: {"splits": int(splits) if splits else int(getattr(L, query)(M, R, T))}
+
+
+_SURFACES = {"sklearn": _lib.LEARN_SKLEARN, "pymf": _lib.LEARN_PYMF}
+
+
+def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every=10, tol=0.0, dtype=None, device=None,
+                     info=False, out_w=None, out_h=None, loop_events=None, splits=0, loss="frobenius"):
+    """Multiplicative updates of BOTH factors, X ~ W H, on the GPU (evc_nmf_learn): W is addressed like the
+    dictionary A of solve_activations, H like its activations.  surface="sklearn": scikit-learn's
+    _fit_multiplicative_update with update_H=True (per iteration H, then W; the error every `check_every` iterations and
+    its stop on `tol`); surface="pymf": pymf's factorize(compute_w=True) (W, then H; columns of W scaled to unit norm).
+    loss: "frobenius" (default), or "kullback-leibler" / "kl" - scikit-learn's beta_loss='kullback-leibler' updates and
+    error sqrt(2 KL(X || W H)), on the sklearn surface only (pymf has no such update: ValueError).
+
+    Returns (W, H) in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out); with
+    info=True also dict(n_iter=int, err=[1 + iters // check_every] errors (the first at the start; NaN where not
+    evaluated), splits=frame ranges of the dictionary update's sums).  out_w / out_h: device tensors updated in place
+    (they then hold the start, W0 / H0 are ignored when None).  splits: tuning and tests, 1..64 frame ranges.
+    No CPU fallback: without a HIP device this raises RuntimeError."""
+    if loss not in _LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_LOSSES)}, got {loss!r}")
+    if _LOSSES[loss] == _lib.LOSS_KL and surface == "pymf":
+        raise ValueError("the pymf surface has no Kullback-Leibler update; use surface='sklearn'")
+    opts = _lib.LearnOpts()
+    opts.surface, opts.loss = _SURFACES[surface], _LOSSES[loss]
+    opts.iters, opts.check_every, opts.tol = int(iters), int(check_every), float(tol)
+    n_slots = 1 + (int(iters) // int(check_every) if check_every > 0 else 0)
+    return _learn("evc_nmf_learn", opts, X, W0, H0, layout=layout,
+                  ws_bytes=lambda L, M, R, T, dcode: int(L.evc_learn_workspace_bytes(M, R, T, dcode)),
+                  unsupported=lambda M, R, T: f"unsupported dictionary-learning shape M={M}, R={R}, T={T}",
+                  trace=("err", n_slots), extra_info=_splits_info("evc_learn_splits", splits), tol=tol, dtype=dtype,
+                  device=device, info=info, out_w=out_w, out_h=out_h, loop_events=loop_events, splits=splits)
 
 
 _BETA_ROUTES = {None: 0, "fused": 1, "unfused": 2}
@@ -652,59 +671,23 @@ def learn_dictionary_beta(X, W0, H0, *, beta, layout, iters, check_every=10, tol
     if len(xshape) == 2 and xshape[0 if lay == _lib.BIN_MAJOR else 1] > _lib.BETA_MAX_M:     # what the ABI answers with -3
         raise ValueError(f"unsupported beta-divergence shape: M = {xshape[0 if lay == _lib.BIN_MAJOR else 1]} bins, the "
                          f"kernel holds at most {_lib.BETA_MAX_M}")
-    torch = _torch()
-    device = require_device(device)
-    L = _lib.lib()
-    tdtype, dcode = _pick_dtype(dtype, X, W0 if W0 is not None else out_w)
-    X_d, x_np = _to_dev(X, tdtype, device)
-    M, T = X_d.shape if lay == _lib.BIN_MAJOR else X_d.shape[::-1]
-
-    def start(a0, out, what):
-        if out is not None:
-            if a0 is not None:
-                out.copy_(_to_dev(a0, tdtype, device)[0])
-            if out.dtype != tdtype or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
-                raise ValueError(f"`out_{what}` must be a device matrix of the call's dtype with unit inner stride")
-            return out
-        a_d, _ = _to_dev(a0, tdtype, device)
-        if isinstance(a0, torch.Tensor) and a_d.data_ptr() == a0.data_ptr():
-            a_d = a_d.clone()       # never clobber the caller's start
-        return a_d
-
-    W_d, H_d = start(W0, out_w, "w"), start(H0, out_h, "h")
-    M2, R = W_d.shape if lay == _lib.BIN_MAJOR else W_d.shape[::-1]
-    R2, T2 = H_d.shape if lay == _lib.BIN_MAJOR else H_d.shape[::-1]
-    if M2 != M or R2 != R or T2 != T:
-        raise ValueError(f"X {tuple(X_d.shape)}, W {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
     opts = _lib.BetaLearnOpts()
-    opts.struct_bytes = C.sizeof(_lib.BetaLearnOpts)
-    opts.dtype, opts.layout, opts.iters, opts.check_every = dcode, lay, int(iters), int(check_every)
-    opts.reserved = ((int(splits) & 0xff) << 8) | (_BETA_ROUTES[route] << 16)
+    opts.iters, opts.check_every = int(iters), int(check_every)
+    opts.reserved = _BETA_ROUTES[route] << 16
     opts.beta, opts.tol = beta, float(tol)
     opts.l1_h, opts.l2_h, opts.l1_w, opts.l2_w = float(l1_h), float(l2_h), float(l1_w), float(l2_w)
-    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
-        opts.ev_loop_start = int(loop_events[0].cuda_event)
-        opts.ev_loop_stop = int(loop_events[1].cuda_event)
-    ws_bytes = int(L.evc_beta_learn_workspace_bytes(M, R, T, dcode))
-    if ws_bytes == 0:
-        raise ValueError(f"unsupported beta-divergence learning shape M={M}, R={R}, T={T} (M <= {_lib.BETA_MAX_M}, R <= 4096)")
     n_slots = 1 + (int(iters) // int(check_every) if check_every > 0 else 0)
-    n_iter = C.c_int(0)
-    err = np.full(n_slots, np.nan) if info else None
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_beta_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
-                              C.byref(opts), ws.data_ptr(), ws.numel(),
-                              C.byref(n_iter) if (info or tol > 0) else None,
-                              err.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
-    _lib.check(st, "evc_beta_learn")
-    to_np = x_np and out_w is None and out_h is None
-    res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
-    if info:
-        res += ({"n_iter": int(n_iter.value), "err": err,
-                 "splits": int(splits) if splits else int(L.evc_beta_learn_splits(M, R, T)),
-                 "route": route or ("fused", "unfused")[int(L.evc_beta_learn_route(M, R, T)) - 1]},)
-    return res
+
+    def extra_info(L, M, R, T):
+        return dict(_splits_info("evc_beta_learn_splits", splits)(L, M, R, T),
+                    route=route or ("fused", "unfused")[int(L.evc_beta_learn_route(M, R, T)) - 1])
+
+    return _learn("evc_beta_learn", opts, X, W0, H0, layout=layout,
+                  ws_bytes=lambda L, M, R, T, dcode: int(L.evc_beta_learn_workspace_bytes(M, R, T, dcode)),
+                  unsupported=lambda M, R, T: f"unsupported beta-divergence learning shape M={M}, R={R}, T={T} "
+                                              f"(M <= {_lib.BETA_MAX_M}, R <= 4096)",
+                  trace=("err", n_slots), extra_info=extra_info, tol=tol, dtype=dtype, device=device, info=info,
+                  out_w=out_w, out_h=out_h, loop_events=loop_events, splits=splits)
 
 
 _CDL_UPDATES = {"both": _lib.CDL_BOTH, "dict": _lib.CDL_DICT_ONLY}
@@ -737,57 +720,16 @@ def learn_dictionary_cd(X, W0, H0, *, layout, max_iter=200, tol=1e-4, l1_h=0.0, 
     RuntimeError."""
     if update not in _CDL_UPDATES:
         raise ValueError(f"update must be one of {sorted(_CDL_UPDATES)}, got {update!r}")
-    torch = _torch()
-    device = require_device(device)
-    L = _lib.lib()
-    lay = _LAYOUTS[layout]
-    tdtype, dcode = _pick_dtype(dtype, X, W0 if W0 is not None else out_w)
-    X_d, x_np = _to_dev(X, tdtype, device)
-    M, T = X_d.shape if lay == _lib.BIN_MAJOR else X_d.shape[::-1]
-
-    def start(a0, out, what):
-        if out is not None:
-            if a0 is not None:
-                out.copy_(_to_dev(a0, tdtype, device)[0])
-            if out.dtype != tdtype or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
-                raise ValueError(f"`out_{what}` must be a device matrix of the call's dtype with unit inner stride")
-            return out
-        a_d, _ = _to_dev(a0, tdtype, device)
-        if isinstance(a0, torch.Tensor) and a_d.data_ptr() == a0.data_ptr():
-            a_d = a_d.clone()       # never clobber the caller's start
-        return a_d
-
-    W_d, H_d = start(W0, out_w, "w"), start(H0, out_h, "h")
-    M2, R = W_d.shape if lay == _lib.BIN_MAJOR else W_d.shape[::-1]
-    R2, T2 = H_d.shape if lay == _lib.BIN_MAJOR else H_d.shape[::-1]
-    if M2 != M or R2 != R or T2 != T:
-        raise ValueError(f"X {tuple(X_d.shape)}, W {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
     opts = _lib.CdLearnOpts()
-    opts.struct_bytes = C.sizeof(_lib.CdLearnOpts)
-    opts.dtype, opts.layout, opts.max_iter, opts.update = dcode, lay, int(max_iter), _CDL_UPDATES[update]
-    opts.reserved = (int(splits) & 0xff) << 8
+    opts.max_iter, opts.update = int(max_iter), _CDL_UPDATES[update]
     opts.tol, opts.l1_h, opts.l2_h, opts.l1_w, opts.l2_w = float(tol), float(l1_h), float(l2_h), float(l1_w), float(l2_w)
-    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
-        opts.ev_loop_start = int(loop_events[0].cuda_event)
-        opts.ev_loop_stop = int(loop_events[1].cuda_event)
-    ws_bytes = _cd_learn_workspace(L, M, R, T, dcode, splits)
-    if ws_bytes == 0:
-        raise ValueError(f"unsupported coordinate-descent learning shape M={M}, R={R}, T={T} (M, R <= 1024)")
-    n_iter = C.c_int(0)
-    viol = np.full((max(int(max_iter), 0), 2), np.nan) if info else None
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_cd_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
-                            C.byref(opts), ws.data_ptr(), ws.numel(),
-                            C.byref(n_iter) if (info or tol > 0) else None,
-                            viol.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
-    _lib.check(st, "evc_cd_learn")
-    to_np = x_np and out_w is None and out_h is None
-    res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
-    if info:
-        res += ({"n_iter": int(n_iter.value), "violation": viol,
-                 "splits": int(splits) if splits else int(L.evc_cd_learn_splits(M, R, T))},)
-    return res
+    return _learn("evc_cd_learn", opts, X, W0, H0, layout=layout,
+                  ws_bytes=lambda L, M, R, T, dcode: _cd_learn_workspace(L, M, R, T, dcode, splits),
+                  unsupported=lambda M, R, T: f"unsupported coordinate-descent learning shape M={M}, R={R}, T={T} "
+                                              f"(M, R <= 1024)",
+                  trace=("violation", (max(int(max_iter), 0), 2)), extra_info=_splits_info("evc_cd_learn_splits", splits),
+                  tol=tol, dtype=dtype, device=device, info=info, out_w=out_w, out_h=out_h, loop_events=loop_events,
+                  splits=splits)
 
 
 def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepared=False, dtype=None, device=None,
