@@ -939,14 +939,6 @@ template <typename T> size_t workspace_typed(int M, int Mb, int N, int T_, int n
     return b;
 }
 
-bool utt_offsets_ok(const int* utt_offsets, int n_utt, int T) {
-    if (!utt_offsets) return n_utt == 1;
-    if (utt_offsets[0] != 0 || utt_offsets[n_utt] != T) return false;
-    for (int i = 0; i < n_utt; ++i)
-        if (utt_offsets[i + 1] < utt_offsets[i]) return false;
-    return true;
-}
-
 template <typename T>
 hipError_t synthesize_typed(const void* B_, int ldb, const void* H_, int ldh, void* Y_, int ldy, int Mb, int N, int T_,
                             bool fm, hipStream_t s) {
@@ -1396,36 +1388,6 @@ int evc_dtw_gather_rows(const void* src, long ld_src, int elem_stride, const int
     else
         return ST_BADARG;
     return ST_OK;
-}
-
-size_t evc_cd_workspace_bytes(int M, int N, int T, int n_utt, int dtype) {
-    if (dtype != EVC_F64 && dtype != EVC_F32) return 0;
-    return cd_workspace_bytes(M, N, T, n_utt, dtype == EVC_F64 ? 8 : 4);
-}
-
-int evc_cd_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
-                 const int* utt_offsets, int n_utt, const evc_cd_opts* opts, void* workspace, size_t workspace_bytes,
-                 int* n_iter_out, double* violation_out, evc_stream_t stream) {
-    if (!opts || opts->struct_bytes != (int)sizeof(evc_cd_opts)) return ST_BADARG;
-    const evc_cd_opts& o = *opts;
-    if (M < 1 || N < 1 || T < 0 || n_utt < 1 || o.max_iter < 0 || o.reserved != 0) return ST_BADARG;
-    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return ST_BADARG;
-    if (o.layout != EVC_FRAME_MAJOR && o.layout != EVC_BIN_MAJOR) return ST_BADARG;
-    if (o.init_mode != EVC_INIT_SKLEARN && o.init_mode != EVC_INIT_GIVEN) return ST_BADARG;
-    if (!(o.tol >= 0.0) || !(o.l1 >= 0.0) || !(o.l2 >= 0.0)) return ST_BADARG;
-    if (!A || !X || !H || !workspace) return ST_BADARG;
-    if (bad_ld(o.layout, lda, N, M) || bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldh, T, N)) return ST_BADARG;
-    if (!utt_offsets_ok(utt_offsets, n_utt, T)) return ST_BADARG;
-    if (M > CD_MAX_M) return ST_UNSUPPORTED;
-    if (workspace_bytes < evc_cd_workspace_bytes(M, N, T, n_utt, o.dtype)) return ST_WORKSPACE;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (o.dtype == EVC_F64)
-        return cd_solve<double>(static_cast<const double*>(A), lda, static_cast<const double*>(X), ldx,
-                                static_cast<double*>(H), ldh, M, N, T, utt_offsets, n_utt, o, workspace,
-                                workspace_bytes, n_iter_out, violation_out, s, nullptr);
-    return cd_solve<float>(static_cast<const float*>(A), lda, static_cast<const float*>(X), ldx, static_cast<float*>(H),
-                           ldh, M, N, T, utt_offsets, n_utt, o, workspace, workspace_bytes, n_iter_out, violation_out, s,
-                           nullptr);
 }
 
 }  // extern "C"

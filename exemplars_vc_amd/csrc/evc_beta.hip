@@ -319,14 +319,14 @@ __global__ void k_beta_fill(T* __restrict__ H, long hs_t, long hs_n, int N, cons
 
 unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 
-// [Ap1 | Ap3 | Xp | errf | tiles | utt_tile0 | utt_frames | stop | h0 | einit | eprev | trace], each 256-byte aligned; the
-// tile count is bounded by ceil(T / 16) + n_utt whatever the split into utterances (ws == NULL: sizes only)
+// [Ap1 | Ap3 | Xp | errf | tiles | utt_tile0 | utt_frames | stop | h0 | einit | eprev | trace], each 256-byte aligned
+// (ws == NULL: sizes only)
 template <typename T>
 BetaWs<T> carve_beta(void* ws, int M, int N, int T_, int n_utt) {
     BetaWs<T> w;
     Carver c = Carver::rounded(ws);
     const size_t MP = (size_t)round_up(M, 16), NP = (size_t)round_up(N, 16);
-    const size_t nt = (size_t)(T_ + BT_F - 1) / BT_F + n_utt;
+    const size_t nt = (size_t)frame_tile_cap(T_, BT_F, n_utt);
     w.Ap1 = c.take<T>(NP * MP);
     w.Ap3 = c.take<T>(NP * MP);
     w.Xp = c.take<T>(nt * MP * BT_F);
@@ -365,34 +365,9 @@ int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, 
     c.n_slots = n_slots;
     c.fm = fm ? 1 : 0;
 
-    // the tile table (host, staged by hipMemcpyAsync from pageable memory at enqueue time)
-    int n_tiles = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        const int tu = utt_offsets ? utt_offsets[u + 1] - utt_offsets[u] : T_;
-        n_tiles += (tu + BT_F - 1) / BT_F;
-    }
+    int n_tiles;
+    HIP_TRY(frame_tiles_stage(BT_F, utt_offsets, n_utt, T_, w.tiles, w.utt_tile0, w.utt_frames, s, &n_tiles));
     c.n_tiles = n_tiles;
-    {
-        int4* h_tiles = static_cast<int4*>(malloc(sizeof(int4) * (n_tiles > 0 ? n_tiles : 1) + sizeof(int) * (2 * n_utt + 1)));
-        if (!h_tiles) return (int)hipErrorOutOfMemory;
-        int* h_t0 = reinterpret_cast<int*>(h_tiles + (n_tiles > 0 ? n_tiles : 1));
-        int* h_fr = h_t0 + n_utt + 1;
-        int t = 0;
-        for (int u = 0; u < n_utt; ++u) {
-            const int f0 = utt_offsets ? utt_offsets[u] : 0;
-            const int tu = utt_offsets ? utt_offsets[u + 1] - f0 : T_;
-            h_t0[u] = t;
-            h_fr[u] = tu;
-            for (int i = 0; i < tu; i += BT_F) h_tiles[t++] = make_int4(u, f0 + i, tu - i < BT_F ? tu - i : BT_F, 0);
-        }
-        h_t0[n_utt] = t;
-        hipError_t e = hipSuccess;
-        if (n_tiles > 0) e = hipMemcpyAsync(w.tiles, h_tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(w.utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(w.utt_frames, h_fr, sizeof(int) * n_utt, hipMemcpyHostToDevice, s);
-        free(h_tiles);      // pageable source: HIP has staged the bytes by the time hipMemcpyAsync returns
-        HIP_TRY(e);
-    }
     hipLaunchKernelGGL(k_beta_state_init, dim3(blocks_of((long)n_utt * n_slots)), dim3(256), 0, s, w.stop, w.trace, n_utt,
                        n_slots);
     HIP_TRY(hipGetLastError());
@@ -511,14 +486,6 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
     return 0;
 }
 
-bool beta_offsets_ok(const int* utt_offsets, int n_utt, int T_) {
-    if (!utt_offsets) return n_utt == 1;
-    if (utt_offsets[0] != 0 || utt_offsets[n_utt] != T_) return false;
-    for (int i = 0; i < n_utt; ++i)
-        if (utt_offsets[i + 1] < utt_offsets[i]) return false;
-    return true;
-}
-
 }  // namespace
 
 }  // namespace evc
@@ -535,17 +502,13 @@ int evc_beta_solve(const void* A, int lda, const void* X, int ldx, void* H, int 
     using namespace evc;
     if (!opts || opts->struct_bytes != (int)sizeof(evc_beta_opts)) return ST_BADARG;
     const evc_beta_opts& o = *opts;
-    if (M < 1 || N < 1 || T < 0 || n_utt < 1 || o.iters < 0 || o.check_every < 0 || o.reserved != 0) return ST_BADARG;
-    if (o.dtype != EVC_F64 && o.dtype != EVC_F32) return ST_BADARG;
-    const bool fm = o.layout == EVC_FRAME_MAJOR;
-    if (!fm && o.layout != EVC_BIN_MAJOR) return ST_BADARG;
+    HIP_TRY(solve_args_ok(M, N, T, n_utt, o.dtype, o.layout, A, workspace, lda, ldx, ldh, utt_offsets));
+    if (o.iters < 0 || o.check_every < 0 || o.reserved != 0) return ST_BADARG;
     if (o.init_mode != EVC_INIT_GIVEN && o.init_mode != EVC_INIT_SKLEARN && o.init_mode != EVC_INIT_CONST) return ST_BADARG;
     if (o.stop_rule != EVC_STOP_NONE && o.stop_rule != EVC_STOP_SKLEARN) return ST_BADARG;
     if (!(o.beta - o.beta == 0.0)) return ST_BADARG;                      // NaN or infinite
     if (!(o.tol >= 0.0) || !(o.l1 >= 0.0) || !(o.l2 >= 0.0) || !(o.init_value - o.init_value == 0.0)) return ST_BADARG;
-    if (!A || !workspace || (T > 0 && (!X || !H))) return ST_BADARG;       // no frames: X and H are never touched
-    if (bad_ld(o.layout, lda, N, M) || bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldh, T, N)) return ST_BADARG;
-    if (!beta_offsets_ok(utt_offsets, n_utt, T)) return ST_BADARG;
+    if (T > 0 && (!X || !H)) return ST_BADARG;                             // no frames: X and H are never touched
     if (o.check_every > 0 && o.iters / o.check_every + 1 > BETA_MAX_SLOTS) return ST_BADARG;
     if (M > BETA_MAX_M) return ST_UNSUPPORTED;
     if (workspace_bytes < beta_workspace_bytes(M, N, T, n_utt, o.dtype)) return ST_WORKSPACE;

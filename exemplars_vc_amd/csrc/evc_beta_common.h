@@ -53,7 +53,7 @@ template <typename T> struct BetaArgs {
     const T* Xp;            // [n_tiles][MP][16] frames of a tile, zero-padded
     T* H;
     long hs_t, hs_n;        // H(n, t) = H[t * hs_t + n * hs_n]
-    const int4* tiles;      // {utterance, first frame, frames, -}
+    const int4* tiles;      // {utterance, first frame, frames, first tile of the utterance: no beta kernel reads .w}
     const int* stop;        // [n_utt] 0: running; else the iteration the utterance stopped at
     double* errf;           // [n_tiles * 16] per-frame share of the divergence
     int M, MP, N, NP;

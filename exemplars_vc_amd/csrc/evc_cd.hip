@@ -276,12 +276,12 @@ template <typename T> struct CdWs {
 };
 
 // The workspace: [Ac | Gb | hess | R | tiles | utt_tile0 | part | stop | vinit | trace], each 256-byte aligned (ws == NULL:
-// sizes only).  The tile count is bounded by ceil(T / F) + n_utt whatever the split into utterances.
+// sizes only).
 template <typename T> CdWs<T> carve_cd(void* ws, const CdGeometry& g, int N, int T_, int n_utt) {
     CdWs<T> w;
     Carver c = Carver::rounded(ws);
     const size_t Np = (size_t)round_up(N, CD_B);
-    const size_t nt = (size_t)(T_ + g.F - 1) / g.F + n_utt;
+    const size_t nt = (size_t)frame_tile_cap(T_, g.F, n_utt);
     w.Ac = c.take<T>(Np * g.Mr);
     w.Gb = c.take<T>(Np * CD_B);
     w.hess = c.take<T>(Np);
@@ -313,39 +313,10 @@ int cd_setup(T* H, int ldh, int M, int N, int T_, const int* utt_offsets, int n_
              double l1, double l2, void* ws, size_t ws_bytes, hipStream_t s, CdArgs<T>* out) {
     const CdGeometry g = cd_geometry(M);
     const int Np = round_up(N, CD_B);
-    // tiles: each utterance starts at a tile boundary
-    int n_tiles = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        const int tu = utt_offsets ? utt_offsets[u + 1] - utt_offsets[u] : T_;
-        n_tiles += (tu + g.F - 1) / g.F;
-    }
-    const int nt_cap = (T_ + g.F - 1) / g.F + n_utt;
-    if (n_tiles > nt_cap) return ST_BADARG;
     const CdWs<T> w = carve_cd<T>(ws, g, N, T_, n_utt);
     if (w.bytes > ws_bytes) return ST_WORKSPACE;
-
-    // the tile table (host, staged by hipMemcpyAsync from pageable memory at enqueue time)
-    int4* h_tiles = static_cast<int4*>(malloc(sizeof(int4) * (n_tiles > 0 ? n_tiles : 1) + sizeof(int) * (n_utt + 1)));
-    if (!h_tiles) return (int)hipErrorOutOfMemory;
-    int* h_t0 = reinterpret_cast<int*>(h_tiles + (n_tiles > 0 ? n_tiles : 1));
-    {
-        int t = 0;
-        for (int u = 0; u < n_utt; ++u) {
-            const int f0 = utt_offsets ? utt_offsets[u] : 0;
-            const int tu = utt_offsets ? utt_offsets[u + 1] - f0 : T_;
-            h_t0[u] = t;
-            for (int i = 0; i < tu; i += g.F) {
-                h_tiles[t] = make_int4(u, f0 + i, tu - i < g.F ? tu - i : g.F, h_t0[u]);
-                ++t;
-            }
-        }
-        h_t0[n_utt] = t;
-    }
-    hipError_t e = hipSuccess;
-    if (n_tiles > 0) e = hipMemcpyAsync(w.tiles, h_tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(w.utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
-    free(h_tiles);      // pageable source: HIP has staged the bytes by the time hipMemcpyAsync returns
-    HIP_TRY(e);
+    int n_tiles;
+    HIP_TRY(frame_tiles_stage(g.F, utt_offsets, n_utt, T_, w.tiles, w.utt_tile0, nullptr, s, &n_tiles));
     {
         const long n = (long)n_utt * CD_TRACE_CAP;
         hipLaunchKernelGGL(k_cd_state_init, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.stop, w.vinit, w.trace,
@@ -383,8 +354,7 @@ int cd_refresh(const CdArgs<T>& a, const T* A, int lda, const T* X, int ldx, int
     return 0;
 }
 
-}  // namespace
-
+// arguments already validated by evc_cd_solve; returns 0, -1, -2 or a hipError_t
 template <typename T>
 int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
              int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
@@ -453,18 +423,12 @@ int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int
     return 0;
 }
 
-template int cd_solve<double>(const double*, int, const double*, int, double*, int, int, int, int, const int*, int,
-                              const evc_cd_opts&, void*, size_t, int*, double*, hipStream_t, int*);
-template int cd_solve<float>(const float*, int, const float*, int, float*, int, int, int, int, const int*, int,
-                             const evc_cd_opts&, void*, size_t, int*, double*, hipStream_t, int*);
-
 // ---- evc_cd_learn: the alternating form (sklearn solver='cd', update_H=True), DESIGN.md §5.8 ----
 //
 // Per iteration the activation half is one k_cd_sweep launch (k = 1: no judging) on the freshly packed dictionary, and
 // the dictionary half is sklearn's _update_coordinate_descent(X^T, H^T, W) in Gram form: G = H H^T + l2 I and
 // P = X H^T - l1 come from k_dict_grad's one-operand contraction (frames split into S ranges, partial sums added in
 // ascending order by k_cdl_finish), then k_cd_dict_sweep runs the M independent row sweeps.
-namespace {
 
 template <typename T> struct CdDictArgs {
     const T* G;             // [Rp][ld] H H^T + l2 I, rows and columns past R zero
@@ -770,6 +734,32 @@ bool cd_learn_sizes_ok(int M, int R, int T, int dtype) {
 using namespace evc;
 
 extern "C" {
+
+size_t evc_cd_workspace_bytes(int M, int N, int T, int n_utt, int dtype) {
+    if (dtype != EVC_F64 && dtype != EVC_F32) return 0;
+    return cd_workspace_bytes(M, N, T, n_utt, dtype == EVC_F64 ? 8 : 4);
+}
+
+int evc_cd_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
+                 const int* utt_offsets, int n_utt, const evc_cd_opts* opts, void* workspace, size_t workspace_bytes,
+                 int* n_iter_out, double* violation_out, evc_stream_t stream) {
+    if (!opts || opts->struct_bytes != (int)sizeof(evc_cd_opts)) return ST_BADARG;
+    const evc_cd_opts& o = *opts;
+    HIP_TRY(solve_args_ok(M, N, T, n_utt, o.dtype, o.layout, A, workspace, lda, ldx, ldh, utt_offsets));
+    if (o.max_iter < 0 || o.reserved != 0 || !X || !H) return ST_BADARG;
+    if (o.init_mode != EVC_INIT_SKLEARN && o.init_mode != EVC_INIT_GIVEN) return ST_BADARG;
+    if (!(o.tol >= 0.0) || !(o.l1 >= 0.0) || !(o.l2 >= 0.0)) return ST_BADARG;
+    if (M > CD_MAX_M) return ST_UNSUPPORTED;
+    if (workspace_bytes < evc_cd_workspace_bytes(M, N, T, n_utt, o.dtype)) return ST_WORKSPACE;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (o.dtype == EVC_F64)
+        return cd_solve<double>(static_cast<const double*>(A), lda, static_cast<const double*>(X), ldx,
+                                static_cast<double*>(H), ldh, M, N, T, utt_offsets, n_utt, o, workspace,
+                                workspace_bytes, n_iter_out, violation_out, s, nullptr);
+    return cd_solve<float>(static_cast<const float*>(A), lda, static_cast<const float*>(X), ldx, static_cast<float*>(H),
+                           ldh, M, N, T, utt_offsets, n_utt, o, workspace, workspace_bytes, n_iter_out, violation_out, s,
+                           nullptr);
+}
 
 int evc_cd_learn_splits(int M, int R, int T) {
     return cd_learn_sizes_ok(M, R, T, EVC_F64) ? learn_splits(M, R, T) : 0;

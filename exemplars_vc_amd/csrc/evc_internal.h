@@ -157,6 +157,61 @@ struct Carver {
     size_t bytes() const { return shift + ((off + 255) & ~size_t(255)); }
 };
 
+// utterance u is frames [utt_offsets[u], utt_offsets[u + 1]) of the call's T_; NULL: the call is one utterance
+// (evc_nmf_solve / evc_nmf_convert, evc_cd_solve, evc_beta_solve)
+inline bool utt_offsets_ok(const int* utt_offsets, int n_utt, int T_) {
+    if (!utt_offsets) return n_utt == 1;
+    if (utt_offsets[0] != 0 || utt_offsets[n_utt] != T_) return false;
+    for (int i = 0; i < n_utt; ++i)
+        if (utt_offsets[i + 1] < utt_offsets[i]) return false;
+    return true;
+}
+
+// The frame-tile table of k_cd_sweep and the beta kernels: every utterance starts a tile of its own, a tile is up to F of
+// its frames, {x: utterance, y: first frame, z: frames, w: first tile of the utterance}.  k_cd_sweep reads .w; the beta
+// kernels ignore it.  utt_tile0[u] is utterance u's first tile ([n_utt]: the tile count), utt_frames[u] its frames.
+// The count is at most frame_tile_cap whatever the split into utterances.
+inline int frame_tile_cap(int T_, int F, int n_utt) { return (T_ + F - 1) / F + n_utt; }
+
+// The table on the host: no HIP call, no global state.  Returns the tile count; tiles == NULL only counts, and either of
+// the other two arrays may be NULL.
+inline int frame_tiles(int F, const int* utt_offsets, int n_utt, int T_, int4* tiles, int* utt_tile0, int* utt_frames) {
+    int t = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        const int f0 = utt_offsets ? utt_offsets[u] : 0;
+        const int tu = utt_offsets ? utt_offsets[u + 1] - f0 : T_;
+        const int t0 = t;
+        if (utt_tile0) utt_tile0[u] = t0;
+        if (utt_frames) utt_frames[u] = tu;
+        for (int i = 0; i < tu; i += F, ++t)
+            if (tiles) tiles[t] = make_int4(u, f0 + i, tu - i < F ? tu - i : F, t0);
+    }
+    if (utt_tile0) utt_tile0[n_utt] = t;
+    return t;
+}
+
+// ... and staged to the device arrays (d_utt_frames may be NULL) on `s`, from pageable memory: HIP has copied the bytes by
+// the time hipMemcpyAsync returns, so the host table is freed here.  ST_OK, ST_BADARG (more tiles than the workspace was
+// carved for) or a hipError_t.
+inline int frame_tiles_stage(int F, const int* utt_offsets, int n_utt, int T_, int4* d_tiles, int* d_utt_tile0,
+                             int* d_utt_frames, hipStream_t s, int* n_tiles_out) {
+    const int n_tiles = frame_tiles(F, utt_offsets, n_utt, T_, nullptr, nullptr, nullptr);
+    if (n_tiles > frame_tile_cap(T_, F, n_utt)) return ST_BADARG;
+    int4* h_tiles = static_cast<int4*>(malloc(sizeof(int4) * (n_tiles > 0 ? n_tiles : 1) + sizeof(int) * (2 * n_utt + 1)));
+    if (!h_tiles) return (int)hipErrorOutOfMemory;
+    int* h_t0 = reinterpret_cast<int*>(h_tiles + (n_tiles > 0 ? n_tiles : 1));
+    int* h_fr = h_t0 + n_utt + 1;
+    frame_tiles(F, utt_offsets, n_utt, T_, h_tiles, h_t0, h_fr);
+    hipError_t e = hipSuccess;
+    if (n_tiles > 0) e = hipMemcpyAsync(d_tiles, h_tiles, sizeof(int4) * n_tiles, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_utt_tile0, h_t0, sizeof(int) * (n_utt + 1), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && d_utt_frames)
+        e = hipMemcpyAsync(d_utt_frames, h_fr, sizeof(int) * n_utt, hipMemcpyHostToDevice, s);
+    free(h_tiles);
+    *n_tiles_out = n_tiles;
+    return (int)e;
+}
+
 // ----- evc_gemm.hip -----
 // C[I x J] = L[I x Kd] * R[J x Kd]^T, all row-major, I % 128 == 0, J % 64 == 0, Kd % 16 == 0.
 // scratch (optional, scratch_elems elements): lets a small-grid, long-K product be split over K.
@@ -447,11 +502,6 @@ struct CdGeometry {
 };
 CdGeometry cd_geometry(int M);
 size_t cd_workspace_bytes(int M, int N, int T_, int n_utt, int esize);
-// arguments already validated by evc_cd_solve; returns 0, -1, -2 or a hipError_t
-template <typename T>
-int cd_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, int N, int T_, const int* utt_offsets,
-             int n_utt, const evc_cd_opts& o, void* ws, size_t ws_bytes, int* n_iter_out, double* violation_out,
-             hipStream_t s, int* launches_out);
 
 // evc_cd_learn (entry and driver in evc_cd.hip): the alternating form
 constexpr int CD_LEARN_MAX_R = 1024;  // 64 lanes x 16 components per lane; keeps learn_bin_tiles(R) within evc_nmf_learn's
@@ -503,6 +553,17 @@ inline int learn_args_ok(int M, int R, int T_, int dtype, int layout, const void
     if (!X || !W || !H || !ws) return ST_BADARG;
     if (bad_ld(layout, ldx, T_, M) || bad_ld(layout, ldw, R, M) || bad_ld(layout, ldh, T_, R)) return ST_BADARG;
     return ST_OK;
+}
+
+// ... and what evc_cd_solve and evc_beta_solve check alike.  The struct_bytes test, the option ranges, the NULL rule of X
+// and H (evc_cd_solve refuses NULL even without frames, evc_beta_solve does not) and the limits stay with each entry.
+inline int solve_args_ok(int M, int N, int T_, int n_utt, int dtype, int layout, const void* A, const void* ws, int lda,
+                         int ldx, int ldh, const int* utt_offsets) {
+    if (M < 1 || N < 1 || T_ < 0 || n_utt < 1 || (dtype != EVC_F64 && dtype != EVC_F32)) return ST_BADARG;
+    if (layout != EVC_FRAME_MAJOR && layout != EVC_BIN_MAJOR) return ST_BADARG;
+    if (!A || !ws) return ST_BADARG;
+    if (bad_ld(layout, lda, N, M) || bad_ld(layout, ldx, T_, M) || bad_ld(layout, ldh, T_, N)) return ST_BADARG;
+    return utt_offsets_ok(utt_offsets, n_utt, T_) ? ST_OK : ST_BADARG;
 }
 
 // The check-and-stop loop of the two multiplicative-update drivers.  step() runs one iteration; error_now(slot, &err)

@@ -14,6 +14,7 @@ import contextlib
 import ctypes as C
 import os
 import threading
+import types
 from typing import Optional, Sequence
 
 import numpy as np
@@ -239,6 +240,80 @@ def convert(A, X, B=None, H0=None, *, want_h=True, **kw):
     return _solve(A, X, H0, B, want_h=want_h, **kw)
 
 
+def _operands(A, X, H0, init, layout, dtype, device, utt_offsets, out=None, want_h=True):
+    """What _solve, solve_activations_cd and solve_activations_beta share in front of their C entry.  A: the dictionary
+    or a PreparedDictionary; device: already resolved (require_device).  Returns a namespace of
+      tdtype, dcode, lay     the call's element type (torch, C ABI) and layout code
+      A_d, X_d, x_np         the operands on the device (A_d None for a prepared dictionary), whether X came as numpy
+      M, N, T, hshape        the sizes and the activations' shape in the caller's orientation
+      init, H_d              the start rule ("given" with H0 unless the caller says otherwise, else "sklearn") and the
+                             tensor the entry writes: `out` when given (H0 copied into it), else H0's device copy - cloned
+                             if that is the caller's own tensor - or a fresh one; None when want_h is False and no start is
+                             given
+      n_utt, off_ptr         the utterance count and the int32 offsets for the C ABI (off_arr keeps them alive)"""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    pd = A if isinstance(A, PreparedDictionary) else None
+    tdtype, dcode = _pick_dtype(dtype, X, None if pd is not None else A)
+    A_d = None if pd is not None else _to_dev(A, tdtype, device)[0]
+    X_d, x_np = _to_dev(X, tdtype, device)
+    if lay == _lib.BIN_MAJOR:
+        M, N = (pd.M, pd.N) if pd is not None else A_d.shape
+        M2, T = X_d.shape
+        hshape = (N, T)
+    else:
+        N, M = (pd.N, pd.M) if pd is not None else A_d.shape
+        T, M2 = X_d.shape
+        hshape = (T, N)
+    if M2 != M:
+        raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
+    if init is None:
+        init = "given" if H0 is not None else "sklearn"
+    if init == "given":
+        if H0 is None:
+            raise ValueError("init='given' needs H0")
+        H_d, _ = _to_dev(H0, tdtype, device)
+        if tuple(H_d.shape) != hshape:
+            raise ValueError(f"H0 has shape {tuple(H_d.shape)}, expected {hshape}")
+        if out is not None:
+            out.copy_(H_d)
+            H_d = out
+        elif isinstance(H0, torch.Tensor) and H_d.data_ptr() == H0.data_ptr():
+            H_d = H_d.clone()       # never clobber the caller's H0
+    elif not want_h:
+        H_d = None
+    else:
+        H_d = out if out is not None else torch.empty(hshape, dtype=tdtype, device=device)
+    if H_d is not None and (tuple(H_d.shape) != hshape or H_d.dtype != tdtype
+                            or (H_d.shape[1] > 1 and H_d.stride(1) != 1)):
+        raise ValueError("`out` must be a contiguous device tensor of the activation shape/dtype")
+    if utt_offsets is None:
+        n_utt, off_arr, off_ptr = 1, None, None
+    else:
+        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
+        n_utt = len(off_arr) - 1
+        if n_utt < 1:
+            raise ValueError("utt_offsets needs at least two entries")
+        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
+    return types.SimpleNamespace(tdtype=tdtype, dcode=dcode, lay=lay, A_d=A_d, X_d=X_d, x_np=x_np, M=M, N=N, T=T,
+                                 hshape=hshape, init=init, H_d=H_d, n_utt=n_utt, off_arr=off_arr, off_ptr=off_ptr)
+
+
+def _loop_events(opts, loop_events):
+    """loop_events = (torch.cuda.Event, torch.cuda.Event), already created: recorded around the entry's iteration loop"""
+    if loop_events is not None:
+        opts.ev_loop_start = int(loop_events[0].cuda_event)
+        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+
+
+def _trace_arrays(n_utt, width, info):
+    """(n_iter, trace, their ctypes pointers) an entry fills per utterance when info is asked for; else four None"""
+    if not info:
+        return None, None, None, None
+    n_iter, trace = np.zeros(n_utt, dtype=np.int32), np.full((n_utt, width), np.nan)
+    return n_iter, trace, n_iter.ctypes.data_as(C.POINTER(C.c_int)), trace.ctypes.data_as(C.POINTER(C.c_double))
+
+
 def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=None,
            l1=0.0, algo="auto", init=None, init_value=0.0, check_every=0,
            stop_rule="none", tol=0.0, utt_offsets: Optional[Sequence[int]] = None,
@@ -255,22 +330,10 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
             dtype = pd.tdtype
         if pd.device != device:
             raise ValueError("the prepared dictionary lives on another device")
-        A = None
-    tdtype, dcode = _pick_dtype(dtype, X, A)
-    if pd is not None and (dcode != pd.dcode or _LOSSES[loss] != pd.loss):
-        raise ValueError("the prepared dictionary was made for another dtype / loss")
-    A_d = None if pd is not None else _to_dev(A, tdtype, device)[0]
-    X_d, x_np = _to_dev(X, tdtype, device)
-    if lay == _lib.BIN_MAJOR:
-        M, N = (pd.M, pd.N) if pd is not None else A_d.shape
-        M2, T = X_d.shape
-        hshape = (N, T)
-    else:
-        N, M = (pd.N, pd.M) if pd is not None else A_d.shape
-        T, M2 = X_d.shape
-        hshape = (T, N)
-    if M2 != M:
-        raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
+        if _pick_dtype(dtype)[1] != pd.dcode or _LOSSES[loss] != pd.loss:
+            raise ValueError("the prepared dictionary was made for another dtype / loss")
+    p = _operands(A, X, H0, init, layout, dtype, device, utt_offsets, out, want_h or B is None)
+    tdtype, dcode, A_d, X_d, H_d, M, N, T, n_utt = p.tdtype, p.dcode, p.A_d, p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt
     Mb = 0
     B_d = None
     if B is True:                 # convert() with the prepared dictionary's own B
@@ -285,40 +348,11 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
     if B is not None:
         yshape = (Mb, T) if lay == _lib.BIN_MAJOR else (T, Mb)
         Y_d = out_y if out_y is not None else torch.empty(yshape, dtype=tdtype, device=device)
-    if init is None:
-        init = "given" if H0 is not None else "sklearn"
-    if init == "given":
-        if H0 is None:
-            raise ValueError("init='given' needs H0")
-        H_d, _ = _to_dev(H0, tdtype, device)
-        if tuple(H_d.shape) != hshape:
-            raise ValueError(f"H0 has shape {tuple(H_d.shape)}, expected {hshape}")
-        if out is not None:
-            out.copy_(H_d)
-            H_d = out
-        elif isinstance(H0, torch.Tensor) and H_d.data_ptr() == H0.data_ptr():
-            H_d = H_d.clone()       # never clobber the caller's H0
-    elif B is not None and not want_h:
-        H_d = None
-    else:
-        H_d = out if out is not None else torch.empty(hshape, dtype=tdtype, device=device)
-    if H_d is not None and (tuple(H_d.shape) != hshape or H_d.dtype != tdtype
-                            or (H_d.shape[1] > 1 and H_d.stride(1) != 1)):
-        raise ValueError("`out` must be a contiguous device tensor of the activation shape/dtype")
-
-    if utt_offsets is None:
-        n_utt, off_arr, off_ptr = 1, None, None
-    else:
-        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
-        n_utt = len(off_arr) - 1
-        if n_utt < 1:
-            raise ValueError("utt_offsets needs at least two entries")
-        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
 
     opts = _lib.SolveOpts()
     opts.struct_bytes = C.sizeof(_lib.SolveOpts)
     opts.dtype, opts.layout, opts.algo = dcode, lay, _ALGOS[algo]
-    opts.iters, opts.eps_mode, opts.init_mode = int(iters), _EPS_MODES[eps_mode], _INITS[init]
+    opts.iters, opts.eps_mode, opts.init_mode = int(iters), _EPS_MODES[eps_mode], _INITS[p.init]
     opts.check_every, opts.stop_rule = int(check_every), _STOPS[stop_rule]
     opts.eps = _EPS_DEFAULT[eps_mode] if eps is None else float(eps)
     opts.l1, opts.tol, opts.init_value = float(l1), float(tol), float(init_value)
@@ -344,16 +378,10 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
         if loss in ("kl", "kullback-leibler") and opts.eps != pd.eps:
             raise ValueError("the prepared dictionary's KL guard differs from this call's eps")
         opts.dict = C.addressof(pd.handle)
-    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
-        opts.ev_loop_start = int(loop_events[0].cuda_event)
-        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    _loop_events(opts, loop_events)
 
     ws_bytes = int(L.evc_workspace_bytes(M, Mb, N, T, n_utt, dcode, opts.algo))
-    n_slots = 1 + (iters // check_every if check_every > 0 else 0)
-    n_iter = np.zeros(n_utt, dtype=np.int32) if info else None
-    err = np.full((n_utt, n_slots), np.nan) if info else None
-    ni_p = n_iter.ctypes.data_as(C.POINTER(C.c_int)) if info else None
-    er_p = err.ctypes.data_as(C.POINTER(C.c_double)) if info else None
+    n_iter, err, ni_p, er_p = _trace_arrays(n_utt, 1 + (iters // check_every if check_every > 0 else 0), info)
     h_ptr, h_ld = (H_d.data_ptr(), _ld(H_d)) if H_d is not None else (None, 0)
     a_ptr, a_ld = (A_d.data_ptr(), _ld(A_d)) if A_d is not None else (None, 0)
     with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
@@ -361,20 +389,20 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
         if B is None:
             st = L.evc_nmf_solve(
                 a_ptr, a_ld, X_d.data_ptr(), _ld(X_d), h_ptr, h_ld,
-                M, N, T, off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p,
+                M, N, T, p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p,
                 C.c_void_p(stream))
         else:
             st = L.evc_nmf_convert(
                 a_ptr, a_ld, X_d.data_ptr(), _ld(X_d), B_d.data_ptr() if B_d is not None else None,
                 _ld(B_d) if B_d is not None else 0,
-                h_ptr, h_ld, Y_d.data_ptr(), _ld(Y_d), M, Mb, N, T, off_ptr, n_utt, C.byref(opts),
+                h_ptr, h_ld, Y_d.data_ptr(), _ld(Y_d), M, Mb, N, T, p.off_ptr, n_utt, C.byref(opts),
                 ws.data_ptr(), ws.numel(), ni_p, er_p, C.c_void_p(stream))
     _lib.check(st, "evc_nmf_solve" if B is None else "evc_nmf_convert")
-    to_np = x_np and out is None
+    to_np = p.x_np and out is None
     H_out = None if H_d is None else (_to_host(H_d) if to_np else H_d)
     res = [H_out] if B is None else ([H_out] if want_h else [])
     if B is not None:
-        res.append(_to_host(Y_d) if (x_np and out_y is None) else Y_d)
+        res.append(_to_host(Y_d) if (p.x_np and out_y is None) else Y_d)
     variant = _lib.decode_variant(int(sinfo.kernel), int(sinfo.variant))
     if info:
         res.append({"n_iter": n_iter, "err": err, "kernel": _lib.KERNEL_NAMES.get(sinfo.kernel, str(sinfo.kernel)),
@@ -401,57 +429,24 @@ def solve_activations_cd(A, X, H0=None, *, layout="bin_major", max_iter=200, tol
     torch = _torch()
     device = require_device(device)
     L = _lib.lib()
-    lay = _LAYOUTS[layout]
-    tdtype, dcode = _pick_dtype(dtype, X, A)
-    A_d, _ = _to_dev(A, tdtype, device)
-    X_d, x_np = _to_dev(X, tdtype, device)
-    if lay == _lib.BIN_MAJOR:
-        M, N = A_d.shape
-        M2, T = X_d.shape
-        hshape = (N, T)
-    else:
-        N, M = A_d.shape
-        T, M2 = X_d.shape
-        hshape = (T, N)
-    if M2 != M:
-        raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
-    if H0 is not None:
-        H_d, _ = _to_dev(H0, tdtype, device)
-        if tuple(H_d.shape) != hshape:
-            raise ValueError(f"H0 has shape {tuple(H_d.shape)}, expected {hshape}")
-        if isinstance(H0, torch.Tensor) and H_d.data_ptr() == H0.data_ptr():
-            H_d = H_d.clone()       # never clobber the caller's H0
-    else:
-        H_d = torch.empty(hshape, dtype=tdtype, device=device)
-    if utt_offsets is None:
-        n_utt, off_ptr = 1, None
-    else:
-        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
-        n_utt = len(off_arr) - 1
-        if n_utt < 1:
-            raise ValueError("utt_offsets needs at least two entries")
-        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
+    p = _operands(A, X, H0, None, layout, dtype, device, utt_offsets)
+    A_d, X_d, H_d, M, N, T, n_utt, dcode = p.A_d, p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt, p.dcode
     opts = _lib.CdOpts()
     opts.struct_bytes = C.sizeof(_lib.CdOpts)
-    opts.dtype, opts.layout = dcode, lay
+    opts.dtype, opts.layout = dcode, p.lay
     opts.init_mode = _lib.INIT_GIVEN if H0 is not None else _lib.INIT_SKLEARN
     opts.max_iter, opts.tol, opts.l1, opts.l2 = int(max_iter), float(tol), float(l1), float(l2)
-    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
-        opts.ev_loop_start = int(loop_events[0].cuda_event)
-        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    _loop_events(opts, loop_events)
     ws_bytes = int(L.evc_cd_workspace_bytes(M, N, T, n_utt, dcode))
     if ws_bytes == 0:
         raise ValueError(f"unsupported coordinate-descent shape M={M}, N={N}, T={T}")
-    n_iter = np.zeros(n_utt, dtype=np.int32) if info else None
-    viol = np.full((n_utt, max(int(max_iter), 0)), np.nan) if info else None
-    ni_p = n_iter.ctypes.data_as(C.POINTER(C.c_int)) if info else None
-    vi_p = viol.ctypes.data_as(C.POINTER(C.c_double)) if info else None
+    n_iter, viol, ni_p, vi_p = _trace_arrays(n_utt, max(int(max_iter), 0), info)
     with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
         stream = torch.cuda.current_stream(device).cuda_stream
         st = L.evc_cd_solve(A_d.data_ptr(), _ld(A_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, N, T,
-                            off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, vi_p, C.c_void_p(stream))
+                            p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, vi_p, C.c_void_p(stream))
     _lib.check(st, "evc_cd_solve")
-    H_out = _to_host(H_d) if x_np else H_d
+    H_out = _to_host(H_d) if p.x_np else H_d
     if info:
         launches = int(max_iter) + 1 if (T > 0 and max_iter > 0) else 0
         return H_out, {"n_iter": n_iter, "violation": viol, "kernel": "k_cd_sweep", "launches": launches}
@@ -486,62 +481,26 @@ def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100
     torch = _torch()
     device = require_device(device)
     L = _lib.lib()
-    tdtype, dcode = _pick_dtype(dtype, X, A)
-    A_d, _ = _to_dev(A, tdtype, device)
-    X_d, x_np = _to_dev(X, tdtype, device)
-    if lay == _lib.BIN_MAJOR:
-        M, N = A_d.shape
-        M2, T = X_d.shape
-        hshape = (N, T)
-    else:
-        N, M = A_d.shape
-        T, M2 = X_d.shape
-        hshape = (T, N)
-    if M2 != M:
-        raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
+    p = _operands(A, X, H0, init, layout, dtype, device, utt_offsets)
+    A_d, X_d, H_d, M, N, T, n_utt, dcode = p.A_d, p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt, p.dcode
     if M < 1 or N < 1:
         raise ValueError(f"empty beta-divergence problem M={M}, N={N}, T={T}")
-    if init is None:
-        init = "given" if H0 is not None else "sklearn"
-    if init == "given":
-        if H0 is None:
-            raise ValueError("init='given' needs H0")
-        H_d, _ = _to_dev(H0, tdtype, device)
-        if tuple(H_d.shape) != hshape:
-            raise ValueError(f"H0 has shape {tuple(H_d.shape)}, expected {hshape}")
-        if isinstance(H0, torch.Tensor) and H_d.data_ptr() == H0.data_ptr():
-            H_d = H_d.clone()       # never clobber the caller's H0
-    else:
-        H_d = torch.empty(hshape, dtype=tdtype, device=device)
-    if utt_offsets is None:
-        n_utt, off_ptr = 1, None
-    else:
-        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
-        n_utt = len(off_arr) - 1
-        if n_utt < 1:
-            raise ValueError("utt_offsets needs at least two entries")
-        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
     iters, check_every = int(iters), int(check_every)
     opts = _lib.BetaOpts()
     opts.struct_bytes = C.sizeof(_lib.BetaOpts)
-    opts.dtype, opts.layout, opts.iters, opts.init_mode = dcode, lay, iters, _INITS[init]
+    opts.dtype, opts.layout, opts.iters, opts.init_mode = dcode, lay, iters, _INITS[p.init]
     opts.check_every, opts.stop_rule = check_every, _STOPS[stop_rule]
     opts.beta, opts.tol, opts.l1, opts.l2, opts.init_value = beta, float(tol), float(l1), float(l2), float(init_value)
-    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
-        opts.ev_loop_start = int(loop_events[0].cuda_event)
-        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    _loop_events(opts, loop_events)
     ws_bytes = int(L.evc_beta_workspace_bytes(M, N, T, n_utt, dcode))
     n_slots = 1 + (iters // check_every if check_every > 0 else 0)
-    n_iter = np.zeros(n_utt, dtype=np.int32) if info else None
-    err = np.full((n_utt, n_slots), np.nan) if info else None
-    ni_p = n_iter.ctypes.data_as(C.POINTER(C.c_int)) if info else None
-    er_p = err.ctypes.data_as(C.POINTER(C.c_double)) if info else None
+    n_iter, err, ni_p, er_p = _trace_arrays(n_utt, n_slots, info)
     with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
         stream = torch.cuda.current_stream(device).cuda_stream
         st = L.evc_beta_solve(A_d.data_ptr(), _ld(A_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, N, T,
-                              off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p, C.c_void_p(stream))
+                              p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p, C.c_void_p(stream))
     _lib.check(st, "evc_beta_solve")
-    H_out = _to_host(H_d) if x_np else H_d
+    H_out = _to_host(H_d) if p.x_np else H_d
     if info:
         launches = iters + 2 * n_slots * (check_every > 0) if T > 0 else 0
         return H_out, {"n_iter": n_iter, "err": err, "kernel": "k_beta_sweep", "launches": launches}
@@ -583,9 +542,7 @@ def _learn(entry, opts, X, W0, H0, *, layout, ws_bytes, unsupported, trace, extr
     opts.struct_bytes = C.sizeof(opts)
     opts.dtype, opts.layout = dcode, lay
     opts.reserved |= (int(splits) & 0xff) << 8
-    if loop_events is not None:     # (torch.cuda.Event, torch.cuda.Event), already created
-        opts.ev_loop_start = int(loop_events[0].cuda_event)
-        opts.ev_loop_stop = int(loop_events[1].cuda_event)
+    _loop_events(opts, loop_events)
     nbytes = ws_bytes(L, M, R, T, dcode)
     if nbytes == 0:
         raise ValueError(unsupported(M, R, T))
