@@ -265,7 +265,7 @@ __global__ void k_dtw_offsets(const int* __restrict__ aoff, const int* __restric
     }
 }
 
-size_t dtw_workspace_bytes(const int* aoff, const int* boff, int n_pairs) {
+static size_t dtw_workspace_bytes(const int* aoff, const int* boff, int n_pairs) {
     size_t cells = 0;
     for (int p = 0; p < n_pairs; ++p)
         cells += (size_t)dtw_tiles(aoff[p + 1] - aoff[p], boff[p + 1] - boff[p]) * DTW_TILE;
@@ -273,11 +273,11 @@ size_t dtw_workspace_bytes(const int* aoff, const int* boff, int n_pairs) {
 }
 
 // LDS of k_dtw_accumulate: (nti + ntj) x 64 border values + 3 (ntj + 1) corners; both utterances of a pair at the limit
-int dtw_max_frames() { return 64 * 120; }
+static int dtw_max_frames() { return 64 * 120; }
 
-hipError_t dtw_run(const double* A, long lda, const int* aoff, const double* B, long ldb, const int* boff,
-                   int D, int n_pairs, int* path_a, int* path_b, int* path_len, double* total, void* ws,
-                   hipStream_t s) {
+static hipError_t dtw_run(const double* A, long lda, const int* aoff, const double* B, long ldb, const int* boff,
+                          int D, int n_pairs, int* path_a, int* path_b, int* path_len, double* total, void* ws,
+                          hipStream_t s) {
     char* p = static_cast<char*>(ws);
     int* d_aoff = reinterpret_cast<int*>(p); p += (((size_t)(n_pairs + 1) * sizeof(int)) + 255) & ~size_t(255);
     int* d_boff = reinterpret_cast<int*>(p); p += (((size_t)(n_pairs + 1) * sizeof(int)) + 255) & ~size_t(255);
@@ -379,23 +379,81 @@ __global__ __launch_bounds__(256) void k_gather_pairs(const T* __restrict__ src,
     }
 }
 
-hipError_t dtw_path_scan(const int* path_len, int n_pairs, int* row_start, hipStream_t s) {
+static hipError_t dtw_path_scan(const int* path_len, int n_pairs, int* row_start, hipStream_t s) {
     hipLaunchKernelGGL(k_path_scan, dim3(1), dim3(1024), 0, s, path_len, n_pairs, row_start);
     return hipGetLastError();
 }
 
 template <typename T>
-hipError_t dtw_gather(const T* src, long ld_src, int elem_stride, const int* path, const int* path_len, const int* src_off,
-                      const int* pair_off, const int* row_start, int n_pairs, int cols, int op, T* dst, long ld_dst,
-                      hipStream_t s) {
+static hipError_t dtw_gather(const T* src, long ld_src, int elem_stride, const int* path, const int* path_len,
+                             const int* src_off, const int* pair_off, const int* row_start, int n_pairs, int cols, int op,
+                             T* dst, long ld_dst, hipStream_t s) {
     const unsigned gx = (unsigned)((cols + 255) / 256);
     hipLaunchKernelGGL((k_gather_pairs<T>), dim3(gx > 4 ? 4 : gx, 64, (unsigned)n_pairs), dim3(256), 0, s, src, ld_src,
                        elem_stride, path, path_len, src_off, pair_off, row_start, cols, op, dst, ld_dst);
     return hipGetLastError();
 }
-template hipError_t dtw_gather<double>(const double*, long, int, const int*, const int*, const int*, const int*, const int*,
-                                       int, int, int, double*, long, hipStream_t);
-template hipError_t dtw_gather<float>(const float*, long, int, const int*, const int*, const int*, const int*, const int*,
-                                      int, int, int, float*, long, hipStream_t);
 
 }  // namespace evc
+
+using namespace evc;
+
+// ---- the C entries (include/evc.h) ----
+static bool dtw_offsets_ok(const int* off, int n_pairs) {
+    if (!off || off[0] != 0) return false;
+    for (int p = 0; p < n_pairs; ++p)
+        if (off[p + 1] < off[p] || off[p + 1] - off[p] > dtw_max_frames()) return false;
+    return true;
+}
+
+extern "C" {
+
+size_t evc_dtw_workspace_bytes(const int* a_offsets, const int* b_offsets, int n_pairs) {
+    if (n_pairs < 1 || !dtw_offsets_ok(a_offsets, n_pairs) || !dtw_offsets_ok(b_offsets, n_pairs)) return 0;
+    return dtw_workspace_bytes(a_offsets, b_offsets, n_pairs);
+}
+
+int evc_dtw_align(const void* A, int lda, const int* a_offsets, const void* B, int ldb,
+                  const int* b_offsets, int D, int n_pairs, int* path_a, int* path_b, int* path_len,
+                  double* total, void* workspace, size_t workspace_bytes, evc_stream_t stream) {
+    if (n_pairs < 1 || D < 1 || lda < D || ldb < D) return ST_BADARG;
+    if (D > 512 || n_pairs > 65535) return ST_UNSUPPORTED;     // LDS tile of the cost kernel; grid z
+    if (!dtw_offsets_ok(a_offsets, n_pairs) || !dtw_offsets_ok(b_offsets, n_pairs)) return ST_BADARG;
+    if (!A || !B || !path_a || !path_b || !path_len || !workspace) return ST_BADARG;
+    if (workspace_bytes < dtw_workspace_bytes(a_offsets, b_offsets, n_pairs)) return ST_WORKSPACE;
+    return (int)dtw_run(static_cast<const double*>(A), lda, a_offsets, static_cast<const double*>(B), ldb,
+                        b_offsets, D, n_pairs, path_a, path_b, path_len, total, workspace,
+                        reinterpret_cast<hipStream_t>(stream));
+}
+
+int evc_dtw_path_rows(const int* path_len, int n_pairs, int* row_start, int* n_rows_out, evc_stream_t stream) {
+    if (!path_len || !row_start || n_pairs < 1 || n_pairs > 65535) return ST_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(dtw_path_scan(path_len, n_pairs, row_start, s));
+    if (n_rows_out) {
+        HIP_TRY(hipMemcpyAsync(n_rows_out, row_start + n_pairs, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return ST_OK;
+}
+
+int evc_dtw_gather_rows(const void* src, long ld_src, int elem_stride, const int* path, const int* path_len,
+                        const int* src_offsets, const int* pair_offsets, const int* row_start, int n_pairs, int cols,
+                        int op, void* dst, long ld_dst, int dtype, evc_stream_t stream) {
+    if (!src || !path || !path_len || !src_offsets || !pair_offsets || !row_start || !dst) return ST_BADARG;
+    if (n_pairs < 1 || n_pairs > 65535 || cols < 1 || elem_stride < 1 || ld_dst < cols) return ST_BADARG;
+    if (ld_src < (long)(cols - 1) * elem_stride + 1) return ST_BADARG;
+    if (op != EVC_GATHER_COPY && op != EVC_GATHER_ABS) return ST_BADARG;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (dtype == EVC_F64)
+        HIP_TRY(dtw_gather<double>(static_cast<const double*>(src), ld_src, elem_stride, path, path_len, src_offsets,
+                                   pair_offsets, row_start, n_pairs, cols, op, static_cast<double*>(dst), ld_dst, s));
+    else if (dtype == EVC_F32)
+        HIP_TRY(dtw_gather<float>(static_cast<const float*>(src), ld_src, elem_stride, path, path_len, src_offsets,
+                                  pair_offsets, row_start, n_pairs, cols, op, static_cast<float*>(dst), ld_dst, s));
+    else
+        return ST_BADARG;
+    return ST_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,8 @@
-// Fused, persistent FACTORED multiplicative update for short dictionaries (M <= 32 bins,
-// float64): the headline kernel of the C2 / C5 configurations (M = 25).
+// Fused, persistent FACTORED multiplicative update for short dictionaries (M <= 32 bins, float64): k_fused_mu, the general
+// kernel of the family.  The headline configurations (M = 25) run on k_fused_all (evc_fused_all.hip) since round 2; this
+// kernel serves what that one and k_fused_res do not take (plan_route, evc_solve_plan.h), the workgroups that hold frames
+// of stopped utterances behind them, and the V = A H / Y = B H pre-passes.  The packing kernels, the import / export of
+// the packed activations and fused_iterate, which launches whichever kernel the route names, are below it.
 //
 //   per iteration, per frame column h (N values):   v = A h            (M values)
 //                                                    d = A^T v, p = A^T x
@@ -511,23 +514,30 @@ static hipError_t launch_general(const FusedLayout& f, const FusedArgs& a, int c
     }
 }
 
+// The arguments every launch of the fused kernels starts from: the operands and sizes, and every switch off (no exchange,
+// no in-kernel start, no tail).  A field added to FusedArgs is off here, once.
+static FusedArgs fused_args(const FusedLayout& f, const double* A1p, const double* A2p, const double* Xp, const double* Hp,
+                            double* Vp, const UttState& u, int N, int T_, int iters, int first) {
+    FusedArgs a{};
+    a.A1p = A1p; a.A2p = A2p; a.Xp = Xp; a.Hp = reinterpret_cast<f64x2*>(const_cast<double*>(Hp)); a.Vp = Vp;
+    a.frame_utt = u.frame_utt; a.active = u.active;
+    a.NT = f.NT; a.TT = f.TT; a.N = N; a.T_ = T_; a.M = f.M;
+    a.iters = iters; a.first = first;
+    a.coop_c = 1; a.spare_q = -1;
+    return a;
+}
+
 // r: the kernel and the member count plan_route chose for this attempt (r.c_req: 0 = automatic, 1 / 2 = the general
 // kernel with that many frame tiles per workgroup: tests, A/B timing).
 // all_live_known: no stopping rule is in force, so every utterance is active for the whole call.
+// tail: the last launch of such a solve only (plan_fused_tail decides), else NULL.
 hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const FusedRoute& r, const UttState& u, int N,
                          int T_, int iters, int first, int write_err, double* err2, int eps_mode, double eps, double l1,
-                         int all_live_known, int loss, hipStream_t s) {
-    FusedArgs a;
-    a.A1p = b.A1p; a.A2p = b.A2p; a.Xp = b.Xp; a.Hp = reinterpret_cast<f64x2*>(b.Hp); a.Vp = b.Vp;
-    a.err2 = err2; a.frame_utt = u.frame_utt; a.active = u.active;
-    a.NT = f.NT; a.TT = f.TT; a.N = N; a.T_ = T_;
-    a.iters = iters; a.first = first; a.write_err = write_err; a.skip_all_live = 0; a.force_live = 0;
+                         int all_live_known, int loss, hipStream_t s, const FusedLaunchTail* tail) {
+    FusedArgs a = fused_args(f, b.A1p, b.A2p, b.Xp, b.Hp, b.Vp, u, N, T_, iters, first);
+    a.err2 = err2; a.write_err = write_err;
     a.loss = loss; a.exact_div = r.exact_div;
     a.eps_mode = eps_mode; a.eps = eps; a.l1 = l1;
-    a.coop_c = 1; a.coop_buf = nullptr; a.coop_cnt = nullptr; a.coop_abort = nullptr; a.groups = 0;
-    a.init_const = 0; a.h0 = nullptr; a.rsum = nullptr; a.Hx = nullptr; a.ldhx = 0; a.hx_frame_major = 0;
-    a.hx_wide = 0; a.Yb2p = nullptr; a.Yslab = nullptr; a.y_stride = 0; a.y_mt = 0; a.skip_hp = 0;
-    a.M = f.M; a.spare_q = -1; a.stagger_cycles = 0;
     const bool xy = r.kernel == EVC_KERNEL_FUSED_XY;
     const bool all_res = xy || r.kernel == EVC_KERNEL_FUSED_ALL;
     if (r.kernel == EVC_KERNEL_FUSED_MU) return launch_general(f, a, r.c_req, s);
@@ -547,11 +557,12 @@ hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const Fuse
     if (all_res) {
         a.coop_c = r.members; a.coop_buf = b.coop_buf; a.coop_cnt = b.coop_cnt;
         a.coop_abort = b.coop_cnt + COOP_MAX_TILES;
-        if (all_live_known) {
-            a.Hx = b.Hx; a.ldhx = b.ldhx; a.hx_frame_major = b.hx_frame_major;
+        if (all_live_known && tail) {
+            a.Hx = tail->Hx; a.ldhx = tail->ldhx; a.hx_frame_major = tail->hx_frame_major;
             a.hx_wide = (a.Hx && a.hx_frame_major && !(reinterpret_cast<uintptr_t>(a.Hx) & 15) && !(a.ldhx & 1)) ? 1 : 0;
-            if (!xy) {       // the tail of k_fused_all's last launch (solve_fused decides; k_fused_xy has none)
-                a.Yb2p = b.Yb2p; a.Yslab = b.Yslab; a.y_stride = b.y_stride; a.y_mt = b.y_mt; a.skip_hp = b.skip_hp;
+            if (!xy) {       // the rest of the tail is k_fused_all's (k_fused_xy has none)
+                a.Yb2p = tail->Yb2p; a.Yslab = tail->Yslab; a.y_stride = tail->y_stride; a.y_mt = tail->y_mt;
+                a.skip_hp = tail->skip_hp;
             }
         }
         e = xy ? fused_xy_launch(f.msteps, a, r.n_cus, s) : fused_all_launch(f.msteps, a, r.n_cus, s);
@@ -574,17 +585,8 @@ hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const Fuse
 hipError_t fused_synthesize(const FusedLayout& fB, const double* B2p, const double* Hp, double* Yp,
                             const UttState& u, int N, int T_, int Mb, double* Y, long ldy, int frame_major,
                             hipStream_t s) {
-    FusedArgs a;
-    a.A1p = B2p; a.A2p = B2p; a.Xp = Yp;        // A1p / Xp are not used by a pure pre-pass
-    a.Hp = reinterpret_cast<f64x2*>(const_cast<double*>(Hp)); a.Vp = Yp;
-    a.err2 = nullptr; a.frame_utt = u.frame_utt; a.active = u.active;
-    a.NT = fB.NT; a.TT = fB.TT; a.N = N; a.T_ = T_;
-    a.iters = 0; a.first = 1; a.write_err = 0; a.skip_all_live = 0; a.force_live = 1; a.loss = EVC_LOSS_FROBENIUS; a.exact_div = 0;
-    a.Hx = nullptr; a.ldhx = 0; a.hx_frame_major = 0;
-    a.hx_wide = 0; a.Yb2p = nullptr; a.Yslab = nullptr; a.y_stride = 0; a.y_mt = 0; a.skip_hp = 0;
-    a.init_const = 0; a.h0 = nullptr; a.rsum = nullptr; a.M = fB.M; a.spare_q = -1; a.stagger_cycles = 0;
-    a.coop_c = 1; a.coop_buf = nullptr; a.coop_cnt = nullptr; a.coop_abort = nullptr; a.groups = 0;
-    a.eps_mode = EVC_EPS_ADD; a.eps = 0; a.l1 = 0;
+    FusedArgs a = fused_args(fB, B2p, B2p, Yp, Hp, Yp, u, N, T_, 0, 1);     // A1p / Xp are not used by a pure pre-pass
+    a.force_live = 1; a.loss = EVC_LOSS_FROBENIUS; a.eps_mode = EVC_EPS_ADD;
     hipError_t e = dispatch_msteps<1>(fB.msteps, a, s);
     if (e != hipSuccess) return e;
     return fused_unpack_y(fB, Yp, 1, 0, T_, Mb, Y, ldy, frame_major, s);

@@ -34,7 +34,7 @@
 // has read every peer's words of the exchange in between, which the peer published after reading this member's words
 // of the exchange before).  Every member sums in the same order: all obtain the bitwise identical V'.  Every wait is
 // bounded (all_polls_out); a member that gives up raises coop_abort, everybody leaves, and the host redoes the solve
-// without inter-workgroup communication (evc_api.hip).
+// without inter-workgroup communication (solve_checked, evc_api.hip).
 //
 // Which exchange (pick_c; template C > 0: that many members, C <= 0: member count at run time):
 //   direct (C = 2, 4, 8; 8 only where the dictionary is in LDS): every member fetches every peer's partial,

@@ -178,7 +178,7 @@ static int gl_gap(int F, int hop) { return (F + hop - 1) / hop; }
 // virtual rows of a batch whose utterances hold T_total frames
 static long gl_virtual_rows(long T_total, int n_utt, int F, int hop) { return T_total + (long)(n_utt - 1) * gl_gap(F, hop); }
 
-size_t gl_workspace_bytes(long T_total, int n_utt, int F, int hop, int iters) {
+static size_t gl_workspace_bytes(long T_total, int n_utt, int F, int hop, int iters) {
     const long R = gl_virtual_rows(T_total, n_utt, F, hop);
     if (R > (1L << 30)) return 0;
     const GlDims d = gl_dims((int)R, F, hop);
@@ -198,8 +198,8 @@ __global__ void k_gl_single_offsets(int* off, int T_) {
     off[1] = T_;
 }
 
-hipError_t gl_run(const double* mag, long ldm, const int* off, int n_utt, int F, int hop, int iters, double* x,
-                  void* ws, double* rmse_host, hipStream_t s) {
+static hipError_t gl_run(const double* mag, long ldm, const int* off, int n_utt, int F, int hop, int iters, double* x,
+                         void* ws, double* rmse_host, hipStream_t s) {
     const int G = gl_gap(F, hop);
     const GlDims d = gl_dims((int)gl_virtual_rows(off[n_utt], n_utt, F, hop), F, hop);
     double* p = static_cast<double*>(ws);
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256) void k_stft_split(const double* __restrict__ S
     im[t * ldim + k] = i;
 }
 
-int stft_frames(long L, int hop, bool center, int F) {
+static int stft_frames(long L, int hop, bool center, int F) {
     if (center) return (int)(1 + L / hop);
     return L < F ? 0 : (int)(1 + (L - F) / hop);
 }
@@ -331,13 +331,13 @@ hipError_t stft_forward_table(int F, int hop, double* Wf, hipStream_t s) {
     return hipGetLastError();
 }
 
-size_t stft_workspace_bytes(long L, int F, int hop, bool center) {
+static size_t stft_workspace_bytes(long L, int F, int hop, bool center) {
     const GlDims d = stft_dims(L, F, hop, center);
     return ((size_t)d.J1 * d.K1 + 9 * (size_t)d.Tp * d.J1 + (size_t)d.Lp + 128) * sizeof(double) + 4 * 256;
 }
 
-hipError_t stft_run(const double* x, long L, int F, int hop, bool center, double* re, long ldre, double* im,
-                    long ldim, void* ws, hipStream_t s) {
+static hipError_t stft_run(const double* x, long L, int F, int hop, bool center, double* re, long ldre, double* im,
+                           long ldim, void* ws, hipStream_t s) {
     const int T_ = stft_frames(L, hop, center, F);
     if (T_ <= 0) return hipSuccess;
     const GlDims d = stft_dims(L, F, hop, center);
@@ -364,3 +364,74 @@ hipError_t stft_run(const double* x, long L, int F, int hop, bool center, double
 }
 
 }  // namespace evc
+
+using namespace evc;
+
+// ---- the C entries (include/evc.h) ----
+static bool gl_offsets_ok(const int* off, int n_utt) {
+    if (!off || n_utt < 1 || off[0] != 0) return false;
+    for (int u = 0; u < n_utt; ++u)
+        if (off[u + 1] < off[u]) return false;
+    return true;
+}
+
+extern "C" {
+
+size_t evc_griffin_lim_workspace_bytes(int T, int fft_size, int hop, int iters) {
+    if (T < 1 || fft_size < 2 || (fft_size & 1) || hop < 1 || iters < 0) return 0;
+    return gl_workspace_bytes(T, 1, fft_size, hop, iters);
+}
+
+int evc_griffin_lim(const void* mag, int ldm, int T, int fft_size, int hop, int iters, void* x,
+                    void* workspace, size_t workspace_bytes, double* rmse_out, evc_stream_t stream) {
+    if (T < 0) return ST_BADARG;
+    const int off[2] = {0, T};
+    return evc_griffin_lim_batch(mag, ldm, off, 1, fft_size, hop, iters, x, workspace, workspace_bytes, rmse_out,
+                                 stream);
+}
+
+size_t evc_griffin_lim_batch_workspace_bytes(const int* frame_offsets, int n_utt, int fft_size, int hop, int iters) {
+    if (!gl_offsets_ok(frame_offsets, n_utt) || frame_offsets[n_utt] < 1 || fft_size < 2 || (fft_size & 1) ||
+        hop < 1 || iters < 0)
+        return 0;
+    return gl_workspace_bytes(frame_offsets[n_utt], n_utt, fft_size, hop, iters);
+}
+
+int evc_griffin_lim_batch(const void* mag, int ldm, const int* frame_offsets, int n_utt, int fft_size, int hop,
+                          int iters, void* x, void* workspace, size_t workspace_bytes, double* rmse_out,
+                          evc_stream_t stream) {
+    if (!gl_offsets_ok(frame_offsets, n_utt) || fft_size < 2 || (fft_size & 1) || hop < 1 || iters < 0)
+        return ST_BADARG;
+    if (frame_offsets[n_utt] == 0) return ST_OK;
+    if (!mag || !x || !workspace || ldm < fft_size / 2 + 1) return ST_BADARG;
+    const size_t need = gl_workspace_bytes(frame_offsets[n_utt], n_utt, fft_size, hop, iters);
+    if (need == 0) return ST_BADARG;
+    if (workspace_bytes < need) return ST_WORKSPACE;
+    return (int)gl_run(static_cast<const double*>(mag), ldm, frame_offsets, n_utt, fft_size, hop, iters,
+                       static_cast<double*>(x), workspace, rmse_out, reinterpret_cast<hipStream_t>(stream));
+}
+
+int evc_stft_frames(long n_samples, int fft_size, int hop, int center) {
+    if (n_samples < 1 || fft_size < 2 || (fft_size & 1) || hop < 1) return 0;
+    return stft_frames(n_samples, hop, center != 0, fft_size);
+}
+
+size_t evc_stft_workspace_bytes(long n_samples, int fft_size, int hop, int center) {
+    if (n_samples < 1 || fft_size < 2 || (fft_size & 1) || hop < 1) return 0;
+    return stft_workspace_bytes(n_samples, fft_size, hop, center != 0);
+}
+
+int evc_stft(const void* x, long n_samples, int fft_size, int hop, int center, void* re, int ldre, void* im,
+             int ldim, void* workspace, size_t workspace_bytes, evc_stream_t stream) {
+    if (n_samples < 0 || fft_size < 2 || (fft_size & 1) || hop < 1) return ST_BADARG;
+    if (n_samples > (1L << 31) - 4096) return ST_BADARG;        // frame counts are ints
+    if (n_samples == 0 || stft_frames(n_samples, hop, center != 0, fft_size) == 0) return ST_OK;
+    const int nb = fft_size / 2 + 1;
+    if (!x || !re || !im || !workspace || ldre < nb || ldim < nb) return ST_BADARG;
+    if (workspace_bytes < stft_workspace_bytes(n_samples, fft_size, hop, center != 0)) return ST_WORKSPACE;
+    return (int)stft_run(static_cast<const double*>(x), n_samples, fft_size, hop, center != 0,
+                         static_cast<double*>(re), ldre, static_cast<double*>(im), ldim, workspace,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

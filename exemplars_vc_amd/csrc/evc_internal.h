@@ -308,7 +308,7 @@ int fused_all_members(int NT, int N, int eps_mode, int exact_div, int loss);
 // workgroups per PAIR of frame tiles k_fused_xy (evc_fused_xy.hip) uses for this problem; 0: it does not apply
 int fused_xy_members(int NT, int N, int eps_mode, int exact_div, int loss);
 bool fused_res_supported(int N, int eps_mode, int exact_div);
-// The M <= 32 part of a solve's route: decided once per attempt (plan_route, evc_api.hip); fused_iterate launches what it
+// The M <= 32 part of a solve's route: decided once per attempt (plan_route, evc_solve_plan.h); fused_iterate launches what it
 // says and evc_solve_info reports the same fields
 struct FusedRoute {
     int kernel;            // EVC_KERNEL_FUSED_MU | FUSED_RES | FUSED_ALL | FUSED_XY
@@ -324,10 +324,14 @@ struct FusedBuffers {
     double* coop_buf;      // exchange buffers of the cooperative launch (see k_fused_res)
     int* coop_cnt;         // [COOP_MAX_TILES] arrival counters, then one abort flag
     double* rsum;          // [32] row sums of the dictionary (k_fused_all's in-kernel start)
-    double* Hx;            // k_fused_all's last launch also writes the caller's H (NULL: off); ldhx, hx_frame_major
+};
+// What the last launch of a solve in which nothing can stop does beyond the updates (plan_fused_tail, evc_solve_plan.h,
+// decides; every other launch passes none); see FusedArgs
+struct FusedLaunchTail {
+    double* Hx;            // the launch also writes the caller's H (NULL: off); ldhx, hx_frame_major
     long ldhx;
     int hx_frame_major;
-    // k_fused_all's last launch also forms the members' shares of Y = B H (Yslab NULL: off), see FusedArgs
+    // k_fused_all only: the launch also forms the members' shares of Y = B H (Yslab NULL: off)
     const double* Yb2p;
     double* Yslab;
     long y_stride;
@@ -364,7 +368,7 @@ hipError_t fused_unpack_y(const FusedLayout& fB, const double* Yp, int members, 
 // Vp from the previous launch); write_err: per-frame squared residuals of the final H -> err2.
 hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const FusedRoute& r, const UttState& u, int N,
                          int T_, int iters, int first, int write_err, double* err2, int eps_mode, double eps, double l1,
-                         int all_live_known, int loss, hipStream_t s);
+                         int all_live_known, int loss, hipStream_t s, const FusedLaunchTail* tail);
 
 // ----- evc_wide.hip -----
 // Fused FACTORED kernel for wide spectra (32 < M <= 208 bins, float32): k_fused_wide, a task queue over
@@ -455,41 +459,9 @@ hipError_t wide_iterate(const Wide64Layout& f, const Wide64Buffers& b, const Utt
 hipError_t wide_err2(const Wide64Layout& f, const Wide64Buffers& b, const UttState& u, int N, int T_, int it, int kl,
                      double eps, double* err2, hipStream_t s);
 
-// ----- evc_gl.hip -----
-size_t gl_workspace_bytes(long T_total, int n_utt, int F, int hop, int iters);
-int stft_frames(long L, int hop, bool center, int F);
-size_t stft_workspace_bytes(long L, int F, int hop, bool center);
-hipError_t stft_run(const double* x, long L, int F, int hop, bool center, double* re, long ldre, double* im,
-                    long ldim, void* ws, hipStream_t s);
-hipError_t gl_run(const double* mag, long ldm, const int* frame_offsets, int n_utt, int F, int hop, int iters, double* x,
-                  void* ws, double* rmse_host, hipStream_t s);
-
+// ----- evc_gl.hip (Griffin-Lim, STFT), evc_mfcc.hip, evc_dtw.hip: entries and drivers sit with their kernels -----
+// W_f with the periodic window alone: the table of evc_mfcc.hip's contraction
 hipError_t stft_forward_table(int F, int hop, double* Wf, hipStream_t s);
-
-// ----- evc_mfcc.hip: MFCC alignment features (evc_mfcc) -----
-constexpr int MFCC_RB = 32;           // virtual rows per workgroup of k_mfcc_mel / k_mfcc_dct; utterances start at multiples
-constexpr int MFCC_QC = 32;           // rows of the DCT basis in LDS at a time
-constexpr int MFCC_CHUNK = 8192;      // rows of S per contraction (a multiple of 128)
-constexpr int MFCC_MAX_MELS = EVC_MFCC_MAX_MELS;   // (MFCC_QC + MFCC_RB) x (n_mels + 1) doubles of LDS: 128.5 KiB of 160
-constexpr int MFCC_MAX_FFT = EVC_MFCC_MAX_FFT;     // 4 x (fft_size / 2 + 1) doubles of LDS: 128 KiB
-// arguments already validated by evc_mfcc
-size_t mfcc_workspace_bytes(const long* sample_offsets, int n_utt, const evc_mfcc_opts& o);
-bool mfcc_has_frames(const long* sample_offsets, int n_utt, const evc_mfcc_opts& o);
-hipError_t mfcc_run(const double* x, const long* sample_offsets, int n_utt, const evc_mfcc_opts& o, double* out, long ldc,
-                    double* re, long ldre, double* im, long ldim, void* ws, hipStream_t s);
-
-// ----- evc_dtw.hip -----
-size_t dtw_workspace_bytes(const int* aoff, const int* boff, int n_pairs);
-int dtw_max_frames();
-hipError_t dtw_run(const double* A, long lda, const int* aoff, const double* B, long ldb, const int* boff,
-                   int D, int n_pairs, int* path_a, int* path_b, int* path_len, double* total, void* ws,
-                   hipStream_t s);
-// aligned-frame gather (evc_dtw.hip): exclusive scan of the path lengths, then rows by the paths
-hipError_t dtw_path_scan(const int* path_len, int n_pairs, int* row_start, hipStream_t s);
-template <typename T>
-hipError_t dtw_gather(const T* src, long ld_src, int elem_stride, const int* path, const int* path_len, const int* src_off,
-                      const int* pair_off, const int* row_start, int n_pairs, int cols, int op, T* dst, long ld_dst,
-                      hipStream_t s);
 
 // ----- evc_cd.hip: coordinate-descent activation solve (evc_cd_solve) -----
 constexpr int CD_MAX_M = 1024;        // 64 lanes x 16 bins per lane

@@ -23,6 +23,12 @@
 
 namespace evc {
 
+constexpr int MFCC_RB = 32;           // virtual rows per workgroup of k_mfcc_mel / k_mfcc_dct; utterances start at multiples
+constexpr int MFCC_QC = 32;           // rows of the DCT basis in LDS at a time
+constexpr int MFCC_CHUNK = 8192;      // rows of S per contraction (a multiple of 128)
+constexpr int MFCC_MAX_MELS = EVC_MFCC_MAX_MELS;   // (MFCC_QC + MFCC_RB) x (n_mels + 1) doubles of LDS: 128.5 KiB of 160
+// (EVC_MFCC_MAX_FFT, checked by mfcc_check: 4 x (fft_size / 2 + 1) doubles of LDS, 128 KiB)
+
 struct MfccDims {
     int F, hop, nb, K1, J1, pad;   // fft size, hop, bins, padded extents of the contraction, reflect padding
     int n_mels, n_mfcc, G;         // G: gap rows ceil(F / hop)
@@ -331,7 +337,7 @@ static bool mfcc_plan(const long* soff, int n_utt, const MfccDims& d, MfccPlan* 
 
 static size_t al32(size_t n) { return (n + 31) & ~size_t(31); }
 
-size_t mfcc_workspace_bytes(const long* soff, int n_utt, const evc_mfcc_opts& o) {
+static size_t mfcc_workspace_bytes(const long* soff, int n_utt, const evc_mfcc_opts& o) {
     const MfccDims d = mfcc_dims(o);
     MfccPlan p;
     if (!mfcc_plan(soff, n_utt, d, &p)) return 0;
@@ -344,13 +350,13 @@ size_t mfcc_workspace_bytes(const long* soff, int n_utt, const evc_mfcc_opts& o)
     return n * sizeof(double) + 256;
 }
 
-bool mfcc_has_frames(const long* soff, int n_utt, const evc_mfcc_opts& o) {
+static bool mfcc_has_frames(const long* soff, int n_utt, const evc_mfcc_opts& o) {
     long frames = 0;
     return mfcc_rows(soff, n_utt, mfcc_dims(o), &frames) > 0 && frames > 0;
 }
 
-hipError_t mfcc_run(const double* x, const long* soff, int n_utt, const evc_mfcc_opts& o, double* out, long ldc,
-                    double* re, long ldre, double* im, long ldim, void* ws, hipStream_t s) {
+static hipError_t mfcc_run(const double* x, const long* soff, int n_utt, const evc_mfcc_opts& o, double* out, long ldc,
+                           double* re, long ldre, double* im, long ldim, void* ws, hipStream_t s) {
     const MfccDims d = mfcc_dims(o);
     MfccPlan pl;
     if (!mfcc_plan(soff, n_utt, d, &pl)) return hipErrorInvalidValue;
@@ -415,3 +421,48 @@ hipError_t mfcc_run(const double* x, const long* soff, int n_utt, const evc_mfcc
 }
 
 }  // namespace evc
+
+using namespace evc;
+
+// ---- the C entries (include/evc.h) ----
+// 0, or the status the options / offsets of an evc_mfcc call earn before anything else is looked at
+static int mfcc_check(const long* soff, int n_utt, const evc_mfcc_opts* o) {
+    if (!o || o->struct_bytes != (int)sizeof(evc_mfcc_opts) || n_utt < 0) return ST_BADARG;
+    if (o->sr < 1 || o->fft_size < 2 || (o->fft_size & 1) || o->hop < 1 || o->n_mels < 1) return ST_BADARG;
+    if (o->n_mfcc < 1 || o->n_mfcc > o->n_mels) return ST_BADARG;
+    const double fmax_ = o->fmax == 0.0 ? 0.5 * o->sr : o->fmax;
+    if (!(o->fmin >= 0.0 && o->fmin < fmax_ && fmax_ <= 0.5 * o->sr) || !(o->amin > 0.0) || o->top_db != o->top_db)
+        return ST_BADARG;
+    if (n_utt > 0) {
+        if (!soff || soff[0] < 0) return ST_BADARG;
+        for (int u = 0; u < n_utt; ++u)
+            if (soff[u + 1] < soff[u]) return ST_BADARG;
+    }
+    if (o->n_mels > EVC_MFCC_MAX_MELS || o->fft_size > EVC_MFCC_MAX_FFT) return ST_UNSUPPORTED;
+    return ST_OK;
+}
+
+extern "C" {
+
+size_t evc_mfcc_workspace_bytes(const long* sample_offsets, int n_utt, const evc_mfcc_opts* opts) {
+    if (mfcc_check(sample_offsets, n_utt, opts) != ST_OK || n_utt < 1) return 0;
+    return mfcc_workspace_bytes(sample_offsets, n_utt, *opts);
+}
+
+int evc_mfcc(const void* x, const long* sample_offsets, int n_utt, const evc_mfcc_opts* opts, void* mfcc, int ldc,
+             void* re, int ldre, void* im, int ldim, void* workspace, size_t workspace_bytes, evc_stream_t stream) {
+    const int st = mfcc_check(sample_offsets, n_utt, opts);
+    if (st != ST_OK) return st;
+    const int nb = opts->fft_size / 2 + 1;
+    if (ldc < opts->n_mfcc || (re && ldre < nb) || (im && ldim < nb)) return ST_BADARG;
+    if (n_utt == 0 || !mfcc_has_frames(sample_offsets, n_utt, *opts)) return ST_OK;
+    if (!x || !mfcc || !workspace) return ST_BADARG;
+    const size_t need = mfcc_workspace_bytes(sample_offsets, n_utt, *opts);
+    if (need == 0) return ST_BADARG;                            // more rows than the int indices hold
+    if (workspace_bytes < need) return ST_WORKSPACE;
+    return (int)mfcc_run(static_cast<const double*>(x), sample_offsets, n_utt, *opts, static_cast<double*>(mfcc), ldc,
+                         static_cast<double*>(re), ldre, static_cast<double*>(im), ldim, workspace,
+                         reinterpret_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -60,7 +60,7 @@
  *         asynchronous (at about half the speed for a lone utterance, ~10 % less for large batches);
  *     (3) evc_nmf_solve / evc_nmf_convert on the task-queue kernels for wide spectra (k_fused_wide: float32,
  *         32 < M <= 208, from one utterance (43 frame tiles) on; k_fused_wide64: float64,
- *         144 < M <= 528, inside the batch windows of use_wide (csrc/evc_api.hip), which keep M <= 176 out:
+ *         144 < M <= 528, inside the batch windows of use_wide (csrc/evc_solve_plan.h), which keep M <= 176 out:
  *         the same round trip, taken BEFORE anything is written to H or Y, so that a solve whose wait ran out is
  *         redone on the two-contraction path from the untouched inputs (evc_solve_info.redo = 1).  Round 3 delivered
  *         NaN under status 0 there.  EVC_FLAG_NO_EXCHANGE routes away from these kernels too.  Batches of up to ~5

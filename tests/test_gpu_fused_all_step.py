@@ -5,7 +5,8 @@ Thread th of the exchanging half owns the elements 2 th and 2 th + 1 of V' (th <
 and 5 have an odd k-step count, so the half's last working wavefront is half filled; M = 1 and 4 leave three of its four
 wavefronts without work, M = 12 and 24 (3 and 6 k-steps) one.  Every shape runs with 2, 4 and 8 members, with and without
 L1, from constant and from given start values.  The sums run in a fixed order (wavefronts, then members), so batch = solo and
-run = re-run hold bitwise, and a voided launch is redone to the result of a call that never exchanged.
+run = re-run hold bitwise, and a voided launch is redone to the result of a call that never exchanged - also where the redo
+must find the caller's start values (float32, widened again) or a prepared dictionary's image as the first attempt did.
 """
 import numpy as np
 import pytest
@@ -83,3 +84,47 @@ def test_a_voided_launch_is_redone_without_exchange(M, N):
     got, ig = evc.solve_activations(p["A"], p["X"], H0.copy(), _fake_coop_timeout=True, info=True, **kw)
     assert ig["redo"] == 1 and ig["exchange"] == 0 and iw["redo"] == 0, (ig, iw)
     assert np.array_equal(got, want)
+
+
+# The one redo path (solve_checked) plans and runs the whole call again.  Two situations in which the second attempt
+# needs something the first one must have left alone: M = 25, N = 1024 (two members: the smallest dictionary that
+# exchanges), one full frame tile and one frame into a second, two launches of two iterations; the flag is up from the
+# start, or goes up in front of the second launch: test_abort_at counts the launches of the loop from 0, so that is 1 (a
+# 2 would never go up in a solve of two launches).
+REDO_KW = dict(iters=4, check_every=2, eps_mode="zero_replace")
+
+
+@pytest.mark.parametrize("fake", [True, 1])
+@pytest.mark.parametrize("frames", [16, 17])
+def test_staged_redo_widens_the_callers_start_again(frames, fake):
+    """float32 on the float64 kernels: the redo widens the caller's H0 a second time, so nothing of the voided attempt may
+    have been narrowed into it"""
+    import torch
+    import exemplars_vc_amd as evc
+    p = oracle().synth_problem(25, 1024, frames, seed=frames)
+    A, X = p["A"].astype(np.float32), p["X"].astype(np.float32)
+    start = (np.random.default_rng(frames).random((1024, frames)) * 0.02 + 1e-4).astype(np.float32)
+    H0 = torch.from_numpy(start).cuda()
+    want, iw = evc.solve_activations(A, X, H0, cooperative=False, info=True, **REDO_KW)
+    out = torch.full_like(H0, -1.0)
+    got, ig = evc.solve_activations(A, X, H0, out=out, _fake_coop_timeout=fake, info=True, **REDO_KW)
+    print(frames, fake, ig, iw)
+    assert ig["redo"] == 1 and ig["exchange"] == 0 and iw["redo"] == 0, (ig, iw)
+    assert got.data_ptr() == out.data_ptr() and np.array_equal(got.cpu().numpy(), want)
+    assert np.array_equal(H0.cpu().numpy(), start)
+
+
+@pytest.mark.parametrize("fake", [True, 1])
+@pytest.mark.parametrize("frames", [16, 17])
+def test_prepared_redo_reuses_the_image(frames, fake):
+    """a prepared dictionary with B (Mb = 25), only Y wanted: the second attempt reads the image the first one read, and
+    forms Y by the pre-pass where the first attempt's last launch would have formed it in the kernel"""
+    import exemplars_vc_amd as evc
+    p = oracle().synth_problem(25, 1024, frames, seed=frames)
+    B = np.random.default_rng(frames + 1).random((25, 1024)) + 0.01
+    pd = evc.prepare_dictionary(p["A"], B, dtype="f64")
+    Yw, iw = evc.convert(pd, p["X"], None, want_h=False, cooperative=False, info=True, **REDO_KW)
+    Y, ig = evc.convert(pd, p["X"], None, want_h=False, _fake_coop_timeout=fake, info=True, **REDO_KW)
+    print(frames, fake, ig, iw)
+    assert ig["redo"] == 1 and ig["prepared"] == 1 and iw["redo"] == 0, (ig, iw)
+    assert np.array_equal(Y, Yw)

@@ -6,7 +6,7 @@ on the same float32 inputs.  Tolerance: float32 trajectories of different summat
 K sqrt(N) 6e-8, hence rtol 2e-3 with an absolute floor of 1e-6 max|H| (north_star asks 1e-4 of the float64 path).
 The exemplar ranges per frame group (c) and the wavefronts per workgroup (W) are forced through the tuning bits so
 that every dependency pattern of the task queue runs: no split, the direct sum of 2-4 partials, the reduce tasks.
-(Small batches are routed to the two-contraction path by default - evc_api.hip, use_wide - so the cases here force
+(Small batches are routed to the two-contraction path by default - evc_solve_plan.h, use_wide - so the cases here force
 the fused kernel through those bits; `fused_w=4` alone means "this kernel, automatic ranges".)"""
 import numpy as np
 import pytest

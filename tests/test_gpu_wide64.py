@@ -51,7 +51,7 @@ def test_wide64_kernel_against_the_oracle(M, N, T, K, c, tpw):
 
 
 def test_wide64_routing_by_batch_size():
-    """(evc_api.hip, use_wide: the fused kernel serves 240 ... 1000 frame tiles, where it beats the two contractions)"""
+    """(evc_solve_plan.h, use_wide: the fused kernel serves 240 ... 1000 frame tiles, where it beats the two contractions)"""
     import exemplars_vc_amd as evc
     o = oracle()
     for T, kernel in ((64, "k_gemm_nt"), (4000, "k_fused_wide64")):

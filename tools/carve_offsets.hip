@@ -9,12 +9,8 @@
 //           -Lexemplars_vc_amd -levc_hip -Wl,-rpath,$PWD/exemplars_vc_amd   # optional: -Xarch_host -fsanitize=address,undefined
 //     ./carve_$u
 //   done
-//
-// -DCARVE_BEFORE_SHARED_CARVER: the signatures the carvers had before they shared evc::Carver (carve_bl took the sizes;
-// the cd solve's carving was inline in cd_setup and has to be hoisted into carve_cd, unchanged, to be reachable).
-#if defined(CARVE_LEARN) && defined(CARVE_BEFORE_SHARED_CARVER)
-#include "../exemplars_vc_amd/csrc/evc_api.hip"       // where evc_nmf_learn's driver used to be
-#elif defined(CARVE_LEARN)
+// (The carvers of the main solve are in a header of their own, csrc/evc_solve_plan.h: tests/solve_plan_host_main.hip.)
+#if defined(CARVE_LEARN)
 #include "../exemplars_vc_amd/csrc/evc_learn.hip"
 #elif defined(CARVE_CD)
 #include "../exemplars_vc_amd/csrc/evc_cd.hip"
@@ -70,11 +66,7 @@ template <typename T> static void one(int M, int R, int T_) {
     }
 #else
     if (M > BETA_MAX_M || R > LEARN_MAX_R) return;
-#if defined(CARVE_BEFORE_SHARED_CARVER)
-    const auto w = carve_bl<T>(g_ws, M, R, T_);
-#else
     const auto w = carve_bl<T>(g_ws, make_dims(es, M, R, T_, 1));
-#endif
     head("carve_bl", M, R, T_, es, w.bytes);
     OFF(w.Xt); OFF(w.Am); OFF(w.Ht); OFF(w.Vt); OFF(w.Q2t); OFF(w.part); OFF(w.beta_ws);
 #endif

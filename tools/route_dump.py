@@ -132,6 +132,9 @@ def solve_cases():
         add("fake=%s_staged" % fake, "f32", 25, 4096, 2, **kw)
         add("fake=%s_wide" % fake, "f32", 201, 4096, 2, **kw)
         add("fake=%s_wide64" % fake, "f64", 513, 1024, 3, **kw)
+        # a widened caller H0 that must survive the first attempt, and a prepared image reused by the second
+        add("fake=%s_staged_given" % fake, "f32", 25, 4096, 2, given=True, **kw)
+        add("fake=%s_prep_all" % fake, "f64", 25, 4096, 2, Mb=25, prepared=True, **kw)
     # k_fused_all, one utterance of 90 frames: every exchange body and both fragment sources.  2 and 4 members (direct,
     # dictionary in LDS), 3 members (ragged slices), M = 12 (ragged, fewer elements than threads), 8 members at M = 28
     # (whole slices, dictionary streamed), 16 members; KL with one member and with 16

@@ -35,7 +35,7 @@ def main():
            "`tools/tune_routing.py` on one MI355X: whole `evc_nmf_solve` calls (import, packing, first pass, K iterations, export of",
            "`H`), device-resident inputs, best of two timed runs after a warm-up; `fused` = `k_fused_wide` (float32) / `k_fused_wide64`",
            "(float64) forced through the tuning bits, `two contractions` = `k_gemm2` / `k_gemm_nt` (`EVC_FLAG_NO_FUSED`). Utterances of",
-           "688 frames.  Raw lines: `r04_tune_routing_k20.jsonl`, `r04_tune_routing_k80.jsonl`.  `use_wide` (`evc_api.hip`) is written",
+           "688 frames.  Raw lines: `r04_tune_routing_k20.jsonl`, `r04_tune_routing_k80.jsonl`.  `use_wide` (`evc_solve_plan.h`) is written",
            "from these tables; the fractions are of whole calls, so they sit below `bench.py`'s loop-only `roofline.frac`.",
            "",
            "Every row is of the final build of round 4 (first tickets by index, later tickets drawn when a task is finished, static",
