@@ -33,7 +33,8 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_learn_workspace_bytes", "evc_learn_splits", "evc_nmf_learn",
            "evc_cd_learn_workspace_bytes", "evc_cd_learn_splits", "evc_cd_learn",
            "evc_mfcc_workspace_bytes", "evc_mfcc", "evc_beta_workspace_bytes", "evc_beta_solve",
-           "evc_beta_learn_workspace_bytes", "evc_beta_learn_splits", "evc_beta_learn_route", "evc_beta_learn")
+           "evc_beta_learn_workspace_bytes", "evc_beta_learn_splits", "evc_beta_learn_route", "evc_beta_learn",
+           "evc_online_workspace_bytes", "evc_online_splits", "evc_online_learn")
 BETA_MAX_M = 528
 MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
@@ -105,6 +106,17 @@ class BetaLearnOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
         ("check_every", C.c_int), ("reserved", C.c_int),
         ("beta", C.c_double), ("tol", C.c_double),
+        ("l1_h", C.c_double), ("l2_h", C.c_double), ("l1_w", C.c_double), ("l2_w", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class OnlineOpts(C.Structure):
+    """Mirror of `evc_online_opts` (include/evc.h): options of the mini-batch dictionary learning."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("batch_size", C.c_int),
+        ("max_iter", C.c_int), ("max_no_improvement", C.c_int), ("resume", C.c_int), ("reserved", C.c_int),
+        ("beta", C.c_double), ("tol", C.c_double), ("forget_factor", C.c_double),
         ("l1_h", C.c_double), ("l2_h", C.c_double), ("l1_w", C.c_double), ("l2_w", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
@@ -297,6 +309,19 @@ def lib():
         C.c_int, C.c_int, C.c_int, C.POINTER(BetaLearnOpts),                # M, R, T, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_online_workspace_bytes.restype = C.c_size_t
+    L.evc_online_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_online_splits.restype = C.c_int
+    L.evc_online_splits.argtypes = [C.c_int] * 3
+    L.evc_online_learn.restype = C.c_int
+    L.evc_online_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, W, H
+        C.c_void_p, C.c_void_p, C.c_int,                                    # acc_a, acc_b, ld_acc
+        C.c_int, C.c_int, C.c_int, C.POINTER(OnlineOpts),                   # M, R, T, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),      # n_iter_out, n_steps_out, trace_out
         C.c_void_p,                                                         # stream
     ]
     _lib = L

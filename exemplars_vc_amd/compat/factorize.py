@@ -15,8 +15,8 @@ import warnings
 
 import numpy as np
 
-from ..solver import (convert as _solve_and_synthesize, learn_dictionary, learn_dictionary_beta, solve_activations,
-                      solve_activations_beta, synthesize)
+from ..solver import (convert as _solve_and_synthesize, learn_dictionary, learn_dictionary_beta, learn_dictionary_online,
+                      solve_activations, solve_activations_beta, synthesize)
 
 try:  # same warning class the reference would raise, when scikit-learn is present
     from sklearn.exceptions import ConvergenceWarning
@@ -199,6 +199,36 @@ def non_negative_factorization_beta(X, W, H, beta_loss, tol=1e-4, max_iter=200, 
                                          l2_h=n_features * alpha_W * (1.0 - l1_ratio), l1_w=n_samples * alpha_H * l1_ratio,
                                          l2_w=n_samples * alpha_H * (1.0 - l1_ratio), device=device, info=True)
     return Wa, Hd, info["n_iter"]
+
+
+def non_negative_factorization_minibatch(X, W, H, *, beta_loss="frobenius", batch_size=1024, max_iter=200, tol=1e-4,
+                                         max_no_improvement=10, forget_factor=0.7, alpha_W=0.0, alpha_H="same",
+                                         l1_ratio=0.0, device=None):
+    """scikit-learn's `MiniBatchNMF(n_components, init='custom', batch_size=..., beta_loss=..., tol=..., max_iter=...,
+    max_no_improvement=..., forget_factor=..., alpha_W=..., alpha_H=..., l1_ratio=..., fresh_restarts=False)
+    .fit_transform(X, W=W, H=H)` on the GPU (evc_online_learn), in scikit-learn's orientation: X (n_samples, n_features),
+    W (n_samples, n_components) the activations, H (n_components, n_features) the dictionary.  Returns (W, H, n_iter,
+    n_steps): what the estimator leaves in the returned W, components_, n_iter_ and n_steps_.  beta <= 0 refuses zeros in X
+    as scikit-learn does.  The penalties of W are scaled by n_features; those of H by the size of each batch, as
+    scikit-learn rescales them per batch.  At most 528 features."""
+    beta = _beta_of(beta_loss)
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError(f"Expected 2D array, got {X.ndim}D array instead")
+    _check_beta_zeros(X, beta)
+    if X.dtype not in (np.float64, np.float32):
+        X = X.astype(np.float64)
+    n_features = X.shape[1]
+    alpha_W = float(alpha_W)
+    alpha_H = alpha_W if isinstance(alpha_H, str) and alpha_H == "same" else float(alpha_H)
+    l1_ratio = float(l1_ratio)
+    Hd, Wa, info = learn_dictionary_online(X, np.asarray(H, dtype=X.dtype), np.asarray(W, dtype=X.dtype), beta=beta,
+                                           layout="frame_major", batch_size=int(batch_size), max_iter=int(max_iter),
+                                           forget_factor=float(forget_factor), tol=float(tol),
+                                           max_no_improvement=max_no_improvement, l1_h=n_features * alpha_W * l1_ratio,
+                                           l2_h=n_features * alpha_W * (1.0 - l1_ratio), l1_w=alpha_H * l1_ratio,
+                                           l2_w=alpha_H * (1.0 - l1_ratio), device=device, info=True)
+    return Wa, Hd, info["n_iter"], info["n_steps"]
 
 
 def factorize_utterances(X_list, W, tol=1e-4, *, device=None, algo="auto", max_iter=MAX_ITER, hint="throughput",

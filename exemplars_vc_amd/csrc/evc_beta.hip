@@ -33,7 +33,8 @@
 //
 // The host steps (beta_begin, beta_pack_dict, beta_sweep, beta_check; evc_beta_common.h) also serve evc_beta_learn, which
 // repacks the dictionary every iteration and sets BetaArgs.flush (an updated activation below it is stored as 0);
-// evc_beta_solve passes 0 and its results are bitwise what they were without the field.
+// evc_beta_solve passes 0 and its results are bitwise what they were without the field.  evc_online_learn hands its
+// batches in as utterances and launches k_beta_sweep / k_beta_err over one batch's tiles (BetaArgs.tile0, 0 elsewhere).
 #include "evc_beta_common.h"
 
 namespace evc {
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_beta_sweep(BetaArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char beta_lds[];
     typedef typename Mma<T>::acc_t acc_t;
     typedef typename Vec4<T>::type vec_t;
-    const int tile = blockIdx.x;
+    const int tile = a.tile0 + blockIdx.x;
     const int4 tl = a.tiles[tile];
     if (a.stop[tl.x] != 0) return;
     T* Q1 = reinterpret_cast<T*>(beta_lds);
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_beta_sweep(BetaArgs<T> a) {
 template <typename T>
 __global__ __launch_bounds__(BT_THREADS) void k_beta_err(BetaArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char beta_lds[];
-    const int tile = blockIdx.x;
+    const int tile = a.tile0 + blockIdx.x;
     const int4 tl = a.tiles[tile];
     if (a.stop[tl.x] != 0) return;
     T* Vs = reinterpret_cast<T*>(beta_lds);
@@ -386,6 +387,7 @@ int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, 
     a.err_mode = beta == 0.0 ? BETA_ERR_IS : beta == 1.0 ? BETA_ERR_KL : beta == 2.0 ? BETA_ERR_FROB : BETA_ERR_GENERIC;
     a.l1 = (T)l1; a.l2 = (T)l2;
     a.flush = (T)flush;
+    a.tile0 = 0;
     if (n_tiles > 0) {
         hipLaunchKernelGGL(k_beta_pack_x<T>, dim3(blocks_of((long)n_tiles * MP * BT_F)), dim3(256), 0, s, X, ldx, fm ? 1 : 0, M,
                            MP, w.tiles, n_tiles, w.Xp);
@@ -417,12 +419,18 @@ template <typename T> int beta_sweep(const BetaCtx<T>& c, hipStream_t s) {
     return 0;
 }
 
-template <typename T>
-int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, double tol, hipStream_t s) {
+template <typename T> int beta_err(const BetaCtx<T>& c, hipStream_t s) {
     if (c.n_tiles == 0) return 0;
     const size_t lds_err = (size_t)c.a.MP * BT_F * sizeof(T) + 3 * 256 * sizeof(double);
     hipLaunchKernelGGL(k_beta_err<T>, dim3(c.n_tiles), dim3(BT_THREADS), lds_err, s, c.a);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, double tol, hipStream_t s) {
+    if (c.n_tiles == 0) return 0;
+    HIP_TRY(beta_err<T>(c, s));
     hipLaunchKernelGGL(k_beta_check, dim3(c.n_utt), dim3(256), 0, s, c.w.errf, c.w.utt_tile0, c.w.stop, c.w.einit, c.w.eprev,
                        c.w.trace, c.n_slots, chk, check_every, stop_rule, tol);
     HIP_TRY(hipGetLastError());
@@ -434,6 +442,7 @@ int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, dou
                                double, double, int, void*, size_t, hipStream_t);                                        \
     template int beta_pack_dict<T>(const BetaCtx<T>&, const T*, int, hipStream_t);                                       \
     template int beta_sweep<T>(const BetaCtx<T>&, hipStream_t);                                                          \
+    template int beta_err<T>(const BetaCtx<T>&, hipStream_t);                                                            \
     template int beta_check<T>(const BetaCtx<T>&, int, int, int, double, hipStream_t);
 BETA_INSTANTIATE(double)
 BETA_INSTANTIATE(float)

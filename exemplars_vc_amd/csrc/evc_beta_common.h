@@ -1,5 +1,6 @@
-// Declarations shared by evc_beta.hip (evc_beta_solve) and evc_beta_learn.hip (evc_beta_learn): the tile geometry, the
-// power evaluation and the host steps of the activation half.
+// Declarations shared by evc_beta.hip (evc_beta_solve), evc_beta_learn.hip (evc_beta_learn) and evc_online.hip
+// (evc_online_learn): the tile geometry, the power evaluation, the host steps of the activation half and the frame sums of
+// the dictionary half.
 #pragma once
 #include "evc_internal.h"
 
@@ -12,6 +13,10 @@ constexpr int BT_GT = 8;            // bin tiles per pass of phase 1 (accumulato
 constexpr int BETA_MAX_M = 528;     // two LDS images of 528 x 16 float64: 135 168 of 163 840 bytes
 constexpr int BETA_MAX_SLOTS = 4097;
 constexpr double BETA_EPS = 1.1920928955078125e-7;
+constexpr double BETA_E64 = 2.220446049250313e-16;      // 2^-52, numpy's float64 epsilon (in both element types)
+constexpr int BDG_MAX_R = 256;        // k_beta_dict_grad: 256 x 20 elements of W and 3 x 16 x 64 of partial sums, 64 KB of LDS in float64
+constexpr int BDG_ROUTE_R = 64;       // the fused route is taken up to this R: measured, DESIGN.md §5.11
+enum { ROUTE_AUTO = 0, ROUTE_FUSED = 1, ROUTE_UNFUSED = 2 };
 enum { BETA_ERR_IS = 0, BETA_ERR_KL = 1, BETA_ERR_FROB = 2, BETA_ERR_GENERIC = 3 };
 
 // x^e: e = k2 / 2 without pow when `general` is 0
@@ -63,6 +68,7 @@ template <typename T> struct BetaArgs {
     T l1, l2;
     T flush;                // > 0: an updated activation below it is stored as 0 (evc_beta_learn, beta < 1); 0: off
     double beta;
+    int tile0;              // workgroup 0's tile: 0, or the first tile of the one batch evc_online_learn launches over
 };
 
 
@@ -99,5 +105,23 @@ template <typename T> int beta_sweep(const BetaCtx<T>& c, hipStream_t s);
 // check number `chk` (0: the start): every utterance's error into its trace slot, then the stop rule on the device
 template <typename T>
 int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, double tol, hipStream_t s);
+// its first half alone: every frame's share of the divergence into errf (evc_online_learn sums one batch's shares itself)
+template <typename T> int beta_err(const BetaCtx<T>& c, hipStream_t s);
+
+// ----- evc_beta_learn.hip: the frame sums of the dictionary half, shared with evc_online_learn -----
+// part[s][0 | 1][m][r] = Num | Den (before the penalties) of the dictionary update over the s-th of S contiguous ranges of
+// the T_ frames given: Xt [>= T_][Mk], Ht [Tp][Np] and Am [Mj][Np] as make_dims pads them (frames as rows; Tp =
+// frame_pad(T_)), Vt and Q2t [Tp][Mj] scratch of the unfused route.  fused: k_beta_dict_grad (R <= BDG_MAX_R), else the
+// generic contraction, k_beta_dict_q and dict_grad.
+template <typename T> struct BetaDictSums {
+    const T *Xt, *Ht, *Am;
+    T *Vt, *Q2t, *part;
+    int M, R, T_, Tp, S;
+    bool fused;
+    double beta;
+};
+template <typename T> int beta_dict_sums(const BetaDictSums<T>& q, hipStream_t s);
+// once per call, before the first beta_dict_sums: the fused kernel's LDS limit
+template <typename T> int beta_dict_sums_prepare(bool fused);
 
 }  // namespace evc

@@ -33,10 +33,6 @@ namespace {
 constexpr int BDG_LD = 20;            // LDS row length of W's tile image: 4 x 20 elements shift the four lane groups by 16 banks
 constexpr int BDG_RB = 2;             // component tiles of 16 per workgroup of k_beta_dict_grad
 constexpr int BDG_WAVES = 4;          // wavefronts per workgroup: each takes a quarter of the frame range
-constexpr int BDG_MAX_R = 256;        // 256 x 20 elements of W and 3 x 16 x 64 of partial sums: 64 KB of LDS in float64
-constexpr int BDG_ROUTE_R = 64;       // the fused route is taken up to this R: measured, DESIGN.md §5.11
-constexpr double BETA_E64 = 2.220446049250313e-16;      // 2^-52, numpy's float64 epsilon (in both element types)
-enum { ROUTE_AUTO = 0, ROUTE_FUSED = 1, ROUTE_UNFUSED = 2 };
 
 template <typename T> struct Vec4;
 template <> struct Vec4<double> { typedef f64x4 type; };
@@ -215,6 +211,46 @@ template <typename T> size_t bdg_lds_bytes(int RP16) {
     return ((size_t)RP16 * BDG_LD + (size_t)(BDG_WAVES - 1) * 2 * BDG_RB * 4 * 64) * sizeof(T);
 }
 
+}  // namespace
+
+template <typename T> int beta_dict_sums_prepare(bool fused) {
+    if (fused)
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_dict_grad<T>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)bdg_lds_bytes<T>(BDG_MAX_R)));
+    return 0;
+}
+
+template <typename T> int beta_dict_sums(const BetaDictSums<T>& q, hipStream_t s) {
+    const int Mk = round_up(q.M, 16), Mj = round_up(q.M, 64), Np = round_up(q.R, 128), MTp = learn_bin_tiles(q.M);
+    const PowSpec p1 = pow_spec(q.beta - 2.0), p2 = pow_spec(q.beta - 1.0);
+    const int clamp_n = q.beta - 2.0 < 0 ? 1 : 0, clamp_d = q.beta - 1.0 < 0 ? 1 : 0;
+    if (q.fused) {
+        BetaDictArgs<T> a;
+        a.Xt = q.Xt; a.Ht = q.Ht; a.Am = q.Am; a.part = q.part;
+        a.ldx = Mk; a.ldh = Np;
+        a.M = q.M; a.R = q.R; a.RP16 = round_up(q.R, 16); a.MTp = MTp; a.T_ = q.T_; a.S = q.S;
+        a.clamp_n = clamp_n; a.clamp_d = clamp_d; a.p1 = p1; a.p2 = p2;
+        const dim3 grid(round_up(q.R, BDG_RB * 16) / (BDG_RB * 16), Mk / 16, q.S);
+        hipLaunchKernelGGL(k_beta_dict_grad<T>, grid, dim3(64 * BDG_WAVES), bdg_lds_bytes<T>(a.RP16), s, a);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    HIP_TRY(gemm_nt<T>(q.Ht, Np, q.Am, Np, q.Vt, Mj, q.Tp, Mj, Np, s, nullptr, 0, nullptr, Mk));
+    const long n = (long)q.T_ * Mk;
+    hipLaunchKernelGGL(k_beta_dict_q<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q.Xt, Mk, q.Vt, q.Q2t, Mj, q.M, Mk,
+                       (long)q.T_, clamp_n, clamp_d, p1, p2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(dict_grad<T>(q.Vt, Mj, q.Q2t, Mj, q.Ht, Np, q.M, q.T_, q.S, q.part, s));
+    return 0;
+}
+
+template int beta_dict_sums_prepare<double>(bool);
+template int beta_dict_sums_prepare<float>(bool);
+template int beta_dict_sums<double>(const BetaDictSums<double>&, hipStream_t);
+template int beta_dict_sums<float>(const BetaDictSums<float>&, hipStream_t);
+
+namespace {
+
 template <typename T> struct BlWs {
     T *Xt, *Am, *Ht, *Vt, *Q2t, *part;
     char* beta_ws;
@@ -266,30 +302,16 @@ int beta_learn(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, in
     HIP_TRY(beta_begin<T>(c, X, ldx, H, ldh, M, R, T_, nullptr, 1, o.layout, beta, o.l1_h, o.l2_h, beta < 1.0 ? BETA_E64 : 0.0,
                           n_slots_for(o.iters, o.check_every), w.beta_ws, w.beta_bytes, s));
     const double gamma = beta_gamma(beta);
-    const PowSpec p1 = pow_spec(beta - 2.0), p2 = pow_spec(beta - 1.0), pg = pow_spec(gamma);
-    const int clamp_n = beta - 2.0 < 0 ? 1 : 0, clamp_d = beta - 1.0 < 0 ? 1 : 0;
+    const PowSpec pg = pow_spec(gamma);
 
+    BetaDictSums<T> q;
+    q.Xt = w.Xt; q.Ht = w.Ht; q.Am = w.Am; q.Vt = w.Vt; q.Q2t = w.Q2t; q.part = w.part;
+    q.M = M; q.R = R; q.T_ = T_; q.Tp = d.Tp; q.S = S; q.fused = fused; q.beta = beta;
     auto update_w = [&]() -> int {
         // frames-as-rows copies of the current factors (Ht is the right operand of the sums over the frames)
         HIP_TRY(copy2d<T>(W, ldw, M, R, fm ? 1 : 0, w.Am, d.Np, d.Mj, d.Np, 0, s));
         HIP_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, w.Ht, d.Np, d.Tp, d.Np, 0, s));
-        if (fused) {
-            BetaDictArgs<T> a;
-            a.Xt = w.Xt; a.Ht = w.Ht; a.Am = w.Am; a.part = w.part;
-            a.ldx = d.Mk; a.ldh = d.Np;
-            a.M = M; a.R = R; a.RP16 = round_up(R, 16); a.MTp = MTp; a.T_ = T_; a.S = S;
-            a.clamp_n = clamp_n; a.clamp_d = clamp_d; a.p1 = p1; a.p2 = p2;
-            const dim3 grid(round_up(R, BDG_RB * 16) / (BDG_RB * 16), d.Mk / 16, S);
-            hipLaunchKernelGGL(k_beta_dict_grad<T>, grid, dim3(64 * BDG_WAVES), bdg_lds_bytes<T>(a.RP16), s, a);
-            HIP_TRY(hipGetLastError());
-        } else {
-            HIP_TRY(gemm_nt<T>(w.Ht, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));
-            const long n = (long)T_ * d.Mk;
-            hipLaunchKernelGGL(k_beta_dict_q<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.Xt, d.Mk, w.Vt, w.Q2t,
-                               d.Mj, M, d.Mk, (long)T_, clamp_n, clamp_d, p1, p2);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(dict_grad<T>(w.Vt, d.Mj, w.Q2t, d.Mj, w.Ht, d.Np, M, T_, S, w.part, s));
-        }
+        HIP_TRY(beta_dict_sums<T>(q, s));
         const long n = (long)M * R;
         hipLaunchKernelGGL(k_beta_dict_apply<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w.part, S,
                            (long)MTp * 16 * d.Np, d.Np, W, (long)ldw, fm ? 0 : 1, M, R, (T)o.l1_w, (T)o.l2_w,
@@ -307,9 +329,7 @@ int beta_learn(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, in
     };
 
     HIP_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
-    if (fused)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_dict_grad<T>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)bdg_lds_bytes<T>(BDG_MAX_R)));
+    HIP_TRY(beta_dict_sums_prepare<T>(fused));
     auto step = [&]() -> int {
         HIP_TRY(beta_pack_dict<T>(c, W, ldw, s));
         HIP_TRY(beta_sweep<T>(c, s));

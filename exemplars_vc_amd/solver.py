@@ -508,12 +508,14 @@ def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100
 
 
 def _learn(entry, opts, X, W0, H0, *, layout, ws_bytes, unsupported, trace, extra_info, tol, dtype, device, info, out_w,
-           out_h, loop_events, splits):
+           out_h, loop_events, splits, call=None):
     """What learn_dictionary, learn_dictionary_beta and learn_dictionary_cd share around their C entry `entry`: the
     operands on the device (out_w / out_h in place, a caller's start never clobbered), the shape check, the common fields
     of `opts` (the entry's own are already set), the workspace lease, the call and the return rule.
     ws_bytes(L, M, R, T, dcode): the entry's workspace, 0 -> ValueError(unsupported(M, R, T)); trace = (name, shape) of the
-    float64 array the entry fills when info is asked for; extra_info(L, M, R, T): the entry's own info fields."""
+    float64 array the entry fills when info is asked for; extra_info(L, M, R, T): the entry's own info fields.
+    call(L, X_d, W_d, H_d, M, R, T, ws, n_iter_ptr, trace_ptr, stream) -> status: an entry whose argument list is not the
+    common one (evc_online_learn) is called through it."""
     torch = _torch()
     device = require_device(device)
     L = _lib.lib()
@@ -551,10 +553,13 @@ def _learn(entry, opts, X, W0, H0, *, layout, ws_bytes, unsupported, trace, extr
     tr = np.full(trace_shape, np.nan) if info else None
     with torch.cuda.device(device), _workspace(nbytes, device) as ws:
         stream = torch.cuda.current_stream(device).cuda_stream
-        st = getattr(L, entry)(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
-                               C.byref(opts), ws.data_ptr(), ws.numel(),
-                               C.byref(n_iter) if (info or tol > 0) else None,
-                               tr.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
+        ni_p = C.byref(n_iter) if (info or tol > 0) else None
+        tr_p = tr.ctypes.data_as(C.POINTER(C.c_double)) if info else None
+        if call is not None:
+            st = call(L, X_d, W_d, H_d, M, R, T, ws, ni_p, tr_p, stream)
+        else:
+            st = getattr(L, entry)(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
+                                   C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, tr_p, C.c_void_p(stream))
     _lib.check(st, entry)
     to_np = x_np and out_w is None and out_h is None
     res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
@@ -647,6 +652,91 @@ def learn_dictionary_beta(X, W0, H0, *, beta, layout, iters, check_every=10, tol
                   out_w=out_w, out_h=out_h, loop_events=loop_events, splits=splits)
 
 
+def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max_iter=200, forget_factor=0.7, tol=1e-4,
+                            max_no_improvement=10, l1_h=0.0, l2_h=0.0, l1_w=0.0, l2_w=0.0, state=None, dtype=None,
+                            device=None, info=False, route=None, splits=None, out_w=None, out_h=None, loop_events=None):
+    """scikit-learn's mini-batch dictionary learning, X ~ W H (MiniBatchNMF(init='custom', fresh_restarts=False,
+    beta_loss=beta).fit_transform), on the GPU (evc_online_learn).  W is addressed like the dictionary A of
+    solve_activations, H like its activations, both start at W0 / H0.  The frames are taken in contiguous batches of
+    min(batch_size, T), in order and cycled; per step the batch's activations by one update of solve_activations_beta's
+    kernel, then the dictionary from the statistics A <- rho A + Num W^(1/gamma), B <- rho B + Den, W <- (A / B)^gamma with
+    rho = forget_factor ** (batch / T).  max_iter counts passes over the frames.  The loop stops when the relative change of
+    W in a step is <= tol (tol = 0: off) or the smoothed batch cost has not improved for max_no_improvement steps (None or
+    negative: off).  l1_h / l2_h are sklearn's scaled l1_reg_W / l2_reg_W (activations, scaled by the bins); l1_w / l2_w
+    are PER FRAME (alpha_H * l1_ratio and alpha_H * (1 - l1_ratio)): each step multiplies them by its batch's frames.  At
+    most 528 bins.  Not served: fresh_restarts=True, partial_fit / transform, sparse X, shuffling.
+
+    Returns (W, H) as learn_dictionary does; with info=True also dict(n_iter=passes begun, n_steps=steps carried out,
+    cost=[steps] batch costs, change=[steps] ||W_new - W_old|| / ||W_new|| (both NaN after the stop), route="fused" |
+    "unfused", state=(A, B) device tensors).  state: the (A, B) of an earlier call's info: the statistics continue from
+    them (the batch cycle and the stop rules restart) instead of starting at A = W0, B = 1.  info=False with tol=0 and
+    max_no_improvement off enqueues max_iter passes without waiting.  route, splits: tests and tuning, as
+    learn_dictionary_beta's (splits: frame ranges per batch).  No CPU fallback: without a HIP device this raises
+    RuntimeError."""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    beta = float(beta)
+    if not np.isfinite(beta):
+        raise ValueError(f"beta must be finite, got {beta!r}")
+    if route not in _BETA_ROUTES:
+        raise ValueError(f"route must be None, 'fused' or 'unfused', got {route!r}")
+    if int(batch_size) < 1:
+        raise ValueError(f"batch_size must be at least 1, got {batch_size!r}")
+    if not 0.0 < float(forget_factor) <= 1.0:
+        raise ValueError(f"forget_factor must lie in (0, 1], got {forget_factor!r}")
+    xshape = tuple(getattr(X, "shape", ()))
+    if len(xshape) != 2:
+        raise ValueError(f"expected a 2-D matrix, got shape {xshape}")
+    bm = lay == _lib.BIN_MAJOR
+    if xshape[0 if bm else 1] > _lib.BETA_MAX_M:          # what the ABI answers with -3
+        raise ValueError(f"unsupported beta-divergence shape: M = {xshape[0 if bm else 1]} bins, the kernel holds at most "
+                         f"{_lib.BETA_MAX_M}")
+    T = int(xshape[1 if bm else 0])
+    bs = max(min(int(batch_size), T), 1)
+    per_pass = -(-T // bs)
+    splits = int(splits or 0)
+    mni = -1 if max_no_improvement is None else int(max_no_improvement)
+    opts = _lib.OnlineOpts()
+    opts.batch_size, opts.max_iter, opts.max_no_improvement = int(batch_size), int(max_iter), mni
+    opts.resume = 0 if state is None else 1
+    opts.reserved = _BETA_ROUTES[route] << 16
+    opts.beta, opts.tol, opts.forget_factor = beta, float(tol), float(forget_factor)
+    opts.l1_h, opts.l2_h, opts.l1_w, opts.l2_w = float(l1_h), float(l2_h), float(l1_w), float(l2_w)
+    n_steps = C.c_int(0)
+    acc = {}
+
+    def call(L, X_d, W_d, H_d, M, R, T, ws, n_iter_p, tr_p, stream):
+        if state is None:
+            A_d, B_d = torch.empty_like(W_d).contiguous(), torch.empty_like(W_d).contiguous()
+        else:
+            A_d, B_d = state
+            for t in (A_d, B_d):
+                if not isinstance(t, torch.Tensor) or t.shape != W_d.shape or t.dtype != W_d.dtype \
+                        or t.device != W_d.device or not t.is_contiguous():
+                    raise ValueError("`state` must be the (A, B) device tensors of an earlier call's info, shaped like W")
+        acc["state"] = (A_d, B_d)
+        quiet = n_iter_p is None
+        return L.evc_online_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d),
+                                  A_d.data_ptr(), B_d.data_ptr(), _ld(A_d), M, R, T, C.byref(opts), ws.data_ptr(), ws.numel(),
+                                  n_iter_p, None if quiet else C.byref(n_steps), tr_p, C.c_void_p(stream))
+
+    def extra_info(L, M, R, T):
+        return {"n_steps": int(n_steps.value), "state": acc["state"],
+                "route": route or ("fused", "unfused")[int(L.evc_beta_learn_route(M, R, T)) - 1]}
+
+    res = _learn("evc_online_learn", opts, X, W0, H0, layout=layout,
+                 ws_bytes=lambda L, M, R, T, dcode: int(L.evc_online_workspace_bytes(M, R, T, int(batch_size), dcode)),
+                 unsupported=lambda M, R, T: f"unsupported mini-batch learning shape M={M}, R={R}, T={T} "
+                                             f"(M <= {_lib.BETA_MAX_M}, R <= 4096)",
+                 trace=("trace", (max(int(max_iter), 0) * per_pass, 2)), extra_info=extra_info,
+                 tol=1.0 if (tol > 0 or mni >= 0) else 0.0, dtype=dtype, device=device, info=info, out_w=out_w, out_h=out_h,
+                 loop_events=loop_events, splits=splits, call=call)
+    if info:
+        tr = res[2].pop("trace")
+        res[2]["cost"], res[2]["change"] = np.ascontiguousarray(tr[:, 0]), np.ascontiguousarray(tr[:, 1])
+    return res
+
+
 _CDL_UPDATES = {"both": _lib.CDL_BOTH, "dict": _lib.CDL_DICT_ONLY}
 
 
@@ -690,7 +780,7 @@ def learn_dictionary_cd(X, W0, H0, *, layout, max_iter=200, tol=1e-4, l1_h=0.0, 
 
 
 def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepared=False, dtype=None, device=None,
-                       loss="frobenius", solver="mu", beta=None):
+                       loss="frobenius", solver="mu", batch_size=None, forget_factor=0.7, beta=None):
     """A compact parallel dictionary: the aligned source and target exemplars are stacked, D = [A; B] ((Ma + Mb) x N),
     and factored jointly, D ~ [Wa; Wb] G, with R << N components by learn_dictionary (scikit-learn surface, the error
     every 10 iterations); (Wa, Wb) then stand in for (A, B) in solve_activations / convert at R / N of the cost.
@@ -703,7 +793,13 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     1024 stacked bins and components; `iters` is its max_iter and `tol` its violation ratio; info as learn_dictionary_cd's).
     beta: when given, the compaction minimises that beta-divergence by learn_dictionary_beta from the same start (0 is
     Itakura-Saito, the usual loss for power spectra; at most 528 stacked bins; info as learn_dictionary_beta's); `loss`
-    must then be left at its default and solver at "mu"."""
+    must then be left at its default and solver at "mu".
+    batch_size: when given, the compaction is learnt online by learn_dictionary_online in batches of that many exemplars
+    (scikit-learn's MiniBatchNMF; forget_factor is its forgetting of old batches) under `beta` (default 2) from the same
+    start; `iters` is then the number of passes and `tol` the stop on the relative change of the dictionary, the
+    no-improvement stop is off; `loss` and `solver` must be left at their defaults; info as learn_dictionary_online's."""
+    if batch_size is not None and (loss != "frobenius" or solver != "mu"):
+        raise ValueError("batch_size selects the online learner: leave `loss` and `solver` at their defaults")
     if beta is not None and (loss != "frobenius" or solver != "mu"):
         raise ValueError("beta names the loss itself: leave `loss` and `solver` at their defaults")
     if loss not in _LOSSES:
@@ -728,7 +824,12 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     pick = torch.div(torch.arange(R, device=device) * N, R, rounding_mode="floor")
     W0 = (D[:, pick] if bm else D[pick, :]).clamp_min(1e-6).contiguous()
     G0 = torch.full((R, N) if bm else (N, R), float(torch.sqrt(D.mean() / R)), dtype=tdtype, device=device)
-    if beta is not None:
+    if batch_size is not None:
+        W, G, info = learn_dictionary_online(D, None, None, beta=2.0 if beta is None else beta, layout=layout,
+                                             batch_size=batch_size, max_iter=iters, forget_factor=forget_factor, tol=tol,
+                                             max_no_improvement=None, dtype=tdtype, device=device, info=True, out_w=W0,
+                                             out_h=G0)
+    elif beta is not None:
         W, G, info = learn_dictionary_beta(D, None, None, beta=beta, layout=layout, iters=iters, tol=tol, check_every=10,
                                            dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0)
     elif solver == "cd":

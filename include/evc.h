@@ -42,6 +42,9 @@
  *                   does not serve: sklearn _fit_multiplicative_update with update_H=True and beta_loss = 'itakura-saito'
  *                   or any float (_nmf.py:526-893); evc_beta_learn_workspace_bytes, evc_beta_learn_splits and
  *                   evc_beta_learn_route size and describe it
+ *   evc_online_learn  replaces MiniBatchNMF(init='custom', fresh_restarts=False).fit_transform(X, W=W, H=H): the mini-batch
+ *                   learner for any beta_loss (sklearn _minibatch_step, _multiplicative_update_h with A, B and rho,
+ *                   _minibatch_convergence); evc_online_workspace_bytes and evc_online_splits size and describe it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -90,6 +93,11 @@
  *         checks are evaluated when err_out is non-NULL or tol > 0.  None of its kernels exchanges data between workgroups
  *         inside a launch, uses float atomics or assumes residency: concurrent calls on several streams are safe, and the
  *         same call gives the same bits every time.
+ *     (10) evc_online_learn: with tol == 0, max_no_improvement < 0 and NULL n_iter_out, n_steps_out and trace_out the call
+ *         is a pure enqueue of max_iter passes.  Otherwise the host reads three doubles after every step (the batch cost
+ *         and the two sums of squares of the dictionary's change ratio) and decides the stop there.  None of its kernels
+ *         exchanges data between workgroups inside a launch, uses float atomics or assumes residency: concurrent calls on
+ *         several streams are safe, and the same call gives the same bits every time.
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
  *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets, sample_offsets) are consumed before the call returns: they are
@@ -723,6 +731,73 @@ int evc_beta_learn_route(int M, int R, int T);
 int evc_beta_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, int M, int R, int T,
                    const evc_beta_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
                    evc_stream_t stream);
+
+/* Mini-batch (online) dictionary learning under any beta-divergence, X ~ W H: scikit-learn 1.7.2's
+ * MiniBatchNMF(init='custom', fresh_restarts=False, beta_loss=beta).fit_transform(X, W=..., H=...) (_nmf.py: _fit_transform,
+ * _minibatch_step, _multiplicative_update_h(..., A, B, rho), _minibatch_convergence).  X is M x T, W is M x R, H is R x T, all
+ * addressed as in evc_beta_learn (sklearn's W is H^T here, its H is W^T); W and H hold the start on entry and are updated in
+ * place.  acc_a and acc_b are the M x R accumulators A and B of the online update, addressed like W with the leading
+ * dimension ld_acc, caller-owned: with resume = 0 the call sets A = W, B = 1 first; with resume = 1 they hold a previous
+ * call's state.
+ * Batches are contiguous ranges of bs = min(batch_size, T) frames, taken in order and cycled (sklearn's gen_batches: the
+ * last of a pass may be short; nothing is shuffled).  rho = forget_factor ^ (bs / T); EPS, E64, gamma and the evaluation of
+ * the powers as in evc_beta_learn.  Step k = 1, 2, ... on batch b of T_b frames:
+ *   activations  one iteration of evc_beta_solve's statement on the batch's columns of H with the current W, l1_h and l2_h;
+ *                then, if beta < 1, H_b[H_b < E64] = 0
+ *   cost         (res + l1_h sum H_b + T_b l1_w sum W + l2_h sum H_b^2 + T_b l2_w sum W^2) / T_b with res =
+ *                _beta_divergence(X_b, H_b, W, beta), neither square-rooted nor clamped at 0, W still the step's start;
+ *                every sum in float64 in a fixed order
+ *   dictionary   with the new H_b, Num and Den over the batch's frames exactly as evc_beta_learn's dictionary half forms
+ *                them, in evc_online_splits(M, R, T_b) frame ranges, Den including T_b l1_w + T_b l2_w W, Den == 0 -> EPS;
+ *                P = W^(1/gamma);  A <- rho A + Num P;  B <- rho B + Den;  W <- (A / B)^gamma;  then, if beta <= 1,
+ *                W[W < E64] = 0
+ *   convergence  on the host, as _minibatch_convergence: step 1 is ignored; from step 2 on ewa = cost the first time, else
+ *                ewa (1 - a) + cost a with a = min(T_b / (T + 1), 1); stop if tol > 0 and ||W_new - W_old||_F / ||W_new||_F
+ *                <= tol; otherwise, if ewa < ewa_min (or there is none yet) it is stored and the counter reset, else the
+ *                counter counts, and the loop stops once max_no_improvement >= 0 and the counter has reached it.  The
+ *                stopping step's updates are kept.
+ * beta = 1 and beta = 2 run this generic statement (to rounding, not bitwise, against sklearn's special cases).  The fused /
+ * unfused route of the frame sums follows evc_beta_learn_route.  The batch cycle and the convergence state restart with
+ * every call: with the stop rules off, a call of p passes followed by a resume = 1 call of q passes gives bitwise the W, H, A
+ * and B of one call of p + q passes.
+ * Out of scope: fresh_restarts=True; partial_fit and transform (both are _solve_W, a fixed-dictionary solve with a
+ * change-of-W stop rule that evc_beta_solve does not have); sparse X; shuffled batches.
+ *   M : 1 .. 528, R : 1 .. 4096 (larger: -3);  T >= 1;  max_iter = 0 returns the start (and sets A and B when resume = 0)
+ *   l1_h, l2_h : already scaled by the number of bins, as in evc_beta_learn_opts
+ *   l1_w, l2_w : PER FRAME (sklearn's alpha_H * l1_ratio and alpha_H * (1 - l1_ratio)): the call multiplies them by T_b
+ *   n_iter_out, n_steps_out : host ints or NULL: ceil(n_steps / ceil(T / bs)) and the steps carried out
+ *   trace_out  : host, max_iter * ceil(T / bs) x 2 doubles or NULL: [k][0] the batch cost of step k + 1, [k][1] its change
+ *                ratio ||W_new - W_old|| / ||W_new||; NaN after the stop
+ * Status -1 (wrong struct_bytes, NaN or infinite beta, negative or NaN tol or penalties, forget_factor outside (0, 1],
+ * batch_size < 1, max_iter < 0, max_iter * ceil(T / bs) beyond an int, resume not 0 or 1, missing pointers, bad leading
+ * dimensions), -3 and -2 are returned before any device work.  Host synchronisation: case (10) of the list at the top. */
+typedef struct evc_online_opts {
+    int struct_bytes;        /* sizeof(evc_online_opts) */
+    int dtype;               /* EVC_F64 | EVC_F32 */
+    int layout;              /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int batch_size;          /* >= 1; clipped to T */
+    int max_iter;            /* passes over the frames, >= 0 */
+    int max_no_improvement;  /* < 0: off */
+    int resume;              /* 0: A = W, B = 1 are set by the call; 1: acc_a / acc_b hold a previous call's state */
+    int reserved;            /* 0; tests and tuning: bits 8..15 that many frame ranges (1 .. 64) per batch, bits 16..17 the
+                                route, as in evc_beta_learn_opts; anything else: status -1 */
+    double beta;             /* the divergence: 0 Itakura-Saito, 1 Kullback-Leibler, 2 Frobenius, or any finite value */
+    double tol;              /* >= 0; 0: the change of W never stops the loop */
+    double forget_factor;    /* in (0, 1] */
+    double l1_h, l2_h;       /* >= 0; activations, already scaled by the number of bins */
+    double l1_w, l2_w;       /* >= 0; dictionary, PER FRAME: multiplied by the batch's frame count */
+    void* ev_loop_start;     /* optional hipEvent_t pair recorded around the launches of the step loop, as in */
+    void* ev_loop_stop;      /* evc_solve_opts; NULL = not recorded */
+} evc_online_opts;
+/* bytes of workspace evc_online_learn needs (0: invalid arguments, M > 528 among them); room for 64 frame ranges is included,
+ * and about 32 KB per batch of a pass (the activation half keeps its per-utterance state per batch) */
+size_t evc_online_workspace_bytes(int M, int R, int T, int batch_size, int dtype);
+/* frame ranges the dictionary half's sums over a batch of batch_frames frames are split into (0: invalid arguments);
+ * evc_beta_learn_splits(M, R, batch_frames): a short last batch has its own count */
+int evc_online_splits(int M, int R, int batch_frames);
+int evc_online_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, void* acc_a, void* acc_b, int ld_acc, int M,
+                     int R, int T, const evc_online_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
+                     int* n_steps_out, double* trace_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
