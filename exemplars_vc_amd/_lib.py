@@ -19,7 +19,7 @@ ALGO_GRAM, ALGO_FACTORED, ALGO_LITERAL, ALGO_AUTO = 0, 1, 2, 3
 INIT_GIVEN, INIT_SKLEARN, INIT_CONST = 0, 1, 2
 STOP_NONE, STOP_SKLEARN, STOP_PYMF = 0, 1, 2
 LOSS_FROBENIUS, LOSS_KL = 0, 1
-FLAG_NO_FUSED, FLAG_EXACT_DIV, FLAG_NO_EXCHANGE, FLAG_NO_ALL_RESIDENT, FLAG_PAIR_TILES = 1, 2, 4, 16, 32
+FLAG_NO_FUSED, FLAG_EXACT_DIV, FLAG_NO_EXCHANGE, FLAG_NO_ALL_RESIDENT, FLAG_PAIR_TILES, FLAG_NO_LONE_BIN = 1, 2, 4, 16, 32, 64
 LEARN_SKLEARN, LEARN_PYMF = 0, 1
 CDL_BOTH, CDL_DICT_ONLY = 0, 1
 

@@ -184,8 +184,13 @@ enum { EVC_LOSS_FROBENIUS = 0, EVC_LOSS_KL = 1 };
  *                    asynchronous (see "Host synchronisation" above); a latency / determinism knob
  *   NO_ALL_RESIDENT  keep k_fused_all out (k_fused_res, with its cooperative launch for few frame tiles)
  *   PAIR_TILES       tuning / experiments: k_fused_xy (two frame tiles per member, exchange phases inside the sweeps)
- *                    instead of k_fused_all where both apply; measured slower (profiles/r04_xy_notes.md) */
-enum { EVC_FLAG_NO_FUSED = 1, EVC_FLAG_EXACT_DIV = 2, EVC_FLAG_NO_EXCHANGE = 4, EVC_FLAG_NO_ALL_RESIDENT = 16, EVC_FLAG_PAIR_TILES = 32 };
+ *                    instead of k_fused_all where both apply; measured slower (profiles/r04_xy_notes.md)
+ *   NO_LONE_BIN      A/B and tests: M = 25 with 2, 4 or 8 members (N = 1024, 2048, 4096) runs k_fused_all's own 15-MFMA
+ *                    unit instead of k_fused_lone's 14 (bin 24 folded into the denominators' start value: the same sums with
+ *                    bin 24 added first, so results differ in the last bits; C2 +1.5 %, profiles/lone_bin_README.md).
+ *                    evc_solve_info reports EVC_KERNEL_FUSED_ALL either way; no other shape is affected */
+enum { EVC_FLAG_NO_FUSED = 1, EVC_FLAG_EXACT_DIV = 2, EVC_FLAG_NO_EXCHANGE = 4, EVC_FLAG_NO_ALL_RESIDENT = 16, EVC_FLAG_PAIR_TILES = 32,
+       EVC_FLAG_NO_LONE_BIN = 64 };
 
 struct evc_solve_info;
 struct evc_dict;
