@@ -34,7 +34,9 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_cd_learn_workspace_bytes", "evc_cd_learn_splits", "evc_cd_learn",
            "evc_mfcc_workspace_bytes", "evc_mfcc", "evc_beta_workspace_bytes", "evc_beta_solve",
            "evc_beta_learn_workspace_bytes", "evc_beta_learn_splits", "evc_beta_learn_route", "evc_beta_learn",
-           "evc_online_workspace_bytes", "evc_online_splits", "evc_online_learn")
+           "evc_online_workspace_bytes", "evc_online_splits", "evc_online_learn",
+           "evc_online_transform_workspace_bytes", "evc_online_transform",
+           "evc_online_fresh_workspace_bytes", "evc_online_learn_fresh")
 BETA_MAX_M = 528
 MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
@@ -118,6 +120,28 @@ class OnlineOpts(C.Structure):
         ("max_iter", C.c_int), ("max_no_improvement", C.c_int), ("resume", C.c_int), ("reserved", C.c_int),
         ("beta", C.c_double), ("tol", C.c_double), ("forget_factor", C.c_double),
         ("l1_h", C.c_double), ("l2_h", C.c_double), ("l1_w", C.c_double), ("l2_w", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class OnlineFreshOpts(C.Structure):
+    """Mirror of `evc_online_fresh_opts` (include/evc.h): the mini-batch learning with fresh restarts."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("batch_size", C.c_int),
+        ("max_iter", C.c_int), ("max_no_improvement", C.c_int), ("resume", C.c_int), ("reserved", C.c_int),
+        ("fresh_max_iter", C.c_int), ("final_max_iter", C.c_int),
+        ("beta", C.c_double), ("tol", C.c_double), ("forget_factor", C.c_double),
+        ("l1_h", C.c_double), ("l2_h", C.c_double), ("l1_w", C.c_double), ("l2_w", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class TransformOpts(C.Structure):
+    """Mirror of `evc_transform_opts` (include/evc.h): options of the mini-batch estimator's activation solve."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("max_iter", C.c_int),
+        ("init_mode", C.c_int), ("reserved", C.c_int),
+        ("beta", C.c_double), ("tol", C.c_double), ("l1", C.c_double), ("l2", C.c_double), ("init_value", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -324,6 +348,22 @@ def lib():
         C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),      # n_iter_out, n_steps_out, trace_out
         C.c_void_p,                                                         # stream
     ]
+    L.evc_online_transform_workspace_bytes.restype = C.c_size_t
+    L.evc_online_transform_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_online_transform.restype = C.c_int
+    L.evc_online_transform.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # W, X, H
+        C.c_int, C.c_int, C.c_int,                                          # M, R, T
+        C.POINTER(C.c_int), C.c_int, C.POINTER(TransformOpts),              # utt_offsets, n_utt, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, change_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_online_fresh_workspace_bytes.restype = C.c_size_t
+    L.evc_online_fresh_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_online_learn_fresh.restype = C.c_int
+    L.evc_online_learn_fresh.argtypes = L.evc_online_learn.argtypes[:12] + [C.POINTER(OnlineFreshOpts)] + \
+        L.evc_online_learn.argtypes[13:]
     _lib = L
     return L
 

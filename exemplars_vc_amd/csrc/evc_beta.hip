@@ -31,6 +31,11 @@
 // utterance's shares in a fixed order, records sqrt(2 max(res, 0)) and applies sklearn's stop rule on the device
 // (stop[u] = the iteration the utterance stopped at; the sweeps of a stopped utterance return at once).
 //
+// k_beta_sweep<T, true> is the change variant of the sweep: the same phases and the same stored h_new, plus every frame's
+// shares of sum (h_new - h_old)^2 and sum h_new^2 in float64; k_beta_change_check sums an utterance's shares, records
+// ||H_new - H_old|| / ||H_new|| and stops the utterance on the device once it is <= tol: MiniBatchNMF._solve_W, behind
+// evc_online_transform and evc_online_learn_fresh (beta_sweep_change, beta_restart, beta_flush).
+//
 // The host steps (beta_begin, beta_pack_dict, beta_sweep, beta_check; evc_beta_common.h) also serve evc_beta_learn, which
 // repacks the dictionary every iteration and sets BetaArgs.flush (an updated activation below it is stored as 0);
 // evc_beta_solve passes 0 and its results are bitwise what they were without the field.  evc_online_learn hands its
@@ -96,7 +101,11 @@ __device__ __forceinline__ void beta_form_v(const BetaArgs<T>& a, const int4 tl,
     }
 }
 
-template <typename T>
+// CHG: the change variant (evc_online_transform).  The same phases and the same stored h_new; phase 3 also forms, per frame
+// of the tile, sum_n (h_new - h_old)^2 and sum_n h_new^2 in float64 in a fixed order - per lane its exemplar tiles in
+// ascending order (rows r = 0..3 inside a tile), then the four lane groups of the frame by wave shuffles in the order 0, 1,
+// 2, 3, then the four wavefronts through LDS in wavefront order - and writes them to chg[slot][0 | 1] (padding slots: 0).
+template <typename T, bool CHG = false>
 __global__ __launch_bounds__(BT_THREADS) void k_beta_sweep(BetaArgs<T> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char beta_lds[];
     typedef typename Mma<T>::acc_t acc_t;
@@ -132,6 +141,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_beta_sweep(BetaArgs<T> a) {
     T* Hf = a.H + (long)(tl.y + (fvalid ? f : 0)) * a.hs_t;
     const int NT = a.NP / 16, MC = a.MP / 16;
     const T eps = (T)BETA_EPS;
+    double d2 = 0.0, n2 = 0.0;
 #pragma unroll 1
     for (int nt = wave; nt < NT; nt += BT_WAVES) {
         acc_t num = acc_t{0, 0, 0, 0}, den = acc_t{0, 0, 0, 0};
@@ -159,7 +169,27 @@ __global__ __launch_bounds__(BT_THREADS) void k_beta_sweep(BetaArgs<T> a) {
                 T hn = h * q;
                 if (a.flush > T(0) && hn < a.flush) hn = T(0);
                 *hp = hn;
+                if constexpr (CHG) {
+                    const double dh = (double)hn - (double)h;
+                    d2 += dh * dh;
+                    n2 += (double)hn * (double)hn;
+                }
             }
+        }
+    }
+    if constexpr (CHG) {
+        double* red = reinterpret_cast<double*>(beta_lds + (size_t)2 * a.MP * BT_F * sizeof(T));      // [4 waves][2][16 frames]
+        const double s2 = ((__shfl(d2, f) + __shfl(d2, f + 16)) + __shfl(d2, f + 32)) + __shfl(d2, f + 48);
+        const double q2 = ((__shfl(n2, f) + __shfl(n2, f + 16)) + __shfl(n2, f + 32)) + __shfl(n2, f + 48);
+        if (lane < 16) {
+            red[wave * 32 + f] = s2;
+            red[wave * 32 + 16 + f] = q2;
+        }
+        __syncthreads();
+        if (threadIdx.x < 32) {
+            const int j = threadIdx.x & 15, k = threadIdx.x >> 4;
+            const double v = ((red[k * 16 + j] + red[32 + k * 16 + j]) + red[64 + k * 16 + j]) + red[96 + k * 16 + j];
+            a.chg[((long)tile * BT_F + j) * 2 + k] = j < tl.z ? v : 0.0;
         }
     }
 }
@@ -250,6 +280,47 @@ __global__ __launch_bounds__(256) void k_beta_check(const double* __restrict__ e
     else eprev[u] = err;
 }
 
+// one block per utterance: the shares of the change variant summed in index order (per thread strided, then a tree, as
+// k_beta_check), ratio = sqrt(d2) / sqrt(n2) into trace slot it - 1, and the stop of MiniBatchNMF._solve_W: a NaN ratio (0 / 0
+// among them) compares false and the utterance runs on, as in numpy
+__global__ __launch_bounds__(256) void k_beta_change_check(const double* __restrict__ chg, const int* __restrict__ utt_tile0,
+                                                           int utt0, int* stop, double* trace, int n_slots, int it,
+                                                           double tol) {
+    __shared__ double red[2][256];
+    const int u = utt0 + blockIdx.x;
+    const long i0 = (long)utt_tile0[u] * BT_F, i1 = (long)utt_tile0[u + 1] * BT_F;
+    if (stop[u] != 0 || i0 == i1) return;       // uniform per block
+    const double2* __restrict__ pair = reinterpret_cast<const double2*>(chg);
+    double d2 = 0.0, n2 = 0.0;
+    // eight loads in flight per thread, added in index order: a long utterance is one workgroup's latency-bound sum
+#pragma unroll 8
+    for (long i = i0 + threadIdx.x; i < i1; i += 256) {
+        const double2 v = pair[i];
+        d2 += v.x;
+        n2 += v.y;
+    }
+    red[0][threadIdx.x] = d2;
+    red[1][threadIdx.x] = n2;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + w];
+            red[1][threadIdx.x] += red[1][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double ratio = sqrt(red[0][0]) / sqrt(red[1][0]);
+    trace[(long)u * n_slots + it - 1] = ratio;
+    if (tol > 0.0 && ratio <= tol) stop[u] = it;
+}
+
+// the stop words of utterances [u0, u0 + n) back to "running" (evc_online_learn_fresh revisits its batches every pass)
+__global__ void k_beta_stop_reset(int* stop, int u0, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) stop[u0 + i] = 0;
+}
+
 __global__ void k_beta_state_init(int* stop, double* trace, int n_utt, int n_slots) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_utt) stop[i] = 0;
@@ -318,6 +389,22 @@ __global__ void k_beta_fill(T* __restrict__ H, long hs_t, long hs_n, int N, cons
     if (f < tl.z) H[(long)(tl.y + f) * hs_t + (long)n * hs_n] = (T)(h0 ? h0[tl.x] : value);
 }
 
+// H < thr -> 0 over the columns of n_tiles tiles: a pass of its own AFTER a solve (MiniBatchNMF._minibatch_step, beta < 1);
+// BetaArgs.flush during the solve's sweeps would pin an entry at 0 that the next update could still have raised
+template <typename T>
+__global__ void k_beta_flush(T* __restrict__ H, long hs_t, long hs_n, int N, const int4* __restrict__ tiles, int n_tiles,
+                             T thr) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)n_tiles * BT_F * N) return;
+    const long slot = i / N;
+    const int n = (int)(i % N), f = (int)(slot % BT_F);
+    const int4 tl = tiles[slot / BT_F];
+    if (f < tl.z) {
+        T* hp = H + (long)(tl.y + f) * hs_t + (long)n * hs_n;
+        if (*hp < thr) *hp = T(0);
+    }
+}
+
 unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 
 // [Ap1 | Ap3 | Xp | errf | tiles | utt_tile0 | utt_frames | stop | h0 | einit | eprev | trace], each 256-byte aligned
@@ -363,6 +450,7 @@ int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, 
     const bool fm = layout == EVC_FRAME_MAJOR;
     const int MP = round_up(M, 16), NP = round_up(N, 16);
     c.n_utt = n_utt;
+    c.utt0 = 0;
     c.n_slots = n_slots;
     c.fm = fm ? 1 : 0;
 
@@ -388,6 +476,7 @@ int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, 
     a.l1 = (T)l1; a.l2 = (T)l2;
     a.flush = (T)flush;
     a.tile0 = 0;
+    a.chg = nullptr;
     if (n_tiles > 0) {
         hipLaunchKernelGGL(k_beta_pack_x<T>, dim3(blocks_of((long)n_tiles * MP * BT_F)), dim3(256), 0, s, X, ldx, fm ? 1 : 0, M,
                            MP, w.tiles, n_tiles, w.Xp);
@@ -396,6 +485,9 @@ int beta_begin(BetaCtx<T>& c, const T* X, int ldx, T* H, int ldh, int M, int N, 
         // different M never shrink it under one another
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_sweep<T>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(2 * BETA_MAX_M * BT_F * sizeof(T))));
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_sweep<T, true>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(2 * BETA_MAX_M * BT_F * sizeof(T) + BETA_CHG_LDS)));
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_beta_err<T>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(BETA_MAX_M * BT_F * sizeof(T) + 3 * 256 * sizeof(double))));
@@ -415,6 +507,55 @@ template <typename T> int beta_pack_dict(const BetaCtx<T>& c, const T* A, int ld
 template <typename T> int beta_sweep(const BetaCtx<T>& c, hipStream_t s) {
     if (c.n_tiles == 0) return 0;
     hipLaunchKernelGGL(k_beta_sweep<T>, dim3(c.n_tiles), dim3(BT_THREADS), (size_t)2 * c.a.MP * BT_F * sizeof(T), s, c.a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T> int beta_sweep_change(const BetaCtx<T>& c, int it, double tol, hipStream_t s) {
+    if (c.n_tiles == 0) return 0;
+    hipLaunchKernelGGL((k_beta_sweep<T, true>), dim3(c.n_tiles), dim3(BT_THREADS),
+                       (size_t)2 * c.a.MP * BT_F * sizeof(T) + BETA_CHG_LDS, s, c.a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_beta_change_check, dim3(c.n_utt), dim3(256), 0, s, c.a.chg, c.w.utt_tile0, c.utt0, c.w.stop,
+                       c.w.trace, c.n_slots, it, tol);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T> int beta_restart(const BetaCtx<T>& c, bool fill, hipStream_t s) {
+    if (c.n_tiles == 0) return 0;
+    hipLaunchKernelGGL(k_beta_stop_reset, dim3(blocks_of(c.n_utt)), dim3(256), 0, s, c.w.stop, c.utt0, c.n_utt);
+    HIP_TRY(hipGetLastError());
+    if (!fill) return 0;
+    hipLaunchKernelGGL(k_beta_fill<T>, dim3(blocks_of((long)c.n_tiles * BT_F * c.a.N)), dim3(256), 0, s, c.a.H, c.a.hs_t,
+                       c.a.hs_n, c.a.N, c.w.tiles + c.a.tile0, c.n_tiles, c.w.h0, 0.0);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T> int beta_h0(const BetaCtx<T>& c, hipStream_t s) {
+    if (c.n_tiles == 0) return 0;
+    hipLaunchKernelGGL(k_beta_h0<T>, dim3(c.n_utt), dim3(256), 0, s, c.w.Xp, c.w.utt_tile0, c.w.utt_frames, c.a.M, c.a.MP,
+                       c.a.N, c.w.h0);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T> int beta_flush(const BetaCtx<T>& c, double thr, hipStream_t s) {
+    if (c.n_tiles == 0) return 0;
+    hipLaunchKernelGGL(k_beta_flush<T>, dim3(blocks_of((long)c.n_tiles * BT_F * c.a.N)), dim3(256), 0, s, c.a.H, c.a.hs_t,
+                       c.a.hs_n, c.a.N, c.w.tiles + c.a.tile0, c.n_tiles, (T)thr);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+template <typename T> int beta_start(const BetaCtx<T>& c, int init_mode, double init_value, hipStream_t s) {
+    if (c.n_tiles == 0 || init_mode == EVC_INIT_GIVEN) return 0;
+    const BetaWs<T>& w = c.w;
+    const bool sk = init_mode == EVC_INIT_SKLEARN;
+    if (sk) HIP_TRY(beta_h0<T>(c, s));
+    hipLaunchKernelGGL(k_beta_fill<T>, dim3(blocks_of((long)c.n_tiles * BT_F * c.a.N)), dim3(256), 0, s, c.a.H, c.a.hs_t,
+                       c.a.hs_n, c.a.N, w.tiles, c.n_tiles, sk ? w.h0 : nullptr, init_value);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -443,6 +584,11 @@ int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, dou
     template int beta_pack_dict<T>(const BetaCtx<T>&, const T*, int, hipStream_t);                                       \
     template int beta_sweep<T>(const BetaCtx<T>&, hipStream_t);                                                          \
     template int beta_err<T>(const BetaCtx<T>&, hipStream_t);                                                            \
+    template int beta_start<T>(const BetaCtx<T>&, int, double, hipStream_t);                                            \
+    template int beta_sweep_change<T>(const BetaCtx<T>&, int, double, hipStream_t);                                     \
+    template int beta_h0<T>(const BetaCtx<T>&, hipStream_t);                                                             \
+    template int beta_restart<T>(const BetaCtx<T>&, bool, hipStream_t);                                                      \
+    template int beta_flush<T>(const BetaCtx<T>&, double, hipStream_t);                                                  \
     template int beta_check<T>(const BetaCtx<T>&, int, int, int, double, hipStream_t);
 BETA_INSTANTIATE(double)
 BETA_INSTANTIATE(float)
@@ -462,16 +608,7 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
     if ((st = beta_pack_dict<T>(c, A, lda, s)) != 0) return st;
     const BetaWs<T>& w = c.w;
     const int n_tiles = c.n_tiles;
-    if (n_tiles > 0 && o.init_mode != EVC_INIT_GIVEN) {
-        const bool sk = o.init_mode == EVC_INIT_SKLEARN;
-        if (sk) {
-            hipLaunchKernelGGL(k_beta_h0<T>, dim3(n_utt), dim3(256), 0, s, w.Xp, w.utt_tile0, w.utt_frames, M, c.a.MP, N, w.h0);
-            HIP_TRY(hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_beta_fill<T>, dim3(blocks_of((long)n_tiles * BT_F * N)), dim3(256), 0, s, H, c.a.hs_t, c.a.hs_n, N,
-                           w.tiles, n_tiles, sk ? w.h0 : nullptr, o.init_value);
-        HIP_TRY(hipGetLastError());
-    }
+    if ((st = beta_start<T>(c, o.init_mode, o.init_value, s)) != 0) return st;
     const bool checks = o.check_every > 0;
     if (checks && (st = beta_check<T>(c, 0, o.check_every, o.stop_rule, o.tol, s)) != 0) return st;
     if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));

@@ -1,5 +1,5 @@
-// Declarations shared by evc_beta.hip (evc_beta_solve), evc_beta_learn.hip (evc_beta_learn) and evc_online.hip
-// (evc_online_learn): the tile geometry, the power evaluation, the host steps of the activation half and the frame sums of
+// Declarations shared by evc_beta.hip (evc_beta_solve), evc_beta_learn.hip (evc_beta_learn), evc_online.hip
+// (evc_online_learn) and evc_transform.hip (evc_online_transform): the tile geometry, the power evaluation, the host steps of the activation half and the frame sums of
 // the dictionary half.
 #pragma once
 #include "evc_internal.h"
@@ -12,6 +12,7 @@ constexpr int BT_THREADS = 64 * BT_WAVES;
 constexpr int BT_GT = 8;            // bin tiles per pass of phase 1 (accumulators held at once)
 constexpr int BETA_MAX_M = 528;     // two LDS images of 528 x 16 float64: 135 168 of 163 840 bytes
 constexpr int BETA_MAX_SLOTS = 4097;
+constexpr int BETA_CHG_LDS = 4 * 2 * 16 * 8;    // the change variant of the sweep: [4 wavefronts][2][16 frames] float64 after Q1 | Q2
 constexpr double BETA_EPS = 1.1920928955078125e-7;
 constexpr double BETA_E64 = 2.220446049250313e-16;      // 2^-52, numpy's float64 epsilon (in both element types)
 constexpr int BDG_MAX_R = 256;        // k_beta_dict_grad: 256 x 20 elements of W and 3 x 16 x 64 of partial sums, 64 KB of LDS in float64
@@ -69,6 +70,8 @@ template <typename T> struct BetaArgs {
     T flush;                // > 0: an updated activation below it is stored as 0 (evc_beta_learn, beta < 1); 0: off
     double beta;
     int tile0;              // workgroup 0's tile: 0, or the first tile of the one batch evc_online_learn launches over
+    double* chg;            // [n_tiles * 16][2] per-frame shares of sum (h_new - h_old)^2 and sum h_new^2: written by the
+                            // change variant of the sweep only (evc_online_transform); NULL elsewhere
 };
 
 
@@ -85,6 +88,7 @@ template <typename T> struct BetaCtx {
     BetaArgs<T> a;
     BetaWs<T> w;
     int n_tiles, n_utt, n_slots, fm;
+    int utt0;               // first utterance of a call that runs over a range (evc_online_learn_fresh: one batch); else 0
 };
 
 // gamma of the multiplicative update (sklearn _nmf.py:780-785)
@@ -107,6 +111,20 @@ template <typename T>
 int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, double tol, hipStream_t s);
 // its first half alone: every frame's share of the divergence into errf (evc_online_learn sums one batch's shares itself)
 template <typename T> int beta_err(const BetaCtx<T>& c, hipStream_t s);
+// the start of the activations: nothing for EVC_INIT_GIVEN, else every activation of utterance u at sqrt(mean(X_u) / N)
+// (EVC_INIT_SKLEARN) or at init_value (EVC_INIT_CONST)
+template <typename T> int beta_start(const BetaCtx<T>& c, int init_mode, double init_value, hipStream_t s);
+// iteration `it` (1, 2, ...) of a solve that stops on the change of its activations (MiniBatchNMF._solve_W): the change
+// variant of the sweep, which also leaves every frame's shares in c.a.chg, then per utterance ratio = ||H_new - H_old||_F /
+// ||H_new||_F into trace slot it - 1 and, if tol > 0 and ratio <= tol, stop[u] = it - all on the device
+template <typename T> int beta_sweep_change(const BetaCtx<T>& c, int it, double tol, hipStream_t s);
+// the pieces evc_online_learn_fresh puts around that solve, over the range c describes (utterances [utt0, utt0 + n_utt), tiles
+// [a.tile0, a.tile0 + n_tiles)): beta_h0 forms every utterance's start value sqrt(mean(X_u) / N) (once per call, over all
+// utterances); beta_restart clears the range's stop words and, with `fill`, sets its columns of H to the start values; beta_flush
+// stores 0 over every activation of the range below thr - a pass of its own after the solve, never BetaArgs.flush during it
+template <typename T> int beta_h0(const BetaCtx<T>& c, hipStream_t s);
+template <typename T> int beta_restart(const BetaCtx<T>& c, bool fill, hipStream_t s);
+template <typename T> int beta_flush(const BetaCtx<T>& c, double thr, hipStream_t s);
 
 // ----- evc_beta_learn.hip: the frame sums of the dictionary half, shared with evc_online_learn -----
 // part[s][0 | 1][m][r] = Num | Den (before the penalties) of the dictionary update over the s-th of S contiguous ranges of

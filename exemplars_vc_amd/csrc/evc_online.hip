@@ -19,6 +19,12 @@
 // The argument checks, the workspace carving and OnlineStop are host-only code in evc_online_plan.h, which a stand-alone
 // program runs under the host sanitizers (tests/online_host_main.hip).
 // With the stop rules off and nothing asked back, the cost kernels are not launched and the call is a pure enqueue.
+// evc_online_learn_fresh is the same driver with MiniBatchNMF's fresh_restarts=True (`fresh` below): a step's activations
+// are not one carried update but a whole _solve_W on the batch - the stop word cleared, the batch's columns of H refilled
+// with sqrt(mean(X_b) / R), up to fresh_max_iter change-variant sweeps stopped on the device by tol (beta_sweep_change,
+// evc_beta.hip), then the flush as a pass of its own - and the fit ends with one such solve over all frames as one
+// utterance (final_max_iter), which has an activation half of its own because batches start at tile boundaries.  DESIGN.md
+// §5.13.
 // Nothing here exchanges data between workgroups inside a launch, uses float atomics or assumes residency: the same call
 // gives bitwise the same W, H, A and B every time.
 #include "evc_online_plan.h"
@@ -154,11 +160,12 @@ __global__ __launch_bounds__(256) void k_online_stats(OnlineStatsArgs a, const T
     a.out[2] = red[2][0];
 }
 
-// arguments already validated by evc_online_learn; returns ST_OK, ST_WORKSPACE or a hipError_t
+// arguments already validated by the entry; returns ST_OK, ST_WORKSPACE or a hipError_t.  fresh: NULL for evc_online_learn,
+// else evc_online_learn_fresh's counts, with fw its two extra pieces of workspace
 template <typename T>
 int online_learn(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, void* A_, void* B_, int ldacc, int M, int R,
                  int T_, const evc_online_opts& o, int forced, bool fused, void* ws, size_t ws_bytes, int* n_iter_out,
-                 int* n_steps_out, double* trace_out, hipStream_t s) {
+                 int* n_steps_out, double* trace_out, hipStream_t s, const FreshPlan* fresh, const FreshWs* fw) {
     const int bs = o.batch_size < T_ ? o.batch_size : T_, nb = (T_ + bs - 1) / bs;
     const OnWs<T> w = carve_online<T>(ws, M, R, T_, bs, nb);
     if (w.bytes > ws_bytes) return ST_WORKSPACE;
@@ -187,10 +194,17 @@ int online_learn(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, 
         for (int b = 0; b < nb; ++b) offs[b] = b * bs;
         offs[nb] = T_;
         BetaCtx<T> c;
+        // a plain step flushes at the sweep's store; a fresh step's solve must not (an entry flushed mid-solve could never
+        // recover): it flushes once, afterwards
         const int st = beta_begin<T>(c, X, ldx, H, ldh, M, R, T_, offs, nb, o.layout, beta, o.l1_h, o.l2_h,
-                                     beta < 1.0 ? BETA_E64 : 0.0, 1, w.beta_ws, w.beta_bytes, s);
+                                     !fresh && beta < 1.0 ? BETA_E64 : 0.0, fresh ? fresh->slots() : 1, w.beta_ws,
+                                     w.beta_bytes, s);
         free(offs);
         HIP_TRY(st);
+        if (fresh) {
+            c.a.chg = fw->chg;
+            HIP_TRY(beta_h0<T>(c, s));      // the batches' means never change: once per call
+        }
         HIP_TRY(copy2d<T>(X, ldx, T_, M, fm ? 0 : 1, w.Xt, d.Mk, d.Tp, d.Mk, 0, s));
         HIP_TRY(beta_dict_sums_prepare<T>(fused));
         const double gamma = beta_gamma(beta);
@@ -207,7 +221,16 @@ int online_learn(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, 
             cb.a.tile0 = b * tiles_full;
             cb.n_tiles = (Tb + BT_F - 1) / BT_F;
             HIP_TRY(beta_pack_dict<T>(c, W, ldw, s));
-            HIP_TRY(beta_sweep<T>(cb, s));
+            if (!fresh) {
+                HIP_TRY(beta_sweep<T>(cb, s));
+            } else {
+                cb.utt0 = b;
+                cb.n_utt = 1;
+                HIP_TRY(beta_restart<T>(cb, true, s));
+                for (int it = 1; it <= fresh->fresh_max_iter; ++it) HIP_TRY(beta_sweep_change<T>(cb, it, o.tol, s));
+                if (beta < 1.0) HIP_TRY(beta_flush<T>(cb, BETA_E64, s));
+                if (reads) HIP_TRY(beta_restart<T>(cb, false, s));      // k_beta_err skips a stopped utterance
+            }
             if (reads) HIP_TRY(beta_err<T>(cb, s));
             // frames-as-rows copies of the dictionary and of the batch's new activations
             const int Tpb = frame_pad((int)sizeof(T), Tb);
@@ -246,6 +269,15 @@ int online_learn(const void* X_, int ldx, void* W_, int ldw, void* H_, int ldh, 
         }
         if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
     }
+    if (fresh && fresh->final_max_iter > 0) {       // _fit_transform's last line: _solve_W over all frames, no flush
+        BetaCtx<T> c2;
+        HIP_TRY(beta_begin<T>(c2, X, ldx, H, ldh, M, R, T_, nullptr, 1, o.layout, beta, o.l1_h, o.l2_h, 0.0, fresh->slots(),
+                              fw->final_ws, fw->final_bytes, s));
+        c2.a.chg = fw->chg;
+        HIP_TRY(beta_pack_dict<T>(c2, W, ldw, s));
+        HIP_TRY(beta_start<T>(c2, EVC_INIT_SKLEARN, 0.0, s));
+        for (int it = 1; it <= fresh->final_max_iter; ++it) HIP_TRY(beta_sweep_change<T>(c2, it, o.tol, s));
+    }
     if (n_steps_out) *n_steps_out = (int)n_steps;
     if (n_iter_out) *n_iter_out = (int)((n_steps + nb - 1) / nb);
     return ST_OK;
@@ -276,7 +308,29 @@ int evc_online_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh,
     return (o.dtype == EVC_F64 ? online_learn<double> : online_learn<float>)(X, ldx, W, ldw, H, ldh, acc_a, acc_b, ld_acc, M,
                                                                               R, T, o, forced, fused, workspace,
                                                                               workspace_bytes, n_iter_out, n_steps_out,
-                                                                              trace_out, s);
+                                                                              trace_out, s, nullptr, nullptr);
+}
+
+size_t evc_online_fresh_workspace_bytes(int M, int R, int T, int batch_size, int dtype) {
+    return evc::online_fresh_workspace_bytes(M, R, T, batch_size, dtype);
+}
+
+int evc_online_learn_fresh(const void* X, int ldx, void* W, int ldw, void* H, int ldh, void* acc_a, void* acc_b, int ld_acc,
+                           int M, int R, int T, const evc_online_fresh_opts* opts, void* workspace, size_t workspace_bytes,
+                           int* n_iter_out, int* n_steps_out, double* trace_out, evc_stream_t stream) {
+    using namespace evc;
+    int forced;
+    bool fused;
+    evc_online_opts o;
+    FreshPlan plan;
+    HIP_TRY(online_fresh_args_check(X, ldx, W, ldw, H, ldh, acc_a, acc_b, ld_acc, M, R, T, opts, workspace, workspace_bytes, &o,
+                                    &plan, &forced, &fused));
+    const FreshWs fw = carve_fresh(workspace, M, R, T, o.batch_size, o.dtype);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    return (o.dtype == EVC_F64 ? online_learn<double> : online_learn<float>)(X, ldx, W, ldw, H, ldh, acc_a, acc_b, ld_acc, M,
+                                                                              R, T, o, forced, fused, fw.online_ws,
+                                                                              fw.online_bytes, n_iter_out, n_steps_out,
+                                                                              trace_out, s, &plan, &fw);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// evc_online_plan.h - what evc_online_learn decides on the host before and between its launches: the argument checks,
-// the workspace carving and the convergence rule.  No device code: tests/online_host_main.hip, a program of its own,
+// evc_online_plan.h - what evc_online_learn and evc_online_learn_fresh decide on the host before and between their launches:
+// the argument checks, the workspace carving and the convergence rule.  No device code: tests/online_host_main.hip, a program of its own,
 // includes it and runs it under the host sanitizers (tests/test_online_host.py).
 #pragma once
 #include "evc_beta_common.h"
@@ -101,6 +101,71 @@ inline int online_args_check(const void* X, int ldx, const void* W, int ldw, con
     if (route == ROUTE_FUSED && R > BDG_MAX_R) return ST_UNSUPPORTED;
     if (workspace_bytes < online_workspace_bytes(M, R, T, o.batch_size, o.dtype)) return ST_WORKSPACE;
     *fused = route == ROUTE_FUSED || (route == ROUTE_AUTO && R <= BDG_ROUTE_R);
+    return ST_OK;
+}
+
+// ----- evc_online_learn_fresh: the same learner with MiniBatchNMF's fresh restarts -----
+// what the fresh-restart entry adds to the step (NULL for evc_online_learn): the iterations of a step's activation solve and
+// of the solve over all frames that ends the fit (0: none)
+struct FreshPlan {
+    int fresh_max_iter, final_max_iter;
+    int slots() const { const int k = fresh_max_iter > final_max_iter ? fresh_max_iter : final_max_iter; return k > 0 ? k : 1; }
+};
+
+struct FreshWs {
+    char *online_ws, *final_ws;
+    double* chg;            // [tiles * 16][2] the change variant's per-frame shares: the batches' table or the final solve's
+    size_t online_bytes, final_bytes, bytes;
+};
+
+// [evc_online_learn's workspace | chg | the final solve's activation half], each 256-byte aligned (ws == NULL: sizes only).
+// Batches start at tile boundaries, so the final solve over all frames as one utterance has a tile table of its own: it
+// gets a second activation half (n_utt = 1) rather than a second table squeezed into the first.
+inline FreshWs carve_fresh(void* ws, int M, int R, int T_, int batch_size, int dtype) {
+    FreshWs w;
+    const int bs = batch_size < T_ ? batch_size : T_, nb = (T_ + bs - 1) / bs;
+    Carver c = Carver::rounded(ws);
+    w.online_bytes = online_workspace_bytes(M, R, T_, batch_size, dtype);
+    w.online_ws = c.take<char>(w.online_bytes);
+    w.chg = c.take<double>((size_t)frame_tile_cap(T_, BT_F, nb) * BT_F * 2);
+    w.final_bytes = beta_workspace_bytes(M, R, T_, 1, dtype);
+    w.final_ws = c.take<char>(w.final_bytes);
+    w.bytes = c.bytes();
+    return w;
+}
+
+inline size_t online_fresh_workspace_bytes(int M, int R, int T_, int batch_size, int dtype) {
+    if (!online_sizes_ok(M, R, T_, dtype) || batch_size < 1) return 0;
+    return carve_fresh(nullptr, M, R, T_, batch_size, dtype).bytes + 256;
+}
+
+// the fields evc_online_fresh_opts shares with evc_online_opts, as one of those
+inline evc_online_opts online_opts_of(const evc_online_fresh_opts& f) {
+    evc_online_opts o;
+    o.struct_bytes = (int)sizeof(evc_online_opts);
+    o.dtype = f.dtype; o.layout = f.layout; o.batch_size = f.batch_size; o.max_iter = f.max_iter;
+    o.max_no_improvement = f.max_no_improvement; o.resume = f.resume; o.reserved = f.reserved;
+    o.beta = f.beta; o.tol = f.tol; o.forget_factor = f.forget_factor;
+    o.l1_h = f.l1_h; o.l2_h = f.l2_h; o.l1_w = f.l1_w; o.l2_w = f.l2_w;
+    o.ev_loop_start = f.ev_loop_start; o.ev_loop_stop = f.ev_loop_stop;
+    return o;
+}
+
+// evc_online_learn_fresh's argument checks: its own two counts, then evc_online_learn's in their order (ST_BADARG,
+// ST_UNSUPPORTED, ST_WORKSPACE against the larger workspace); *o: the shared options, *plan: the two counts
+inline int online_fresh_args_check(const void* X, int ldx, const void* W, int ldw, const void* H, int ldh, const void* acc_a,
+                                   const void* acc_b, int ld_acc, int M, int R, int T, const evc_online_fresh_opts* opts,
+                                   const void* workspace, size_t workspace_bytes, evc_online_opts* o, FreshPlan* plan,
+                                   int* forced, bool* fused) {
+    if (!opts || opts->struct_bytes != (int)sizeof(evc_online_fresh_opts)) return ST_BADARG;
+    if (opts->fresh_max_iter < 1 || opts->fresh_max_iter > BETA_MAX_SLOTS) return ST_BADARG;
+    if (opts->final_max_iter < 0 || opts->final_max_iter > BETA_MAX_SLOTS) return ST_BADARG;
+    *o = online_opts_of(*opts);
+    plan->fresh_max_iter = opts->fresh_max_iter;
+    plan->final_max_iter = opts->final_max_iter;
+    const int st = online_args_check(X, ldx, W, ldw, H, ldh, acc_a, acc_b, ld_acc, M, R, T, o, workspace, (size_t)-1, forced, fused);
+    if (st != ST_OK) return st;
+    if (workspace_bytes < online_fresh_workspace_bytes(M, R, T, o->batch_size, o->dtype)) return ST_WORKSPACE;
     return ST_OK;
 }
 

@@ -509,6 +509,58 @@ def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100
     return H_out
 
 
+def transform_online(W, X, *, beta=2.0, layout, max_iter=200, tol=1e-4, l1=0.0, l2=0.0, H0=None, init=None,
+                     utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False, init_value=0.0,
+                     out=None, loop_events=None):
+    """scikit-learn's MiniBatchNMF.transform (_solve_W) with the dictionary W fixed, on the GPU (evc_online_transform): the
+    activations of X under a dictionary learned online (learn_dictionary_online, compact_dictionary(batch_size=...)).
+    Multiplicative updates under any beta-divergence as in solve_activations_beta, checked EVERY iteration: an utterance stops
+    once ||H_new - H_old||_F / ||H_new||_F <= tol and keeps that update (tol = 0: never).  One utterance (utt_offsets) is one
+    transform call: its own start sqrt(mean(X_u) / R), ratio and stop, all decided on the device.  init: "sklearn" (the
+    default without H0), "given" (H0) or "const" (init_value).  l1 / l2 are sklearn's scaled l1_reg_W / l2_reg_W.  At most 528
+    bins.  out: a device tensor of the activations' shape and type (rows may be padded) that receives them.
+
+    Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out); with
+    info=True also dict(n_iter=int array per utterance, change=[n_utt, max_iter] the ratio of every iteration carried out
+    (NaN after the stop), kernel="k_beta_sweep<change>").  info=False enqueues without waiting.  No CPU fallback: without a
+    HIP device this raises RuntimeError."""
+    lay = _LAYOUTS[layout]
+    beta = float(beta)
+    if not np.isfinite(beta):
+        raise ValueError(f"beta must be finite, got {beta!r}")
+    max_iter = int(max_iter)
+    if max_iter < 0:
+        raise ValueError(f"max_iter must not be negative, got {max_iter!r}")
+    wshape = tuple(getattr(W, "shape", ()))
+    if len(wshape) == 2 and wshape[0 if lay == _lib.BIN_MAJOR else 1] > _lib.BETA_MAX_M:     # what the ABI answers with -3
+        raise ValueError(f"unsupported beta-divergence shape: M = {wshape[0 if lay == _lib.BIN_MAJOR else 1]} bins, the "
+                         f"kernel holds at most {_lib.BETA_MAX_M}")
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    p = _operands(W, X, H0, init, layout, dtype, device, utt_offsets, out=out)
+    W_d, X_d, H_d, M, R, T, n_utt, dcode = p.A_d, p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt, p.dcode
+    if M < 1 or R < 1:
+        raise ValueError(f"empty beta-divergence problem M={M}, R={R}, T={T}")
+    opts = _lib.TransformOpts()
+    opts.struct_bytes = C.sizeof(_lib.TransformOpts)
+    opts.dtype, opts.layout, opts.max_iter, opts.init_mode = dcode, lay, max_iter, _INITS[p.init]
+    opts.beta, opts.tol, opts.l1, opts.l2, opts.init_value = beta, float(tol), float(l1), float(l2), float(init_value)
+    _loop_events(opts, loop_events)
+    ws_bytes = int(L.evc_online_transform_workspace_bytes(M, R, T, n_utt, dcode))
+    n_iter, change, ni_p, ch_p = _trace_arrays(n_utt, max_iter, info)
+    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_online_transform(W_d.data_ptr(), _ld(W_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, R, T,
+                                    p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, ch_p,
+                                    C.c_void_p(stream))
+    _lib.check(st, "evc_online_transform")
+    H_out = _to_host(H_d) if p.x_np else H_d
+    if info:
+        return H_out, {"n_iter": n_iter, "change": change, "kernel": "k_beta_sweep<change>"}
+    return H_out
+
+
 def _learn(entry, opts, X, W0, H0, *, layout, ws_bytes, unsupported, trace, extra_info, tol, dtype, device, info, out_w,
            out_h, loop_events, splits, call=None):
     """What learn_dictionary, learn_dictionary_beta and learn_dictionary_cd share around their C entry `entry`: the
@@ -656,7 +708,8 @@ def learn_dictionary_beta(X, W0, H0, *, beta, layout, iters, check_every=10, tol
 
 def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max_iter=200, forget_factor=0.7, tol=1e-4,
                             max_no_improvement=10, l1_h=0.0, l2_h=0.0, l1_w=0.0, l2_w=0.0, state=None, dtype=None,
-                            device=None, info=False, route=None, splits=None, out_w=None, out_h=None, loop_events=None):
+                            device=None, info=False, route=None, splits=None, out_w=None, out_h=None, loop_events=None,
+                            fresh_restarts=False, fresh_restarts_max_iter=30, transform_max_iter=None):
     """scikit-learn's mini-batch dictionary learning, X ~ W H (MiniBatchNMF(init='custom', fresh_restarts=False,
     beta_loss=beta).fit_transform), on the GPU (evc_online_learn).  W is addressed like the dictionary A of
     solve_activations, H like its activations, both start at W0 / H0.  The frames are taken in contiguous batches of
@@ -666,7 +719,11 @@ def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max
     W in a step is <= tol (tol = 0: off) or the smoothed batch cost has not improved for max_no_improvement steps (None or
     negative: off).  l1_h / l2_h are sklearn's scaled l1_reg_W / l2_reg_W (activations, scaled by the bins); l1_w / l2_w
     are PER FRAME (alpha_H * l1_ratio and alpha_H * (1 - l1_ratio)): each step multiplies them by its batch's frames.  At
-    most 528 bins.  Not served: fresh_restarts=True, partial_fit / transform, sparse X, shuffling.
+    most 528 bins.  transform_online gives the activations of new frames under the learned W (MiniBatchNMF.transform).
+    fresh_restarts=True (evc_online_learn_fresh) solves every step's activations afresh - from sqrt(mean(X_b) / R), up to
+    fresh_restarts_max_iter updates, stopped by tol on their own change - and ends with such a solve over all frames
+    (transform_max_iter updates; None: max_iter; 0: none): H0's values are then ignored, and H0 may be None.  Not served:
+    sparse X, shuffling.
 
     Returns (W, H) as learn_dictionary does; with info=True also dict(n_iter=passes begun, n_steps=steps carried out,
     cost=[steps] batch costs, change=[steps] ||W_new - W_old|| / ||W_new|| (both NaN after the stop), route="fused" |
@@ -698,7 +755,19 @@ def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max
     per_pass = -(-T // bs)
     splits = int(splits or 0)
     mni = -1 if max_no_improvement is None else int(max_no_improvement)
-    opts = _lib.OnlineOpts()
+    fresh = bool(fresh_restarts)
+    entry = "evc_online_learn_fresh" if fresh else "evc_online_learn"
+    opts = _lib.OnlineFreshOpts() if fresh else _lib.OnlineOpts()
+    if fresh:
+        opts.fresh_max_iter = int(fresh_restarts_max_iter)
+        opts.final_max_iter = int(max_iter if transform_max_iter is None else transform_max_iter)
+        if opts.fresh_max_iter < 1 or opts.final_max_iter < 0:
+            raise ValueError("fresh_restarts_max_iter must be at least 1 and transform_max_iter must not be negative")
+        if H0 is None and out_h is None:        # the start is ignored: any matrix of the activations' shape
+            R = int(tuple(W0.shape)[1 if bm else 0])
+            hshape = (R, T) if bm else (T, R)
+            H0 = torch.empty(hshape, dtype=W0.dtype, device=W0.device) if isinstance(W0, torch.Tensor) \
+                else np.empty(hshape, dtype=np.asarray(W0).dtype)
     opts.batch_size, opts.max_iter, opts.max_no_improvement = int(batch_size), int(max_iter), mni
     opts.resume = 0 if state is None else 1
     opts.reserved = _BETA_ROUTES[route] << 16
@@ -718,16 +787,17 @@ def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max
                     raise ValueError("`state` must be the (A, B) device tensors of an earlier call's info, shaped like W")
         acc["state"] = (A_d, B_d)
         quiet = n_iter_p is None
-        return L.evc_online_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d),
-                                  A_d.data_ptr(), B_d.data_ptr(), _ld(A_d), M, R, T, C.byref(opts), ws.data_ptr(), ws.numel(),
-                                  n_iter_p, None if quiet else C.byref(n_steps), tr_p, C.c_void_p(stream))
+        return getattr(L, entry)(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d),
+                                 A_d.data_ptr(), B_d.data_ptr(), _ld(A_d), M, R, T, C.byref(opts), ws.data_ptr(), ws.numel(),
+                                 n_iter_p, None if quiet else C.byref(n_steps), tr_p, C.c_void_p(stream))
 
     def extra_info(L, M, R, T):
         return {"n_steps": int(n_steps.value), "state": acc["state"],
                 "route": route or ("fused", "unfused")[int(L.evc_beta_learn_route(M, R, T)) - 1]}
 
-    res = _learn("evc_online_learn", opts, X, W0, H0, layout=layout,
-                 ws_bytes=lambda L, M, R, T, dcode: int(L.evc_online_workspace_bytes(M, R, T, int(batch_size), dcode)),
+    ws_query = "evc_online_fresh_workspace_bytes" if fresh else "evc_online_workspace_bytes"
+    res = _learn(entry, opts, X, W0, H0, layout=layout,
+                 ws_bytes=lambda L, M, R, T, dcode: int(getattr(L, ws_query)(M, R, T, int(batch_size), dcode)),
                  unsupported=lambda M, R, T: f"unsupported mini-batch learning shape M={M}, R={R}, T={T} "
                                              f"(M <= {_lib.BETA_MAX_M}, R <= 4096)",
                  trace=("trace", (max(int(max_iter), 0) * per_pass, 2)), extra_info=extra_info,

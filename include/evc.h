@@ -45,6 +45,13 @@
  *   evc_online_learn  replaces MiniBatchNMF(init='custom', fresh_restarts=False).fit_transform(X, W=W, H=H): the mini-batch
  *                   learner for any beta_loss (sklearn _minibatch_step, _multiplicative_update_h with A, B and rho,
  *                   _minibatch_convergence); evc_online_workspace_bytes and evc_online_splits size and describe it
+ *   evc_online_transform  replaces MiniBatchNMF.transform(X) with a dictionary learned online (sklearn _solve_W,
+ *                   _nmf.py:2046-2071): the activation solve that stops on the change of its activations, checked every
+ *                   iteration on the device; evc_online_transform_workspace_bytes sizes it
+ *   evc_online_learn_fresh  replaces MiniBatchNMF(init='custom', fresh_restarts=True).fit_transform(X, W=W, H=H) and, one
+ *                   step at a time, MiniBatchNMF.partial_fit: evc_online_learn whose every step solves its batch's
+ *                   activations afresh (_solve_W) and whose fit ends with that solve over all frames;
+ *                   evc_online_fresh_workspace_bytes sizes it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -98,6 +105,14 @@
  *         and the two sums of squares of the dictionary's change ratio) and decides the stop there.  None of its kernels
  *         exchanges data between workgroups inside a launch, uses float atomics or assumes residency: concurrent calls on
  *         several streams are safe, and the same call gives the same bits every time.
+ *     (11) evc_online_transform: n_iter_out / change_out non-NULL (the call returns after copying them back); otherwise the
+ *         call is a pure enqueue of max_iter iterations: the change ratio is formed and the stop decided on the device, per
+ *         utterance, without a host round trip.  None of its kernels exchanges data between workgroups inside a launch, uses
+ *         float atomics or assumes residency: concurrent calls on several streams are safe, and the same call gives the
+ *         same bits every time.
+ *     (12) evc_online_learn_fresh: as case (10) - with tol == 0, max_no_improvement < 0 and NULL n_iter_out, n_steps_out and
+ *         trace_out the call is a pure enqueue (every solve runs its full count); otherwise the host reads three doubles
+ *         after every step.  The solves inside a step and the one that ends the fit stop on the device, as in case (11).
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
  *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets, sample_offsets) are consumed before the call returns: they are
@@ -765,8 +780,9 @@ int evc_beta_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, i
  * unfused route of the frame sums follows evc_beta_learn_route.  The batch cycle and the convergence state restart with
  * every call: with the stop rules off, a call of p passes followed by a resume = 1 call of q passes gives bitwise the W, H, A
  * and B of one call of p + q passes.
- * Out of scope: fresh_restarts=True; partial_fit and transform (both are _solve_W, a fixed-dictionary solve with a
- * change-of-W stop rule that evc_beta_solve does not have); sparse X; shuffled batches.
+ * transform (MiniBatchNMF._solve_W, the fixed-dictionary solve that stops on the change of its activations) is served by
+ * evc_online_transform below; fresh_restarts=True and partial_fit (both put that solve inside the step) by
+ * evc_online_learn_fresh.  Out of scope in all three: sparse X; shuffled batches.
  *   M : 1 .. 528, R : 1 .. 4096 (larger: -3);  T >= 1;  max_iter = 0 returns the start (and sets A and B when resume = 0)
  *   l1_h, l2_h : already scaled by the number of bins, as in evc_beta_learn_opts
  *   l1_w, l2_w : PER FRAME (sklearn's alpha_H * l1_ratio and alpha_H * (1 - l1_ratio)): the call multiplies them by T_b
@@ -803,6 +819,91 @@ int evc_online_splits(int M, int R, int batch_frames);
 int evc_online_learn(const void* X, int ldx, void* W, int ldw, void* H, int ldh, void* acc_a, void* acc_b, int ld_acc, int M,
                      int R, int T, const evc_online_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
                      int* n_steps_out, double* trace_out, evc_stream_t stream);
+
+/* The activation solve of the mini-batch estimator: scikit-learn 1.7.2's MiniBatchNMF.transform(X), that is
+ * MiniBatchNMF._solve_W(X, components_, transform_max_iter) (_nmf.py:2046-2071), with the dictionary W (M x R) fixed.  X is
+ * M x T, H is R x T, all addressed as in evc_beta_solve (W is its A; sklearn's W is H^T here, its H is W^T).  One utterance is
+ * one transform call.  Per utterance u:
+ *   start      every activation at sqrt(mean(X_u) / R) (EVC_INIT_SKLEARN, what scikit-learn does; EVC_INIT_GIVEN and
+ *              EVC_INIT_CONST as in evc_beta_solve)
+ *   iteration  one multiplicative update, evc_beta_solve's statement with l1 and l2 (the same kernel and the same stored
+ *              values: EPS, gamma and the evaluation of the powers as there); nothing is flushed to 0
+ *   check      after EVERY iteration ratio = ||H_new - H_old||_F / ||H_new||_F over the utterance's frames, both sums of squares
+ *              in float64 in a fixed order; if tol > 0 and ratio <= tol the utterance stops and keeps that update (a NaN
+ *              ratio, 0 / 0 among them, compares false and never stops, as in numpy)
+ * The ratio is formed and the stop decided on the device: per iteration one sweep launch, which also leaves every frame's
+ * shares of the two sums, and one small launch that sums them per utterance; a stopped utterance's frames are frozen while
+ * the others go on.  With tol = 0 the activations are bitwise those of evc_beta_solve with the same start, `max_iter`
+ * iterations and check_every = 0.  A batch of utterances gives bitwise the activations, counts and ratios of one call per
+ * utterance; a NaN or infinity in a frame of X stays in that frame's column, except through the utterance's start value and
+ * its stop decision.  float32 inputs are solved in float32; the ratio is float64 for both types.
+ *   M      : 1 .. 528 bins (larger: -3);  any R >= 1, T >= 0 (an utterance may be empty: nothing is done for it, its n_iter
+ *            is max_iter and its ratios stay NaN);  max_iter = 0 leaves the start in H
+ *   max_iter : 0 .. 4097, evc_beta_solve's slot limit (more: -1)
+ *   l1, l2 : already scaled, as evc_beta_opts has them: sklearn's l1_reg_W = M alpha_W l1_ratio, l2_reg_W = M alpha_W (1 - l1_ratio)
+ *   n_iter_out : host, n_utt ints or NULL: the iteration each utterance stopped at, or max_iter
+ *   change_out : host, n_utt * max_iter doubles or NULL: [u][i] the ratio of iteration i + 1; NaN after the stop
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: case (11) of the list at the top. */
+typedef struct evc_transform_opts {
+    int struct_bytes;  /* sizeof(evc_transform_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int max_iter;      /* maximum number of multiplicative updates, 0 .. 4097 */
+    int init_mode;     /* EVC_INIT_SKLEARN | EVC_INIT_GIVEN | EVC_INIT_CONST */
+    int reserved;      /* 0 */
+    double beta;       /* the divergence: 0 Itakura-Saito, 1 Kullback-Leibler, 2 Frobenius, or any finite value */
+    double tol;        /* >= 0; 0: never stops */
+    double l1, l2;     /* >= 0 */
+    double init_value; /* EVC_INIT_CONST */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_transform_opts;
+/* bytes of workspace evc_online_transform needs (0: invalid arguments, M > 528 among them) */
+size_t evc_online_transform_workspace_bytes(int M, int R, int T, int n_utt, int dtype);
+int evc_online_transform(const void* W, int ldw, const void* X, int ldx, void* H, int ldh, int M, int R, int T,
+                         const int* utt_offsets, int n_utt, const evc_transform_opts* opts, void* workspace,
+                         size_t workspace_bytes, int* n_iter_out, double* change_out, evc_stream_t stream);
+
+/* evc_online_learn with scikit-learn's fresh restarts: MiniBatchNMF(init='custom', fresh_restarts=True,
+ * fresh_restarts_max_iter=fresh_max_iter, transform_max_iter=final_max_iter).fit_transform(X, W=..., H=...) (_nmf.py:2082-2083,
+ * :2307-2308).  Arguments, batches, rho, accumulators, cost, dictionary half, convergence rule, statuses and outputs are
+ * evc_online_learn's; the caller's H is ignored as a start (as in scikit-learn) and receives the result.  What differs,
+ * step k on batch b:
+ *   activations  evc_online_transform's solve on the batch as one utterance against the current W: every activation of the
+ *                batch starts at sqrt(mean(X_b) / R), up to fresh_max_iter updates with l1_h and l2_h, stopped on the device
+ *                once tol > 0 and ||H_new - H_old||_F / ||H_new||_F <= tol over the batch; nothing is flushed during the
+ *                solve (an entry flushed mid-solve could never recover); then, if beta < 1, H_b[H_b < E64] = 0 in a pass
+ *                of its own
+ * and after the loop, if final_max_iter > 0, one such solve over ALL frames as one utterance (start sqrt(mean(X) / R), the
+ * ratio over all frames, up to final_max_iter updates, no flush) against the final W: the H the call returns.
+ * One step with batch_size >= T, max_iter = 1, final_max_iter = 0, max_no_improvement < 0 and resume = 1 from the second call
+ * on is MiniBatchNMF.partial_fit on that chunk (forget_factor then is scikit-learn's rho itself: the exponent is 1).
+ *   fresh_max_iter : 1 .. 4097;  final_max_iter : 0 .. 4097 (outside: -1)
+ * Host synchronisation: case (12) of the list at the top. */
+typedef struct evc_online_fresh_opts {
+    int struct_bytes;        /* sizeof(evc_online_fresh_opts) */
+    int dtype;               /* the next seven as in evc_online_opts */
+    int layout;
+    int batch_size;
+    int max_iter;
+    int max_no_improvement;
+    int resume;
+    int reserved;
+    int fresh_max_iter;      /* updates of a step's activation solve at most (sklearn's fresh_restarts_max_iter) */
+    int final_max_iter;      /* updates of the solve over all frames that ends the fit (sklearn's transform_max_iter); 0: none */
+    double beta;             /* as in evc_online_opts */
+    double tol;              /* >= 0; stops the loop on the change of W AND every activation solve on the change of H; 0: neither */
+    double forget_factor;
+    double l1_h, l2_h;
+    double l1_w, l2_w;
+    void* ev_loop_start;
+    void* ev_loop_stop;
+} evc_online_fresh_opts;
+/* bytes of workspace evc_online_learn_fresh needs (0: invalid arguments): evc_online_learn's plus the final solve's */
+size_t evc_online_fresh_workspace_bytes(int M, int R, int T, int batch_size, int dtype);
+int evc_online_learn_fresh(const void* X, int ldx, void* W, int ldw, void* H, int ldh, void* acc_a, void* acc_b, int ld_acc,
+                           int M, int R, int T, const evc_online_fresh_opts* opts, void* workspace, size_t workspace_bytes,
+                           int* n_iter_out, int* n_steps_out, double* trace_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
