@@ -36,8 +36,10 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_beta_learn_workspace_bytes", "evc_beta_learn_splits", "evc_beta_learn_route", "evc_beta_learn",
            "evc_online_workspace_bytes", "evc_online_splits", "evc_online_learn",
            "evc_online_transform_workspace_bytes", "evc_online_transform",
-           "evc_online_fresh_workspace_bytes", "evc_online_learn_fresh")
+           "evc_online_fresh_workspace_bytes", "evc_online_learn_fresh",
+           "evc_deconv_workspace_bytes", "evc_deconv_solve", "evc_deconv_synthesize")
 BETA_MAX_M = 528
+DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
 
@@ -142,6 +144,16 @@ class TransformOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("max_iter", C.c_int),
         ("init_mode", C.c_int), ("reserved", C.c_int),
         ("beta", C.c_double), ("tol", C.c_double), ("l1", C.c_double), ("l2", C.c_double), ("init_value", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class DeconvOpts(C.Structure):
+    """Mirror of `evc_deconv_opts` (include/evc.h): options of the activation solve with multi-frame exemplars."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("loss", C.c_int), ("taps", C.c_int),
+        ("iters", C.c_int), ("init_mode", C.c_int), ("check_every", C.c_int), ("stop_rule", C.c_int), ("reserved", C.c_int),
+        ("tol", C.c_double), ("l1", C.c_double), ("l2", C.c_double), ("init_value", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -364,6 +376,25 @@ def lib():
     L.evc_online_learn_fresh.restype = C.c_int
     L.evc_online_learn_fresh.argtypes = L.evc_online_learn.argtypes[:12] + [C.POINTER(OnlineFreshOpts)] + \
         L.evc_online_learn.argtypes[13:]
+    L.evc_deconv_workspace_bytes.restype = C.c_size_t
+    L.evc_deconv_workspace_bytes.argtypes = [C.c_int] * 6
+    L.evc_deconv_solve.restype = C.c_int
+    L.evc_deconv_solve.argtypes = [
+        C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_int,    # A (lda, tap_stride), X, H
+        C.c_int, C.c_int, C.c_int,                                          # M, N, T
+        C.POINTER(C.c_int), C.c_int, C.POINTER(DeconvOpts),                 # utt_offsets, n_utt, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_deconv_synthesize.restype = C.c_int
+    L.evc_deconv_synthesize.argtypes = [
+        C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_int,    # B (ldb, tap_stride), H, Y
+        C.c_int, C.c_int, C.c_int,                                          # Mb, N, T
+        C.POINTER(C.c_int), C.c_int,                                        # utt_offsets, n_utt
+        C.c_int, C.c_int, C.c_int,                                          # taps, layout, dtype
+        C.c_void_p,                                                         # stream
+    ]
     _lib = L
     return L
 

@@ -9,7 +9,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..solver import _dtw_gather_device, _mfcc_device, _torch, dtw_align, dtw_dictionary, prepare_dictionary, require_device
+from ..solver import (_dtw_gather_device, _mfcc_device, _torch, dtw_align, dtw_dictionary, multiframe_dictionary, prepare_dictionary,
+                      require_device)
 
 
 def _dtw_alignment(feat_A, feat_B, *, device=None):
@@ -45,7 +46,7 @@ def align_sp_ap_f0(src_feat, tar_feat, src_W, tar_W, *, use_stft=True):
     return aligned_src, aligned_tar
 
 
-def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, key=None, device=None):
+def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, key=None, device=None, taps=None):
     """`dtw_alignment` + `make_exemplar_dict_W` + `align_sp_ap_f0` + the stacking of `factorize()` / `convert()`
     (01_make_dict_parallel.py:215-249,291-292; 04_align_n_nmf.py:100-169,230-246,320-324,350-361) in one pass on the GPU:
     the DTW paths are consumed on the device and the aligned frames never visit the host (the
@@ -54,8 +55,11 @@ def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, k
       dtw_src[i], dtw_tar[i] : (order, n_frames) alignment features as the reference holds them
       src_feat[i], tar_feat[i]: the scripts' feature dicts; use_stft=True takes |real(f["stft"])| (:320-324), else
                                 f[key] for key in "sp" | "ap" | "f0"
+      taps                    : None, or L >= 1 for multi-frame exemplars: exemplar n is the L aligned frames from n on,
+                                cut (zero columns) at the end of its file
     Returns a PreparedDictionary (A = aligned source frames, B = aligned target frames) for `solve_activations` /
-    `convert`, and the first dictionary row of every file."""
+    `convert`, and the first dictionary row of every file.  With taps: the parallel (A_taps, B_taps), device tensors
+    (L, N, bins) in frame_major for `solve_activations_deconv` / `convert_deconv`, and the rows."""
     if use_stft:
         sa = [np.asarray(f["stft"]) for f in src_feat]
         sb = [np.asarray(f["stft"]) for f in tar_feat]
@@ -68,6 +72,9 @@ def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, k
         A, B, rows = dtw_dictionary([np.asarray(a).T for a in dtw_src], [np.asarray(b).T for b in dtw_tar],
                                     [col(np.asarray(f[key])) for f in src_feat], [col(np.asarray(f[key])) for f in tar_feat],
                                     device=device)
+    if taps is not None:
+        return (multiframe_dictionary(A, rows, taps, layout="frame_major"),
+                multiframe_dictionary(B, rows, taps, layout="frame_major")), rows
     return prepare_dictionary(A, B, layout="frame_major", device=device), rows
 
 

@@ -561,6 +561,178 @@ def transform_online(W, X, *, beta=2.0, layout, max_iter=200, tol=1e-4, l1=0.0, 
     return H_out
 
 
+def multiframe_dictionary(frames, seg_offsets, L, *, layout="bin_major"):
+    """The taps of a multi-frame exemplar dictionary from an aligned frame sequence: exemplar n is the segment of L
+    consecutive frames that starts at frame n, so tap tau's column n is frame n + tau - or zero where that frame belongs to
+    another source file (seg_offsets: the first frame of every file, then the frame count, as utt_offsets).  frames is
+    (M, N) for bin_major, (N, M) for frame_major; returns (L, M, N) or (L, N, M) of the same kind (numpy array in, numpy
+    array out, without a GPU; a tensor on any device in, a tensor there out).  L = 1 returns the frames themselves."""
+    lay = _LAYOUTS[layout]
+    L = int(L)
+    if L < 1:
+        raise ValueError(f"L must be at least 1, got {L!r}")
+    offs = np.asarray(seg_offsets, dtype=np.int64)
+    if frames.ndim != 2:
+        raise ValueError(f"expected a 2-D matrix of frames, got shape {tuple(frames.shape)}")
+    N = int(frames.shape[1 if lay == _lib.BIN_MAJOR else 0])
+    if offs.ndim != 1 or len(offs) < 2 or offs[0] != 0 or offs[-1] != N or np.any(np.diff(offs) < 0):
+        raise ValueError(f"seg_offsets must rise from 0 to the frame count {N}")
+    n = np.arange(N)
+    end = offs[np.searchsorted(offs, n, side="right")] if N else n          # the end of every frame's file
+    is_np = isinstance(frames, np.ndarray)
+    taps = []
+    for tau in range(L):
+        inside = n + tau < end
+        src = np.where(inside, n + tau, 0)
+        if is_np:
+            where, zero = np.where, frames.dtype.type(0)
+        else:
+            torch = _torch()
+            src, inside = torch.from_numpy(src).to(frames.device), torch.from_numpy(inside).to(frames.device)
+            where, zero = torch.where, torch.zeros((), dtype=frames.dtype, device=frames.device)
+        if lay == _lib.BIN_MAJOR:
+            taps.append(where(inside[None, :], frames[:, src], zero))
+        else:
+            taps.append(where(inside[:, None], frames[src, :], zero))
+    return np.stack(taps) if is_np else _torch().stack(taps)
+
+
+def _taps_to_dev(D_taps, tdtype, device, what):
+    """(L, rows, cols) array / tensor -> device tensor with unit inner stride (a padded view stays one); (tensor, was_numpy)"""
+    torch = _torch()
+    was_numpy = not isinstance(D_taps, torch.Tensor)
+    D = torch.from_numpy(np.ascontiguousarray(np.asarray(D_taps))) if was_numpy else D_taps
+    if D.dim() != 3:
+        raise ValueError(f"{what} must be 3-D (taps, rows, columns), got shape {tuple(D.shape)}")
+    D = D.to(device=device, dtype=tdtype)
+    if (D.shape[2] > 1 and D.stride(2) != 1) or (D.shape[1] > 1 and D.stride(1) < D.shape[2]) or \
+            (D.shape[0] > 1 and D.stride(0) < 0):
+        D = D.contiguous()
+    return D, was_numpy
+
+
+def _deconv_limits(shape, lay, max_bins, what):
+    if len(shape) != 3:
+        raise ValueError(f"{what} must be 3-D (taps, rows, columns), got shape {shape}")
+    bins = shape[1 if lay == _lib.BIN_MAJOR else 2]
+    if shape[0] > _lib.DECONV_MAX_TAPS or bins > max_bins:       # what the ABI answers with -3
+        raise ValueError(f"unsupported deconvolution shape: {shape[0]} taps and {bins} bins, the kernels hold at most "
+                         f"{_lib.DECONV_MAX_TAPS} taps and {max_bins} bins")
+    if shape[0] < 1:
+        raise ValueError(f"{what} needs at least one tap")
+
+
+def solve_activations_deconv(A_taps, X, H0=None, *, loss="frobenius", layout="bin_major", iters=100, l1=0.0, l2=0.0, init=None,
+                             init_value=0.0, check_every=0, stop_rule="none", tol=0.0,
+                             utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False, out=None,
+                             loop_events=None):
+    """The activation solve with multi-frame exemplars (non-negative spectrogram deconvolution), on the GPU
+    (evc_deconv_solve): X[:, t] ~ sum_tau A_tau H[:, t - tau] per utterance, multiplicative updates under loss "frobenius"
+    or "kullback-leibler".  A_taps: (L, M, N) for bin_major, (L, N, M) for frame_major (multiframe_dictionary builds it); at
+    most 16 taps and 256 bins.  With L = 1 this is scikit-learn's fixed-dictionary update.  init, l1 / l2, check_every,
+    stop_rule, tol and utt_offsets as in solve_activations_beta; nothing crosses an utterance boundary.  out: a device tensor of
+    the activations' shape and type (rows may be padded) that receives them.
+
+    Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out); with
+    info=True also dict(n_iter=int array per utterance, err=[n_utt, 1 + iters // check_every] array (NaN where not
+    evaluated), kernel="k_deconv_update", taps=L).  No CPU fallback: without a HIP device this raises RuntimeError."""
+    lay = _LAYOUTS[layout]
+    if loss not in _LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_LOSSES)}, got {loss!r}")
+    if stop_rule not in ("none", "sklearn"):
+        raise ValueError("stop_rule must be 'none' or 'sklearn'")
+    _deconv_limits(tuple(getattr(A_taps, "shape", ())), lay, _lib.DECONV_MAX_M, "A_taps")
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    tdtype, _ = _pick_dtype(dtype, X, A_taps)
+    A_d, _ = _taps_to_dev(A_taps, tdtype, device, "A_taps")
+    taps = int(A_d.shape[0])
+    p = _operands(A_d[0], X, H0, init, layout, tdtype, device, utt_offsets, out=out)
+    X_d, H_d, M, N, T, n_utt, dcode = p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt, p.dcode
+    if M < 1 or N < 1:
+        raise ValueError(f"empty deconvolution problem M={M}, N={N}, T={T}")
+    iters, check_every = int(iters), int(check_every)
+    opts = _lib.DeconvOpts()
+    opts.struct_bytes = C.sizeof(_lib.DeconvOpts)
+    opts.dtype, opts.layout, opts.loss, opts.taps, opts.iters = dcode, lay, _LOSSES[loss], taps, iters
+    opts.init_mode, opts.check_every, opts.stop_rule = _INITS[p.init], check_every, _STOPS[stop_rule]
+    opts.tol, opts.l1, opts.l2, opts.init_value = float(tol), float(l1), float(l2), float(init_value)
+    _loop_events(opts, loop_events)
+    ws_bytes = int(L.evc_deconv_workspace_bytes(M, N, T, n_utt, taps, dcode))
+    n_slots = 1 + (iters // check_every if check_every > 0 else 0)
+    n_iter, err, ni_p, er_p = _trace_arrays(n_utt, n_slots, info)
+    tap_stride = int(A_d.stride(0)) if taps > 1 else 0
+    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_deconv_solve(A_d.data_ptr(), _ld(A_d[0]), tap_stride, X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d),
+                                M, N, T, p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p,
+                                C.c_void_p(stream))
+    _lib.check(st, "evc_deconv_solve")
+    H_out = _to_host(H_d) if p.x_np else H_d
+    if info:
+        return H_out, {"n_iter": n_iter, "err": err, "kernel": "k_deconv_update", "taps": taps}
+    return H_out
+
+
+def synthesize_deconv(B_taps, H, *, layout="bin_major", utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None):
+    """Y[:, t] = sum_tau B_tau H[:, t - tau] per utterance (evc_deconv_synthesize): the target rebuilt from the parallel target
+    segments.  B_taps: (L, Mb, N) for bin_major, (L, N, Mb) for frame_major, at most 16 taps and 1056 bins; H and the
+    returned Y as in synthesize."""
+    lay = _LAYOUTS[layout]
+    _deconv_limits(tuple(getattr(B_taps, "shape", ())), lay, _lib.DECONV_MAX_MB, "B_taps")
+    torch = _torch()
+    device = require_device(device)
+    L = _lib.lib()
+    tdtype, dcode = _pick_dtype(dtype, H, B_taps)
+    B_d, _ = _taps_to_dev(B_taps, tdtype, device, "B_taps")
+    H_d, h_np = _to_dev(H, tdtype, device)
+    taps = int(B_d.shape[0])
+    if lay == _lib.BIN_MAJOR:
+        Mb, N = B_d.shape[1:]
+        N2, T = H_d.shape
+        yshape = (Mb, T)
+    else:
+        N, Mb = B_d.shape[1:]
+        T, N2 = H_d.shape
+        yshape = (T, Mb)
+    if N2 != N:
+        raise ValueError(f"B_taps and H disagree on the number of exemplars: {N} vs {N2}")
+    if utt_offsets is None:
+        n_utt, off_arr, off_ptr = 1, None, None
+    else:
+        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
+        n_utt = len(off_arr) - 1
+        if n_utt < 1:
+            raise ValueError("utt_offsets needs at least two entries")
+        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
+    Y = torch.empty(yshape, dtype=tdtype, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_deconv_synthesize(B_d.data_ptr(), _ld(B_d[0]), int(B_d.stride(0)) if taps > 1 else 0, H_d.data_ptr(),
+                                     _ld(H_d), Y.data_ptr(), _ld(Y), Mb, N, T, off_ptr, n_utt, taps, lay, dcode,
+                                     C.c_void_p(stream))
+    _lib.check(st, "evc_deconv_synthesize")
+    return _to_host(Y) if h_np else Y
+
+
+def convert_deconv(A_taps, X, B_taps, H0=None, *, layout="bin_major", utt_offsets: Optional[Sequence[int]] = None, dtype=None,
+                   device=None, info=False, **kw):
+    """solve_activations_deconv followed by synthesize_deconv on the same activations: returns (Y, H), with info=True
+    (Y, H, info).  Keywords as for solve_activations_deconv."""
+    torch = _torch()
+    device = require_device(device)
+    tdtype, _ = _pick_dtype(dtype, X, A_taps)
+    x_np = not isinstance(X, torch.Tensor)
+    X_d, _ = _to_dev(X, tdtype, device)
+    out = solve_activations_deconv(A_taps, X_d, H0, layout=layout, utt_offsets=utt_offsets, dtype=tdtype, device=device,
+                                   info=info, **kw)
+    H_d, inf = out if info else (out, None)
+    Y_d = synthesize_deconv(B_taps, H_d, layout=layout, utt_offsets=utt_offsets, dtype=tdtype, device=device)
+    Y, H = (_to_host(Y_d), _to_host(H_d)) if x_np else (Y_d, H_d)
+    return (Y, H, inf) if info else (Y, H)
+
+
 def _learn(entry, opts, X, W0, H0, *, layout, ws_bytes, unsupported, trace, extra_info, tol, dtype, device, info, out_w,
            out_h, loop_events, splits, call=None):
     """What learn_dictionary, learn_dictionary_beta and learn_dictionary_cd share around their C entry `entry`: the

@@ -52,6 +52,11 @@
  *                   step at a time, MiniBatchNMF.partial_fit: evc_online_learn whose every step solves its batch's
  *                   activations afresh (_solve_W) and whose fit ends with that solve over all frames;
  *                   evc_online_fresh_workspace_bytes sizes it
+ *   evc_deconv_solve  has no counterpart in the reference, whose README cites the method and switches to a "simpler version
+ *                   of exemplar-based method" first: the activation solve with multi-frame exemplars (non-negative spectrogram deconvolution, Wu et
+ *                   al.), X[:, t] ~ sum_tau A_tau H[:, t - tau]; with one tap it is scikit-learn's fixed-dictionary
+ *                   multiplicative update.  evc_deconv_workspace_bytes sizes it, evc_deconv_synthesize forms
+ *                   Y[:, t] = sum_tau B_tau H[:, t - tau] from the parallel target segments
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -113,6 +118,10 @@
  *     (12) evc_online_learn_fresh: as case (10) - with tol == 0, max_no_improvement < 0 and NULL n_iter_out, n_steps_out and
  *         trace_out the call is a pure enqueue (every solve runs its full count); otherwise the host reads three doubles
  *         after every step.  The solves inside a step and the one that ends the fit stop on the device, as in case (11).
+ *     (13) evc_deconv_solve: n_iter_out / err_out non-NULL (the call returns after copying them back); otherwise the call
+ *         is a pure enqueue: the errors are summed and the stop decided on the device, per utterance.  evc_deconv_synthesize
+ *         never waits.  None of their kernels exchanges data between workgroups inside a launch, uses float atomics or
+ *         assumes residency: concurrent calls on several streams are safe, and the same call gives the same bits every time.
  *   No global mutable state: calls on distinct streams/devices are independent and the
  *   caller's current device (hipSetDevice) is honoured.  Nothing is read from the process environment.
  *   Host arrays (utt_offsets, frame_offsets, a_offsets / b_offsets, sample_offsets) are consumed before the call returns: they are
@@ -904,6 +913,66 @@ size_t evc_online_fresh_workspace_bytes(int M, int R, int T, int batch_size, int
 int evc_online_learn_fresh(const void* X, int ldx, void* W, int ldw, void* H, int ldh, void* acc_a, void* acc_b, int ld_acc,
                            int M, int R, int T, const evc_online_fresh_opts* opts, void* workspace, size_t workspace_bytes,
                            int* n_iter_out, int* n_steps_out, double* trace_out, evc_stream_t stream);
+
+/* The activation solve with multi-frame exemplars (non-negative spectrogram deconvolution): exemplar n is a segment of `taps`
+ * consecutive aligned frames, tap tau of the dictionary is the M x N matrix A_tau of the segments' frames tau, and one
+ * activation places the whole segment.  Utterance u has frames 0 .. T_u - 1 (utt_offsets as in evc_beta_solve); nothing crosses
+ * an utterance boundary.  With L = taps and EPS = 1.1920929e-7 (2^-23, in both element types), one iteration is
+ *     V[:, t]   = sum_{tau <= min(L-1, t)} A_tau H[:, t - tau]
+ *     Frobenius : Q = X;                Num[n, t] = sum_{tau: t + tau < T_u} A_tau[:, n] . Q[:, t + tau]
+ *                                       Den[n, t] = sum_{tau: t + tau < T_u} A_tau[:, n] . V[:, t + tau]
+ *     KL        : Q = X / max(V, EPS);  Num as above;  Den[n, t] = sum_{tau: t + tau < T_u} sum_m A_tau[m, n]
+ *     Den += l1 + l2 h;  Den == 0 -> EPS;  h <- h * (Num / Den)
+ * With one tap this is scikit-learn's multiplicative update with the dictionary fixed (update_H=False, beta_loss 2 or 1).
+ * The error of utterance u, at the start and after every `check_every` iterations, is evc_beta_solve's for beta = 2 and
+ * beta = 1: ||X - V||_F, or sqrt(2 max(sum* (X log(X / max(V, EPS)) - X) + sum_all V, 0)) with sum* over the entries with
+ * X > EPS.  EVC_STOP_SKLEARN stops an utterance at a check when (err_prev - err) / err_at_start < tol; its frames are frozen
+ * while the others go on.  EVC_INIT_SKLEARN starts every activation of utterance u at sqrt(mean(X_u) / N).
+ * Two launches per iteration over tiles of 16 frames (an utterance starts a tile of its own): k_deconv_v forms V on the
+ * matrix cores and writes the images Qn = Q and Qd (V, or 1 under KL: the constant denominator is the same contraction over
+ * ones), exact zeros beyond the utterance's end - that is what truncates the sums; k_deconv_update loads its tile's and the
+ * next tile's images (32 frame columns, hence at most 16 taps), forms Num | Den per exemplar tile and updates H in place.  V
+ * passes through memory, so no workgroup reads activations another one writes in the same launch.  A check is k_deconv_v once
+ * more, leaving every frame's share of the error in float64, and a per-utterance sum in a fixed order (no float atomics): the
+ * same call gives bitwise the same output every time, and a batch gives bitwise the activations, counts and errors of one
+ * call per utterance.  A NaN in a frame spreads over its own utterance (the model couples neighbouring frames) and leaves
+ * every other utterance bitwise unchanged.  float32 inputs are solved in float32; the errors are float64 for both types.
+ *   A, lda, tap_stride : tap tau is the matrix at A + tau * tap_stride elements, addressed with lda and layout exactly like
+ *            evc_beta_solve's A (tap_stride >= 0; taps may overlap in memory)
+ *   M : 1 .. 256 bins, taps : 1 .. 16 (larger: -3);  any N >= 1, T >= 0 (an utterance may be empty: nothing is done for it, its
+ *            n_iter is `iters` and its errors stay NaN);  iters = 0 leaves the start in H
+ *   l1, l2 : >= 0, added to the denominator as in evc_beta_solve
+ *   n_iter_out, err_out : host, as in evc_beta_solve (at most 4097 error slots per utterance; more: -1)
+ * Status -1 (wrong struct_bytes, NaN or negative tol or penalties, taps < 1, bad enums, too many error slots), then -3 (beyond
+ * the limits), then -2 (workspace too small), all before any device work.  Host synchronisation: case (13) of the list at
+ * the top. */
+typedef struct evc_deconv_opts {
+    int struct_bytes;  /* sizeof(evc_deconv_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int loss;          /* EVC_LOSS_FROBENIUS | EVC_LOSS_KL */
+    int taps;          /* frames per exemplar, 1 .. 16 */
+    int iters;         /* maximum number of multiplicative updates (>= 0) */
+    int init_mode;     /* EVC_INIT_GIVEN | EVC_INIT_SKLEARN | EVC_INIT_CONST */
+    int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
+    int stop_rule;     /* EVC_STOP_NONE | EVC_STOP_SKLEARN */
+    int reserved;      /* 0 */
+    double tol;        /* >= 0: threshold of stop_rule */
+    double l1, l2;     /* >= 0 */
+    double init_value; /* EVC_INIT_CONST */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_deconv_opts;
+/* bytes of workspace evc_deconv_solve needs (0: invalid or unsupported arguments, M > 256 and taps > 16 among them) */
+size_t evc_deconv_workspace_bytes(int M, int N, int T, int n_utt, int taps, int dtype);
+int evc_deconv_solve(const void* A, int lda, long tap_stride, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
+                     const int* utt_offsets, int n_utt, const evc_deconv_opts* opts, void* workspace, size_t workspace_bytes,
+                     int* n_iter_out, double* err_out, evc_stream_t stream);
+/* Y[:, t] = sum_{tau <= min(taps - 1, t)} B_tau H[:, t - tau] per utterance, on the matrix cores: B_tau (Mb x N) at
+ * B + tau * tap_stride elements, B, H and Y addressed as in evc_synthesize, one launch per utterance that has frames, straight
+ * from and to the caller's memory (no workspace).  Mb : 1 .. 1056, taps : 1 .. 16 (larger: -3); invalid arguments: -1. */
+int evc_deconv_synthesize(const void* B, int ldb, long tap_stride, const void* H, int ldh, void* Y, int ldy, int Mb, int N, int T,
+                          const int* utt_offsets, int n_utt, int taps, int layout, int dtype, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
