@@ -22,6 +22,7 @@ LOSS_FROBENIUS, LOSS_KL = 0, 1
 FLAG_NO_FUSED, FLAG_EXACT_DIV, FLAG_NO_EXCHANGE, FLAG_NO_ALL_RESIDENT, FLAG_PAIR_TILES, FLAG_NO_LONE_BIN = 1, 2, 4, 16, 32, 64
 LEARN_SKLEARN, LEARN_PYMF = 0, 1
 CDL_BOTH, CDL_DICT_ONLY = 0, 1
+DCL_BOTH, DCL_DICT_ONLY = 0, 1
 
 # every symbol include/evc.h declares; tests check that the library exports all of them
 SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_bytes",
@@ -37,9 +38,11 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_online_workspace_bytes", "evc_online_splits", "evc_online_learn",
            "evc_online_transform_workspace_bytes", "evc_online_transform",
            "evc_online_fresh_workspace_bytes", "evc_online_learn_fresh",
-           "evc_deconv_workspace_bytes", "evc_deconv_solve", "evc_deconv_synthesize")
+           "evc_deconv_workspace_bytes", "evc_deconv_solve", "evc_deconv_synthesize",
+           "evc_deconv_learn_workspace_bytes", "evc_deconv_learn_splits", "evc_deconv_learn")
 BETA_MAX_M = 528
 DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
+DECONV_LEARN_MAX_R = 4096
 MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
 
@@ -154,6 +157,16 @@ class DeconvOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("loss", C.c_int), ("taps", C.c_int),
         ("iters", C.c_int), ("init_mode", C.c_int), ("check_every", C.c_int), ("stop_rule", C.c_int), ("reserved", C.c_int),
         ("tol", C.c_double), ("l1", C.c_double), ("l2", C.c_double), ("init_value", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class DeconvLearnOpts(C.Structure):
+    """Mirror of `evc_deconv_learn_opts` (include/evc.h): options of the convolutive dictionary learning."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("loss", C.c_int), ("taps", C.c_int),
+        ("iters", C.c_int), ("check_every", C.c_int), ("update", C.c_int), ("reserved", C.c_int),
+        ("tol", C.c_double), ("l1_h", C.c_double), ("l2_h", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -393,6 +406,19 @@ def lib():
         C.c_int, C.c_int, C.c_int,                                          # Mb, N, T
         C.POINTER(C.c_int), C.c_int,                                        # utt_offsets, n_utt
         C.c_int, C.c_int, C.c_int,                                          # taps, layout, dtype
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_deconv_learn_workspace_bytes.restype = C.c_size_t
+    L.evc_deconv_learn_workspace_bytes.argtypes = [C.c_int] * 7
+    L.evc_deconv_learn_splits.restype = C.c_int
+    L.evc_deconv_learn_splits.argtypes = [C.c_int] * 5
+    L.evc_deconv_learn.restype = C.c_int
+    L.evc_deconv_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_int,    # X, W (ldw, tap_stride), H
+        C.c_int, C.c_int, C.c_int,                                          # M, R, T
+        C.POINTER(C.c_int), C.c_int, C.POINTER(DeconvLearnOpts),            # utt_offsets, n_utt, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
         C.c_void_p,                                                         # stream
     ]
     _lib = L

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ..solver import (_dtw_gather_device, _mfcc_device, _torch, dtw_align, dtw_dictionary, multiframe_dictionary, prepare_dictionary,
+from ..solver import (_dtw_gather_device, _mfcc_device, _torch, compact_dictionary_deconv, dtw_align, dtw_dictionary, multiframe_dictionary, prepare_dictionary,
                       require_device)
 
 
@@ -46,7 +46,8 @@ def align_sp_ap_f0(src_feat, tar_feat, src_W, tar_W, *, use_stft=True):
     return aligned_src, aligned_tar
 
 
-def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, key=None, device=None, taps=None):
+def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, key=None, device=None, taps=None,
+                       compact=None):
     """`dtw_alignment` + `make_exemplar_dict_W` + `align_sp_ap_f0` + the stacking of `factorize()` / `convert()`
     (01_make_dict_parallel.py:215-249,291-292; 04_align_n_nmf.py:100-169,230-246,320-324,350-361) in one pass on the GPU:
     the DTW paths are consumed on the device and the aligned frames never visit the host (the
@@ -57,6 +58,8 @@ def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, k
                                 f[key] for key in "sp" | "ap" | "f0"
       taps                    : None, or L >= 1 for multi-frame exemplars: exemplar n is the L aligned frames from n on,
                                 cut (zero columns) at the end of its file
+      compact                 : None, or R (with taps): the raw segments are factored into R parallel multi-frame
+                                components by compact_dictionary_deconv and those are returned in their place
     Returns a PreparedDictionary (A = aligned source frames, B = aligned target frames) for `solve_activations` /
     `convert`, and the first dictionary row of every file.  With taps: the parallel (A_taps, B_taps), device tensors
     (L, N, bins) in frame_major for `solve_activations_deconv` / `convert_deconv`, and the rows."""
@@ -72,6 +75,11 @@ def aligned_dictionary(dtw_src, dtw_tar, src_feat, tar_feat, *, use_stft=True, k
         A, B, rows = dtw_dictionary([np.asarray(a).T for a in dtw_src], [np.asarray(b).T for b in dtw_tar],
                                     [col(np.asarray(f[key])) for f in src_feat], [col(np.asarray(f[key])) for f in tar_feat],
                                     device=device)
+    if compact is not None:
+        if taps is None:
+            raise ValueError("compact needs taps: compact_dictionary serves one-frame exemplars")
+        Wa, Wb, _, _ = compact_dictionary_deconv(A, B, rows, compact, taps, layout="frame_major", device=device)
+        return (Wa, Wb), rows
     if taps is not None:
         return (multiframe_dictionary(A, rows, taps, layout="frame_major"),
                 multiframe_dictionary(B, rows, taps, layout="frame_major")), rows

@@ -1090,6 +1090,185 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     return Wa, Wb, G, info
 
 
+_DCL_UPDATES = {"both": _lib.DCL_BOTH, "dict": _lib.DCL_DICT_ONLY}
+
+
+def _taps_overlap(t):
+    """whether the taps of a (L, rows, columns) tensor share memory: they are written, so they must not"""
+    return t.shape[0] > 1 and t.stride(0) < (t.shape[1] - 1) * t.stride(1) + t.shape[2]
+
+
+def learn_dictionary_deconv(X, W0_taps, H0, *, loss="frobenius", layout, iters, check_every=10, tol=0.0, l1_h=0.0, l2_h=0.0,
+                            update="both", utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False,
+                            out_w=None, out_h=None, loop_events=None, splits=0):
+    """Convolutive NMF (NMFD) on the GPU (evc_deconv_learn): BOTH factors of X[:, t] ~ sum_tau W_tau H[:, t - tau] per
+    utterance by multiplicative updates under loss "frobenius" or "kullback-leibler" - solve_activations_deconv's model with
+    the taps learnt too.  W0_taps: (L, M, R) for bin_major, (L, R, M) for frame_major; X and H0 as in learn_dictionary.  Per
+    iteration H by one update of solve_activations_deconv's kernels (penalties l1_h / l2_h), then every tap of W from the
+    same model of the new H (scikit-learn's order; with L = 1 this is learn_dictionary's scikit-learn surface).  One error for
+    the call every `check_every` iterations, and the stop when (err_prev - err) / err_at_start < tol.  update="dict": the
+    activations stay at H0 and only the dictionary half runs (target taps fitted under the source's activations).
+    At most 16 taps and 4096 components; 256 bins under update="both", 1056 under update="dict".  utt_offsets as in
+    solve_activations_deconv: nothing crosses an utterance boundary.
+
+    Returns (W_taps, H) in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out); with
+    info=True also dict(n_iter=int, err=[1 + iters // check_every] errors (the first at the start; NaN where not evaluated),
+    splits=frame ranges of the dictionary half's sums).  out_w / out_h: device tensors updated in place (they then hold the
+    start, W0_taps / H0 are ignored when None); the taps of out_w must not overlap in memory.  splits: tuning and tests,
+    1..64 frame ranges.  This driver does not go through _learn: its dictionary is three-dimensional and its frames belong to
+    utterances.  No CPU fallback: without a HIP device this raises RuntimeError."""
+    lay = _LAYOUTS[layout]
+    bm = lay == _lib.BIN_MAJOR
+    if loss not in _LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_LOSSES)}, got {loss!r}")
+    if update not in _DCL_UPDATES:
+        raise ValueError(f"update must be one of {sorted(_DCL_UPDATES)}, got {update!r}")
+    w_src = W0_taps if W0_taps is not None else out_w
+    wshape = tuple(getattr(w_src, "shape", ()))
+    if len(wshape) != 3:
+        raise ValueError(f"W0_taps must be 3-D (taps, rows, columns), got shape {wshape}")
+    max_bins = _lib.DECONV_MAX_M if update == "both" else _lib.DECONV_MAX_MB
+    bins, comps = (wshape[1], wshape[2]) if bm else (wshape[2], wshape[1])
+    if wshape[0] > _lib.DECONV_MAX_TAPS or bins > max_bins or comps > _lib.DECONV_LEARN_MAX_R:     # what the ABI answers with -3
+        raise ValueError(f"unsupported convolutive learning shape: {wshape[0]} taps, {bins} bins and {comps} components; "
+                         f"update={update!r} holds at most {_lib.DECONV_MAX_TAPS} taps, {max_bins} bins and "
+                         f"{_lib.DECONV_LEARN_MAX_R} components")
+    if wshape[0] < 1:
+        raise ValueError("W0_taps needs at least one tap")
+    torch = _torch()
+    if out_w is not None:
+        if not isinstance(out_w, torch.Tensor) or out_w.dim() != 3 or (out_w.shape[2] > 1 and out_w.stride(2) != 1):
+            raise ValueError("`out_w` must be a 3-D device tensor (taps, rows, columns) with unit inner stride")
+        if _taps_overlap(out_w):
+            raise ValueError("the taps of `out_w` overlap in memory: they are written, so tap_stride must cover one tap")
+    device = require_device(device)
+    L = _lib.lib()
+    tdtype, dcode = _pick_dtype(dtype, X, w_src)
+    X_d, x_np = _to_dev(X, tdtype, device)
+    M, T = X_d.shape if bm else X_d.shape[::-1]
+    if out_w is not None:
+        if W0_taps is not None:
+            out_w.copy_(_taps_to_dev(W0_taps, tdtype, device, "W0_taps")[0])
+        if out_w.dtype != tdtype:
+            raise ValueError("`out_w` must have the call's dtype")
+        W_d = out_w
+    else:
+        W_d, _ = _taps_to_dev(W0_taps, tdtype, device, "W0_taps")
+        if _taps_overlap(W_d):
+            W_d = W_d.contiguous()
+        elif isinstance(W0_taps, torch.Tensor) and W_d.data_ptr() == W0_taps.data_ptr():
+            W_d = W_d.clone()       # never clobber the caller's start
+    if out_h is not None:
+        if H0 is not None:
+            out_h.copy_(_to_dev(H0, tdtype, device)[0])
+        if out_h.dtype != tdtype or out_h.dim() != 2 or (out_h.shape[1] > 1 and out_h.stride(1) != 1):
+            raise ValueError("`out_h` must be a device matrix of the call's dtype with unit inner stride")
+        H_d = out_h
+    else:
+        H_d, _ = _to_dev(H0, tdtype, device)
+        if update == "both" and isinstance(H0, torch.Tensor) and H_d.data_ptr() == H0.data_ptr():
+            H_d = H_d.clone()
+    taps = int(W_d.shape[0])
+    M2, R = W_d.shape[1:] if bm else W_d.shape[:0:-1]
+    R2, T2 = H_d.shape if bm else H_d.shape[::-1]
+    if M2 != M or R2 != R or T2 != T:
+        raise ValueError(f"X {tuple(X_d.shape)}, W_taps {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
+    if utt_offsets is None:
+        n_utt, off_arr, off_ptr = 1, None, None
+    else:
+        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
+        n_utt = len(off_arr) - 1
+        if n_utt < 1:
+            raise ValueError("utt_offsets needs at least two entries")
+        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
+    iters, check_every = int(iters), int(check_every)
+    opts = _lib.DeconvLearnOpts()
+    opts.struct_bytes = C.sizeof(opts)
+    opts.dtype, opts.layout, opts.loss, opts.taps = dcode, lay, _LOSSES[loss], taps
+    opts.iters, opts.check_every, opts.update = iters, check_every, _DCL_UPDATES[update]
+    opts.reserved = (int(splits) & 0xff) << 8
+    opts.tol, opts.l1_h, opts.l2_h = float(tol), float(l1_h), float(l2_h)
+    _loop_events(opts, loop_events)
+    nbytes = int(L.evc_deconv_learn_workspace_bytes(M, R, T, n_utt, taps, opts.update, dcode))
+    if nbytes == 0:
+        raise ValueError(f"unsupported convolutive learning shape M={M}, R={R}, T={T}, taps={taps}")
+    n_iter = C.c_int(0)
+    err = np.full(1 + (iters // check_every if check_every > 0 else 0), np.nan) if info else None
+    with torch.cuda.device(device), _workspace(nbytes, device) as ws:
+        stream = torch.cuda.current_stream(device).cuda_stream
+        st = L.evc_deconv_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d[0]), int(W_d.stride(0)) if taps > 1 else 0,
+                                H_d.data_ptr(), _ld(H_d), M, R, T, off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(),
+                                C.byref(n_iter) if (info or tol > 0) else None,
+                                err.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
+    _lib.check(st, "evc_deconv_learn")
+    to_np = x_np and out_w is None and out_h is None
+    res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
+    if info:
+        res += ({"n_iter": int(n_iter.value), "err": err,
+                 "splits": int(splits) if splits else int(L.evc_deconv_learn_splits(M, R, T, n_utt, taps))},)
+    return res
+
+
+def compact_dictionary_deconv(A_frames, B_frames, seg_offsets, R, taps, *, iters=100, tol=0.0, loss="frobenius",
+                              layout="bin_major", dtype=None, device=None):
+    """A compact parallel MULTI-FRAME dictionary: what compact_dictionary is for one-frame exemplars, for taps > 1.
+    A_frames / B_frames: the aligned source and target frames of the training files ((Ma, N) and (Mb, N) for bin_major,
+    (N, Ma) and (N, Mb) for frame_major), seg_offsets the first frame of every file and then N, as multiframe_dictionary
+    takes them.  With Ma + Mb <= 256 the stacked frames D = [A; B] are learnt jointly by learn_dictionary_deconv,
+    D[:, t] ~ sum_tau [Wa_tau; Wb_tau] G[:, t - tau] within every file.  Otherwise (Wa, G) are learnt on the source frames
+    (Ma <= 256) and Wb is then fitted to the target frames under update="dict" with G fixed, for `iters` iterations
+    (Mb <= 1056).  The error is checked every 10 iterations.
+
+    The start is deterministic: W0_tau = the frames tau after R evenly spaced ones (beyond their file's end: 0), floored at
+    1e-6; G0 = sqrt(mean(D) / R) everywhere, D the frames the first stage factors.  With taps = 1 that is compact_dictionary's
+    start.  Returns (Wa_taps, Wb_taps, G, info), ready for convert_deconv(Wa_taps, X, Wb_taps); info as
+    learn_dictionary_deconv's, plus stages=1 | 2 and, for two stages, err_b (the second stage's errors)."""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    bm = lay == _lib.BIN_MAJOR
+    taps, R = int(taps), int(R)
+    if not 1 <= taps <= _lib.DECONV_MAX_TAPS:
+        raise ValueError(f"taps must be between 1 and {_lib.DECONV_MAX_TAPS} taps, got {taps}")
+    ashape, bshape = tuple(getattr(A_frames, "shape", ())), tuple(getattr(B_frames, "shape", ()))
+    if len(ashape) != 2 or len(bshape) != 2:
+        raise ValueError(f"expected 2-D matrices of frames, got shapes {ashape} and {bshape}")
+    Ma, Mb, N = (ashape[0], bshape[0], ashape[1]) if bm else (ashape[1], bshape[1], ashape[0])
+    joint = Ma + Mb <= _lib.DECONV_MAX_M
+    if not joint and (Ma > _lib.DECONV_MAX_M or Mb > _lib.DECONV_MAX_MB):
+        raise ValueError(f"unsupported compaction shape: {Ma} source and {Mb} target bins; the two-stage route holds at most "
+                         f"{_lib.DECONV_MAX_M} source and {_lib.DECONV_MAX_MB} target bins")
+    if not 1 <= R <= min(N, _lib.DECONV_LEARN_MAX_R):
+        raise ValueError(f"R must be between 1 and min(frames, {_lib.DECONV_LEARN_MAX_R}) = "
+                         f"{min(N, _lib.DECONV_LEARN_MAX_R)}, got {R}")
+    device = require_device(device)
+    tdtype, _ = _pick_dtype(dtype, A_frames, B_frames)
+    A_d, a_np = _to_dev(A_frames, tdtype, device)
+    B_d, _ = _to_dev(B_frames, tdtype, device)
+    offs = [int(v) for v in seg_offsets]
+    pick = torch.div(torch.arange(R, device=device) * N, R, rounding_mode="floor")
+
+    def start(F):
+        t = multiframe_dictionary(F, offs, taps, layout=layout)
+        return (t[:, :, pick] if bm else t[:, pick, :]).clamp_min(1e-6).contiguous()
+
+    def g0(F):
+        return torch.full((R, N) if bm else (N, R), float(torch.sqrt(F.mean() / R)), dtype=tdtype, device=device)
+
+    kw = dict(loss=loss, layout=layout, iters=iters, check_every=10, utt_offsets=offs, dtype=tdtype, device=device, info=True)
+    if joint:
+        D = torch.cat([A_d, B_d], dim=0 if bm else 1)
+        W, G, info = learn_dictionary_deconv(D, None, None, tol=tol, out_w=start(D), out_h=g0(D), **kw)
+        Wa, Wb = (W[:, :Ma], W[:, Ma:]) if bm else (W[:, :, :Ma], W[:, :, Ma:])
+        info["stages"] = 1
+    else:
+        Wa, G, info = learn_dictionary_deconv(A_d, None, None, tol=tol, out_w=start(A_d), out_h=g0(A_d), **kw)
+        Wb, _, info_b = learn_dictionary_deconv(B_d, None, None, update="dict", out_w=start(B_d), out_h=G, **kw)
+        info["stages"], info["err_b"] = 2, info_b["err"]
+    if a_np:
+        return Wa.cpu().numpy(), Wb.cpu().numpy(), _to_host(G), info
+    return Wa, Wb, G, info
+
+
 def synthesize(B, H, *, layout="bin_major", dtype=None, device=None):
     """Y = B H (bin_major, (Mb,T)) or H B (frame_major: np.matmul(H.T, B) of
     04_align_n_nmf.py:391 with H already frames-as-rows, giving (T,Mb))."""

@@ -57,6 +57,10 @@
  *                   al.), X[:, t] ~ sum_tau A_tau H[:, t - tau]; with one tap it is scikit-learn's fixed-dictionary
  *                   multiplicative update.  evc_deconv_workspace_bytes sizes it, evc_deconv_synthesize forms
  *                   Y[:, t] = sum_tau B_tau H[:, t - tau] from the parallel target segments
+ *   evc_deconv_learn  is evc_deconv_solve's learning counterpart, convolutive NMF (NMFD): both factors of
+ *                   X ~ sum_tau W_tau shift_tau(H) by multiplicative updates; with one tap it is scikit-learn's
+ *                   _fit_multiplicative_update with update_H=True, as evc_nmf_learn.  evc_deconv_learn_workspace_bytes
+ *                   and evc_deconv_learn_splits size and describe it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -91,6 +95,7 @@
  *         host reads one double (the error) at each check that is evaluated and decides the stop there; checks are
  *         evaluated when err_out is non-NULL or tol > 0.  Its own kernels never exchange data between workgroups inside a
  *         launch, and its activation step runs with EVC_FLAG_NO_EXCHANGE: concurrent calls on several streams are safe.
+ *         evc_deconv_learn follows the same rule with its own kernels.
  *     (6) evc_cd_learn: only with tol == 0 and NULL n_iter_out / violation_out is the call a pure enqueue of max_iter
  *         iterations.  Otherwise the host reads the iteration's two violations (two doubles) after every iteration and
  *         decides the stop there.  None of its kernels exchanges data between workgroups inside a launch, uses atomics or
@@ -973,6 +978,65 @@ int evc_deconv_solve(const void* A, int lda, long tap_stride, const void* X, int
  * from and to the caller's memory (no workspace).  Mb : 1 .. 1056, taps : 1 .. 16 (larger: -3); invalid arguments: -1. */
 int evc_deconv_synthesize(const void* B, int ldb, long tap_stride, const void* H, int ldh, void* Y, int ldy, int Mb, int N, int T,
                           const int* utt_offsets, int n_utt, int taps, int layout, int dtype, evc_stream_t stream);
+
+/* Convolutive NMF (NMFD): the multi-frame model of evc_deconv_solve learnt in BOTH factors, X ~ sum_tau W_tau shift_tau(H), one
+ * dictionary of R components and L = taps taps for all utterances.  X is M x T, W_tau M x R, H R x T; utterance u owns the
+ * frames utt_offsets[u] .. utt_offsets[u + 1] - 1 and nothing crosses an utterance boundary.  EPS = 2^-23 in both element
+ * types.  With Hs_tau[r, t] = H[r, t - tau] where t - tau lies in t's utterance, else 0, one iteration is scikit-learn's order:
+ *   1. activations: one iteration of evc_deconv_solve's statement with A_tau = W_tau and the penalties l1_h, l2_h (with
+ *      iters = 1 H is bitwise evc_deconv_solve's after one iteration from the same start);
+ *   2. dictionary, every tap from the same V[:, t] = sum_tau W_tau Hs_tau[:, t] of the new H:
+ *        Frobenius : Num_tau = X Hs_tau^T, Den_tau = V Hs_tau^T, Den == 0 -> EPS, W_tau <- W_tau * (Num_tau / Den_tau)
+ *        KL        : Q = X / max(V, EPS), Num_tau = Q Hs_tau^T, s_tau[r] = sum_t Hs_tau[r, t], s == 0 -> 1,
+ *                    W_tau <- W_tau * (Num_tau / s_tau[r])
+ *      (the multiplicative update of the stacked M x LR dictionary under the stacked shifted activations: the error never
+ *      rises; no flush of tiny entries, no dictionary penalties, no normalisation).
+ * EVC_DCL_DICT_ONLY skips step 1: H is only read (target taps fitted to target frames under the source's activations).
+ * The error is one value for the call - ||X - V||_F, or sqrt(2 max(sum* (X log(X / max(V, EPS)) - X) + sum V, 0)) with sum*
+ * over the entries with X > EPS - evaluated at the start and after every check_every iterations, summed from per-frame shares
+ * in float64 in a fixed order; the loop stops when (err_prev - err) / err_at_start < tol (tol = 0: never).
+ * Kernels: the activation half is k_deconv_v + k_deconv_update on the current W (its two packed tap images are repacked every
+ * iteration); V, Q and the error shares come from k_deconv_v (EVC_DCL_DICT_ONLY: from k_deconv_learn_v, which forms V in groups
+ * of 8 bin tiles straight from the caller's W, so that M may reach 1056); k_deconv_dict_grad contracts k_deconv_v's tile images
+ * with the shifted, masked rows of H on the matrix cores over S ranges of frame tiles and leaves one slab of sums per range and
+ * tap; k_deconv_dict_apply adds the slabs in the order s = 0 .. S-1 and updates the caller's W_tau in place.  No exchange
+ * between workgroups inside a launch, no float atomics, no residency assumption: the same call gives bitwise the same W and H.
+ *   X, H, W : addressed as in evc_nmf_learn; tap tau of W is the matrix at W + tau * tap_stride elements.  W and H hold the
+ *            start on entry and are updated in place (EVC_DCL_DICT_ONLY: H is untouched).  The taps are written, so they must
+ *            not overlap: with taps > 1, a tap_stride smaller than one tap's extent is -1
+ *   taps : 1 .. 16;  R : 1 .. 4096;  M : 1 .. 256 (EVC_DCL_BOTH) or 1 .. 1056 (EVC_DCL_DICT_ONLY);  beyond: -3.  T >= 1 in all;
+ *            single utterances may be empty (nothing is done for them)
+ *   n_iter_out : host, the iterations carried out;  err_out : host, 1 + iters / check_every doubles, NaN where not evaluated
+ *            (at most 4097 slots; more: -1)
+ * S = evc_deconv_learn_splits(...) depends on the sizes only; the slabs of one launch stay within 128 MiB: S drops, down to 1,
+ * when taps * M * R is large, and beyond that the taps are contracted and applied a few at a time.
+ * Status: every -1 first, then -3, then -2, all before any device work.  Host synchronisation: as evc_nmf_learn's, case (5) of
+ * the list at the top - one double is read back per evaluated check; without checks the call is a pure enqueue. */
+enum { EVC_DCL_BOTH = 0, EVC_DCL_DICT_ONLY = 1 };
+typedef struct evc_deconv_learn_opts {
+    int struct_bytes;  /* sizeof(evc_deconv_learn_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int loss;          /* EVC_LOSS_FROBENIUS | EVC_LOSS_KL */
+    int taps;          /* frames per component, 1 .. 16 */
+    int iters;         /* maximum number of iterations (>= 0) */
+    int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
+    int update;        /* EVC_DCL_BOTH | EVC_DCL_DICT_ONLY */
+    int reserved;      /* 0; bits 8..15: forced number of frame ranges 1..64 (tests and tuning; lowered to what the slab cap
+                          allows); anything else: -1 */
+    double tol;        /* >= 0 */
+    double l1_h, l2_h; /* >= 0: the activation half's penalties */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_deconv_learn_opts;
+/* bytes of workspace evc_deconv_learn needs (0: invalid or unsupported arguments: wherever the call would return -1 or -3 for
+ * these sizes) */
+size_t evc_deconv_learn_workspace_bytes(int M, int R, int T, int n_utt, int taps, int update, int dtype);
+/* frame ranges of the dictionary half's sums, 1 .. 64: a function of the sizes only (0: invalid sizes) */
+int evc_deconv_learn_splits(int M, int R, int T, int n_utt, int taps);
+int evc_deconv_learn(const void* X, int ldx, void* W, int ldw, long tap_stride, void* H, int ldh, int M, int R, int T,
+                     const int* utt_offsets, int n_utt, const evc_deconv_learn_opts* opts, void* workspace,
+                     size_t workspace_bytes, int* n_iter_out, double* err_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
