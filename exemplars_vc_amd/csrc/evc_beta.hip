@@ -578,6 +578,21 @@ int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, dou
     return 0;
 }
 
+template <typename T>
+int beta_report(const BetaCtx<T>& c, int iters, int* n_iter_out, double* trace_out, int slots, hipStream_t s) {
+    if (!n_iter_out && !trace_out) return 0;
+    int* ni_h = static_cast<int*>(malloc(sizeof(int) * c.n_utt));
+    if (!ni_h) return (int)hipErrorOutOfMemory;
+    hipError_t e = hipMemcpyAsync(ni_h, c.w.stop, sizeof(int) * c.n_utt, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && trace_out && slots > 0)
+        e = hipMemcpyAsync(trace_out, c.w.trace, sizeof(double) * c.n_utt * slots, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    for (int u = 0; e == hipSuccess && n_iter_out && u < c.n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : iters;
+    free(ni_h);
+    HIP_TRY(e);
+    return 0;
+}
+
 #define BETA_INSTANTIATE(T)                                                                                              \
     template int beta_begin<T>(BetaCtx<T>&, const T*, int, T*, int, int, int, int, const int*, int, int, double, double, \
                                double, double, int, void*, size_t, hipStream_t);                                        \
@@ -589,7 +604,8 @@ int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, dou
     template int beta_h0<T>(const BetaCtx<T>&, hipStream_t);                                                             \
     template int beta_restart<T>(const BetaCtx<T>&, bool, hipStream_t);                                                      \
     template int beta_flush<T>(const BetaCtx<T>&, double, hipStream_t);                                                  \
-    template int beta_check<T>(const BetaCtx<T>&, int, int, int, double, hipStream_t);
+    template int beta_check<T>(const BetaCtx<T>&, int, int, int, double, hipStream_t);                                  \
+    template int beta_report<T>(const BetaCtx<T>&, int, int*, double*, int, hipStream_t);
 BETA_INSTANTIATE(double)
 BETA_INSTANTIATE(float)
 
@@ -606,7 +622,6 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
                            ws_bytes, s);
     if (st != 0) return st;
     if ((st = beta_pack_dict<T>(c, A, lda, s)) != 0) return st;
-    const BetaWs<T>& w = c.w;
     const int n_tiles = c.n_tiles;
     if ((st = beta_start<T>(c, o.init_mode, o.init_value, s)) != 0) return st;
     const bool checks = o.check_every > 0;
@@ -618,18 +633,7 @@ int beta_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
             return st;
     }
     if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    if (n_iter_out || err_out) {
-        int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
-        if (!ni_h) return (int)hipErrorOutOfMemory;
-        hipError_t e = hipMemcpyAsync(ni_h, w.stop, sizeof(int) * n_utt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && err_out)
-            e = hipMemcpyAsync(err_out, w.trace, sizeof(double) * n_utt * n_slots, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        for (int u = 0; e == hipSuccess && n_iter_out && u < n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : o.iters;
-        free(ni_h);
-        HIP_TRY(e);
-    }
-    return 0;
+    return beta_report<T>(c, o.iters, n_iter_out, err_out, n_slots, s);
 }
 
 }  // namespace

@@ -109,6 +109,11 @@ template <typename T> int beta_sweep(const BetaCtx<T>& c, hipStream_t s);
 // check number `chk` (0: the start): every utterance's error into its trace slot, then the stop rule on the device
 template <typename T>
 int beta_check(const BetaCtx<T>& c, int chk, int check_every, int stop_rule, double tol, hipStream_t s);
+// the read-back that ends a fixed-dictionary solve (evc_beta_solve, evc_online_transform, evc_deconv_solve): nothing when
+// neither output is asked for (the call then stays asynchronous); else stop[] and `slots` trace values per utterance to the
+// host (no trace copy when slots is 0), one synchronisation, and n_iter_out[u] = stop[u], or `iters` where u never stopped
+template <typename T>
+int beta_report(const BetaCtx<T>& c, int iters, int* n_iter_out, double* trace_out, int slots, hipStream_t s);
 // its first half alone: every frame's share of the divergence into errf (evc_online_learn sums one batch's shares itself)
 template <typename T> int beta_err(const BetaCtx<T>& c, hipStream_t s);
 // the start of the activations: nothing for EVC_INIT_GIVEN, else every activation of utterance u at sqrt(mean(X_u) / N)

@@ -95,18 +95,7 @@ int deconv_solve(const T* A, int lda, long tap_stride, const T* X, int ldx, T* H
         }
     }
     if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    if (n_iter_out || err_out) {
-        int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
-        if (!ni_h) return (int)hipErrorOutOfMemory;
-        hipError_t e = hipMemcpyAsync(ni_h, c.w.stop, sizeof(int) * n_utt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && err_out)
-            e = hipMemcpyAsync(err_out, c.w.trace, sizeof(double) * n_utt * n_slots, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        for (int u = 0; e == hipSuccess && n_iter_out && u < n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : o.iters;
-        free(ni_h);
-        HIP_TRY(e);
-    }
-    return 0;
+    return beta_report<T>(c, o.iters, n_iter_out, err_out, n_slots, s);
 }
 
 template <typename T>

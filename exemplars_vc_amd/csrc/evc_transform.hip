@@ -32,18 +32,7 @@ int online_transform(const void* W_, int ldw, const void* X_, int ldx, void* H_,
     if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
     for (int it = 1; it <= o.max_iter; ++it) HIP_TRY(beta_sweep_change<T>(c, it, o.tol, s));
     if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    if (n_iter_out || change_out) {
-        int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
-        if (!ni_h) return (int)hipErrorOutOfMemory;
-        hipError_t e = hipMemcpyAsync(ni_h, c.w.stop, sizeof(int) * n_utt, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && change_out && o.max_iter > 0)
-            e = hipMemcpyAsync(change_out, c.w.trace, sizeof(double) * n_utt * o.max_iter, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        for (int u = 0; e == hipSuccess && n_iter_out && u < n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : o.max_iter;
-        free(ni_h);
-        HIP_TRY(e);
-    }
-    return ST_OK;
+    return beta_report<T>(c, o.max_iter, n_iter_out, change_out, o.max_iter, s);     // max_iter = 0: no slot, no trace copy
 }
 
 }  // namespace

@@ -241,8 +241,8 @@ def convert(A, X, B=None, H0=None, *, want_h=True, **kw):
 
 
 def _operands(A, X, H0, init, layout, dtype, device, utt_offsets, out=None, want_h=True):
-    """What _solve, solve_activations_cd and solve_activations_beta share in front of their C entry.  A: the dictionary
-    or a PreparedDictionary; device: already resolved (require_device).  Returns a namespace of
+    """What _solve and the fixed-dictionary solves (cd, beta, transform, deconv) share in front of their C entry.  A: the
+    dictionary (deconv: its first tap) or a PreparedDictionary; device: already resolved (require_device).  Returns a namespace of
       tdtype, dcode, lay     the call's element type (torch, C ABI) and layout code
       A_d, X_d, x_np         the operands on the device (A_d None for a prepared dictionary), whether X came as numpy
       M, N, T, hshape        the sizes and the activations' shape in the caller's orientation
@@ -287,20 +287,49 @@ def _operands(A, X, H0, init, layout, dtype, device, utt_offsets, out=None, want
     if H_d is not None and (tuple(H_d.shape) != hshape or H_d.dtype != tdtype
                             or (H_d.shape[1] > 1 and H_d.stride(1) != 1)):
         raise ValueError("`out` must be a contiguous device tensor of the activation shape/dtype")
-    if utt_offsets is None:
-        n_utt, off_arr, off_ptr = 1, None, None
-    else:
-        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
-        n_utt = len(off_arr) - 1
-        if n_utt < 1:
-            raise ValueError("utt_offsets needs at least two entries")
-        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
+    n_utt, off_arr, off_ptr = _offsets(utt_offsets)
     return types.SimpleNamespace(tdtype=tdtype, dcode=dcode, lay=lay, A_d=A_d, X_d=X_d, x_np=x_np, M=M, N=N, T=T,
                                  hshape=hshape, init=init, H_d=H_d, n_utt=n_utt, off_arr=off_arr, off_ptr=off_ptr)
 
 
-def _loop_events(opts, loop_events):
-    """loop_events = (torch.cuda.Event, torch.cuda.Event), already created: recorded around the entry's iteration loop"""
+def _offsets(utt_offsets):
+    """utt_offsets -> (n_utt, the int32 array, its pointer for the C ABI); the array keeps the pointer alive.  None is one
+    utterance and a NULL pointer."""
+    if utt_offsets is None:
+        return 1, None, None
+    off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
+    n_utt = len(off_arr) - 1
+    if n_utt < 1:
+        raise ValueError("utt_offsets needs at least two entries")
+    return n_utt, off_arr, off_arr.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _n_slots(iters, check_every):
+    """the error slots of a loop checked every `check_every` iterations: one at the start, one per check"""
+    return 1 + (int(iters) // int(check_every) if check_every > 0 else 0)
+
+
+def _finite_beta(beta):
+    beta = float(beta)
+    if not np.isfinite(beta):
+        raise ValueError(f"beta must be finite, got {beta!r}")
+    return beta
+
+
+def _beta_bins_limit(shape, lay):
+    """the bins of a 2-D operand addressed like the dictionary, against the beta kernels' limit - before the device is asked for"""
+    if len(shape) == 2 and shape[0 if lay == _lib.BIN_MAJOR else 1] > _lib.BETA_MAX_M:     # what the ABI answers with -3
+        raise ValueError(f"unsupported beta-divergence shape: M = {shape[0 if lay == _lib.BIN_MAJOR else 1]} bins, the "
+                         f"kernel holds at most {_lib.BETA_MAX_M}")
+
+
+def _common_opts(opts, dcode, lay, loop_events, splits=0):
+    """The fields every options struct has (the entry's own are set by its wrapper): its size, the element type, the layout,
+    forced `splits` in bits 8..15 of `reserved`, and loop_events = (torch.cuda.Event, torch.cuda.Event), already created:
+    recorded around the entry's iteration loop."""
+    opts.struct_bytes = C.sizeof(opts)
+    opts.dtype, opts.layout = dcode, lay
+    opts.reserved |= (int(splits) & 0xff) << 8
     if loop_events is not None:
         opts.ev_loop_start = int(loop_events[0].cuda_event)
         opts.ev_loop_stop = int(loop_events[1].cuda_event)
@@ -312,6 +341,21 @@ def _trace_arrays(n_utt, width, info):
         return None, None, None, None
     n_iter, trace = np.zeros(n_utt, dtype=np.int32), np.full((n_utt, width), np.nan)
     return n_iter, trace, n_iter.ctypes.data_as(C.POINTER(C.c_int)), trace.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _call(L, entry, device, head, ws_bytes=None, tail=()):
+    """The one native-call path: `entry`(*head[, workspace, its size], *tail, stream) on the device's current stream, with the
+    stream's workspace leased for the duration of the call when the entry takes one (ws_bytes is not None).  A status other
+    than 0 raises EvcError naming the entry."""
+    torch = _torch()
+    lease = _workspace(ws_bytes, device) if ws_bytes is not None else contextlib.nullcontext()
+    with torch.cuda.device(device), lease as ws:
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        if ws is None:
+            st = getattr(L, entry)(*head, *tail, stream)
+        else:
+            st = getattr(L, entry)(*head, ws.data_ptr(), ws.numel(), *tail, stream)
+    _lib.check(st, entry)
 
 
 def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=None,
@@ -350,8 +394,7 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
         Y_d = out_y if out_y is not None else torch.empty(yshape, dtype=tdtype, device=device)
 
     opts = _lib.SolveOpts()
-    opts.struct_bytes = C.sizeof(_lib.SolveOpts)
-    opts.dtype, opts.layout, opts.algo = dcode, lay, _ALGOS[algo]
+    opts.algo = _ALGOS[algo]
     opts.iters, opts.eps_mode, opts.init_mode = int(iters), _EPS_MODES[eps_mode], _INITS[p.init]
     opts.check_every, opts.stop_rule = int(check_every), _STOPS[stop_rule]
     opts.eps = _EPS_DEFAULT[eps_mode] if eps is None else float(eps)
@@ -380,26 +423,18 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
         if loss in ("kl", "kullback-leibler") and opts.eps != pd.eps:
             raise ValueError("the prepared dictionary's KL guard differs from this call's eps")
         opts.dict = C.addressof(pd.handle)
-    _loop_events(opts, loop_events)
+    _common_opts(opts, dcode, lay, loop_events)
 
     ws_bytes = int(L.evc_workspace_bytes(M, Mb, N, T, n_utt, dcode, opts.algo))
-    n_iter, err, ni_p, er_p = _trace_arrays(n_utt, 1 + (iters // check_every if check_every > 0 else 0), info)
-    h_ptr, h_ld = (H_d.data_ptr(), _ld(H_d)) if H_d is not None else (None, 0)
-    a_ptr, a_ld = (A_d.data_ptr(), _ld(A_d)) if A_d is not None else (None, 0)
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        if B is None:
-            st = L.evc_nmf_solve(
-                a_ptr, a_ld, X_d.data_ptr(), _ld(X_d), h_ptr, h_ld,
-                M, N, T, p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p,
-                C.c_void_p(stream))
-        else:
-            st = L.evc_nmf_convert(
-                a_ptr, a_ld, X_d.data_ptr(), _ld(X_d), B_d.data_ptr() if B_d is not None else None,
-                _ld(B_d) if B_d is not None else 0,
-                h_ptr, h_ld, Y_d.data_ptr(), _ld(Y_d), M, Mb, N, T, p.off_ptr, n_utt, C.byref(opts),
-                ws.data_ptr(), ws.numel(), ni_p, er_p, C.c_void_p(stream))
-    _lib.check(st, "evc_nmf_solve" if B is None else "evc_nmf_convert")
+    n_iter, err, ni_p, er_p = _trace_arrays(n_utt, _n_slots(iters, check_every), info)
+    h_args = (H_d.data_ptr(), _ld(H_d)) if H_d is not None else (None, 0)
+    ax_args = ((A_d.data_ptr(), _ld(A_d)) if A_d is not None else (None, 0)) + (X_d.data_ptr(), _ld(X_d))
+    if B is None:
+        entry, head = "evc_nmf_solve", (*ax_args, *h_args, M, N, T)
+    else:
+        b_args = (B_d.data_ptr(), _ld(B_d)) if B_d is not None else (None, 0)
+        entry, head = "evc_nmf_convert", (*ax_args, *b_args, *h_args, Y_d.data_ptr(), _ld(Y_d), M, Mb, N, T)
+    _call(L, entry, device, (*head, p.off_ptr, n_utt, C.byref(opts)), ws_bytes, (ni_p, er_p))
     to_np = p.x_np and out is None
     H_out = None if H_d is None else (_to_host(H_d) if to_np else H_d)
     res = [H_out] if B is None else ([H_out] if want_h else [])
@@ -417,6 +452,22 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
     return res[0] if len(res) == 1 else tuple(res)
 
 
+def _solve_fixed(L, entry, device, p, dict_args, opts, ws_bytes, trace, info, **extra):
+    """The call and the return rule of the solves with the dictionary fixed (cd, beta, transform, deconv), after the wrapper
+    has validated, staged the operands `p` (_operands) and filled `opts`.  dict_args: the dictionary as the entry takes it
+    (pointer, leading dimension - and the tap stride where it has taps); trace = (name, width) of the per-utterance float64
+    array the entry fills when info is asked for; extra: the wrapper's own info fields.  Returns the activations like X came
+    (numpy or device tensor), with info=True also dict(n_iter, <name>, **extra).  Without info both outputs are NULL and the
+    call stays asynchronous."""
+    n_iter, tr, ni_p, tr_p = _trace_arrays(p.n_utt, trace[1], info)
+    _call(L, entry, device, (*dict_args, p.X_d.data_ptr(), _ld(p.X_d), p.H_d.data_ptr(), _ld(p.H_d), p.M, p.N, p.T, p.off_ptr,
+                             p.n_utt, C.byref(opts)), ws_bytes, (ni_p, tr_p))
+    H_out = _to_host(p.H_d) if p.x_np else p.H_d
+    if info:
+        return H_out, {"n_iter": n_iter, trace[0]: tr, **extra}
+    return H_out
+
+
 def solve_activations_cd(A, X, H0=None, *, layout="bin_major", max_iter=200, tol=1e-4, l1=0.0, l2=0.0,
                          utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False,
                          loop_events=None):
@@ -428,31 +479,20 @@ def solve_activations_cd(A, X, H0=None, *, layout="bin_major", max_iter=200, tol
     Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor
     out); with info=True also dict(n_iter=int array per utterance, violation=[n_utt, max_iter] array (NaN after the
     stop), kernel="k_cd_sweep", launches=int).  No CPU fallback: without a HIP device this raises RuntimeError."""
-    torch = _torch()
     device = require_device(device)
     L = _lib.lib()
     p = _operands(A, X, H0, None, layout, dtype, device, utt_offsets)
-    A_d, X_d, H_d, M, N, T, n_utt, dcode = p.A_d, p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt, p.dcode
+    M, N, T = p.M, p.N, p.T
     opts = _lib.CdOpts()
-    opts.struct_bytes = C.sizeof(_lib.CdOpts)
-    opts.dtype, opts.layout = dcode, p.lay
     opts.init_mode = _lib.INIT_GIVEN if H0 is not None else _lib.INIT_SKLEARN
     opts.max_iter, opts.tol, opts.l1, opts.l2 = int(max_iter), float(tol), float(l1), float(l2)
-    _loop_events(opts, loop_events)
-    ws_bytes = int(L.evc_cd_workspace_bytes(M, N, T, n_utt, dcode))
+    _common_opts(opts, p.dcode, p.lay, loop_events)
+    ws_bytes = int(L.evc_cd_workspace_bytes(M, N, T, p.n_utt, p.dcode))
     if ws_bytes == 0:
         raise ValueError(f"unsupported coordinate-descent shape M={M}, N={N}, T={T}")
-    n_iter, viol, ni_p, vi_p = _trace_arrays(n_utt, max(int(max_iter), 0), info)
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_cd_solve(A_d.data_ptr(), _ld(A_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, N, T,
-                            p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, vi_p, C.c_void_p(stream))
-    _lib.check(st, "evc_cd_solve")
-    H_out = _to_host(H_d) if p.x_np else H_d
-    if info:
-        launches = int(max_iter) + 1 if (T > 0 and max_iter > 0) else 0
-        return H_out, {"n_iter": n_iter, "violation": viol, "kernel": "k_cd_sweep", "launches": launches}
-    return H_out
+    return _solve_fixed(L, "evc_cd_solve", device, p, (p.A_d.data_ptr(), _ld(p.A_d)), opts, ws_bytes,
+                        ("violation", max(int(max_iter), 0)), info, kernel="k_cd_sweep",
+                        launches=int(max_iter) + 1 if (T > 0 and max_iter > 0) else 0)
 
 
 def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100, init=None, init_value=0.0, check_every=0,
@@ -471,42 +511,26 @@ def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100
     iteration, two kernels per error slot, whether or not an utterance has stopped; the import and start kernels are not
     counted).  No CPU fallback: without a HIP device this raises RuntimeError."""
     lay = _LAYOUTS[layout]
-    beta = float(beta)
-    if not np.isfinite(beta):
-        raise ValueError(f"beta must be finite, got {beta!r}")
+    beta = _finite_beta(beta)
     if stop_rule not in ("none", "sklearn"):
         raise ValueError("stop_rule must be 'none' or 'sklearn'")
-    ashape = tuple(getattr(A, "shape", ()))
-    if len(ashape) == 2 and ashape[0 if lay == _lib.BIN_MAJOR else 1] > _lib.BETA_MAX_M:     # what the ABI answers with -3
-        raise ValueError(f"unsupported beta-divergence shape: M = {ashape[0 if lay == _lib.BIN_MAJOR else 1]} bins, the "
-                         f"kernel holds at most {_lib.BETA_MAX_M}")
-    torch = _torch()
+    _beta_bins_limit(tuple(getattr(A, "shape", ())), lay)
     device = require_device(device)
     L = _lib.lib()
     p = _operands(A, X, H0, init, layout, dtype, device, utt_offsets)
-    A_d, X_d, H_d, M, N, T, n_utt, dcode = p.A_d, p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt, p.dcode
+    M, N, T = p.M, p.N, p.T
     if M < 1 or N < 1:
         raise ValueError(f"empty beta-divergence problem M={M}, N={N}, T={T}")
     iters, check_every = int(iters), int(check_every)
     opts = _lib.BetaOpts()
-    opts.struct_bytes = C.sizeof(_lib.BetaOpts)
-    opts.dtype, opts.layout, opts.iters, opts.init_mode = dcode, lay, iters, _INITS[p.init]
+    opts.iters, opts.init_mode = iters, _INITS[p.init]
     opts.check_every, opts.stop_rule = check_every, _STOPS[stop_rule]
     opts.beta, opts.tol, opts.l1, opts.l2, opts.init_value = beta, float(tol), float(l1), float(l2), float(init_value)
-    _loop_events(opts, loop_events)
-    ws_bytes = int(L.evc_beta_workspace_bytes(M, N, T, n_utt, dcode))
-    n_slots = 1 + (iters // check_every if check_every > 0 else 0)
-    n_iter, err, ni_p, er_p = _trace_arrays(n_utt, n_slots, info)
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_beta_solve(A_d.data_ptr(), _ld(A_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, N, T,
-                              p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p, C.c_void_p(stream))
-    _lib.check(st, "evc_beta_solve")
-    H_out = _to_host(H_d) if p.x_np else H_d
-    if info:
-        launches = iters + 2 * n_slots * (check_every > 0) if T > 0 else 0
-        return H_out, {"n_iter": n_iter, "err": err, "kernel": "k_beta_sweep", "launches": launches}
-    return H_out
+    _common_opts(opts, p.dcode, lay, loop_events)
+    ws_bytes = int(L.evc_beta_workspace_bytes(M, N, T, p.n_utt, p.dcode))
+    n_slots = _n_slots(iters, check_every)
+    return _solve_fixed(L, "evc_beta_solve", device, p, (p.A_d.data_ptr(), _ld(p.A_d)), opts, ws_bytes, ("err", n_slots), info,
+                        kernel="k_beta_sweep", launches=iters + 2 * n_slots * (check_every > 0) if T > 0 else 0)
 
 
 def transform_online(W, X, *, beta=2.0, layout, max_iter=200, tol=1e-4, l1=0.0, l2=0.0, H0=None, init=None,
@@ -525,40 +549,24 @@ def transform_online(W, X, *, beta=2.0, layout, max_iter=200, tol=1e-4, l1=0.0, 
     (NaN after the stop), kernel="k_beta_sweep<change>").  info=False enqueues without waiting.  No CPU fallback: without a
     HIP device this raises RuntimeError."""
     lay = _LAYOUTS[layout]
-    beta = float(beta)
-    if not np.isfinite(beta):
-        raise ValueError(f"beta must be finite, got {beta!r}")
+    beta = _finite_beta(beta)
     max_iter = int(max_iter)
     if max_iter < 0:
         raise ValueError(f"max_iter must not be negative, got {max_iter!r}")
-    wshape = tuple(getattr(W, "shape", ()))
-    if len(wshape) == 2 and wshape[0 if lay == _lib.BIN_MAJOR else 1] > _lib.BETA_MAX_M:     # what the ABI answers with -3
-        raise ValueError(f"unsupported beta-divergence shape: M = {wshape[0 if lay == _lib.BIN_MAJOR else 1]} bins, the "
-                         f"kernel holds at most {_lib.BETA_MAX_M}")
-    torch = _torch()
+    _beta_bins_limit(tuple(getattr(W, "shape", ())), lay)
     device = require_device(device)
     L = _lib.lib()
     p = _operands(W, X, H0, init, layout, dtype, device, utt_offsets, out=out)
-    W_d, X_d, H_d, M, R, T, n_utt, dcode = p.A_d, p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt, p.dcode
+    M, R, T = p.M, p.N, p.T
     if M < 1 or R < 1:
         raise ValueError(f"empty beta-divergence problem M={M}, R={R}, T={T}")
     opts = _lib.TransformOpts()
-    opts.struct_bytes = C.sizeof(_lib.TransformOpts)
-    opts.dtype, opts.layout, opts.max_iter, opts.init_mode = dcode, lay, max_iter, _INITS[p.init]
+    opts.max_iter, opts.init_mode = max_iter, _INITS[p.init]
     opts.beta, opts.tol, opts.l1, opts.l2, opts.init_value = beta, float(tol), float(l1), float(l2), float(init_value)
-    _loop_events(opts, loop_events)
-    ws_bytes = int(L.evc_online_transform_workspace_bytes(M, R, T, n_utt, dcode))
-    n_iter, change, ni_p, ch_p = _trace_arrays(n_utt, max_iter, info)
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_online_transform(W_d.data_ptr(), _ld(W_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, R, T,
-                                    p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, ch_p,
-                                    C.c_void_p(stream))
-    _lib.check(st, "evc_online_transform")
-    H_out = _to_host(H_d) if p.x_np else H_d
-    if info:
-        return H_out, {"n_iter": n_iter, "change": change, "kernel": "k_beta_sweep<change>"}
-    return H_out
+    _common_opts(opts, p.dcode, lay, loop_events)
+    ws_bytes = int(L.evc_online_transform_workspace_bytes(M, R, T, p.n_utt, p.dcode))
+    return _solve_fixed(L, "evc_online_transform", device, p, (p.A_d.data_ptr(), _ld(p.A_d)), opts, ws_bytes,
+                        ("change", max_iter), info, kernel="k_beta_sweep<change>")
 
 
 def multiframe_dictionary(frames, seg_offsets, L, *, layout="bin_major"):
@@ -611,6 +619,11 @@ def _taps_to_dev(D_taps, tdtype, device, what):
     return D, was_numpy
 
 
+def _taps_args(D):
+    """(L, rows, cols) device taps as the deconvolution entries take them: pointer, row stride, tap stride (0 for one tap)"""
+    return D.data_ptr(), _ld(D[0]), int(D.stride(0)) if D.shape[0] > 1 else 0
+
+
 def _deconv_limits(shape, lay, max_bins, what):
     if len(shape) != 3:
         raise ValueError(f"{what} must be 3-D (taps, rows, columns), got shape {shape}")
@@ -642,37 +655,40 @@ def solve_activations_deconv(A_taps, X, H0=None, *, loss="frobenius", layout="bi
     if stop_rule not in ("none", "sklearn"):
         raise ValueError("stop_rule must be 'none' or 'sklearn'")
     _deconv_limits(tuple(getattr(A_taps, "shape", ())), lay, _lib.DECONV_MAX_M, "A_taps")
-    torch = _torch()
     device = require_device(device)
     L = _lib.lib()
     tdtype, _ = _pick_dtype(dtype, X, A_taps)
     A_d, _ = _taps_to_dev(A_taps, tdtype, device, "A_taps")
     taps = int(A_d.shape[0])
     p = _operands(A_d[0], X, H0, init, layout, tdtype, device, utt_offsets, out=out)
-    X_d, H_d, M, N, T, n_utt, dcode = p.X_d, p.H_d, p.M, p.N, p.T, p.n_utt, p.dcode
+    M, N, T = p.M, p.N, p.T
     if M < 1 or N < 1:
         raise ValueError(f"empty deconvolution problem M={M}, N={N}, T={T}")
     iters, check_every = int(iters), int(check_every)
     opts = _lib.DeconvOpts()
-    opts.struct_bytes = C.sizeof(_lib.DeconvOpts)
-    opts.dtype, opts.layout, opts.loss, opts.taps, opts.iters = dcode, lay, _LOSSES[loss], taps, iters
+    opts.loss, opts.taps, opts.iters = _LOSSES[loss], taps, iters
     opts.init_mode, opts.check_every, opts.stop_rule = _INITS[p.init], check_every, _STOPS[stop_rule]
     opts.tol, opts.l1, opts.l2, opts.init_value = float(tol), float(l1), float(l2), float(init_value)
-    _loop_events(opts, loop_events)
-    ws_bytes = int(L.evc_deconv_workspace_bytes(M, N, T, n_utt, taps, dcode))
-    n_slots = 1 + (iters // check_every if check_every > 0 else 0)
-    n_iter, err, ni_p, er_p = _trace_arrays(n_utt, n_slots, info)
-    tap_stride = int(A_d.stride(0)) if taps > 1 else 0
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_deconv_solve(A_d.data_ptr(), _ld(A_d[0]), tap_stride, X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d),
-                                M, N, T, p.off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, er_p,
-                                C.c_void_p(stream))
-    _lib.check(st, "evc_deconv_solve")
-    H_out = _to_host(H_d) if p.x_np else H_d
-    if info:
-        return H_out, {"n_iter": n_iter, "err": err, "kernel": "k_deconv_update", "taps": taps}
-    return H_out
+    _common_opts(opts, p.dcode, lay, loop_events)
+    ws_bytes = int(L.evc_deconv_workspace_bytes(M, N, T, p.n_utt, taps, p.dcode))
+    return _solve_fixed(L, "evc_deconv_solve", device, p, _taps_args(A_d), opts, ws_bytes,
+                        ("err", _n_slots(iters, check_every)), info, kernel="k_deconv_update", taps=taps)
+
+
+def _synthesis_target(bshape, H_d, lay, what):
+    """The sizes (Mb, N, T) and the empty Y of a synthesis, from the shape of the target dictionary's matrix (one tap's, where
+    it has taps) and the activations on the device; `what` names the dictionary in the error."""
+    if lay == _lib.BIN_MAJOR:
+        Mb, N = bshape
+        N2, T = H_d.shape
+        yshape = (Mb, T)
+    else:
+        N, Mb = bshape
+        T, N2 = H_d.shape
+        yshape = (T, Mb)
+    if N2 != N:
+        raise ValueError(f"{what} and H disagree on the number of exemplars: {N} vs {N2}")
+    return Mb, N, T, _torch().empty(yshape, dtype=H_d.dtype, device=H_d.device)
 
 
 def synthesize_deconv(B_taps, H, *, layout="bin_major", utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None):
@@ -681,38 +697,15 @@ def synthesize_deconv(B_taps, H, *, layout="bin_major", utt_offsets: Optional[Se
     returned Y as in synthesize."""
     lay = _LAYOUTS[layout]
     _deconv_limits(tuple(getattr(B_taps, "shape", ())), lay, _lib.DECONV_MAX_MB, "B_taps")
-    torch = _torch()
     device = require_device(device)
     L = _lib.lib()
     tdtype, dcode = _pick_dtype(dtype, H, B_taps)
     B_d, _ = _taps_to_dev(B_taps, tdtype, device, "B_taps")
     H_d, h_np = _to_dev(H, tdtype, device)
-    taps = int(B_d.shape[0])
-    if lay == _lib.BIN_MAJOR:
-        Mb, N = B_d.shape[1:]
-        N2, T = H_d.shape
-        yshape = (Mb, T)
-    else:
-        N, Mb = B_d.shape[1:]
-        T, N2 = H_d.shape
-        yshape = (T, Mb)
-    if N2 != N:
-        raise ValueError(f"B_taps and H disagree on the number of exemplars: {N} vs {N2}")
-    if utt_offsets is None:
-        n_utt, off_arr, off_ptr = 1, None, None
-    else:
-        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
-        n_utt = len(off_arr) - 1
-        if n_utt < 1:
-            raise ValueError("utt_offsets needs at least two entries")
-        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
-    Y = torch.empty(yshape, dtype=tdtype, device=device)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_deconv_synthesize(B_d.data_ptr(), _ld(B_d[0]), int(B_d.stride(0)) if taps > 1 else 0, H_d.data_ptr(),
-                                     _ld(H_d), Y.data_ptr(), _ld(Y), Mb, N, T, off_ptr, n_utt, taps, lay, dcode,
-                                     C.c_void_p(stream))
-    _lib.check(st, "evc_deconv_synthesize")
+    Mb, N, T, Y = _synthesis_target(B_d.shape[1:], H_d, lay, "B_taps")
+    n_utt, off_arr, off_ptr = _offsets(utt_offsets)
+    _call(L, "evc_deconv_synthesize", device, (*_taps_args(B_d), H_d.data_ptr(), _ld(H_d), Y.data_ptr(), _ld(Y), Mb, N, T,
+                                               off_ptr, n_utt, int(B_d.shape[0]), lay, dcode))
     return _to_host(Y) if h_np else Y
 
 
@@ -733,70 +726,98 @@ def convert_deconv(A_taps, X, B_taps, H0=None, *, layout="bin_major", utt_offset
     return (Y, H, inf) if info else (Y, H)
 
 
-def _learn(entry, opts, X, W0, H0, *, layout, ws_bytes, unsupported, trace, extra_info, tol, dtype, device, info, out_w,
-           out_h, loop_events, splits, call=None):
-    """What learn_dictionary, learn_dictionary_beta and learn_dictionary_cd share around their C entry `entry`: the
-    operands on the device (out_w / out_h in place, a caller's start never clobbered), the shape check, the common fields
-    of `opts` (the entry's own are already set), the workspace lease, the call and the return rule.
-    ws_bytes(L, M, R, T, dcode): the entry's workspace, 0 -> ValueError(unsupported(M, R, T)); trace = (name, shape) of the
-    float64 array the entry fills when info is asked for; extra_info(L, M, R, T): the entry's own info fields.
-    call(L, X_d, W_d, H_d, M, R, T, ws, n_iter_ptr, trace_ptr, stream) -> status: an entry whose argument list is not the
-    common one (evc_online_learn) is called through it."""
+def _taps_overlap(t):
+    """whether the taps of a (L, rows, columns) tensor share memory: they are written, so they must not"""
+    return t.shape[0] > 1 and t.stride(0) < (t.shape[1] - 1) * t.stride(1) + t.shape[2]
+
+
+def _factor_start(a0, out, what, tdtype, device, rank=2, written=True):
+    """The device tensor a learner's entry updates in place, for one factor (rank 2: a matrix; rank 3: taps): `out_<what>`
+    itself when given (the start a0, if any, copied into it), else a0's device copy - never the caller's own tensor when the
+    entry writes it (written), and never taps that overlap in memory."""
     torch = _torch()
+    if rank == 2:
+        to_dev = lambda a: _to_dev(a, tdtype, device)[0]
+    else:
+        to_dev = lambda a: _taps_to_dev(a, tdtype, device, "W0_taps")[0]
+    if out is not None:
+        if a0 is not None:
+            out.copy_(to_dev(a0))
+        if rank == 2 and (out.dtype != tdtype or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1)):
+            raise ValueError(f"`out_{what}` must be a device matrix of the call's dtype with unit inner stride")
+        if rank == 3 and out.dtype != tdtype:   # its rank, inner stride and overlap: checked before the device was asked for
+            raise ValueError(f"`out_{what}` must have the call's dtype")
+        return out
+    a_d = to_dev(a0)
+    if rank == 3 and _taps_overlap(a_d):
+        return a_d.contiguous()
+    if written and isinstance(a0, torch.Tensor) and a_d.data_ptr() == a0.data_ptr():
+        a_d = a_d.clone()       # never clobber the caller's start
+    return a_d
+
+
+# The dictionary learners (learn_dictionary, _beta, _cd, _online, _deconv) are four stages around their C entry, composed by
+# each wrapper after its own validation: _learn_operands (operands and shapes), _common_opts (the options every struct has;
+# the entry's own are set by the wrapper), _learn_run (workspace, call, counters and trace) and _learn_result (return rule).
+
+def _learn_operands(X, W0, H0, out_w, out_h, layout, dtype, device, w_rank=2, h_written=True):
+    """Stage 1: the device is resolved and the operands staged on it - X, and the two factors by _factor_start (out_w / out_h
+    in place, a caller's start never clobbered; w_rank 3: the dictionary has taps; h_written False: the entry only reads the
+    activations) - and their shapes checked against each other.  Returns a namespace of device, lay, tdtype, dcode, X_d, x_np
+    (X came as numpy), W_d, H_d, M, R, T."""
     device = require_device(device)
-    L = _lib.lib()
     lay = _LAYOUTS[layout]
     tdtype, dcode = _pick_dtype(dtype, X, W0 if W0 is not None else out_w)
     X_d, x_np = _to_dev(X, tdtype, device)
-    M, T = X_d.shape if lay == _lib.BIN_MAJOR else X_d.shape[::-1]
-
-    def start(a0, out, what):
-        if out is not None:
-            if a0 is not None:
-                out.copy_(_to_dev(a0, tdtype, device)[0])
-            if out.dtype != tdtype or out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1):
-                raise ValueError(f"`out_{what}` must be a device matrix of the call's dtype with unit inner stride")
-            return out
-        a_d, _ = _to_dev(a0, tdtype, device)
-        if isinstance(a0, torch.Tensor) and a_d.data_ptr() == a0.data_ptr():
-            a_d = a_d.clone()       # never clobber the caller's start
-        return a_d
-
-    W_d, H_d = start(W0, out_w, "w"), start(H0, out_h, "h")
-    M2, R = W_d.shape if lay == _lib.BIN_MAJOR else W_d.shape[::-1]
-    R2, T2 = H_d.shape if lay == _lib.BIN_MAJOR else H_d.shape[::-1]
+    W_d = _factor_start(W0, out_w, "w", tdtype, device, w_rank)
+    H_d = _factor_start(H0, out_h, "h", tdtype, device, written=h_written)
+    bm = lay == _lib.BIN_MAJOR
+    M, T = X_d.shape if bm else X_d.shape[::-1]
+    M2, R = W_d.shape[-2:] if bm else W_d.shape[:-3:-1]
+    R2, T2 = H_d.shape if bm else H_d.shape[::-1]
     if M2 != M or R2 != R or T2 != T:
-        raise ValueError(f"X {tuple(X_d.shape)}, W {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
-    opts.struct_bytes = C.sizeof(opts)
-    opts.dtype, opts.layout = dcode, lay
-    opts.reserved |= (int(splits) & 0xff) << 8
-    _loop_events(opts, loop_events)
-    nbytes = ws_bytes(L, M, R, T, dcode)
+        raise ValueError(f"X {tuple(X_d.shape)}, {'W' if w_rank == 2 else 'W_taps'} {tuple(W_d.shape)} and H "
+                         f"{tuple(H_d.shape)} do not fit ({layout})")
+    return types.SimpleNamespace(device=device, lay=lay, tdtype=tdtype, dcode=dcode, X_d=X_d, x_np=x_np, W_d=W_d, H_d=H_d,
+                                 M=M, R=R, T=T)
+
+
+def _xwh_args(p):
+    """the argument list most learning entries start with: X, W, H with their leading dimensions, then M, R, T"""
+    return (p.X_d.data_ptr(), _ld(p.X_d), p.W_d.data_ptr(), _ld(p.W_d), p.H_d.data_ptr(), _ld(p.H_d), p.M, p.R, p.T)
+
+
+def _learn_run(L, entry, p, head, opts, nbytes, unsupported, trace_shape, want_counts, info, n_counts=1):
+    """Stage 3: `entry`(*head, opts, workspace of nbytes, its n_counts int outputs, its trace, stream).  nbytes == 0 ->
+    ValueError(unsupported).  The int outputs (n_iter_out, and n_steps_out where the entry has one) are asked for only with
+    want_counts, the float64 trace of trace_shape only with info: with both NULL the entry enqueues without waiting.
+    Returns (the counts, the trace or None)."""
     if nbytes == 0:
-        raise ValueError(unsupported(M, R, T))
-    n_iter = C.c_int(0)
-    trace_name, trace_shape = trace
+        raise ValueError(unsupported)
+    counts = [C.c_int(0) for _ in range(n_counts)]
     tr = np.full(trace_shape, np.nan) if info else None
-    with torch.cuda.device(device), _workspace(nbytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        ni_p = C.byref(n_iter) if (info or tol > 0) else None
-        tr_p = tr.ctypes.data_as(C.POINTER(C.c_double)) if info else None
-        if call is not None:
-            st = call(L, X_d, W_d, H_d, M, R, T, ws, ni_p, tr_p, stream)
-        else:
-            st = getattr(L, entry)(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d), M, R, T,
-                                   C.byref(opts), ws.data_ptr(), ws.numel(), ni_p, tr_p, C.c_void_p(stream))
-    _lib.check(st, entry)
-    to_np = x_np and out_w is None and out_h is None
-    res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
-    if info:
-        res += ({"n_iter": int(n_iter.value), trace_name: tr, **extra_info(L, M, R, T)},)
-    return res
+    tail = [C.byref(c) if want_counts else None for c in counts]
+    tail.append(tr.ctypes.data_as(C.POINTER(C.c_double)) if info else None)
+    _call(L, entry, p.device, (*head, C.byref(opts)), nbytes, tail)
+    return [int(c.value) for c in counts], tr
 
 
-def _splits_info(query, splits):
+def _learn_result(p, out_w, out_h, info):
+    """Stage 4: (W, H) like X came - numpy for numpy operands unless out_w / out_h were given, else the device tensors - and
+    the wrapper's info dict appended when there is one."""
+    to_np = p.x_np and out_w is None and out_h is None
+    res = (_to_host(p.W_d), _to_host(p.H_d)) if to_np else (p.W_d, p.H_d)
+    return res + (info,) if info is not None else res
+
+
+def _splits_info(splits, query, *sizes):
     """the `splits` field of info: what the caller forced, else the library's own choice"""
-    return lambda L, M, R, T: {"splits": int(splits) if splits else int(getattr(L, query)(M, R, T))}
+    return int(splits) if splits else int(query(*sizes))
+
+
+def _route_info(L, route, M, R, T):
+    """the `route` field of info: what the caller forced, else the library's own choice"""
+    return route or ("fused", "unfused")[int(L.evc_beta_learn_route(M, R, T)) - 1]
 
 
 _SURFACES = {"sklearn": _lib.LEARN_SKLEARN, "pymf": _lib.LEARN_PYMF}
@@ -823,12 +844,15 @@ def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every
     opts = _lib.LearnOpts()
     opts.surface, opts.loss = _SURFACES[surface], _LOSSES[loss]
     opts.iters, opts.check_every, opts.tol = int(iters), int(check_every), float(tol)
-    n_slots = 1 + (int(iters) // int(check_every) if check_every > 0 else 0)
-    return _learn("evc_nmf_learn", opts, X, W0, H0, layout=layout,
-                  ws_bytes=lambda L, M, R, T, dcode: int(L.evc_learn_workspace_bytes(M, R, T, dcode)),
-                  unsupported=lambda M, R, T: f"unsupported dictionary-learning shape M={M}, R={R}, T={T}",
-                  trace=("err", n_slots), extra_info=_splits_info("evc_learn_splits", splits), tol=tol, dtype=dtype,
-                  device=device, info=info, out_w=out_w, out_h=out_h, loop_events=loop_events, splits=splits)
+    p = _learn_operands(X, W0, H0, out_w, out_h, layout, dtype, device)
+    L = _lib.lib()
+    _common_opts(opts, p.dcode, p.lay, loop_events, splits)
+    M, R, T = p.M, p.R, p.T
+    (n_iter,), err = _learn_run(L, "evc_nmf_learn", p, _xwh_args(p), opts, int(L.evc_learn_workspace_bytes(M, R, T, p.dcode)),
+                                f"unsupported dictionary-learning shape M={M}, R={R}, T={T}", _n_slots(iters, check_every),
+                                info or tol > 0, info)
+    return _learn_result(p, out_w, out_h, {"n_iter": n_iter, "err": err,
+                                           "splits": _splits_info(splits, L.evc_learn_splits, M, R, T)} if info else None)
 
 
 _BETA_ROUTES = {None: 0, "fused": 1, "unfused": 2}
@@ -849,33 +873,26 @@ def learn_dictionary_beta(X, W0, H0, *, beta, layout, iters, check_every=10, tol
     splits=frame ranges of the dictionary half's sums, route="fused" | "unfused": the kernels that formed those sums).
     out_w / out_h, loop_events, splits: as learn_dictionary's.  route: tests and tuning, "fused" or "unfused" instead of
     the library's choice.  No CPU fallback: without a HIP device this raises RuntimeError."""
-    lay = _LAYOUTS[layout]
-    beta = float(beta)
-    if not np.isfinite(beta):
-        raise ValueError(f"beta must be finite, got {beta!r}")
+    beta = _finite_beta(beta)
     if route not in _BETA_ROUTES:
         raise ValueError(f"route must be None, 'fused' or 'unfused', got {route!r}")
-    xshape = tuple(getattr(X, "shape", ()))
-    if len(xshape) == 2 and xshape[0 if lay == _lib.BIN_MAJOR else 1] > _lib.BETA_MAX_M:     # what the ABI answers with -3
-        raise ValueError(f"unsupported beta-divergence shape: M = {xshape[0 if lay == _lib.BIN_MAJOR else 1]} bins, the "
-                         f"kernel holds at most {_lib.BETA_MAX_M}")
+    _beta_bins_limit(tuple(getattr(X, "shape", ())), _LAYOUTS[layout])
     opts = _lib.BetaLearnOpts()
     opts.iters, opts.check_every = int(iters), int(check_every)
     opts.reserved = _BETA_ROUTES[route] << 16
     opts.beta, opts.tol = beta, float(tol)
     opts.l1_h, opts.l2_h, opts.l1_w, opts.l2_w = float(l1_h), float(l2_h), float(l1_w), float(l2_w)
-    n_slots = 1 + (int(iters) // int(check_every) if check_every > 0 else 0)
-
-    def extra_info(L, M, R, T):
-        return dict(_splits_info("evc_beta_learn_splits", splits)(L, M, R, T),
-                    route=route or ("fused", "unfused")[int(L.evc_beta_learn_route(M, R, T)) - 1])
-
-    return _learn("evc_beta_learn", opts, X, W0, H0, layout=layout,
-                  ws_bytes=lambda L, M, R, T, dcode: int(L.evc_beta_learn_workspace_bytes(M, R, T, dcode)),
-                  unsupported=lambda M, R, T: f"unsupported beta-divergence learning shape M={M}, R={R}, T={T} "
-                                              f"(M <= {_lib.BETA_MAX_M}, R <= 4096)",
-                  trace=("err", n_slots), extra_info=extra_info, tol=tol, dtype=dtype, device=device, info=info,
-                  out_w=out_w, out_h=out_h, loop_events=loop_events, splits=splits)
+    p = _learn_operands(X, W0, H0, out_w, out_h, layout, dtype, device)
+    L = _lib.lib()
+    _common_opts(opts, p.dcode, p.lay, loop_events, splits)
+    M, R, T = p.M, p.R, p.T
+    (n_iter,), err = _learn_run(L, "evc_beta_learn", p, _xwh_args(p), opts,
+                                int(L.evc_beta_learn_workspace_bytes(M, R, T, p.dcode)),
+                                f"unsupported beta-divergence learning shape M={M}, R={R}, T={T} "
+                                f"(M <= {_lib.BETA_MAX_M}, R <= 4096)", _n_slots(iters, check_every), info or tol > 0, info)
+    return _learn_result(p, out_w, out_h, {"n_iter": n_iter, "err": err,
+                                           "splits": _splits_info(splits, L.evc_beta_learn_splits, M, R, T),
+                                           "route": _route_info(L, route, M, R, T)} if info else None)
 
 
 def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max_iter=200, forget_factor=0.7, tol=1e-4,
@@ -906,9 +923,7 @@ def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max
     RuntimeError."""
     torch = _torch()
     lay = _LAYOUTS[layout]
-    beta = float(beta)
-    if not np.isfinite(beta):
-        raise ValueError(f"beta must be finite, got {beta!r}")
+    beta = _finite_beta(beta)
     if route not in _BETA_ROUTES:
         raise ValueError(f"route must be None, 'fused' or 'unfused', got {route!r}")
     if int(batch_size) < 1:
@@ -919,9 +934,7 @@ def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max
     if len(xshape) != 2:
         raise ValueError(f"expected a 2-D matrix, got shape {xshape}")
     bm = lay == _lib.BIN_MAJOR
-    if xshape[0 if bm else 1] > _lib.BETA_MAX_M:          # what the ABI answers with -3
-        raise ValueError(f"unsupported beta-divergence shape: M = {xshape[0 if bm else 1]} bins, the kernel holds at most "
-                         f"{_lib.BETA_MAX_M}")
+    _beta_bins_limit(xshape, lay)
     T = int(xshape[1 if bm else 0])
     bs = max(min(int(batch_size), T), 1)
     per_pass = -(-T // bs)
@@ -945,40 +958,31 @@ def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max
     opts.reserved = _BETA_ROUTES[route] << 16
     opts.beta, opts.tol, opts.forget_factor = beta, float(tol), float(forget_factor)
     opts.l1_h, opts.l2_h, opts.l1_w, opts.l2_w = float(l1_h), float(l2_h), float(l1_w), float(l2_w)
-    n_steps = C.c_int(0)
-    acc = {}
-
-    def call(L, X_d, W_d, H_d, M, R, T, ws, n_iter_p, tr_p, stream):
-        if state is None:
-            A_d, B_d = torch.empty_like(W_d).contiguous(), torch.empty_like(W_d).contiguous()
-        else:
-            A_d, B_d = state
-            for t in (A_d, B_d):
-                if not isinstance(t, torch.Tensor) or t.shape != W_d.shape or t.dtype != W_d.dtype \
-                        or t.device != W_d.device or not t.is_contiguous():
-                    raise ValueError("`state` must be the (A, B) device tensors of an earlier call's info, shaped like W")
-        acc["state"] = (A_d, B_d)
-        quiet = n_iter_p is None
-        return getattr(L, entry)(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), H_d.data_ptr(), _ld(H_d),
-                                 A_d.data_ptr(), B_d.data_ptr(), _ld(A_d), M, R, T, C.byref(opts), ws.data_ptr(), ws.numel(),
-                                 n_iter_p, None if quiet else C.byref(n_steps), tr_p, C.c_void_p(stream))
-
-    def extra_info(L, M, R, T):
-        return {"n_steps": int(n_steps.value), "state": acc["state"],
-                "route": route or ("fused", "unfused")[int(L.evc_beta_learn_route(M, R, T)) - 1]}
-
-    ws_query = "evc_online_fresh_workspace_bytes" if fresh else "evc_online_workspace_bytes"
-    res = _learn(entry, opts, X, W0, H0, layout=layout,
-                 ws_bytes=lambda L, M, R, T, dcode: int(getattr(L, ws_query)(M, R, T, int(batch_size), dcode)),
-                 unsupported=lambda M, R, T: f"unsupported mini-batch learning shape M={M}, R={R}, T={T} "
-                                             f"(M <= {_lib.BETA_MAX_M}, R <= 4096)",
-                 trace=("trace", (max(int(max_iter), 0) * per_pass, 2)), extra_info=extra_info,
-                 tol=1.0 if (tol > 0 or mni >= 0) else 0.0, dtype=dtype, device=device, info=info, out_w=out_w, out_h=out_h,
-                 loop_events=loop_events, splits=splits, call=call)
-    if info:
-        tr = res[2].pop("trace")
-        res[2]["cost"], res[2]["change"] = np.ascontiguousarray(tr[:, 0]), np.ascontiguousarray(tr[:, 1])
-    return res
+    p = _learn_operands(X, W0, H0, out_w, out_h, layout, dtype, device)
+    L = _lib.lib()
+    _common_opts(opts, p.dcode, p.lay, loop_events, splits)
+    M, R, T, W_d = p.M, p.R, p.T, p.W_d
+    ws_query = L.evc_online_fresh_workspace_bytes if fresh else L.evc_online_workspace_bytes
+    nbytes = int(ws_query(M, R, T, int(batch_size), p.dcode))
+    unsupported = f"unsupported mini-batch learning shape M={M}, R={R}, T={T} (M <= {_lib.BETA_MAX_M}, R <= 4096)"
+    if nbytes == 0:         # refused here already, before `state` is looked at
+        raise ValueError(unsupported)
+    if state is None:
+        A_d, B_d = torch.empty_like(W_d).contiguous(), torch.empty_like(W_d).contiguous()
+    else:
+        A_d, B_d = state
+        for t in (A_d, B_d):
+            if not isinstance(t, torch.Tensor) or t.shape != W_d.shape or t.dtype != W_d.dtype \
+                    or t.device != W_d.device or not t.is_contiguous():
+                raise ValueError("`state` must be the (A, B) device tensors of an earlier call's info, shaped like W")
+    xwh = _xwh_args(p)
+    (n_iter, n_steps), tr = _learn_run(L, entry, p, (*xwh[:6], A_d.data_ptr(), B_d.data_ptr(), _ld(A_d), *xwh[6:]), opts,
+                                       nbytes, unsupported, (max(int(max_iter), 0) * per_pass, 2), info or tol > 0 or mni >= 0,
+                                       info, n_counts=2)
+    return _learn_result(p, out_w, out_h, {"n_iter": n_iter, "n_steps": n_steps, "state": (A_d, B_d),
+                                           "route": _route_info(L, route, M, R, T),
+                                           "cost": np.ascontiguousarray(tr[:, 0]),
+                                           "change": np.ascontiguousarray(tr[:, 1])} if info else None)
 
 
 _CDL_UPDATES = {"both": _lib.CDL_BOTH, "dict": _lib.CDL_DICT_ONLY}
@@ -1014,13 +1018,15 @@ def learn_dictionary_cd(X, W0, H0, *, layout, max_iter=200, tol=1e-4, l1_h=0.0, 
     opts = _lib.CdLearnOpts()
     opts.max_iter, opts.update = int(max_iter), _CDL_UPDATES[update]
     opts.tol, opts.l1_h, opts.l2_h, opts.l1_w, opts.l2_w = float(tol), float(l1_h), float(l2_h), float(l1_w), float(l2_w)
-    return _learn("evc_cd_learn", opts, X, W0, H0, layout=layout,
-                  ws_bytes=lambda L, M, R, T, dcode: _cd_learn_workspace(L, M, R, T, dcode, splits),
-                  unsupported=lambda M, R, T: f"unsupported coordinate-descent learning shape M={M}, R={R}, T={T} "
-                                              f"(M, R <= 1024)",
-                  trace=("violation", (max(int(max_iter), 0), 2)), extra_info=_splits_info("evc_cd_learn_splits", splits),
-                  tol=tol, dtype=dtype, device=device, info=info, out_w=out_w, out_h=out_h, loop_events=loop_events,
-                  splits=splits)
+    p = _learn_operands(X, W0, H0, out_w, out_h, layout, dtype, device)
+    L = _lib.lib()
+    _common_opts(opts, p.dcode, p.lay, loop_events, splits)
+    M, R, T = p.M, p.R, p.T
+    (n_iter,), viol = _learn_run(L, "evc_cd_learn", p, _xwh_args(p), opts, _cd_learn_workspace(L, M, R, T, p.dcode, splits),
+                                 f"unsupported coordinate-descent learning shape M={M}, R={R}, T={T} (M, R <= 1024)",
+                                 (max(int(max_iter), 0), 2), info or tol > 0, info)
+    return _learn_result(p, out_w, out_h, {"n_iter": n_iter, "violation": viol,
+                                           "splits": _splits_info(splits, L.evc_cd_learn_splits, M, R, T)} if info else None)
 
 
 def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepared=False, dtype=None, device=None,
@@ -1093,11 +1099,6 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
 _DCL_UPDATES = {"both": _lib.DCL_BOTH, "dict": _lib.DCL_DICT_ONLY}
 
 
-def _taps_overlap(t):
-    """whether the taps of a (L, rows, columns) tensor share memory: they are written, so they must not"""
-    return t.shape[0] > 1 and t.stride(0) < (t.shape[1] - 1) * t.stride(1) + t.shape[2]
-
-
 def learn_dictionary_deconv(X, W0_taps, H0, *, loss="frobenius", layout, iters, check_every=10, tol=0.0, l1_h=0.0, l2_h=0.0,
                             update="both", utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False,
                             out_w=None, out_h=None, loop_events=None, splits=0):
@@ -1115,8 +1116,7 @@ def learn_dictionary_deconv(X, W0_taps, H0, *, loss="frobenius", layout, iters, 
     info=True also dict(n_iter=int, err=[1 + iters // check_every] errors (the first at the start; NaN where not evaluated),
     splits=frame ranges of the dictionary half's sums).  out_w / out_h: device tensors updated in place (they then hold the
     start, W0_taps / H0 are ignored when None); the taps of out_w must not overlap in memory.  splits: tuning and tests,
-    1..64 frame ranges.  This driver does not go through _learn: its dictionary is three-dimensional and its frames belong to
-    utterances.  No CPU fallback: without a HIP device this raises RuntimeError."""
+    1..64 frame ranges.  No CPU fallback: without a HIP device this raises RuntimeError."""
     lay = _LAYOUTS[layout]
     bm = lay == _lib.BIN_MAJOR
     if loss not in _LOSSES:
@@ -1141,72 +1141,24 @@ def learn_dictionary_deconv(X, W0_taps, H0, *, loss="frobenius", layout, iters, 
             raise ValueError("`out_w` must be a 3-D device tensor (taps, rows, columns) with unit inner stride")
         if _taps_overlap(out_w):
             raise ValueError("the taps of `out_w` overlap in memory: they are written, so tap_stride must cover one tap")
-    device = require_device(device)
+    p = _learn_operands(X, W0_taps, H0, out_w, out_h, layout, dtype, device, w_rank=3, h_written=update == "both")
     L = _lib.lib()
-    tdtype, dcode = _pick_dtype(dtype, X, w_src)
-    X_d, x_np = _to_dev(X, tdtype, device)
-    M, T = X_d.shape if bm else X_d.shape[::-1]
-    if out_w is not None:
-        if W0_taps is not None:
-            out_w.copy_(_taps_to_dev(W0_taps, tdtype, device, "W0_taps")[0])
-        if out_w.dtype != tdtype:
-            raise ValueError("`out_w` must have the call's dtype")
-        W_d = out_w
-    else:
-        W_d, _ = _taps_to_dev(W0_taps, tdtype, device, "W0_taps")
-        if _taps_overlap(W_d):
-            W_d = W_d.contiguous()
-        elif isinstance(W0_taps, torch.Tensor) and W_d.data_ptr() == W0_taps.data_ptr():
-            W_d = W_d.clone()       # never clobber the caller's start
-    if out_h is not None:
-        if H0 is not None:
-            out_h.copy_(_to_dev(H0, tdtype, device)[0])
-        if out_h.dtype != tdtype or out_h.dim() != 2 or (out_h.shape[1] > 1 and out_h.stride(1) != 1):
-            raise ValueError("`out_h` must be a device matrix of the call's dtype with unit inner stride")
-        H_d = out_h
-    else:
-        H_d, _ = _to_dev(H0, tdtype, device)
-        if update == "both" and isinstance(H0, torch.Tensor) and H_d.data_ptr() == H0.data_ptr():
-            H_d = H_d.clone()
-    taps = int(W_d.shape[0])
-    M2, R = W_d.shape[1:] if bm else W_d.shape[:0:-1]
-    R2, T2 = H_d.shape if bm else H_d.shape[::-1]
-    if M2 != M or R2 != R or T2 != T:
-        raise ValueError(f"X {tuple(X_d.shape)}, W_taps {tuple(W_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
-    if utt_offsets is None:
-        n_utt, off_arr, off_ptr = 1, None, None
-    else:
-        off_arr = np.ascontiguousarray(np.asarray(utt_offsets, dtype=np.int32))
-        n_utt = len(off_arr) - 1
-        if n_utt < 1:
-            raise ValueError("utt_offsets needs at least two entries")
-        off_ptr = off_arr.ctypes.data_as(C.POINTER(C.c_int))
+    M, R, T, taps = p.M, p.R, p.T, int(p.W_d.shape[0])
+    n_utt, off_arr, off_ptr = _offsets(utt_offsets)
     iters, check_every = int(iters), int(check_every)
     opts = _lib.DeconvLearnOpts()
-    opts.struct_bytes = C.sizeof(opts)
-    opts.dtype, opts.layout, opts.loss, opts.taps = dcode, lay, _LOSSES[loss], taps
+    opts.loss, opts.taps = _LOSSES[loss], taps
     opts.iters, opts.check_every, opts.update = iters, check_every, _DCL_UPDATES[update]
-    opts.reserved = (int(splits) & 0xff) << 8
     opts.tol, opts.l1_h, opts.l2_h = float(tol), float(l1_h), float(l2_h)
-    _loop_events(opts, loop_events)
-    nbytes = int(L.evc_deconv_learn_workspace_bytes(M, R, T, n_utt, taps, opts.update, dcode))
-    if nbytes == 0:
-        raise ValueError(f"unsupported convolutive learning shape M={M}, R={R}, T={T}, taps={taps}")
-    n_iter = C.c_int(0)
-    err = np.full(1 + (iters // check_every if check_every > 0 else 0), np.nan) if info else None
-    with torch.cuda.device(device), _workspace(nbytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_deconv_learn(X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d[0]), int(W_d.stride(0)) if taps > 1 else 0,
-                                H_d.data_ptr(), _ld(H_d), M, R, T, off_ptr, n_utt, C.byref(opts), ws.data_ptr(), ws.numel(),
-                                C.byref(n_iter) if (info or tol > 0) else None,
-                                err.ctypes.data_as(C.POINTER(C.c_double)) if info else None, C.c_void_p(stream))
-    _lib.check(st, "evc_deconv_learn")
-    to_np = x_np and out_w is None and out_h is None
-    res = (_to_host(W_d), _to_host(H_d)) if to_np else (W_d, H_d)
-    if info:
-        res += ({"n_iter": int(n_iter.value), "err": err,
-                 "splits": int(splits) if splits else int(L.evc_deconv_learn_splits(M, R, T, n_utt, taps))},)
-    return res
+    _common_opts(opts, p.dcode, lay, loop_events, splits)
+    head = (p.X_d.data_ptr(), _ld(p.X_d), *_taps_args(p.W_d), p.H_d.data_ptr(), _ld(p.H_d), M, R, T, off_ptr, n_utt)
+    (n_iter,), err = _learn_run(L, "evc_deconv_learn", p, head, opts,
+                                int(L.evc_deconv_learn_workspace_bytes(M, R, T, n_utt, taps, opts.update, p.dcode)),
+                                f"unsupported convolutive learning shape M={M}, R={R}, T={T}, taps={taps}",
+                                _n_slots(iters, check_every), info or tol > 0, info)
+    return _learn_result(p, out_w, out_h, {"n_iter": n_iter, "err": err,
+                                           "splits": _splits_info(splits, L.evc_deconv_learn_splits, M, R, T, n_utt, taps)}
+                         if info else None)
 
 
 def compact_dictionary_deconv(A_frames, B_frames, seg_offsets, R, taps, *, iters=100, tol=0.0, loss="frobenius",
@@ -1272,29 +1224,15 @@ def compact_dictionary_deconv(A_frames, B_frames, seg_offsets, R, taps, *, iters
 def synthesize(B, H, *, layout="bin_major", dtype=None, device=None):
     """Y = B H (bin_major, (Mb,T)) or H B (frame_major: np.matmul(H.T, B) of
     04_align_n_nmf.py:391 with H already frames-as-rows, giving (T,Mb))."""
-    torch = _torch()
     device = require_device(device)
     L = _lib.lib()
     lay = _LAYOUTS[layout]
     tdtype, dcode = _pick_dtype(dtype, H, B)
     B_d, _ = _to_dev(B, tdtype, device)
     H_d, h_np = _to_dev(H, tdtype, device)
-    if lay == _lib.BIN_MAJOR:
-        Mb, N = B_d.shape
-        N2, T = H_d.shape
-        yshape = (Mb, T)
-    else:
-        N, Mb = B_d.shape
-        T, N2 = H_d.shape
-        yshape = (T, Mb)
-    if N2 != N:
-        raise ValueError(f"B and H disagree on the number of exemplars: {N} vs {N2}")
-    Y = torch.empty(yshape, dtype=tdtype, device=device)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_synthesize(B_d.data_ptr(), _ld(B_d), H_d.data_ptr(), _ld(H_d), Y.data_ptr(),
-                              _ld(Y), Mb, N, T, lay, dcode, C.c_void_p(stream))
-    _lib.check(st, "evc_synthesize")
+    Mb, N, T, Y = _synthesis_target(B_d.shape, H_d, lay, "B")
+    _call(L, "evc_synthesize", device, (B_d.data_ptr(), _ld(B_d), H_d.data_ptr(), _ld(H_d), Y.data_ptr(), _ld(Y), Mb, N, T,
+                                        lay, dcode))
     return _to_host(Y) if h_np else Y
 
 
@@ -1316,12 +1254,8 @@ def frame_residuals(A, X, H, *, layout="bin_major", dtype=None, device=None):
         T = X_d.shape[0]
     err2 = torch.zeros(max(T, 1), dtype=torch.float64, device=device)
     ws_bytes = int(L.evc_workspace_bytes(M, 0, N, T, 1, dcode, _lib.ALGO_GRAM))
-    with torch.cuda.device(device), _workspace(ws_bytes, device) as ws:
-        stream = torch.cuda.current_stream(device).cuda_stream
-        st = L.evc_residual(A_d.data_ptr(), _ld(A_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(),
-                            _ld(H_d), M, N, T, lay, dcode, err2.data_ptr(), ws.data_ptr(),
-                            ws.numel(), C.c_void_p(stream))
-    _lib.check(st, "evc_residual")
+    _call(L, "evc_residual", device, (A_d.data_ptr(), _ld(A_d), X_d.data_ptr(), _ld(X_d), H_d.data_ptr(), _ld(H_d), M, N, T,
+                                      lay, dcode, err2.data_ptr()), ws_bytes)
     err2 = err2[:T]
     return err2.cpu().numpy() if x_np else err2
 
