@@ -39,10 +39,12 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_online_transform_workspace_bytes", "evc_online_transform",
            "evc_online_fresh_workspace_bytes", "evc_online_learn_fresh",
            "evc_deconv_workspace_bytes", "evc_deconv_solve", "evc_deconv_synthesize",
-           "evc_deconv_learn_workspace_bytes", "evc_deconv_learn_splits", "evc_deconv_learn")
+           "evc_deconv_learn_workspace_bytes", "evc_deconv_learn_splits", "evc_deconv_learn",
+           "evc_semi_workspace_bytes", "evc_semi_solve")
 BETA_MAX_M = 528
 DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 DECONV_LEARN_MAX_R = 4096
+SEMI_MAX_M, SEMI_MAX_N = 1056, 16384
 MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
 
@@ -167,6 +169,16 @@ class DeconvLearnOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("loss", C.c_int), ("taps", C.c_int),
         ("iters", C.c_int), ("check_every", C.c_int), ("update", C.c_int), ("reserved", C.c_int),
         ("tol", C.c_double), ("l1_h", C.c_double), ("l2_h", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class SemiOpts(C.Structure):
+    """Mirror of `evc_semi_opts` (include/evc.h): options of the semi-NMF activation solve."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
+        ("init_mode", C.c_int), ("check_every", C.c_int), ("stop_rule", C.c_int), ("reserved", C.c_int),
+        ("eps", C.c_double), ("tol", C.c_double), ("init_value", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -417,6 +429,17 @@ def lib():
         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_int,    # X, W (ldw, tap_stride), H
         C.c_int, C.c_int, C.c_int,                                          # M, R, T
         C.POINTER(C.c_int), C.c_int, C.POINTER(DeconvLearnOpts),            # utt_offsets, n_utt, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_semi_workspace_bytes.restype = C.c_size_t
+    L.evc_semi_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_semi_solve.restype = C.c_int
+    L.evc_semi_solve.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # A, X, H
+        C.c_int, C.c_int, C.c_int,                                          # M, N, T
+        C.POINTER(C.c_int), C.c_int, C.POINTER(SemiOpts),                   # utt_offsets, n_utt, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
         C.c_void_p,                                                         # stream

@@ -11,6 +11,10 @@ update still goes through the GPU solver - a drop-in must not raise on the defau
 (round 3 did).  A RuntimeWarning says so once per call.
 `NMF(..., dictionary_update="device")` opts in to the accelerated loop instead: both updates run on the GPU in one
 call (evc_nmf_learn, pymf surface), W and H are updated in place and `ferr` is as pymf makes it.
+
+`SNMF` is pymf's semi-NMF (pymf/snmf.py): `data` and `W` are signed, only `H` is non-negative.  `compute_w=False` is one
+native call (evc_semi_solve); the default `compute_w=True` forms W = data H^T (H H^T)^-1 on the host (snmf.py:61-64) and
+runs one GPU activation update per iteration, with the same warning.
 """
 from __future__ import annotations
 
@@ -18,7 +22,7 @@ import logging
 
 import numpy as np
 
-from ..solver import frame_residuals, learn_dictionary, solve_activations, synthesize
+from ..solver import frame_residuals, learn_dictionary, solve_activations, solve_activations_semi, synthesize
 
 _EPS = np.finfo(float).eps
 
@@ -65,6 +69,15 @@ class NMF:
         self.W /= W2
         self.W /= np.sqrt(np.sum(self.W ** 2.0, axis=0))
 
+    def _activation_solve(self, niter, check, info):
+        """`niter` updates of H with W fixed, one native call.  info: also the counts and, with `check`, the error after every
+        update and pymf's stop -> (H, info); else H alone"""
+        kw = dict(check_every=1 if check else 0, stop_rule="pymf" if check else "none", tol=self._EPS, info=True) if info else {}
+        return solve_activations(
+            np.asarray(self.W, dtype=np.float64), np.asarray(self.data, dtype=np.float64),
+            np.asarray(self.H, dtype=np.float64), layout="bin_major", iters=niter,
+            eps_mode="add", eps=10 ** -9, init="given", algo=self._algo, device=self._device, **kw)
+
     def _factorize_on_device(self, niter, compute_err):
         """pymf/base.py:238-270 with compute_w=True in one native call: per iteration W, then H, then the error and
         the machine-epsilon stop test; W and H are updated in place"""
@@ -110,10 +123,7 @@ class NMF:
         for i in range(niter):
             self._update_w()
             if compute_h:
-                self.H[...] = solve_activations(
-                    self.W, np.asarray(self.data, dtype=np.float64), np.asarray(self.H, dtype=np.float64),
-                    layout="bin_major", iters=1, eps_mode="add", eps=10 ** -9, init="given", algo=self._algo,
-                    device=self._device)
+                self.H[...] = self._activation_solve(1, False, False)
             if compute_err:
                 self.ferr[i] = self.frobenius_norm()
                 self._logger.info("FN: %s (%s/%s)" % (self.ferr[i], i + 1, niter))
@@ -141,12 +151,7 @@ class NMF:
             self.ferr = np.zeros(niter)
         if not compute_h or niter <= 0:
             return
-        H, info = solve_activations(
-            np.asarray(self.W, dtype=np.float64), np.asarray(self.data, dtype=np.float64),
-            np.asarray(self.H, dtype=np.float64), layout="bin_major", iters=niter,
-            eps_mode="add", eps=10 ** -9, init="given", algo=self._algo,
-            check_every=1 if compute_err else 0, stop_rule="pymf" if compute_err else "none",
-            tol=self._EPS, device=self._device, info=True)
+        H, info = self._activation_solve(niter, compute_err, True)
         self.H[...] = H                     # in place, like `self.H *= ...; self.H /= ...`
         if compute_err:
             n = int(info["n_iter"][0])      # updates applied
@@ -158,3 +163,27 @@ class NMF:
                 self.ferr[:n] = ferr
             for i, e in enumerate(self.ferr):
                 self._logger.info("FN: %s (%s/%s)" % (e, i + 1, niter))
+
+
+class SNMF(NMF):
+    """pymf's SNMF(data, num_bases): semi-NMF, data ~ W H with signed data and W and H >= 0 (pymf/snmf.py:21-85).  The loop,
+    `ferr` and the stop are NMF's (pymf/base.py); the two updates are its own."""
+
+    def __init__(self, data, num_bases=4, **kwargs):
+        NMF.__init__(self, data, num_bases, **kwargs)
+        if self._dictionary_update != "host":
+            raise ValueError("SNMF updates its dictionary on the host only")
+
+    def _update_w(self):
+        """pymf/snmf.py:61-64: W = data H^T (H H^T)^-1.  Host numpy: outside the accelerated path."""
+        W1 = np.dot(self.data[:, :], self.H.T)
+        W2 = np.dot(self.H, self.H.T)
+        self.W = np.dot(W1, np.linalg.inv(W2))
+
+    def _activation_solve(self, niter, check, info):
+        """pymf/snmf.py:66-85, `niter` times in one native call (evc_semi_solve)"""
+        kw = dict(check_every=1 if check else 0, stop_rule="pymf" if check else "none", tol=self._EPS, info=True) if info else {}
+        return solve_activations_semi(
+            np.asarray(self.W, dtype=np.float64), np.asarray(self.data, dtype=np.float64),
+            np.asarray(self.H, dtype=np.float64), layout="bin_major", iters=niter, eps=10 ** -9, init="given", dtype="f64",
+            device=self._device, **kw)

@@ -533,6 +533,84 @@ def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100
                         kernel="k_beta_sweep", launches=iters + 2 * n_slots * (check_every > 0) if T > 0 else 0)
 
 
+def _semi_shapes(A, X, lay):
+    """the sizes (M, N) of a semi-NMF call from the operands' shapes alone, checked against each other and against the
+    kernel's limits - before the device is asked for"""
+    ashape, xshape = tuple(getattr(A, "shape", ())), tuple(getattr(X, "shape", ()))
+    if len(ashape) != 2 or len(xshape) != 2:
+        raise ValueError(f"A and X must be 2-D, got shapes {ashape} and {xshape}")
+    M, N = ashape if lay == _lib.BIN_MAJOR else ashape[::-1]
+    M2 = xshape[0 if lay == _lib.BIN_MAJOR else 1]
+    if M2 != M:
+        raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
+    if M < 1 or N < 1:
+        raise ValueError(f"empty semi-NMF problem M={M}, N={N}")
+    if M > _lib.SEMI_MAX_M or N > _lib.SEMI_MAX_N:           # what the ABI answers with -3
+        raise ValueError(f"unsupported semi-NMF shape: M = {M} bins, N = {N} exemplars; the kernel holds at most "
+                         f"{_lib.SEMI_MAX_M} bins and {_lib.SEMI_MAX_N} exemplars")
+    return M, N
+
+
+def solve_activations_semi(A, X, H0=None, *, layout="bin_major", iters=100, eps=1e-9, init=None, init_value=0.0,
+                           check_every=0, stop_rule="none", tol=0.0, utt_offsets: Optional[Sequence[int]] = None, dtype=None,
+                           device=None, info=False, loop_events=None):
+    """Semi-NMF activations with the dictionary fixed (Ding, Li and Jordan; pymf's SNMF with compute_w=False), on the GPU
+    (evc_semi_solve): A and X are SIGNED - mel-cepstra, MFCCs - and only H >= 0.  Per iteration
+    H <- H * sqrt((pos(A^T X) + neg(A^T A) H) / (neg(A^T X) + pos(A^T A) H + eps)).  init: "given" (H0, non-negative) or
+    "const" (init_value); default "given", so H0 is needed unless init="const".  stop_rule "pymf": per utterance, from
+    the third check on, stop when |err - err_prev| / T_u < tol (pymf: check_every=1, tol=2.22e-16).  At most 1056 bins and
+    16384 exemplars.
+
+    Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out);
+    with info=True also dict(n_iter=int array per utterance, err=[n_utt, 1 + iters // check_every] array of
+    ||X_u - A H_u||_F (NaN where not evaluated), kernel="k_semi_sweep", launches=int: one sweep per iteration and three
+    kernels per error slot).  No CPU fallback: without a HIP device this raises RuntimeError."""
+    lay = _LAYOUTS[layout]
+    if stop_rule not in ("none", "pymf"):
+        raise ValueError("stop_rule must be 'none' or 'pymf'")
+    if init is None:
+        init = "given"
+    if init not in ("given", "const"):
+        raise ValueError("init must be 'given' or 'const'")
+    _semi_shapes(A, X, lay)
+    _pick_dtype(dtype, X, A)
+    device = require_device(device)
+    L = _lib.lib()
+    p = _operands(A, X, H0, init, layout, dtype, device, utt_offsets)
+    M, N, T = p.M, p.N, p.T
+    iters, check_every = int(iters), int(check_every)
+    opts = _lib.SemiOpts()
+    opts.iters, opts.init_mode = iters, _INITS[p.init]
+    opts.check_every, opts.stop_rule = check_every, _STOPS[stop_rule]
+    opts.eps, opts.tol, opts.init_value = float(eps), float(tol), float(init_value)
+    _common_opts(opts, p.dcode, lay, loop_events)
+    ws_bytes = int(L.evc_semi_workspace_bytes(M, N, T, p.n_utt, p.dcode))
+    n_slots = _n_slots(iters, check_every)
+    return _solve_fixed(L, "evc_semi_solve", device, p, (p.A_d.data_ptr(), _ld(p.A_d)), opts, ws_bytes, ("err", n_slots), info,
+                        kernel="k_semi_sweep", launches=iters + 3 * n_slots * (check_every > 0) if T > 0 else 0)
+
+
+def convert_semi(A, B, X, H0=None, *, layout="bin_major", dtype=None, device=None, info=False, **kw):
+    """solve_activations_semi on the signed source side (A, X) followed by synthesize with the parallel target dictionary B
+    (non-negative spectra, or signed) on the same activations: returns (Y, H), with info=True (Y, H, info).  Keywords as for
+    solve_activations_semi."""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    _, N = _semi_shapes(A, X, lay)
+    bshape = tuple(getattr(B, "shape", ()))
+    if len(bshape) != 2 or bshape[1 if lay == _lib.BIN_MAJOR else 0] != N:
+        raise ValueError(f"A and B disagree on the number of exemplars: {N} vs shape {bshape}")
+    tdtype, _ = _pick_dtype(dtype, X, A)
+    device = require_device(device)
+    x_np = not isinstance(X, torch.Tensor)
+    X_d, _ = _to_dev(X, tdtype, device)
+    out = solve_activations_semi(A, X_d, H0, layout=layout, dtype=tdtype, device=device, info=info, **kw)
+    H_d, inf = out if info else (out, None)
+    Y_d = synthesize(B, H_d, layout=layout, dtype=tdtype, device=device)
+    Y, H = (_to_host(Y_d), _to_host(H_d)) if x_np else (Y_d, H_d)
+    return (Y, H, inf) if info else (Y, H)
+
+
 def transform_online(W, X, *, beta=2.0, layout, max_iter=200, tol=1e-4, l1=0.0, l2=0.0, H0=None, init=None,
                      utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False, init_value=0.0,
                      out=None, loop_events=None):

@@ -61,6 +61,9 @@
  *                   X ~ sum_tau W_tau shift_tau(H) by multiplicative updates; with one tap it is scikit-learn's
  *                   _fit_multiplicative_update with update_H=True, as evc_nmf_learn.  evc_deconv_learn_workspace_bytes
  *                   and evc_deconv_learn_splits size and describe it
+ *   evc_semi_solve  replaces pymf's SNMF(data, num_bases).factorize(compute_w=False) (pymf/snmf.py:66-85,
+ *                   pymf/base.py:208-270): semi-NMF activations, signed data and dictionary, non-negative activations -
+ *                   the solve for the signed mel-cepstra of the dictionary build; evc_semi_workspace_bytes sizes it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -1037,6 +1040,57 @@ int evc_deconv_learn_splits(int M, int R, int T, int n_utt, int taps);
 int evc_deconv_learn(const void* X, int ldx, void* W, int ldw, long tap_stride, void* H, int ldh, int M, int R, int T,
                      const int* utt_offsets, int n_utt, const evc_deconv_learn_opts* opts, void* workspace,
                      size_t workspace_bytes, int* n_iter_out, double* err_out, evc_stream_t stream);
+
+/* Semi-NMF activations with the dictionary fixed (Ding, Li and Jordan 2010; pymf snmf.py:66-85 with compute_w=False): X (M x T)
+ * and A (M x N) are SIGNED, only H (N x T, a non-negative start) is constrained.  With pos(m) = (|m| + m) / 2 and
+ * neg(m) = (|m| - m) / 2, formed as written (absolute value, add, halve; a NaN propagates), per iteration:
+ *     P  = A^T X (N x T);   G = A^T A (N x N)          - both fixed while A is: formed once per call
+ *     H1 = pos(P) + neg(G) H;   H2 = (neg(P) + pos(G) H) + eps
+ *     H  <- H * sqrt(H1 / H2)
+ * neg(G) H and pos(G) H are two sums of non-negative products of their own (never (|G| H -+ G H) / 2): H1 stays >= 0, exact
+ * zeros stay exact, H1 == 0 gives H = 0, which is absorbing.  eps = 0 is accepted and may give 0 / 0 = NaN, as in pymf.
+ * The error of utterance u (T_u frames), at the start and after every `check_every` iterations, is ||X_u - A H_u||_F.
+ * EVC_STOP_PYMF stops an utterance at check c >= 3 when |err_c - err_(c-1)| / T_u < tol (pymf: check_every = 1,
+ * tol = 2.22e-16: base.py:189-206, 266-270); its frames are frozen while the others go on.
+ * One kernel launch per iteration (k_semi_sweep): a workgroup owns 128 exemplar rows x 64 frames (64 rows where that
+ * would leave compute units empty: decided from N and T alone, and no output's bits depend on it), streams G and H over all
+ * of N in ascending order through LDS, splits every fragment of G into pos and neg in registers and feeds two accumulators
+ * per output on the matrix cores; the update is its epilogue.  H' goes to a second buffer and the two swap; whatever the
+ * parity of `iters`, the result ends in H with the caller's strides and nothing outside H's N x T elements is written.
+ * The order of every sum depends on N only: no split over k, no float atomics, no exchange between workgroups, no
+ * residency assumption.  The same call gives the same bits; a batch gives bitwise the activations, counts and errors of one
+ * call per utterance; a NaN or infinity in a frame of X stays in that frame's column (a NaN in A reaches every activation).
+ * float32 inputs are solved in float32; the errors are summed in float64, per utterance in a fixed order.
+ *   M      : 1 .. 1056 bins, N : 1 .. 16384 exemplars (larger: -3); T >= 0 (an utterance may be empty: nothing is done for
+ *            it, its n_iter is `iters` and its errors stay NaN);  iters = 0 leaves the start in H
+ *   init_mode : EVC_INIT_GIVEN (H holds the start) | EVC_INIT_CONST (every activation starts at init_value)
+ *   layout, leading dimensions, utt_offsets, n_utt, n_iter_out, err_out : as for evc_beta_solve (at most 4097 error slots per
+ *            utterance; more: -1)
+ * The workspace holds G (round_up(N, 128)^2 elements: 2 GiB at N = 16384 in float64), P, the second H, A H at a check, the
+ * stop state and the error trace: ask evc_semi_workspace_bytes.
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: as evc_beta_solve, case (8) of the list at
+ * the top: n_iter_out / err_out non-NULL (the call returns after copying them back); otherwise the call is a pure enqueue,
+ * the stop is decided on the device; concurrent calls on several streams are safe. */
+typedef struct evc_semi_opts {
+    int struct_bytes;  /* sizeof(evc_semi_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int iters;         /* maximum number of updates (>= 0) */
+    int init_mode;     /* EVC_INIT_GIVEN | EVC_INIT_CONST */
+    int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
+    int stop_rule;     /* EVC_STOP_NONE | EVC_STOP_PYMF */
+    int reserved;      /* 0 */
+    double eps;        /* >= 0, added to H2 (pymf: 1e-9) */
+    double tol;        /* >= 0: threshold of stop_rule */
+    double init_value; /* EVC_INIT_CONST */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_semi_opts;
+/* bytes of workspace evc_semi_solve needs (0: invalid or unsupported arguments, M > 1056 and N > 16384 among them) */
+size_t evc_semi_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
+int evc_semi_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
+                   const int* utt_offsets, int n_utt, const evc_semi_opts* opts, void* workspace, size_t workspace_bytes,
+                   int* n_iter_out, double* err_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
