@@ -6,5 +6,6 @@
   griffin_lim - `zz_audio_utilities.reconstruct_signal_griffin_lim` (the STFT back end)
   make_dict  - `_dtw_alignment` / `dtw_alignment` / `align_sp_ap_f0` (dictionary construction)
   minibatch  - scikit-learn's `MiniBatchNMF` estimator (fit_transform, transform, partial_fit; init='custom')
+  decomp     - deComP's `lasso.solve` / `nnls.solve` (ista, fista, ista_pos, fista_pos: sparse activations with exact zeros)
 """
-from . import factorize, griffin_lim, make_dict, minibatch, nmf_tool, pymf  # noqa: F401
+from . import decomp, factorize, griffin_lim, make_dict, minibatch, nmf_tool, pymf  # noqa: F401

@@ -1,0 +1,76 @@
+"""Drop-in mirror of deComP's `lasso.solve` and `nnls.solve` (decomp/lasso.py, decomp/nnls.py) on the GPU.
+
+    from exemplars_vc_amd.compat.decomp import lasso, nnls      # instead of: from decomp import lasso, nnls
+    it, x = lasso.solve(y, A, alpha, tol=1e-3, method='fista', maxiter=1000)
+    it, x = nnls.solve(y, A, alpha, method='fista')             # lasso.solve with method + '_pos'
+
+deComP's orientation: y is [..., n_channels], A is [n_features, n_channels] (exemplars as rows), x is [..., n_features];
+leading dimensions of y are flattened to frames.  It minimises 1 / (2 n_channels) ||y - x A||^2 + alpha |x| per frame in the
+scaling that gives every exemplar unit norm, with the step of the Gershgorin bound, checks max(|dx| - tol_n) < 0 over the
+whole call every 10th iteration, and returns (it, x): the index of the last iteration and the activations.  The methods
+`ista`, `fista`, `ista_pos` and `fista_pos` are one native call each (evc_prox_solve).
+
+Not mirrored, NotImplementedError: `mask`, complex input, `cd`, `parallel_cd`, `admm` - and `acc_ista`, which at an exhausted
+`maxiter` returns the iterate before the last (lasso.py:357); its schedule is offered natively,
+solve_activations_prox(momentum="nesterov"), where the last iterate is returned.
+"""
+from __future__ import annotations
+
+import types
+
+import numpy as np
+
+from ..solver import solve_activations_prox
+
+AVAILABLE_METHODS = ['ista', 'cd', 'acc_ista', 'fista', 'parallel_cd', 'admm']
+AVAILABLE_NNLS_METHODS = ['ista_pos', 'cd_pos', 'acc_ista_pos', 'fista_pos', 'parallel_cd_pos', 'admm_pos']
+_NATIVE = {"ista": "ista", "fista": "fista"}
+
+
+def _lasso_solve(y, A, alpha, x=None, tol=1.0e-3, method='ista', maxiter=1000, mask=None, device=None, **kwargs):
+    """deComP's lasso.solve -> (it, x).  `device`: the GPU to run on (default: the current one)."""
+    if mask is not None:
+        raise NotImplementedError("compat.decomp: missing data (`mask`) is not mirrored")
+    if kwargs:
+        raise NotImplementedError("compat.decomp: unknown options %s" % sorted(kwargs))
+    if method not in AVAILABLE_METHODS + AVAILABLE_NNLS_METHODS:
+        raise ValueError('Available methods are {0:s}. Given {1:s}'.format(str(AVAILABLE_METHODS), method))
+    positive = method.endswith("_pos")
+    base = method[:-4] if positive else method
+    if base not in _NATIVE:
+        raise NotImplementedError("compat.decomp: method '%s' is not mirrored (ista, fista, ista_pos, fista_pos are)" % method)
+    y, A = np.asarray(y), np.asarray(A)
+    if y.dtype.kind == 'c' or A.dtype.kind == 'c' or (x is not None and np.asarray(x).dtype.kind == 'c'):
+        raise NotImplementedError("compat.decomp: complex input is not mirrored")
+    if A.ndim != 2:
+        raise ValueError("A must be 2-D [n_features, n_channels], got shape %s" % (A.shape,))
+    if y.ndim < 1 or y.shape[-1] != A.shape[1]:
+        raise ValueError("y %s and A %s disagree on the number of channels" % (y.shape, A.shape))
+    dtype = np.float32 if y.dtype == np.float32 else np.float64
+    lead, N = y.shape[:-1], A.shape[0]
+    frames = y.reshape(-1, y.shape[-1])
+    x0 = None
+    if x is not None:
+        x = np.asarray(x)
+        if x.shape != lead + (N,):
+            raise ValueError("x has shape %s, expected %s" % (x.shape, lead + (N,)))
+        x0 = np.ascontiguousarray(x.reshape(-1, N), dtype=dtype)
+    maxiter = int(maxiter)
+    if maxiter <= 0:                             # no update: deComP returns the start, scaled and unscaled
+        return maxiter - 1, (np.zeros(lead + (N,), dtype=dtype) if x0 is None else x0.reshape(lead + (N,)).copy())
+    H, info = solve_activations_prox(np.ascontiguousarray(A, dtype=dtype), np.ascontiguousarray(frames, dtype=dtype), x0,
+                                     alpha=float(alpha), positive=positive, momentum=_NATIVE[base], normalize=True,
+                                     iters=maxiter, tol=float(tol), check_every=10, stop_rule="decomp", layout="frame_major",
+                                     dtype="f64" if dtype == np.float64 else "f32", device=device, info=True)
+    return int(info["n_iter"][0]) - 1, np.asarray(H).reshape(lead + (N,))
+
+
+def _nnls_solve(y, A, alpha, x=None, tol=1.0e-3, method='ista_pos', maxiter=1000, mask=None, **kwargs):
+    """deComP's nnls.solve: lasso.solve with method + '_pos' (its own default, 'ista_pos', therefore names no method: pass
+    method='ista' or 'fista')"""
+    return _lasso_solve(y, A, alpha, x, tol, method + '_pos', maxiter, mask, **kwargs)
+
+
+lasso = types.SimpleNamespace(solve=_lasso_solve, AVAILABLE_METHODS=AVAILABLE_METHODS,
+                              AVAILABLE_NNLS_METHODS=AVAILABLE_NNLS_METHODS)
+nnls = types.SimpleNamespace(solve=_nnls_solve)

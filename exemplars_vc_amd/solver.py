@@ -29,6 +29,8 @@ _ALGOS = {"gram": _lib.ALGO_GRAM, "factored": _lib.ALGO_FACTORED, "literal": _li
           "auto": _lib.ALGO_AUTO}
 _INITS = {"given": _lib.INIT_GIVEN, "sklearn": _lib.INIT_SKLEARN, "const": _lib.INIT_CONST}
 _STOPS = {"none": _lib.STOP_NONE, "sklearn": _lib.STOP_SKLEARN, "pymf": _lib.STOP_PYMF}
+_PROX_STOPS = {"none": _lib.STOP_NONE, "decomp": _lib.STOP_DECOMP}      # evc_prox_solve's own: no other entry takes "decomp"
+_PROX_MOMENTA = {"ista": _lib.PROX_ISTA, "fista": _lib.PROX_FISTA, "nesterov": _lib.PROX_NESTEROV}
 _LAYOUTS = {"frame_major": _lib.FRAME_MAJOR, "bin_major": _lib.BIN_MAJOR}
 _LOSSES = {"frobenius": _lib.LOSS_FROBENIUS, "kullback-leibler": _lib.LOSS_KL, "kl": _lib.LOSS_KL}
 
@@ -533,7 +535,7 @@ def solve_activations_beta(A, X, H0=None, *, beta, layout="bin_major", iters=100
                         kernel="k_beta_sweep", launches=iters + 2 * n_slots * (check_every > 0) if T > 0 else 0)
 
 
-def _semi_shapes(A, X, lay):
+def _semi_shapes(A, X, lay, what="semi-NMF"):
     """the sizes (M, N) of a semi-NMF call from the operands' shapes alone, checked against each other and against the
     kernel's limits - before the device is asked for"""
     ashape, xshape = tuple(getattr(A, "shape", ())), tuple(getattr(X, "shape", ()))
@@ -544,9 +546,9 @@ def _semi_shapes(A, X, lay):
     if M2 != M:
         raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
     if M < 1 or N < 1:
-        raise ValueError(f"empty semi-NMF problem M={M}, N={N}")
+        raise ValueError(f"empty {what} problem M={M}, N={N}")
     if M > _lib.SEMI_MAX_M or N > _lib.SEMI_MAX_N:           # what the ABI answers with -3
-        raise ValueError(f"unsupported semi-NMF shape: M = {M} bins, N = {N} exemplars; the kernel holds at most "
+        raise ValueError(f"unsupported {what} shape: M = {M} bins, N = {N} exemplars; the kernel holds at most "
                          f"{_lib.SEMI_MAX_M} bins and {_lib.SEMI_MAX_N} exemplars")
     return M, N
 
@@ -605,6 +607,78 @@ def convert_semi(A, B, X, H0=None, *, layout="bin_major", dtype=None, device=Non
     x_np = not isinstance(X, torch.Tensor)
     X_d, _ = _to_dev(X, tdtype, device)
     out = solve_activations_semi(A, X_d, H0, layout=layout, dtype=tdtype, device=device, info=info, **kw)
+    H_d, inf = out if info else (out, None)
+    Y_d = synthesize(B, H_d, layout=layout, dtype=tdtype, device=device)
+    Y, H = (_to_host(Y_d), _to_host(H_d)) if x_np else (Y_d, H_d)
+    return (Y, H, inf) if info else (Y, H)
+
+
+def _prox_slots(iters, check_every):
+    """the statistic slots of evc_prox_solve: one per check, at iterations 0, check_every, 2 check_every, ... < iters"""
+    return (int(iters) - 1) // int(check_every) + 1 if (check_every > 0 and iters > 0) else 0
+
+
+def solve_activations_prox(A, X, H0=None, *, alpha, positive=True, momentum="fista", normalize=True, iters=1000, tol=1e-3,
+                           check_every=10, stop_rule="decomp", lipschitz=None, layout="bin_major",
+                           utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False, loop_events=None):
+    """Sparse activations by proximal gradient (deComP's lasso.solve / nnls.solve: ISTA, FISTA), on the GPU (evc_prox_solve):
+    min_h 1/2 ||x - A h||^2 + sum_n lambda_n h_n per frame, h >= 0 (positive=True) or signed; A and X may be signed.
+    Activations the threshold cuts are exactly 0.  momentum: "ista", "fista" or "nesterov" (c_i = i / (i + 3)).
+    normalize=True solves in deComP's scaling (unit-norm exemplars, lambda_n = alpha M / ||a_n||, tol_n = tol ||a_n||);
+    False solves the problem as given (lambda_n = alpha).  The step is 1 / L with L the Gershgorin bound of A^T A, or
+    `lipschitz`.  H0 None starts at 0.  stop_rule "decomp": per utterance, at iterations 0, check_every, ... stop when
+    max(|H_new - H_old| - tol_n) < 0.  At most 1056 bins and 16384 exemplars.
+
+    Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out);
+    with info=True also dict(n_iter=int array per utterance: the updates applied, change=[n_utt, slots] array of the stop
+    statistic at every check (NaN where not evaluated), kernel="k_prox_sweep", launches=int).  No CPU fallback: without a
+    HIP device this raises RuntimeError."""
+    lay = _LAYOUTS[layout]
+    if stop_rule not in _PROX_STOPS:
+        raise ValueError("stop_rule must be 'none' or 'decomp'")
+    if momentum not in _PROX_MOMENTA:
+        raise ValueError("momentum must be 'ista', 'fista' or 'nesterov'")
+    alpha, tol, lipschitz = float(alpha), float(tol), 0.0 if lipschitz is None else float(lipschitz)
+    if not (alpha >= 0.0 and np.isfinite(alpha)) or not (tol >= 0.0 and np.isfinite(tol)):
+        raise ValueError("alpha and tol must be finite and >= 0")
+    if not (lipschitz >= 0.0 and np.isfinite(lipschitz)):
+        raise ValueError("lipschitz must be finite and > 0, or None")
+    iters, check_every = int(iters), int(check_every)
+    n_slots = _prox_slots(iters, check_every)
+    if iters < 0 or check_every < 0 or n_slots > _lib.PROX_MAX_SLOTS:
+        raise ValueError(f"iters and check_every must be >= 0 with at most {_lib.PROX_MAX_SLOTS} checks")
+    _semi_shapes(A, X, lay, "proximal-gradient")
+    _pick_dtype(dtype, X, A)
+    device = require_device(device)
+    L = _lib.lib()
+    p = _operands(A, X, H0, "given" if H0 is not None else "const", layout, dtype, device, utt_offsets)
+    opts = _lib.ProxOpts()
+    opts.iters, opts.init_mode = iters, _INITS[p.init]
+    opts.mode = _lib.PROX_POSITIVE if positive else _lib.PROX_SIGNED
+    opts.momentum, opts.normalize = _PROX_MOMENTA[momentum], 1 if normalize else 0
+    opts.check_every, opts.stop_rule = check_every, _PROX_STOPS[stop_rule]
+    opts.alpha, opts.tol, opts.init_value, opts.lipschitz = alpha, tol, 0.0, lipschitz
+    _common_opts(opts, p.dcode, lay, loop_events)
+    ws_bytes = int(L.evc_prox_workspace_bytes(p.M, p.N, p.T, p.n_utt, p.dcode))
+    live = p.T > 0 and iters > 0
+    return _solve_fixed(L, "evc_prox_solve", device, p, (p.A_d.data_ptr(), _ld(p.A_d)), opts, ws_bytes, ("change", n_slots),
+                        info, kernel="k_prox_sweep", launches=iters + n_slots if live else 0)
+
+
+def convert_prox(A, B, X, H0=None, *, layout="bin_major", dtype=None, device=None, info=False, **kw):
+    """solve_activations_prox on the source side (A, X) followed by synthesize with the parallel target dictionary B on the
+    same activations: returns (Y, H), with info=True (Y, H, info).  Keywords as for solve_activations_prox."""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    _, N = _semi_shapes(A, X, lay, "proximal-gradient")
+    bshape = tuple(getattr(B, "shape", ()))
+    if len(bshape) != 2 or bshape[1 if lay == _lib.BIN_MAJOR else 0] != N:
+        raise ValueError(f"A and B disagree on the number of exemplars: {N} vs shape {bshape}")
+    tdtype, _ = _pick_dtype(dtype, X, A)
+    device = require_device(device)
+    x_np = not isinstance(X, torch.Tensor)
+    X_d, _ = _to_dev(X, tdtype, device)
+    out = solve_activations_prox(A, X_d, H0, layout=layout, dtype=tdtype, device=device, info=info, **kw)
     H_d, inf = out if info else (out, None)
     Y_d = synthesize(B, H_d, layout=layout, dtype=tdtype, device=device)
     Y, H = (_to_host(Y_d), _to_host(H_d)) if x_np else (Y_d, H_d)

@@ -64,6 +64,9 @@
  *   evc_semi_solve  replaces pymf's SNMF(data, num_bases).factorize(compute_w=False) (pymf/snmf.py:66-85,
  *                   pymf/base.py:208-270): semi-NMF activations, signed data and dictionary, non-negative activations -
  *                   the solve for the signed mel-cepstra of the dictionary build; evc_semi_workspace_bytes sizes it
+ *   evc_prox_solve  replaces deComP's lasso.solve / nnls.solve with method ista, fista, ista_pos, fista_pos
+ *                   (decomp/lasso.py:97-189, 274-297, 388-415): L1-penalised activations by proximal gradient, signed or
+ *                   non-negative, with exact zeros; evc_prox_workspace_bytes sizes it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -196,8 +199,11 @@ enum { EVC_INIT_GIVEN = 0, EVC_INIT_SKLEARN = 1, EVC_INIT_CONST = 2 };
  *   NONE     errors are recorded (if check_every > 0) but never stop the loop
  *   SKLEARN  stop when (err_prev - err) / err_at_init < tol       (_nmf.py:871-884)
  *   PYMF     from the third recorded error on, stop when |err - err_prev| / T_u < tol
- *            (pymf/base.py:189-206,266-270)                                               */
-enum { EVC_STOP_NONE = 0, EVC_STOP_SKLEARN = 1, EVC_STOP_PYMF = 2 };
+ *            (pymf/base.py:189-206,266-270)
+ *   DECOMP   evc_prox_solve only, on the change of the activations instead of the error: at iterations
+ *            i = 0, check_every, 2 check_every, ... stop when max(|X_new - X_old| - tol_n) < 0 over the
+ *            utterance's frames and all exemplars (deComP lasso.py:293, check_every = 10)     */
+enum { EVC_STOP_NONE = 0, EVC_STOP_SKLEARN = 1, EVC_STOP_PYMF = 2, EVC_STOP_DECOMP = 3 };
 
 /* divergence minimised by the multiplicative update
  *   FROBENIUS  H <- H (.) A^T X (/) (A^T A H)                       (what the scripts force, :210)
@@ -1091,6 +1097,73 @@ size_t evc_semi_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
 int evc_semi_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
                    const int* utt_offsets, int n_utt, const evc_semi_opts* opts, void* workspace, size_t workspace_bytes,
                    int* n_iter_out, double* err_out, evc_stream_t stream);
+
+/* Sparse activations by proximal gradient (ISTA / FISTA; deComP lasso.py:97-189, 228-256, 274-297, 331-357, 388-415 and
+ * math_utils/eigen.py:9-20):   min_h  1/2 ||x - A h||^2 + sum_n lambda_n h_n,   h >= 0 (EVC_PROX_POSITIVE) or h signed
+ * (EVC_PROX_SIGNED), every frame on its own.  X (M x T) and A (M x N) may be signed.  Once per call, on the device:
+ *     G = A^T A (N x N);   P = A^T X (N x T)
+ *     normalize != 0 (deComP):  d_n = sqrt(G_nn);  G <- G / (d d^T);  P_n <- P_n / d_n;  lambda_n = alpha M / d_n;
+ *                               tol_n = tol d_n;  the start is multiplied by d_n and the result divided by it at the end
+ *     normalize == 0:           the problem as given: lambda_n = alpha, tol_n = tol, d = 1
+ *     L = max_n sum_k |G_kn| (Gershgorin; a device reduction in a fixed order), or `lipschitz` when that is > 0;
+ *     s = 1 / L;  thr_n = s lambda_n
+ * Per iteration i = 0, 1, ..., with W_0 = X_0 (the start):
+ *     V     = W + s (P - G W)
+ *     X_new = max(V - thr, 0)                      (EVC_PROX_POSITIVE)
+ *           = sign(V) max(|V| - thr, 0)            (EVC_PROX_SIGNED)
+ *     W'    = X_new + c_i (X_new - X_old)
+ * c_i = 0 (EVC_PROX_ISTA);  (beta_i - 1) / beta_(i+1) with beta_(i+1) = (1 + sqrt(1 + 4 beta_i^2)) / 2, beta_0 = 1
+ * (EVC_PROX_FISTA);  i / (i + 3) (EVC_PROX_NESTEROV, deComP's acc_ista) - computed on the host in double precision.
+ * A NaN propagates through the thresholds as numpy's maximum does.  Activations that the threshold cuts are exactly 0.
+ * At iterations with i % check_every == 0 the statistic max(|X_new - X_old| - tol_n) over the utterance's frames and all n
+ * is recorded in change_out; under EVC_STOP_DECOMP the utterance stops when it is < 0 (a NaN compares false: it runs on).
+ * The result of a stopped utterance is X_new of that iteration; its frames are frozen while the others run on, and its
+ * n_iter is i + 1, the updates applied (deComP returns i).  deComP takes the maximum over the whole call: ours equals one
+ * deComP call per utterance.
+ * One kernel launch per iteration (k_prox_sweep): a workgroup owns 128 exemplar rows x 64 frames (64 rows where that
+ * would leave compute units empty: decided from N and T alone, and no output's bits depend on it), streams G and W over
+ * all of N in ascending order through LDS into one accumulator per output on the matrix cores; the threshold, the momentum
+ * and the per-frame share of the stop statistic are its epilogue.  X is updated in place in H with the caller's strides, W
+ * alternates between two workspace buffers.  No split over k, no float atomics, no exchange between workgroups, no
+ * residency assumption: the same call gives the same bits; a batch gives bitwise the activations, counts and statistics of
+ * one call per utterance; a NaN or infinity in a frame of X stays in that frame's column (a NaN in A reaches every
+ * activation).  float32 inputs are solved in float32.
+ *   M      : 1 .. 1056 bins, N : 1 .. 16384 exemplars (larger: -3); T >= 0 (an empty utterance: nothing is done for it, its
+ *            n_iter is `iters`);  iters = 0 leaves the start in H (EVC_INIT_CONST: init_value), neither scaled nor unscaled
+ *   init_mode : EVC_INIT_GIVEN (H holds the start) | EVC_INIT_CONST (every activation starts at init_value; deComP: 0)
+ *   layout, leading dimensions, utt_offsets, n_utt, n_iter_out : as for evc_semi_solve
+ *   change_out : NULL or [n_utt][slots] doubles, slots = (iters - 1) / check_every + 1 (0 when iters or check_every is 0;
+ *            at most 4097, more: -1): the statistic of every check that was evaluated, NaN elsewhere
+ * The workspace holds G (round_up(N, 128)^2 elements), P, the two W buffers, the per-exemplar vectors, the per-frame shares
+ * of the statistic and the stop state: ask evc_prox_workspace_bytes.
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: as evc_semi_solve. */
+enum { EVC_PROX_POSITIVE = 0, EVC_PROX_SIGNED = 1 };
+enum { EVC_PROX_ISTA = 0, EVC_PROX_FISTA = 1, EVC_PROX_NESTEROV = 2 };
+typedef struct evc_prox_opts {
+    int struct_bytes;  /* sizeof(evc_prox_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int iters;         /* maximum number of updates (>= 0; deComP: maxiter) */
+    int mode;          /* EVC_PROX_POSITIVE | EVC_PROX_SIGNED */
+    int momentum;      /* EVC_PROX_ISTA | EVC_PROX_FISTA | EVC_PROX_NESTEROV */
+    int normalize;     /* 0 | 1: solve in deComP's unit-norm scaling of the exemplars */
+    int check_every;   /* 0: the change is never evaluated; k > 0: at iterations 0, k, 2k, ... (deComP: 10) */
+    int stop_rule;     /* EVC_STOP_NONE | EVC_STOP_DECOMP */
+    int init_mode;     /* EVC_INIT_GIVEN | EVC_INIT_CONST */
+    int reserved;      /* 0 */
+    int reserved2;     /* 0 */
+    double alpha;      /* >= 0: the penalty (normalize: per bin, as deComP's 1 / (2 M) scaling of the squared error) */
+    double tol;        /* >= 0: threshold of stop_rule */
+    double init_value; /* EVC_INIT_CONST */
+    double lipschitz;  /* > 0: used as L instead of the Gershgorin bound; 0: the bound */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_prox_opts;
+/* bytes of workspace evc_prox_solve needs (0: invalid or unsupported arguments, M > 1056 and N > 16384 among them) */
+size_t evc_prox_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
+int evc_prox_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
+                   const int* utt_offsets, int n_utt, const evc_prox_opts* opts, void* workspace, size_t workspace_bytes,
+                   int* n_iter_out, double* change_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
