@@ -20,6 +20,7 @@ INIT_GIVEN, INIT_SKLEARN, INIT_CONST = 0, 1, 2
 STOP_NONE, STOP_SKLEARN, STOP_PYMF, STOP_DECOMP = 0, 1, 2, 3
 PROX_POSITIVE, PROX_SIGNED = 0, 1
 PROX_ISTA, PROX_FISTA, PROX_NESTEROV = 0, 1, 2
+PROX_LIP_MEAN, PROX_LIP_MAX = 0, 1
 LOSS_FROBENIUS, LOSS_KL = 0, 1
 FLAG_NO_FUSED, FLAG_EXACT_DIV, FLAG_NO_EXCHANGE, FLAG_NO_ALL_RESIDENT, FLAG_PAIR_TILES, FLAG_NO_LONE_BIN = 1, 2, 4, 16, 32, 64
 LEARN_SKLEARN, LEARN_PYMF = 0, 1
@@ -43,7 +44,8 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_deconv_workspace_bytes", "evc_deconv_solve", "evc_deconv_synthesize",
            "evc_deconv_learn_workspace_bytes", "evc_deconv_learn_splits", "evc_deconv_learn",
            "evc_semi_workspace_bytes", "evc_semi_solve",
-           "evc_prox_workspace_bytes", "evc_prox_solve")
+           "evc_prox_workspace_bytes", "evc_prox_solve",
+           "evc_prox_masked_workspace_bytes", "evc_prox_masked_solve")
 BETA_MAX_M = 528
 DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 DECONV_LEARN_MAX_R = 4096
@@ -193,6 +195,18 @@ class ProxOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
         ("mode", C.c_int), ("momentum", C.c_int), ("normalize", C.c_int), ("check_every", C.c_int),
         ("stop_rule", C.c_int), ("init_mode", C.c_int), ("reserved", C.c_int), ("reserved2", C.c_int),
+        ("alpha", C.c_double), ("tol", C.c_double), ("init_value", C.c_double), ("lipschitz", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class ProxMaskedOpts(C.Structure):
+    """Mirror of `evc_prox_masked_opts` (include/evc.h): `evc_prox_opts` plus the weights of the Gershgorin bound."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
+        ("mode", C.c_int), ("momentum", C.c_int), ("normalize", C.c_int), ("check_every", C.c_int),
+        ("stop_rule", C.c_int), ("init_mode", C.c_int), ("reserved", C.c_int), ("reserved2", C.c_int),
+        ("lip_weights", C.c_int), ("reserved3", C.c_int),
         ("alpha", C.c_double), ("tol", C.c_double), ("init_value", C.c_double), ("lipschitz", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
@@ -466,6 +480,17 @@ def lib():
         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # A, X, H
         C.c_int, C.c_int, C.c_int,                                          # M, N, T
         C.POINTER(C.c_int), C.c_int, C.POINTER(ProxOpts),                   # utt_offsets, n_utt, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, change_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_prox_masked_workspace_bytes.restype = C.c_size_t
+    L.evc_prox_masked_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_prox_masked_solve.restype = C.c_int
+    L.evc_prox_masked_solve.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # A, X, mask, H
+        C.c_int, C.c_int, C.c_int,                                          # M, N, T
+        C.POINTER(C.c_int), C.c_int, C.POINTER(ProxMaskedOpts),             # utt_offsets, n_utt, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, change_out
         C.c_void_p,                                                         # stream

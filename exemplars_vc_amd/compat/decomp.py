@@ -10,9 +10,14 @@ scaling that gives every exemplar unit norm, with the step of the Gershgorin bou
 whole call every 10th iteration, and returns (it, x): the index of the last iteration and the activations.  The methods
 `ista`, `fista`, `ista_pos` and `fista_pos` are one native call each (evc_prox_solve).
 
-Not mirrored, NotImplementedError: `mask`, complex input, `cd`, `parallel_cd`, `admm` - and `acc_ista`, which at an exhausted
-`maxiter` returns the iterate before the last (lasso.py:357); its schedule is offered natively,
-solve_activations_prox(momentum="nesterov"), where the last iterate is returned.
+`mask` (missing data): a float array of y's shape and dtype kind, >= 0, that weights every bin of every frame; a zero marks a
+missing bin.  It runs natively for the same four methods (evc_prox_masked_solve, the factored sweep), with deComP's step:
+the Gershgorin bound of A diag(mean of the mask over all frames) A^T.  A negative mask is refused with AssertionError and
+a mask that is not float with ValueError (deComP: DtypeMismatchError, a ValueError), where deComP's assertions refuse them.
+
+Not mirrored, NotImplementedError: a 1-D `mask` (weights per bin: multiply y and A by them), complex input, `cd`,
+`parallel_cd`, `admm` - and `acc_ista`, which at an exhausted `maxiter` returns the iterate before the last (lasso.py:357);
+its schedule is offered natively, solve_activations_prox(momentum="nesterov"), where the last iterate is returned.
 """
 from __future__ import annotations
 
@@ -30,7 +35,12 @@ _NATIVE = {"ista": "ista", "fista": "fista"}
 def _lasso_solve(y, A, alpha, x=None, tol=1.0e-3, method='ista', maxiter=1000, mask=None, device=None, **kwargs):
     """deComP's lasso.solve -> (it, x).  `device`: the GPU to run on (default: the current one)."""
     if mask is not None:
-        raise NotImplementedError("compat.decomp: missing data (`mask`) is not mirrored")
+        mask = np.asarray(mask)
+        if mask.dtype.kind != 'f':               # deComP: assert_dtypes(mask=mask, dtypes='f')
+            raise ValueError("compat.decomp: Data type should be one of f, but given %s for mask" % mask.dtype)
+        assert (mask >= 0.0).all()               # deComP: assert_nonnegative(mask)
+        if mask.ndim == 1:
+            raise NotImplementedError("compat.decomp: a 1-D `mask` (weights per bin) is not mirrored: multiply y and A by it")
     if kwargs:
         raise NotImplementedError("compat.decomp: unknown options %s" % sorted(kwargs))
     if method not in AVAILABLE_METHODS + AVAILABLE_NNLS_METHODS:
@@ -49,6 +59,10 @@ def _lasso_solve(y, A, alpha, x=None, tol=1.0e-3, method='ista', maxiter=1000, m
     dtype = np.float32 if y.dtype == np.float32 else np.float64
     lead, N = y.shape[:-1], A.shape[0]
     frames = y.reshape(-1, y.shape[-1])
+    if mask is not None:
+        if mask.shape != y.shape:
+            raise ValueError("mask has shape %s, expected y's shape %s" % (mask.shape, y.shape))
+        mask = np.ascontiguousarray(mask.reshape(frames.shape), dtype=dtype)
     x0 = None
     if x is not None:
         x = np.asarray(x)
@@ -61,7 +75,8 @@ def _lasso_solve(y, A, alpha, x=None, tol=1.0e-3, method='ista', maxiter=1000, m
     H, info = solve_activations_prox(np.ascontiguousarray(A, dtype=dtype), np.ascontiguousarray(frames, dtype=dtype), x0,
                                      alpha=float(alpha), positive=positive, momentum=_NATIVE[base], normalize=True,
                                      iters=maxiter, tol=float(tol), check_every=10, stop_rule="decomp", layout="frame_major",
-                                     dtype="f64" if dtype == np.float64 else "f32", device=device, info=True)
+                                     dtype="f64" if dtype == np.float64 else "f32", device=device, info=True,
+                                     **({} if mask is None else dict(mask=mask, lip_weights="mean")))
     return int(info["n_iter"][0]) - 1, np.asarray(H).reshape(lead + (N,))
 
 

@@ -454,15 +454,16 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
     return res[0] if len(res) == 1 else tuple(res)
 
 
-def _solve_fixed(L, entry, device, p, dict_args, opts, ws_bytes, trace, info, **extra):
+def _solve_fixed(L, entry, device, p, dict_args, opts, ws_bytes, trace, info, mid=(), **extra):
     """The call and the return rule of the solves with the dictionary fixed (cd, beta, transform, deconv), after the wrapper
     has validated, staged the operands `p` (_operands) and filled `opts`.  dict_args: the dictionary as the entry takes it
     (pointer, leading dimension - and the tap stride where it has taps); trace = (name, width) of the per-utterance float64
-    array the entry fills when info is asked for; extra: the wrapper's own info fields.  Returns the activations like X came
+    array the entry fills when info is asked for; mid: what the entry takes between X and H (evc_prox_masked_solve: the mask
+    and its leading dimension); extra: the wrapper's own info fields.  Returns the activations like X came
     (numpy or device tensor), with info=True also dict(n_iter, <name>, **extra).  Without info both outputs are NULL and the
     call stays asynchronous."""
     n_iter, tr, ni_p, tr_p = _trace_arrays(p.n_utt, trace[1], info)
-    _call(L, entry, device, (*dict_args, p.X_d.data_ptr(), _ld(p.X_d), p.H_d.data_ptr(), _ld(p.H_d), p.M, p.N, p.T, p.off_ptr,
+    _call(L, entry, device, (*dict_args, p.X_d.data_ptr(), _ld(p.X_d), *mid, p.H_d.data_ptr(), _ld(p.H_d), p.M, p.N, p.T, p.off_ptr,
                              p.n_utt, C.byref(opts)), ws_bytes, (ni_p, tr_p))
     H_out = _to_host(p.H_d) if p.x_np else p.H_d
     if info:
@@ -618,9 +619,28 @@ def _prox_slots(iters, check_every):
     return (int(iters) - 1) // int(check_every) + 1 if (check_every > 0 and iters > 0) else 0
 
 
+_PROX_LIPS = {"mean": _lib.PROX_LIP_MEAN, "max": _lib.PROX_LIP_MAX}
+
+
+def _prox_mask_ok(mask, X):
+    """the mask of solve_activations_prox against X: same shape, finite, >= 0 - a numpy mask before any device is touched"""
+    torch = _torch()
+    mshape, xshape = tuple(getattr(mask, "shape", ())), tuple(getattr(X, "shape", ()))
+    if mshape != xshape:
+        raise ValueError(f"mask has shape {mshape}, expected X's shape {xshape}")
+    if isinstance(mask, torch.Tensor):
+        ok = mask.dtype.is_floating_point and bool(torch.isfinite(mask).all()) and bool((mask >= 0).all())
+    else:
+        m = np.asarray(mask)
+        ok = m.dtype.kind in "fiub" and bool(np.isfinite(m).all()) and bool((m >= 0).all())
+    if not ok:
+        raise ValueError("mask must hold finite weights >= 0")
+
+
 def solve_activations_prox(A, X, H0=None, *, alpha, positive=True, momentum="fista", normalize=True, iters=1000, tol=1e-3,
                            check_every=10, stop_rule="decomp", lipschitz=None, layout="bin_major",
-                           utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False, loop_events=None):
+                           utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False, loop_events=None,
+                           mask=None, factored=False, lip_weights="max"):
     """Sparse activations by proximal gradient (deComP's lasso.solve / nnls.solve: ISTA, FISTA), on the GPU (evc_prox_solve):
     min_h 1/2 ||x - A h||^2 + sum_n lambda_n h_n per frame, h >= 0 (positive=True) or signed; A and X may be signed.
     Activations the threshold cuts are exactly 0.  momentum: "ista", "fista" or "nesterov" (c_i = i / (i + 3)).
@@ -629,10 +649,19 @@ def solve_activations_prox(A, X, H0=None, *, alpha, positive=True, momentum="fis
     `lipschitz`.  H0 None starts at 0.  stop_rule "decomp": per utterance, at iterations 0, check_every, ... stop when
     max(|H_new - H_old| - tol_n) < 0.  At most 1056 bins and 16384 exemplars.
 
+    mask: missing data (deComP's 2-D `mask`): finite weights >= 0 of X's shape, one per bin of every frame, a zero marks a
+    missing bin; the squared error of a frame becomes sum_m mask_m (x_m - (A h)_m)^2 and, with normalize, lambda_n =
+    alpha cnt_t / ||a_n|| with cnt_t the frame's sum of weights.  It runs on the factored sweep (evc_prox_masked_solve), which
+    never forms A^T A: 4 M N flop per frame and iteration instead of 2 N^2.  factored=True runs that sweep without a mask -
+    the same problem in another summation order, for M << N.  lip_weights: the per-bin weights wbar of the bound
+    L_u = Gershgorin(A diag(wbar) A^T) of every utterance: "max" (the largest weight of the bin over the utterance, an upper
+    bound of every frame's curvature) or "mean" (deComP's choice, which is none); `lipschitz` overrides both.  Per-bin (1-D)
+    weights are not offered: multiply A and X by them.  With mask=None and factored=False everything is as before.
+
     Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out);
     with info=True also dict(n_iter=int array per utterance: the updates applied, change=[n_utt, slots] array of the stop
-    statistic at every check (NaN where not evaluated), kernel="k_prox_sweep", launches=int).  No CPU fallback: without a
-    HIP device this raises RuntimeError."""
+    statistic at every check (NaN where not evaluated), kernel="k_prox_sweep" or "k_prox_resid+k_prox_back", launches=int).
+    No CPU fallback: without a HIP device this raises RuntimeError."""
     lay = _LAYOUTS[layout]
     if stop_rule not in _PROX_STOPS:
         raise ValueError("stop_rule must be 'none' or 'decomp'")
@@ -647,20 +676,33 @@ def solve_activations_prox(A, X, H0=None, *, alpha, positive=True, momentum="fis
     n_slots = _prox_slots(iters, check_every)
     if iters < 0 or check_every < 0 or n_slots > _lib.PROX_MAX_SLOTS:
         raise ValueError(f"iters and check_every must be >= 0 with at most {_lib.PROX_MAX_SLOTS} checks")
+    if lip_weights not in _PROX_LIPS:
+        raise ValueError("lip_weights must be 'mean' or 'max'")
     _semi_shapes(A, X, lay, "proximal-gradient")
+    if mask is not None:
+        _prox_mask_ok(mask, X)
+    masked = mask is not None or bool(factored)
     _pick_dtype(dtype, X, A)
     device = require_device(device)
     L = _lib.lib()
     p = _operands(A, X, H0, "given" if H0 is not None else "const", layout, dtype, device, utt_offsets)
-    opts = _lib.ProxOpts()
+    opts = _lib.ProxMaskedOpts() if masked else _lib.ProxOpts()
     opts.iters, opts.init_mode = iters, _INITS[p.init]
     opts.mode = _lib.PROX_POSITIVE if positive else _lib.PROX_SIGNED
     opts.momentum, opts.normalize = _PROX_MOMENTA[momentum], 1 if normalize else 0
     opts.check_every, opts.stop_rule = check_every, _PROX_STOPS[stop_rule]
     opts.alpha, opts.tol, opts.init_value, opts.lipschitz = alpha, tol, 0.0, lipschitz
     _common_opts(opts, p.dcode, lay, loop_events)
-    ws_bytes = int(L.evc_prox_workspace_bytes(p.M, p.N, p.T, p.n_utt, p.dcode))
     live = p.T > 0 and iters > 0
+    if masked:
+        opts.lip_weights = _PROX_LIPS[lip_weights]
+        mask_d = None if mask is None else _to_dev(mask, p.tdtype, device)[0]
+        mid = (None, 0) if mask_d is None else (mask_d.data_ptr(), _ld(mask_d))
+        ws_bytes = int(L.evc_prox_masked_workspace_bytes(p.M, p.N, p.T, p.n_utt, p.dcode))
+        return _solve_fixed(L, "evc_prox_masked_solve", device, p, (p.A_d.data_ptr(), _ld(p.A_d)), opts, ws_bytes,
+                            ("change", n_slots), info, mid=mid, kernel="k_prox_resid+k_prox_back",
+                            launches=2 * iters + n_slots if live else 0)
+    ws_bytes = int(L.evc_prox_workspace_bytes(p.M, p.N, p.T, p.n_utt, p.dcode))
     return _solve_fixed(L, "evc_prox_solve", device, p, (p.A_d.data_ptr(), _ld(p.A_d)), opts, ws_bytes, ("change", n_slots),
                         info, kernel="k_prox_sweep", launches=iters + n_slots if live else 0)
 
@@ -674,6 +716,8 @@ def convert_prox(A, B, X, H0=None, *, layout="bin_major", dtype=None, device=Non
     bshape = tuple(getattr(B, "shape", ()))
     if len(bshape) != 2 or bshape[1 if lay == _lib.BIN_MAJOR else 0] != N:
         raise ValueError(f"A and B disagree on the number of exemplars: {N} vs shape {bshape}")
+    if kw.get("mask") is not None:
+        _prox_mask_ok(kw["mask"], X)
     tdtype, _ = _pick_dtype(dtype, X, A)
     device = require_device(device)
     x_np = not isinstance(X, torch.Tensor)

@@ -67,6 +67,9 @@
  *   evc_prox_solve  replaces deComP's lasso.solve / nnls.solve with method ista, fista, ista_pos, fista_pos
  *                   (decomp/lasso.py:97-189, 274-297, 388-415): L1-penalised activations by proximal gradient, signed or
  *                   non-negative, with exact zeros; evc_prox_workspace_bytes sizes it
+ *   evc_prox_masked_solve  the same solves with deComP's 2-D `mask` (missing data: a weight per bin of every frame,
+ *                   lasso.py:306-328, 418-445) on a factored sweep without the N x N Gram matrix; a NULL mask is the unmasked
+ *                   problem on that sweep, for M << N; evc_prox_masked_workspace_bytes sizes it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -1164,6 +1167,67 @@ size_t evc_prox_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
 int evc_prox_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
                    const int* utt_offsets, int n_utt, const evc_prox_opts* opts, void* workspace, size_t workspace_bytes,
                    int* n_iter_out, double* change_out, evc_stream_t stream);
+
+/* evc_prox_solve with a weight per bin of every frame (missing data; deComP lasso.py:120-189, 259-271, 306-328, 418-445),
+ * on a factored sweep that never forms A^T A:
+ *     min_h  1/2 sum_m mask_m (x_m - (A h)_m)^2 + sum_n lambda_n h_n      per frame, mask >= 0 (a zero: the bin is missing)
+ * `mask` has X's dtype, layout and shape (M x T) with its own leading dimension ldm; NULL means every weight is 1 - the
+ * unmasked problem of evc_prox_solve on the factored sweep, which does 4 M N flop per frame and iteration instead of
+ * 2 N^2.  Once per call, on the device:
+ *     normalize != 0 (deComP):  d_n = sqrt(sum_m A_mn^2) from the UNMASKED A;  A <- A / d;  tol_n = tol d_n;
+ *                               cnt_t = sum_m mask_mt (M without a mask);  lambda_tn = (alpha / d_n) cnt_t;
+ *                               the start is multiplied by d_n and the result divided by it at the end
+ *     normalize == 0:           the problem as given: d = 1, lambda_tn = alpha (no cnt_t), tol_n = tol
+ *     wbar_m = the mean (EVC_PROX_LIP_MEAN, deComP) or the maximum (EVC_PROX_LIP_MAX) of mask_mt over the utterance's frames;
+ *     L_u = max_n sum_k | sum_m A_mk wbar_m A_mn | (Gershgorin), or `lipschitz` when that is > 0;  s_u = 1 / L_u
+ *     P = A^T (mask . X)
+ * The mean is deComP's choice and no upper bound of a single frame's curvature A^T diag(mask_t) A; the maximum is one.
+ * Per iteration i, with W_0 = X_0:
+ *     R = mask . (A W);   V = W + s_u (P - A^T R);   X_new = threshold(V, s_u lambda_tn);   W' = X_new + c_i (X_new - X_old)
+ * Thresholds, momentum schedules, the statistic max(|X_new - X_old| - tol_n) at i % check_every == 0, the freezing of
+ * stopped utterances, n_iter = i + 1 and the NaN rules are evc_prox_solve's.  wbar, s and the statistic are per utterance:
+ * a call equals one deComP call per utterance.  An utterance whose mask is all zero has L = 0 and gets what that arithmetic
+ * gives (NaN), inside that utterance only.  Negative weights are not looked for.
+ * Two launches per iteration on k_prox_sweep's slab loop (16-deep k-slabs double-buffered in LDS, 16x16x4 MFMAs, one
+ * accumulator per output, k ascending over the whole contraction): k_prox_resid contracts over N and stores R (M x T),
+ * k_prox_back contracts over M and carries evc_prox_solve's epilogue.  Every reduction - cnt, wbar, the column sums, their
+ * maximum, the statistic - runs in an order fixed by the sizes and by a frame's position inside its utterance: no float
+ * atomics, no split contractions; a batch gives bitwise the activations, counts and statistics of one call per
+ * utterance, and a NULL mask the bits of a mask of ones.  A NaN in a frame of X stays in that frame's column; a NaN in a
+ * frame of the mask does too when `lipschitz` is given (through wbar it reaches its utterance's step, as in deComP).
+ *   sizes, layouts, leading dimensions, utt_offsets, init_mode, n_iter_out, change_out : as for evc_prox_solve
+ * The workspace holds the scaled dictionary in both orientations (zero-padded), P, the two W buffers, R and mask . X
+ * (M x T each), per utterance the column sums (N) and wbar (M), and the per-frame state: it grows as N (M + T) and holds
+ * nothing N x N.  Ask evc_prox_masked_workspace_bytes.
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: as evc_semi_solve. */
+enum { EVC_PROX_LIP_MEAN = 0, EVC_PROX_LIP_MAX = 1 };
+typedef struct evc_prox_masked_opts {
+    int struct_bytes;  /* sizeof(evc_prox_masked_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int iters;         /* maximum number of updates (>= 0; deComP: maxiter) */
+    int mode;          /* EVC_PROX_POSITIVE | EVC_PROX_SIGNED */
+    int momentum;      /* EVC_PROX_ISTA | EVC_PROX_FISTA | EVC_PROX_NESTEROV */
+    int normalize;     /* 0 | 1: solve in deComP's unit-norm scaling of the exemplars */
+    int check_every;   /* 0: the change is never evaluated; k > 0: at iterations 0, k, 2k, ... (deComP: 10) */
+    int stop_rule;     /* EVC_STOP_NONE | EVC_STOP_DECOMP */
+    int init_mode;     /* EVC_INIT_GIVEN | EVC_INIT_CONST */
+    int reserved;      /* 0 */
+    int reserved2;     /* 0 */
+    int lip_weights;   /* EVC_PROX_LIP_MEAN | EVC_PROX_LIP_MAX: the per-bin weights of the Gershgorin bound */
+    int reserved3;     /* 0 */
+    double alpha;      /* >= 0: the penalty (normalize: per valid bin, as deComP's 1 / (2 cnt_t) scaling of the squared error) */
+    double tol;        /* >= 0: threshold of stop_rule */
+    double init_value; /* EVC_INIT_CONST */
+    double lipschitz;  /* > 0: used as L for every utterance, the bound is not computed; 0: the bound */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_prox_masked_opts;
+/* bytes of workspace evc_prox_masked_solve needs (0: invalid or unsupported arguments, M > 1056 and N > 16384 among them) */
+size_t evc_prox_masked_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
+int evc_prox_masked_solve(const void* A, int lda, const void* X, int ldx, const void* mask, int ldm, void* H, int ldh, int M,
+                          int N, int T, const int* utt_offsets, int n_utt, const evc_prox_masked_opts* opts, void* workspace,
+                          size_t workspace_bytes, int* n_iter_out, double* change_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
