@@ -45,12 +45,14 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_deconv_learn_workspace_bytes", "evc_deconv_learn_splits", "evc_deconv_learn",
            "evc_semi_workspace_bytes", "evc_semi_solve",
            "evc_prox_workspace_bytes", "evc_prox_solve",
-           "evc_prox_masked_workspace_bytes", "evc_prox_masked_solve")
+           "evc_prox_masked_workspace_bytes", "evc_prox_masked_solve",
+           "evc_prox_learn_workspace_bytes", "evc_prox_learn_block", "evc_prox_learn")
 BETA_MAX_M = 528
 DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 DECONV_LEARN_MAX_R = 4096
 SEMI_MAX_M, SEMI_MAX_N = 1056, 16384
 PROX_MAX_M, PROX_MAX_N, PROX_MAX_SLOTS = 1056, 16384, 4097
+PROX_LEARN_MAX_M, PROX_LEARN_MAX_N = 1056, 4096
 MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
 
@@ -208,6 +210,17 @@ class ProxMaskedOpts(C.Structure):
         ("stop_rule", C.c_int), ("init_mode", C.c_int), ("reserved", C.c_int), ("reserved2", C.c_int),
         ("lip_weights", C.c_int), ("reserved3", C.c_int),
         ("alpha", C.c_double), ("tol", C.c_double), ("init_value", C.c_double), ("lipschitz", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class ProxLearnOpts(C.Structure):
+    """Mirror of `evc_prox_learn_opts` (include/evc.h): options of the sparse dictionary learning."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("batch_size", C.c_int),
+        ("epochs", C.c_int), ("lasso_iters", C.c_int), ("lasso_check_every", C.c_int), ("mode", C.c_int),
+        ("momentum", C.c_int), ("resume", C.c_int), ("reserved", C.c_int), ("reserved2", C.c_int),
+        ("alpha", C.c_double), ("tol", C.c_double), ("lasso_tol", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -493,6 +506,19 @@ def lib():
         C.POINTER(C.c_int), C.c_int, C.POINTER(ProxMaskedOpts),             # utt_offsets, n_utt, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, change_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_prox_learn_workspace_bytes.restype = C.c_size_t
+    L.evc_prox_learn_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_prox_learn_block.restype = C.c_int
+    L.evc_prox_learn_block.argtypes = [C.c_int] * 2
+    L.evc_prox_learn.restype = C.c_int
+    L.evc_prox_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, D, H
+        C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int),   # stats, ld_stats, count_io, order
+        C.c_int, C.c_int, C.c_int, C.POINTER(ProxLearnOpts),                # M, N, T, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),      # n_epochs_out, n_steps_out, trace_out
         C.c_void_p,                                                         # stream
     ]
     _lib = L

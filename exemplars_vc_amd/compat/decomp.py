@@ -18,6 +18,11 @@ a mask that is not float with ValueError (deComP: DtypeMismatchError, a ValueErr
 Not mirrored, NotImplementedError: a 1-D `mask` (weights per bin: multiply y and A by them), complex input, `cd`,
 `parallel_cd`, `admm` - and `acc_ista`, which at an exhausted `maxiter` returns the iterate before the last (lasso.py:357);
 its schedule is offered natively, solve_activations_prox(momentum="nesterov"), where the last iterate is returned.
+
+`dictionary_learning.solve(y, D, alpha, x=None, tol, minibatch, maxiter, method='block_cd', lasso_method=..., ...)` mirrors
+deComP's online sparse dictionary learning (decomp/dictionary_learning.py) as one native call (evc_prox_learn) and returns
+(it, D, x) with D in deComP's orientation, atoms as rows.  Its lasso half is one of the four methods above, which must be
+named: deComP's default there, 'cd', is not mirrored.
 """
 from __future__ import annotations
 
@@ -86,6 +91,54 @@ def _nnls_solve(y, A, alpha, x=None, tol=1.0e-3, method='ista_pos', maxiter=1000
     return _lasso_solve(y, A, alpha, x, tol, method + '_pos', maxiter, mask, **kwargs)
 
 
+def _dictionary_learning_solve(y, D, alpha, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='block_cd',
+                               lasso_method='cd', lasso_iter=10, lasso_tol=1.0e-5, mask=None, random_seed=None, device=None):
+    """deComP's dictionary_learning.solve -> (it, D, x): y is [n_samples, n_channels], D [n_features, n_channels] (atoms as
+    rows), x [n_samples, n_features] (None: ones).  One native call (evc_prox_learn) of maxiter - 1 epochs over
+    int(n_samples / minibatch) batches each, the frames in the order deComP shuffles them with `random_seed`; `it` is the
+    epoch (from 1) in which max |D_new - D| < tol stopped the loop, else maxiter.  Mirrored lasso methods: ista, fista,
+    ista_pos, fista_pos.  NotImplementedError: deComP's default lasso_method='cd' (name one of the four), 'parallel_cd',
+    'admm', 'acc_ista' (its exhausted-maxiter quirk, see the module's text), `mask`, complex input, minibatch=None (deComP
+    itself raises there) and any method but 'block_cd'."""
+    from ..solver import decomp_frame_order, learn_dictionary_sparse
+    if minibatch is None:
+        raise NotImplementedError('Only online methods are implemented. minibatch is required.')
+    if method != 'block_cd':
+        raise NotImplementedError("compat.decomp: method '%s' is not mirrored (block_cd is)" % method)
+    if mask is not None:
+        raise NotImplementedError("compat.decomp: dictionary_learning with a `mask` is not mirrored")
+    positive = lasso_method.endswith("_pos")
+    base = lasso_method[:-4] if positive else lasso_method
+    if base not in _NATIVE:
+        raise NotImplementedError("compat.decomp: lasso_method '%s' is not mirrored: name one of ista, fista, ista_pos, "
+                                  "fista_pos" % lasso_method)
+    y, D = np.asarray(y), np.asarray(D)
+    if y.dtype.kind == 'c' or D.dtype.kind == 'c' or (x is not None and np.asarray(x).dtype.kind == 'c'):
+        raise NotImplementedError("compat.decomp: complex input is not mirrored")
+    if y.ndim != 2 or D.ndim != 2 or y.shape[1] != D.shape[1]:
+        raise ValueError("y %s and D %s must be 2-D and agree on the number of channels" % (y.shape, D.shape))
+    dtype = np.float32 if y.dtype == np.float32 else np.float64
+    T, N = y.shape[0], D.shape[0]
+    minibatch = int(minibatch)
+    if T < minibatch:                            # deComP: MinibatchBase.__init__
+        raise ValueError('Minibatch size should be smaller than the total size. Given {} < {}'.format(T, minibatch))
+    x0 = np.ones((T, N), dtype=dtype) if x is None else np.ascontiguousarray(x, dtype=dtype)
+    if x0.shape != (T, N):
+        raise ValueError("x has shape %s, expected %s" % (x0.shape, (T, N)))
+    maxiter = int(maxiter)
+    epochs = max(maxiter - 1, 0)
+    Dn, H, info = learn_dictionary_sparse(np.ascontiguousarray(y, dtype=dtype), np.ascontiguousarray(D, dtype=dtype), x0,
+                                          alpha=float(alpha), layout="frame_major", batch_size=minibatch, epochs=epochs,
+                                          tol=float(tol), lasso_iters=int(lasso_iter), lasso_tol=float(lasso_tol),
+                                          positive=positive, momentum=_NATIVE[base],
+                                          order=decomp_frame_order(T, epochs, random_seed),   # None: unseeded, as deComP
+                                          dtype="f64" if dtype == np.float64 else "f32", device=device, info=True)
+    change = info["change"][:info["n_steps"]]
+    stopped = info["n_steps"] > 0 and bool(change[-1] < float(tol))
+    return (info["n_epochs"] if stopped else maxiter), np.asarray(Dn), np.asarray(H)
+
+
 lasso = types.SimpleNamespace(solve=_lasso_solve, AVAILABLE_METHODS=AVAILABLE_METHODS,
                               AVAILABLE_NNLS_METHODS=AVAILABLE_NNLS_METHODS)
 nnls = types.SimpleNamespace(solve=_nnls_solve)
+dictionary_learning = types.SimpleNamespace(solve=_dictionary_learning_solve)

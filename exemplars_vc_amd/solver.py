@@ -1181,6 +1181,139 @@ def learn_dictionary_online(X, W0, H0, *, beta=2.0, layout, batch_size=1024, max
                                            "change": np.ascontiguousarray(tr[:, 1])} if info else None)
 
 
+def decomp_frame_order(T, epochs, seed):
+    """The frame orders of `epochs` passes as deComP's dictionary_learning.solve shuffles them with random_seed=seed: an
+    index array shuffled in place and cumulatively by RandomState(seed) every epoch, applied to the already shuffled frames.
+    Returns an int32 array (epochs, T): row e lists the frames in the order epoch e takes them."""
+    rng = np.random.RandomState(seed)
+    index, pos = np.arange(int(T)), np.arange(int(T))
+    rows = np.empty((max(int(epochs), 0), int(T)), dtype=np.int32)
+    for e in range(rows.shape[0]):
+        rng.shuffle(index)
+        pos = pos[index]
+        rows[e] = pos
+    return rows
+
+
+def learn_dictionary_sparse(X, D0, H0=None, *, alpha, layout, batch_size, epochs, tol=0.0, lasso_iters=10, lasso_tol=1e-5,
+                            positive=True, momentum="fista", order=None, seed=None, state=None, dtype=None, device=None,
+                            info=False, out_w=None, out_h=None, loop_events=None, lasso_check_every=10, skip=()):
+    """Sparse dictionary learning, X ~ D H with sparse H and atoms of norm <= 1, on the GPU (evc_prox_learn): Mairal et al.'s
+    online method as deComP's dictionary_learning.solve(method='block_cd') runs it.  D is addressed like the dictionary A of
+    solve_activations_prox, H like its activations; D0 is divided by its atoms' norms first, H0 None starts at ones (deComP's
+    default).  An epoch takes floor(T / batch_size) batches of batch_size frames in the order of its row of `order`
+    ((epochs, T) ints, every row a permutation; None: as the frames lie), the last T mod batch_size frames of the row are
+    left alone; seed (when order is None) builds the rows as deComP does with random_seed=seed (decomp_frame_order).  Per
+    step: the batch's activations by solve_activations_prox's statement (normalize, alpha, lasso_iters updates, lasso_tol,
+    positive, momentum), the statistics S <- beta S + H_F H_F^T, Q <- beta Q + H_F X_F^T, one block-coordinate sweep over the
+    atoms with the projection |d_j| <= 1; the call stops when max |D_new - D| < tol (tol = 0: never).  At most 1056 bins and
+    4096 atoms.
+
+    Returns (D, H) as learn_dictionary does; with info=True also dict(n_epochs=epochs begun, n_steps=steps carried out,
+    change=[epochs * (T // batch_size)] max |D_new - D| of every step (NaN after the stop), block=atoms per block of the
+    sweep, state=(stats, count): the N x (N + M) device tensor [S | Q] and the step count).  state: that of an earlier
+    call's info: the statistics and the count continue (D is then not normalised again); the caller passes the remaining rows
+    of `order`.  info=False with tol=0 enqueues without waiting.  skip: measurement only (tools/bench_prox_learn.py), the halves
+    of the step to leave out, of "lasso", "statistics", "sweep".  No CPU fallback: without a HIP device this raises
+    RuntimeError."""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    if momentum not in _PROX_MOMENTA:
+        raise ValueError("momentum must be 'ista', 'fista' or 'nesterov'")
+    alpha, tol, lasso_tol = float(alpha), float(tol), float(lasso_tol)
+    if not all(v >= 0.0 and np.isfinite(v) for v in (alpha, tol, lasso_tol)):
+        raise ValueError("alpha, tol and lasso_tol must be finite and >= 0")
+    batch_size, epochs, lasso_iters, lasso_check_every = int(batch_size), int(epochs), int(lasso_iters), int(lasso_check_every)
+    xshape = tuple(getattr(X, "shape", ()))
+    if len(xshape) != 2:
+        raise ValueError(f"expected a 2-D matrix, got shape {xshape}")
+    bm = lay == _lib.BIN_MAJOR
+    T = int(xshape[1 if bm else 0])
+    if not 1 <= batch_size <= T:
+        raise ValueError(f"batch_size must be between 1 and the number of frames ({T}), got {batch_size}")
+    if epochs < 0 or lasso_iters < 0 or lasso_check_every < 0:
+        raise ValueError("epochs, lasso_iters and lasso_check_every must be >= 0")
+    if order is None and seed is not None:
+        order = decomp_frame_order(T, epochs, seed)
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        if order.shape != (epochs, T) or (epochs and not np.array_equal(np.sort(order, axis=1),
+                                                                          np.broadcast_to(np.arange(T), (epochs, T)))):
+            raise ValueError(f"order must hold {epochs} rows, each a permutation of the {T} frames")
+    if H0 is None and out_h is None:
+        N0 = int(tuple((D0 if D0 is not None else out_w).shape)[1 if bm else 0])
+        hshape = (N0, T) if bm else (T, N0)
+        ref = D0 if D0 is not None else out_w
+        H0 = torch.ones(hshape, dtype=ref.dtype, device=ref.device) if isinstance(ref, torch.Tensor) \
+            else np.ones(hshape, dtype=np.asarray(ref).dtype)
+    opts = _lib.ProxLearnOpts()
+    opts.batch_size, opts.epochs, opts.lasso_iters, opts.lasso_check_every = batch_size, epochs, lasso_iters, lasso_check_every
+    opts.mode = _lib.PROX_POSITIVE if positive else _lib.PROX_SIGNED
+    opts.momentum, opts.resume = _PROX_MOMENTA[momentum], 0 if state is None else 1
+    opts.alpha, opts.tol, opts.lasso_tol = alpha, tol, lasso_tol
+    opts.reserved = sum({"lasso": 1, "statistics": 2, "sweep": 4}[h] for h in set(skip))
+    p = _learn_operands(X, D0, H0, out_w, out_h, layout, dtype, device)
+    L = _lib.lib()
+    _common_opts(opts, p.dcode, p.lay, loop_events)
+    M, N = p.M, p.R
+    nbytes = int(L.evc_prox_learn_workspace_bytes(M, N, T, batch_size, p.dcode))
+    unsupported = (f"unsupported sparse dictionary-learning shape M={M}, N={N}, T={T} (M <= {_lib.PROX_LEARN_MAX_M}, "
+                   f"N <= {_lib.PROX_LEARN_MAX_N})")
+    if nbytes == 0:         # refused here already, before `state` is looked at
+        raise ValueError(unsupported)
+    if state is None:
+        stats, count = torch.empty((N, N + M), dtype=p.tdtype, device=p.device), C.c_longlong(0)
+    else:
+        stats, count = state[0], C.c_longlong(int(state[1]))
+        if not isinstance(stats, torch.Tensor) or tuple(stats.shape) != (N, N + M) or stats.dtype != p.tdtype \
+                or stats.device != p.W_d.device or not stats.is_contiguous() or count.value < 0:
+            raise ValueError("`state` must be the (stats, count) of an earlier call's info: an N x (N + M) device tensor and "
+                             "a step count")
+    xwh = _xwh_args(p)
+    order_p = None if order is None else order.ctypes.data_as(C.POINTER(C.c_int))
+    (n_epochs, n_steps), tr = _learn_run(L, "evc_prox_learn", p,
+                                         (*xwh[:6], stats.data_ptr(), _ld(stats), C.byref(count), order_p, *xwh[6:]), opts,
+                                         nbytes, unsupported, (epochs * (T // batch_size),), info or tol > 0, info, n_counts=2)
+    return _learn_result(p, out_w, out_h, {"n_epochs": n_epochs, "n_steps": n_steps, "change": tr,
+                                           "block": int(L.evc_prox_learn_block(M, p.dcode)),
+                                           "state": (stats, int(count.value))} if info else None)
+
+
+def compact_dictionary_sparse(A, B, R, *, alpha, batch_size, epochs=10, tol=0.0, layout="bin_major", prepared=False, dtype=None,
+                              device=None, seed=None, **kw):
+    """A compact parallel dictionary for the sparse solve: the aligned source and target exemplars are stacked, D = [A; B]
+    ((Ma + Mb) x N) as compact_dictionary stacks them, and R << N joint atoms [Wa; Wb] are learnt by
+    learn_dictionary_sparse with the exemplars as the frames, from R evenly spaced exemplars and activations of ones.  The
+    stacked atoms have norm <= 1.  Returns (Wa, Wb, G, info) in the caller's orientation, info as
+    learn_dictionary_sparse's; prepared=True: (PreparedDictionary of (Wa, Wb), G, info).  The pair is ready for
+    convert_prox(Wa, Wb, X, ...).  Further keywords (lasso_iters, lasso_tol, positive, momentum, order) go to
+    learn_dictionary_sparse."""
+    torch = _torch()
+    device = require_device(device)
+    lay = _LAYOUTS[layout]
+    tdtype, _ = _pick_dtype(dtype, A, B)
+    A_d, a_np = _to_dev(A, tdtype, device)
+    B_d, _ = _to_dev(B, tdtype, device)
+    bm = lay == _lib.BIN_MAJOR
+    D = torch.cat([A_d, B_d], dim=0 if bm else 1)              # bin-major: (Ma + Mb, N); frame-major: (N, Ma + Mb)
+    Ma = A_d.shape[0] if bm else A_d.shape[1]
+    N = D.shape[1] if bm else D.shape[0]
+    R = int(R)
+    if not 1 <= R <= N:
+        raise ValueError(f"R must be between 1 and the number of exemplars ({N}), got {R}")
+    pick = torch.div(torch.arange(R, device=device) * N, R, rounding_mode="floor")
+    W0 = (D[:, pick] if bm else D[pick, :]).contiguous()
+    G0 = torch.ones((R, N) if bm else (N, R), dtype=tdtype, device=device)
+    W, G, info = learn_dictionary_sparse(D, None, None, alpha=alpha, layout=layout, batch_size=batch_size, epochs=epochs,
+                                         tol=tol, seed=seed, dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0, **kw)
+    Wa, Wb = (W[:Ma], W[Ma:]) if bm else (W[:, :Ma], W[:, Ma:])
+    if prepared:
+        return prepare_dictionary(Wa, Wb, layout=layout, dtype=tdtype, device=device), (_to_host(G) if a_np else G), info
+    if a_np:
+        return _to_host(Wa), _to_host(Wb), _to_host(G), info
+    return Wa, Wb, G, info
+
+
 _CDL_UPDATES = {"both": _lib.CDL_BOTH, "dict": _lib.CDL_DICT_ONLY}
 
 

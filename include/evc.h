@@ -70,6 +70,10 @@
  *   evc_prox_masked_solve  the same solves with deComP's 2-D `mask` (missing data: a weight per bin of every frame,
  *                   lasso.py:306-328, 418-445) on a factored sweep without the N x N Gram matrix; a NULL mask is the unmasked
  *                   problem on that sweep, for M << N; evc_prox_masked_workspace_bytes sizes it
+ *   evc_prox_learn  replaces deComP's dictionary_learning.solve(method='block_cd') (decomp/dictionary_learning.py:114-168):
+ *                   online sparse dictionary learning (Mairal et al.) - per mini-batch evc_prox_solve's lasso, the forgetting
+ *                   update of two sufficient statistics and one block-coordinate sweep over the atoms with |d_j| <= 1;
+ *                   evc_prox_learn_workspace_bytes sizes it, evc_prox_learn_block tells the sweep's block width
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -1228,6 +1232,71 @@ size_t evc_prox_masked_workspace_bytes(int M, int N, int T, int n_utt, int dtype
 int evc_prox_masked_solve(const void* A, int lda, const void* X, int ldx, const void* mask, int ldm, void* H, int ldh, int M,
                           int N, int T, const int* utt_offsets, int n_utt, const evc_prox_masked_opts* opts, void* workspace,
                           size_t workspace_bytes, int* n_iter_out, double* change_out, evc_stream_t stream);
+
+/* Sparse dictionary learning, X ~ D H with sparse H and atoms of norm <= 1: Mairal et al.'s online dictionary learning as
+ * deComP's dictionary_learning.solve(method='block_cd') runs it (dictionary_learning.py:114-168; utils/data.py:101-121;
+ * utils/normalize.py).  X is M x T, D is the M x N dictionary (atoms as columns; deComP's D is its transpose), H is N x T
+ * (deComP's x is its transpose); layouts and leading dimensions as in evc_prox_solve, D addressed like its A.  D and H hold
+ * the start on entry and are updated in place.  `stats` is the N x (N + M) matrix [S | Q] of the two sufficient statistics,
+ * row-major with the leading dimension ld_stats >= N + M, in the call's dtype, and *count_io the number of steps so far:
+ * both caller-owned, as acc_a / acc_b of evc_online_learn.  resume = 0: the call first divides every atom of D by its
+ * Euclidean norm (a zero atom becomes NaN, as numpy's 0 / 0), zeroes `stats` and *count_io; resume = 1: nothing is touched.
+ * Epoch e = 0 .. epochs - 1 has floor(T / bs) batches, bs = batch_size; batch b takes the frames
+ * order[e][b bs .. (b + 1) bs) (order == NULL: the identity), and the last T mod bs frames of the row are not touched in that
+ * epoch.  One step on the batch's frames F:
+ *   lasso       evc_prox_solve's statement on X[:, F] and H[:, F] as ONE utterance with the current D: normalize = 1, alpha,
+ *               tol = lasso_tol, iters = lasso_iters, check_every = lasso_check_every, EVC_STOP_DECOMP, EVC_INIT_GIVEN, mode,
+ *               momentum, the Gershgorin step.  The batch's columns are gathered into the workspace and the result is
+ *               scattered back; the frames are never moved.
+ *   statistics  theta = count bs + 1, beta = (theta - bs) / theta in double precision on the host;
+ *               S <- beta S + H_F H_F^T;  Q <- beta Q + H_F X_F^T
+ *   sweep       for k = 0 .. N - 1 in order, D_cur holding the new atoms j < k and the old atoms j >= k:
+ *               u = (Q[k, :] - sum_j S[k, j] d_j) / (S[k, k] + 1e-15) + d_k;   d_k <- u / sqrt(max(|u|^2, 1))
+ *   stop        stat = max |D_new - D|, recorded in trace_out; count += 1; stat < tol ends the call (a NaN compares false and
+ *               runs on).  The stopping step's D and H are kept.
+ * Kernels: k_plearn_stats forms beta [S | Q] + H_F [H_F; X_F]^T in one launch on the matrix cores, frames ascending in
+ * LDS-staged slabs, the decay in the epilogue.  The sweep is blocked and right-looking with nb = 32, 16, 8 or 4 atoms per
+ * block (from M and the dtype alone): Rm = Q - S D^T once per step, then one launch of k_plearn_block per block, in which
+ * every workgroup redoes the block's nb sequential atom updates (the same instructions in the same order) and then takes
+ * the block's changes off its own rows of Rm behind the block; workgroup 0 alone stores the new atoms.  ceil(N / nb)
+ * dependent launches instead of N, no exchange between workgroups inside a launch, no residency assumption, no float
+ * atomics: the same call gives the same bits, and with tol = 0 a call of p epochs followed by a resume = 1 call of q epochs
+ * on the remaining rows of `order` gives bitwise the D, H, stats and count of one call of p + q epochs.
+ *   M : 1 .. 1056, N : 1 .. 4096 (larger: -3);  T >= 1;  1 <= batch_size <= T;  epochs >= 0 (0: the start after the
+ *       resume = 0 preparation)
+ *   order : NULL or host int[epochs][T], every row a permutation of 0 .. T - 1 (anything else: -1)
+ *   n_epochs_out, n_steps_out : host ints or NULL: e + 1 of the stopping step (else `epochs`), and the steps carried out
+ *   trace_out : host, epochs * floor(T / bs) doubles or NULL: stat of every step, NaN after the stop
+ * Ask evc_prox_learn_workspace_bytes for the workspace (the gathered batch, Rm, a copy of D, the lasso's workspace).
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: one read of one double per step when
+ * tol > 0 or trace_out is given, as evc_online_learn for its convergence; else the call is a pure enqueue. */
+typedef struct evc_prox_learn_opts {
+    int struct_bytes;        /* sizeof(evc_prox_learn_opts) */
+    int dtype;               /* EVC_F64 | EVC_F32 */
+    int layout;              /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int batch_size;          /* 1 .. T */
+    int epochs;              /* passes over the frames, >= 0 (deComP: maxiter - 1) */
+    int lasso_iters;         /* updates of a step's lasso, >= 0 (deComP: 10) */
+    int lasso_check_every;   /* as evc_prox_opts.check_every (deComP: 10) */
+    int mode;                /* EVC_PROX_POSITIVE | EVC_PROX_SIGNED */
+    int momentum;            /* EVC_PROX_ISTA | EVC_PROX_FISTA | EVC_PROX_NESTEROV */
+    int resume;              /* 0: D is normalised, stats and count are zeroed by the call; 1: they hold a previous call's state */
+    int reserved;            /* 0; measurement only: bit 0 the steps run without their lasso, bit 1 without their statistics,
+                                bit 2 without their sweep (and then without a stop statistic); anything else: status -1 */
+    int reserved2;           /* 0 */
+    double alpha;            /* >= 0: the lasso's penalty, per bin */
+    double tol;              /* >= 0: the call stops when max |D_new - D| < tol; 0: never */
+    double lasso_tol;        /* >= 0: the lasso's stop threshold (deComP: 1e-5) */
+    void* ev_loop_start;     /* optional hipEvent_t pair recorded around the launches of the step loop, as in */
+    void* ev_loop_stop;      /* evc_solve_opts; NULL = not recorded */
+} evc_prox_learn_opts;
+/* bytes of workspace evc_prox_learn needs (0: invalid or unsupported arguments, M > 1056, N > 4096 and batch_size > T among them) */
+size_t evc_prox_learn_workspace_bytes(int M, int N, int T, int batch_size, int dtype);
+/* atoms per block of the sweep for M bins: 32, 16, 8 or 4 (0: invalid arguments) */
+int evc_prox_learn_block(int M, int dtype);
+int evc_prox_learn(const void* X, int ldx, void* D, int ldd, void* H, int ldh, void* stats, int ld_stats, long long* count_io,
+                   const int* order, int M, int N, int T, const evc_prox_learn_opts* opts, void* workspace,
+                   size_t workspace_bytes, int* n_epochs_out, int* n_steps_out, double* trace_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
