@@ -46,13 +46,15 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_semi_workspace_bytes", "evc_semi_solve",
            "evc_prox_workspace_bytes", "evc_prox_solve",
            "evc_prox_masked_workspace_bytes", "evc_prox_masked_solve",
-           "evc_prox_learn_workspace_bytes", "evc_prox_learn_block", "evc_prox_learn")
+           "evc_prox_learn_workspace_bytes", "evc_prox_learn_block", "evc_prox_learn",
+           "evc_prox_masked_learn_workspace_bytes", "evc_prox_masked_learn")
 BETA_MAX_M = 528
 DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 DECONV_LEARN_MAX_R = 4096
 SEMI_MAX_M, SEMI_MAX_N = 1056, 16384
 PROX_MAX_M, PROX_MAX_N, PROX_MAX_SLOTS = 1056, 16384, 4097
 PROX_LEARN_MAX_M, PROX_LEARN_MAX_N = 1056, 4096
+PROX_MASKED_LEARN_MAX_M, PROX_MASKED_LEARN_MAX_N, PROX_MASKED_LEARN_MAX_S = 1056, 1024, 1 << 28
 MFCC_MAX_MELS, MFCC_MAX_FFT = 256, 8192
 
 
@@ -223,6 +225,11 @@ class ProxLearnOpts(C.Structure):
         ("alpha", C.c_double), ("tol", C.c_double), ("lasso_tol", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
+
+
+class ProxMaskedLearnOpts(C.Structure):
+    """Mirror of `evc_prox_masked_learn_opts` (include/evc.h): `evc_prox_learn_opts`' fields for the learning with a mask."""
+    _fields_ = list(ProxLearnOpts._fields_)
 
 
 class Dict(C.Structure):
@@ -517,6 +524,18 @@ def lib():
         C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, D, H
         C.c_void_p, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_int),   # stats, ld_stats, count_io, order
         C.c_int, C.c_int, C.c_int, C.POINTER(ProxLearnOpts),                # M, N, T, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),      # n_epochs_out, n_steps_out, trace_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_prox_masked_learn_workspace_bytes.restype = C.c_size_t
+    L.evc_prox_masked_learn_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_prox_masked_learn.restype = C.c_int
+    L.evc_prox_masked_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, mask, D, H
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int,                           # stats_s, ld_s, stats_q, ld_q
+        C.POINTER(C.c_longlong), C.POINTER(C.c_int),                        # count_io, order
+        C.c_int, C.c_int, C.c_int, C.POINTER(ProxMaskedLearnOpts),          # M, N, T, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),      # n_epochs_out, n_steps_out, trace_out
         C.c_void_p,                                                         # stream

@@ -22,7 +22,8 @@ its schedule is offered natively, solve_activations_prox(momentum="nesterov"), w
 `dictionary_learning.solve(y, D, alpha, x=None, tol, minibatch, maxiter, method='block_cd', lasso_method=..., ...)` mirrors
 deComP's online sparse dictionary learning (decomp/dictionary_learning.py) as one native call (evc_prox_learn) and returns
 (it, D, x) with D in deComP's orientation, atoms as rows.  Its lasso half is one of the four methods above, which must be
-named: deComP's default there, 'cd', is not mirrored.
+named: deComP's default there, 'cd', is not mirrored.  Its `mask` is refused here with NotImplementedError;
+exemplars_vc_amd.learn_dictionary_sparse(mask=..., seed=...) runs deComP's masked learning natively (evc_prox_masked_learn).
 """
 from __future__ import annotations
 
@@ -106,7 +107,8 @@ def _dictionary_learning_solve(y, D, alpha, x=None, tol=1.0e-3, minibatch=None, 
     if method != 'block_cd':
         raise NotImplementedError("compat.decomp: method '%s' is not mirrored (block_cd is)" % method)
     if mask is not None:
-        raise NotImplementedError("compat.decomp: dictionary_learning with a `mask` is not mirrored")
+        raise NotImplementedError("compat.decomp: dictionary_learning with a `mask` is not mirrored here; "
+                                  "learn_dictionary_sparse(mask=..., seed=...) runs it natively (evc_prox_masked_learn)")
     positive = lasso_method.endswith("_pos")
     base = lasso_method[:-4] if positive else lasso_method
     if base not in _NATIVE:

@@ -1197,7 +1197,7 @@ def decomp_frame_order(T, epochs, seed):
 
 def learn_dictionary_sparse(X, D0, H0=None, *, alpha, layout, batch_size, epochs, tol=0.0, lasso_iters=10, lasso_tol=1e-5,
                             positive=True, momentum="fista", order=None, seed=None, state=None, dtype=None, device=None,
-                            info=False, out_w=None, out_h=None, loop_events=None, lasso_check_every=10, skip=()):
+                            info=False, out_w=None, out_h=None, loop_events=None, lasso_check_every=10, skip=(), mask=None):
     """Sparse dictionary learning, X ~ D H with sparse H and atoms of norm <= 1, on the GPU (evc_prox_learn): Mairal et al.'s
     online method as deComP's dictionary_learning.solve(method='block_cd') runs it.  D is addressed like the dictionary A of
     solve_activations_prox, H like its activations; D0 is divided by its atoms' norms first, H0 None starts at ones (deComP's
@@ -1214,8 +1214,17 @@ def learn_dictionary_sparse(X, D0, H0=None, *, alpha, layout, batch_size, epochs
     sweep, state=(stats, count): the N x (N + M) device tensor [S | Q] and the step count).  state: that of an earlier
     call's info: the statistics and the count continue (D is then not normalised again); the caller passes the remaining rows
     of `order`.  info=False with tol=0 enqueues without waiting.  skip: measurement only (tools/bench_prox_learn.py), the halves
-    of the step to leave out, of "lasso", "statistics", "sweep".  No CPU fallback: without a HIP device this raises
-    RuntimeError."""
+    of the step to leave out, of "lasso", "statistics", "sweep".
+
+    mask: missing data (deComP's dictionary_learning.solve(..., mask=)): finite weights >= 0 of X's shape, one per bin of
+    every frame, a zero marks a missing bin.  The call then runs evc_prox_masked_learn, another algorithm: the lasso is
+    solve_activations_prox(mask=, lip_weights="mean")'s, the Gram statistic is one N x N matrix per bin, Q takes mask . X,
+    and all atoms are updated at once from the old dictionary (a Jacobi step) with one denominator per atom, the sum over the
+    bins of S_m[k, k] + 1e-15 - a mask of ones does NOT give the unmasked call's result.  info["state"] is then (stats_s,
+    stats_q, count): the (M, N, N) and (N, M) device tensors and the step count, and resumes likewise; info["block"] is 0;
+    "sweep" in skip stands for the atom update.  At most 1056 bins, 1024 atoms and M N^2 <= 2^28.
+
+    No CPU fallback: without a HIP device this raises RuntimeError."""
     torch = _torch()
     lay = _LAYOUTS[layout]
     if momentum not in _PROX_MOMENTA:
@@ -1240,13 +1249,15 @@ def learn_dictionary_sparse(X, D0, H0=None, *, alpha, layout, batch_size, epochs
         if order.shape != (epochs, T) or (epochs and not np.array_equal(np.sort(order, axis=1),
                                                                           np.broadcast_to(np.arange(T), (epochs, T)))):
             raise ValueError(f"order must hold {epochs} rows, each a permutation of the {T} frames")
+    if mask is not None:
+        _prox_mask_ok(mask, X)
     if H0 is None and out_h is None:
         N0 = int(tuple((D0 if D0 is not None else out_w).shape)[1 if bm else 0])
         hshape = (N0, T) if bm else (T, N0)
         ref = D0 if D0 is not None else out_w
         H0 = torch.ones(hshape, dtype=ref.dtype, device=ref.device) if isinstance(ref, torch.Tensor) \
             else np.ones(hshape, dtype=np.asarray(ref).dtype)
-    opts = _lib.ProxLearnOpts()
+    opts = _lib.ProxLearnOpts() if mask is None else _lib.ProxMaskedLearnOpts()
     opts.batch_size, opts.epochs, opts.lasso_iters, opts.lasso_check_every = batch_size, epochs, lasso_iters, lasso_check_every
     opts.mode = _lib.PROX_POSITIVE if positive else _lib.PROX_SIGNED
     opts.momentum, opts.resume = _PROX_MOMENTA[momentum], 0 if state is None else 1
@@ -1256,6 +1267,8 @@ def learn_dictionary_sparse(X, D0, H0=None, *, alpha, layout, batch_size, epochs
     L = _lib.lib()
     _common_opts(opts, p.dcode, p.lay, loop_events)
     M, N = p.M, p.R
+    if mask is not None:
+        return _learn_sparse_masked(L, p, opts, mask, order, state, T, batch_size, epochs, tol, info, out_w, out_h)
     nbytes = int(L.evc_prox_learn_workspace_bytes(M, N, T, batch_size, p.dcode))
     unsupported = (f"unsupported sparse dictionary-learning shape M={M}, N={N}, T={T} (M <= {_lib.PROX_LEARN_MAX_M}, "
                    f"N <= {_lib.PROX_LEARN_MAX_N})")
@@ -1279,16 +1292,56 @@ def learn_dictionary_sparse(X, D0, H0=None, *, alpha, layout, batch_size, epochs
                                            "state": (stats, int(count.value))} if info else None)
 
 
+def _learn_sparse_masked(L, p, opts, mask, order, state, T, batch_size, epochs, tol, info, out_w, out_h):
+    """learn_dictionary_sparse's tail with a mask: the statistics' tensors, evc_prox_masked_learn and the result"""
+    torch = _torch()
+    M, N = p.M, p.R
+    mask_d = _to_dev(mask, p.tdtype, p.device)[0]
+    nbytes = int(L.evc_prox_masked_learn_workspace_bytes(M, N, T, batch_size, p.dcode))
+    unsupported = (f"unsupported masked sparse dictionary-learning shape M={M}, N={N}, T={T} (M <= "
+                   f"{_lib.PROX_MASKED_LEARN_MAX_M}, N <= {_lib.PROX_MASKED_LEARN_MAX_N}, M N^2 <= "
+                   f"{_lib.PROX_MASKED_LEARN_MAX_S})")
+    if nbytes == 0:         # refused here already, before `state` is looked at
+        raise ValueError(unsupported)
+    if state is None:
+        stats_s = torch.empty((M, N, N), dtype=p.tdtype, device=p.device)
+        stats_q, count = torch.empty((N, M), dtype=p.tdtype, device=p.device), C.c_longlong(0)
+    else:
+        ok = len(state) == 3
+        if ok:
+            stats_s, stats_q, count = state[0], state[1], C.c_longlong(int(state[2]))
+            ok = count.value >= 0 and all(isinstance(t, torch.Tensor) and tuple(t.shape) == shape and t.dtype == p.tdtype
+                                          and t.device == p.W_d.device and t.is_contiguous()
+                                          for t, shape in ((stats_s, (M, N, N)), (stats_q, (N, M))))
+        if not ok:
+            raise ValueError("`state` must be the (stats_s, stats_q, count) of an earlier masked call's info: (M, N, N) and "
+                             "(N, M) device tensors and a step count")
+    xwh = _xwh_args(p)
+    order_p = None if order is None else order.ctypes.data_as(C.POINTER(C.c_int))
+    head = (*xwh[:2], mask_d.data_ptr(), _ld(mask_d), *xwh[2:6], stats_s.data_ptr(), N, stats_q.data_ptr(), M, C.byref(count),
+            order_p, *xwh[6:])
+    (n_epochs, n_steps), tr = _learn_run(L, "evc_prox_masked_learn", p, head, opts, nbytes, unsupported,
+                                         (epochs * (T // batch_size),), info or tol > 0, info, n_counts=2)
+    return _learn_result(p, out_w, out_h, {"n_epochs": n_epochs, "n_steps": n_steps, "change": tr, "block": 0,
+                                           "state": (stats_s, stats_q, int(count.value))} if info else None)
+
+
 def compact_dictionary_sparse(A, B, R, *, alpha, batch_size, epochs=10, tol=0.0, layout="bin_major", prepared=False, dtype=None,
-                              device=None, seed=None, **kw):
+                              device=None, seed=None, mask_a=None, mask_b=None, **kw):
     """A compact parallel dictionary for the sparse solve: the aligned source and target exemplars are stacked, D = [A; B]
     ((Ma + Mb) x N) as compact_dictionary stacks them, and R << N joint atoms [Wa; Wb] are learnt by
     learn_dictionary_sparse with the exemplars as the frames, from R evenly spaced exemplars and activations of ones.  The
     stacked atoms have norm <= 1.  Returns (Wa, Wb, G, info) in the caller's orientation, info as
     learn_dictionary_sparse's; prepared=True: (PreparedDictionary of (Wa, Wb), G, info).  The pair is ready for
-    convert_prox(Wa, Wb, X, ...).  Further keywords (lasso_iters, lasso_tol, positive, momentum, order) go to
+    convert_prox(Wa, Wb, X, ...).  mask_a, mask_b: weights >= 0 of A's and B's shape (a zero: the bin of that exemplar is
+    missing), stacked as the exemplars are, a side not given counting as ones; with either the atoms are learnt by
+    learn_dictionary_sparse(mask=...).  Further keywords (lasso_iters, lasso_tol, positive, momentum, order) go to
     learn_dictionary_sparse."""
     torch = _torch()
+    if mask_a is not None:
+        _prox_mask_ok(mask_a, A)
+    if mask_b is not None:
+        _prox_mask_ok(mask_b, B)
     device = require_device(device)
     lay = _LAYOUTS[layout]
     tdtype, _ = _pick_dtype(dtype, A, B)
@@ -1304,8 +1357,13 @@ def compact_dictionary_sparse(A, B, R, *, alpha, batch_size, epochs=10, tol=0.0,
     pick = torch.div(torch.arange(R, device=device) * N, R, rounding_mode="floor")
     W0 = (D[:, pick] if bm else D[pick, :]).contiguous()
     G0 = torch.ones((R, N) if bm else (N, R), dtype=tdtype, device=device)
+    mask = None
+    if mask_a is not None or mask_b is not None:
+        sides = [torch.ones_like(side) if m is None else _to_dev(m, tdtype, device)[0] for m, side in ((mask_a, A_d), (mask_b, B_d))]
+        mask = torch.cat(sides, dim=0 if bm else 1)
     W, G, info = learn_dictionary_sparse(D, None, None, alpha=alpha, layout=layout, batch_size=batch_size, epochs=epochs,
-                                         tol=tol, seed=seed, dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0, **kw)
+                                         tol=tol, seed=seed, dtype=tdtype, device=device, info=True, out_w=W0, out_h=G0,
+                                         mask=mask, **kw)
     Wa, Wb = (W[:Ma], W[Ma:]) if bm else (W[:, :Ma], W[:, Ma:])
     if prepared:
         return prepare_dictionary(Wa, Wb, layout=layout, dtype=tdtype, device=device), (_to_host(G) if a_np else G), info

@@ -74,6 +74,9 @@
  *                   online sparse dictionary learning (Mairal et al.) - per mini-batch evc_prox_solve's lasso, the forgetting
  *                   update of two sufficient statistics and one block-coordinate sweep over the atoms with |d_j| <= 1;
  *                   evc_prox_learn_workspace_bytes sizes it, evc_prox_learn_block tells the sweep's block width
+ *   evc_prox_masked_learn  the same learning with deComP's `mask` (dictionary_learning.py:171-231): evc_prox_masked_solve's
+ *                   lasso, one Gram statistic per bin and a Jacobi update of all atoms from the old dictionary;
+ *                   evc_prox_masked_learn_workspace_bytes sizes it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -1297,6 +1300,68 @@ int evc_prox_learn_block(int M, int dtype);
 int evc_prox_learn(const void* X, int ldx, void* D, int ldd, void* H, int ldh, void* stats, int ld_stats, long long* count_io,
                    const int* order, int M, int N, int T, const evc_prox_learn_opts* opts, void* workspace,
                    size_t workspace_bytes, int* n_epochs_out, int* n_steps_out, double* trace_out, evc_stream_t stream);
+
+/* evc_prox_learn with a weight per bin of every frame (missing data): deComP's dictionary_learning.solve(..., mask=), its
+ * solve_cd_mask (dictionary_learning.py:171-231).  X, D, H, layouts, leading dimensions, batches, `order`, *count_io, resume,
+ * the outputs and the host synchronisation are evc_prox_learn's.  `mask` has X's dtype, layout and shape (M x T) with its own
+ * leading dimension ldm, weights >= 0 (a zero: the bin is missing; negative weights are not looked for); NULL is status -1 -
+ * a caller without a mask wants evc_prox_learn, which is another algorithm.  With a mask the Gram statistic is one N x N
+ * matrix PER BIN: `stats_s` holds M planes of N rows, plane m at stats_s + m N ld_s, row-major with ld_s >= N; `stats_q` is
+ * N x M, row-major with ld_q >= M; both caller-owned, in the call's dtype, zeroed by a resume = 0 call.
+ * One step on the batch's frames F:
+ *   lasso       evc_prox_masked_solve's statement on X[:, F], mask[:, F] and H[:, F] as ONE utterance with the current D:
+ *               normalize = 1, EVC_PROX_LIP_MEAN (deComP's step), EVC_STOP_DECOMP, EVC_INIT_GIVEN; alpha, tol = lasso_tol,
+ *               iters = lasso_iters, check_every = lasso_check_every, mode and momentum from the options
+ *   statistics  theta = count bs + 1, beta = (theta - bs) / theta in double precision on the host;
+ *               S_m[k][j] <- beta S_m[k][j] + sum_{t in F} (H[k][t] mask[m][t]) H[j][t]  for every bin m
+ *               Q <- beta Q + H_F (mask_F . X_F)^T
+ *   atoms       every atom from the OLD dictionary (a Jacobi step, as dictionary_learning.py:218 contracts with D, not D_new):
+ *               G[k][m] = sum_j S_m[k][j] d_j[m];  a_k = sum_m (S_m[k][k] + 1e-15), m ascending - ONE scalar per atom, deComP's
+ *               (line 219), mirrored and not corrected;  u = (Q[k, :] - G[k, :]) / a_k + d_k;  d_k <- u / sqrt(max(|u|^2, 1))
+ *   stop        stat = max |D_new - D|, recorded in trace_out; count += 1; stat < tol ends the call (a NaN runs on)
+ * A frame whose mask is all zero runs with threshold 0; a bin missing in a whole batch is fine; a batch whose mask is all
+ * zero has L = 0 and gets what evc_prox_masked_solve documents for that (NaN), and the dictionary becomes NaN.
+ * Kernels: k_pmlearn_stats - a workgroup owns one bin and one panel of 64 rows of its plane and walks the panel's column tiles
+ * in ascending j: per tile the frames ascending in LDS-staged slabs of 16 (float32: 32), the left operand multiplied by the bin's weights
+ * as it is staged, 16x16x4 MFMAs, one chain per output; the epilogue applies the decay, stores the tile, multiplies it by
+ * d_j[m] into per-row running sums (one fixed lane reduce at the end gives G[k][m]) and stores the diagonal entries.  The
+ * tensor is read once and written once per step.  k_pmlearn_q forms Q, k_pmlearn_atoms updates all atoms in one launch, one
+ * workgroup per atom.  No exchange between workgroups, no residency assumption, no float atomics: the same call gives the
+ * same bits, and with tol = 0 a call of p epochs followed by a resume = 1 call of q epochs on the remaining rows of `order`
+ * gives bitwise the D, H, stats_s, stats_q and count of one call of p + q epochs.
+ *   M : 1 .. 1056, N : 1 .. 1024, M N^2 <= 2^28 elements (larger: -3);  T, batch_size, epochs, order, n_epochs_out,
+ *       n_steps_out, trace_out : as for evc_prox_learn
+ * Ask evc_prox_masked_learn_workspace_bytes for the workspace (the gathered batch [H_F | X_F | mask_F], G, the diagonals, a
+ * copy of D, the shares, the epoch's order row, the lasso's workspace).  Status -1 / -3 / -2 are returned before any device
+ * work. */
+typedef struct evc_prox_masked_learn_opts {
+    int struct_bytes;        /* sizeof(evc_prox_masked_learn_opts) */
+    int dtype;               /* EVC_F64 | EVC_F32 */
+    int layout;              /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int batch_size;          /* 1 .. T */
+    int epochs;              /* passes over the frames, >= 0 (deComP: maxiter - 1) */
+    int lasso_iters;         /* updates of a step's lasso, >= 0 (deComP: 10) */
+    int lasso_check_every;   /* as evc_prox_opts.check_every (deComP: 10) */
+    int mode;                /* EVC_PROX_POSITIVE | EVC_PROX_SIGNED */
+    int momentum;            /* EVC_PROX_ISTA | EVC_PROX_FISTA | EVC_PROX_NESTEROV */
+    int resume;              /* 0: D is normalised, the statistics and count are zeroed by the call; 1: they hold a previous call's state */
+    int reserved;            /* 0; measurement only, as evc_prox_learn_opts.reserved: bit 0 the steps run without their lasso,
+                                bit 1 without their statistics, bit 2 without their atom update (and then without a stop
+                                statistic); anything else: status -1 */
+    int reserved2;           /* 0 */
+    double alpha;            /* >= 0: the lasso's penalty, per valid bin */
+    double tol;              /* >= 0: the call stops when max |D_new - D| < tol; 0: never */
+    double lasso_tol;        /* >= 0: the lasso's stop threshold (deComP: 1e-5) */
+    void* ev_loop_start;     /* optional hipEvent_t pair recorded around the launches of the step loop, as in */
+    void* ev_loop_stop;      /* evc_solve_opts; NULL = not recorded */
+} evc_prox_masked_learn_opts;
+/* bytes of workspace evc_prox_masked_learn needs (0: invalid or unsupported arguments, M > 1056, N > 1024, M N^2 > 2^28 and
+ * batch_size > T among them) */
+size_t evc_prox_masked_learn_workspace_bytes(int M, int N, int T, int batch_size, int dtype);
+int evc_prox_masked_learn(const void* X, int ldx, const void* mask, int ldm, void* D, int ldd, void* H, int ldh, void* stats_s,
+                          int ld_s, void* stats_q, int ld_q, long long* count_io, const int* order, int M, int N, int T,
+                          const evc_prox_masked_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_epochs_out,
+                          int* n_steps_out, double* trace_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
