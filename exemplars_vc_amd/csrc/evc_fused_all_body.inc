@@ -22,6 +22,10 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
 #endif
     using S = AllShape<MSTEPS, C, KL>;
     constexpr int DS = LONE ? MSTEPS - 1 : MSTEPS;   // k-steps of the D and P chains
+    // the update's range test decided once per sweep (mu_tile_hoisted, evc_fused_common.h): the instances whose step is
+    // the sweep - one member and the direct exchange, Frobenius.  The reduce-scatter instances (their step is the
+    // exchange) and KL (no division) keep their code.
+    constexpr bool HOIST = !KL && C >= 1;
     constexpr int MT = S::MT;
     constexpr int E = S::E;
     constexpr int NE = S::NE;
@@ -38,6 +42,9 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
     __shared__ double s_dict[S::LDS_DICT ? ATILES * TPD : 1];   // the member's dictionary (see AllShape)
     __shared__ unsigned s_hb[2];                 // arrivals of a half's wavefronts at its LDS barrier
     __shared__ int s_fail;
+    // HOIST: [half][w] - did every element of V that wavefront w of the half wrote in the last exchange lie in
+    // [2^-100, 2^100)?  Written by its owner alone (no atomics), 0 from the tile's start to its first exchange.
+    __shared__ __attribute__((aligned(16))) unsigned s_vok[HOIST ? 2 : 1][HOIST ? AW : 1];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = w8 >> 2, w = w8 & 3, th = tid & (AW * 64 - 1);
@@ -151,6 +158,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
     const f64x4 dinit = {d0, d0, d0, d0};
     const unsigned lo = fast_lo(mode, eps);
     unsigned seq = 0;                            // exchanges done by this half's group so far
+    bool tame = false;                           // HOIST: the member's bound, found once per launch (below, in front of run)
     // reduce-scatter exchange with ragged slices (C < 0): what this thread publishes and fetches, the same in every exchange
     int rs_es = 1, rs_len = 0, rs_pub0 = 0, rs_pub1 = 0, rs_src0 = -1, rs_src1 = -1, rs_src2 = -1;
     if (C < 0) {
@@ -239,6 +247,9 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 h[k][0] = h01[0]; h[k][1] = h01[1]; h[k][2] = h23[0]; h[k][3] = h23[1];
             }
         }
+        if constexpr (HOIST) {                   // a tile's first sweep keeps the per-unit test
+            if (lane == 0) s_vok[half][w] = 0u;
+        }
         __syncthreads();
         if (valid && !KL) {                      // numerator tiles, once per frame tile
             double x[DS], xl = 0.0;
@@ -278,8 +289,22 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 asm volatile("" : "+s"(sw));
                 double v[DS], vl = 0.0;
 #pragma unroll
-                for (int s = 0; s < DS; ++s) v[s] = KL ? rL[s * 64 + lane] : vL[s * 64 + lane];
+                for (int s = 0; s < DS; ++s) {
+                    v[s] = KL ? rL[s * 64 + lane] : vL[s * 64 + lane];
+                    // (two k-steps, dictionary in LDS, HOIST: the compiler lays this sweep straight behind the numerator
+                    // pass, and tests/test_fused_all_lds_host.py, which takes MFMAs less than 200 lines apart for one run,
+                    // then counts the sweep's head with the sweep: no paired read here either)
+                    if constexpr (HOIST && MSTEPS == 2 && decltype(lds)::value) LDS_NO_PAIR();
+                }
                 if constexpr (LONE) vl = vL[DS * 64 + (lane & 15)];
+                // HOIST: one scalar for the sweep's 8 units - the member is tame and the half's four wavefronts found
+                // every element of this V in range (read behind the step barrier that orders the v[] reads above)
+                bool safe = false;
+                if constexpr (HOIST) {
+                    static_assert(AW == 4, "the half's four words are one 16-byte read");
+                    const all_u32x4 ok4 = *reinterpret_cast<const all_u32x4*>(s_vok[half]);
+                    safe = tame && __builtin_amdgcn_readfirstlane((int)(ok4[0] & ok4[1] & ok4[2] & ok4[3])) != 0;
+                }
                 // (from LDS the first unit's fragments come at the start of the sweep: held across the exchange step
                 // instead, they cost 14 registers there, and the compiler spilled around the sweep)
                 if constexpr (decltype(lds)::value) load_a1(a1, 0, lds);
@@ -317,6 +342,8 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                     if (KL) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) h[k][r] *= d[r];
+                    } else if constexpr (HOIST) {
+                        mu_tile_hoisted(h[k], p[k], d, mode, eps, lo, safe);
                     } else {
                         mu_tile_guarded(h[k], p[k], d, mode, eps, lo);
                     }
@@ -342,6 +369,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 const bool act = th < NE / 2;
                 const int ep = act ? 2 * th : 0;
                 f64x2 sm = {0.0, 0.0};
+                unsigned vok = 1u;                  // (a wavefront that moves nothing vouches for nothing)
                 if (w * 64 < NE / 2) {
                     f64x2 pv[AW];
 #pragma unroll
@@ -407,6 +435,11 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                         v2[1] += __longlong_as_double(b[m][1] & ~1LL);
                     }
                     if (!ok) s_fail = 1;
+                    if constexpr (HOIST) {
+                        // the pair's bin (both elements lie in one lane group of one k-step); bins >= M hold exact zeros
+                        const bool real = act && bin_of(ep >> 6, (ep & 63) >> 4) < a.M;
+                        vok = __all(!real || (range_v_ok(v2[0]) && range_v_ok(v2[1]))) ? 1u : 0u;
+                    }
                     if (act) {
                         *reinterpret_cast<f64x2*>(vL + ep) = v2;
                         if (KL) {
@@ -415,6 +448,9 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                                 f64x2{x2[0] / (v2[0] < a.eps ? a.eps : v2[0]), x2[1] / (v2[1] < a.eps ? a.eps : v2[1])};
                         }
                     }
+                }
+                if constexpr (HOIST) {
+                    if (lane == 0) s_vok[half][w] = vok;
                 }
                 ++seq;
                 __builtin_amdgcn_s_setprio(0);
@@ -574,6 +610,12 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 }
                 vL[e0] = s0;
                 if (has1) vL[e1] = s1;
+                if constexpr (HOIST) {               // (one member: threads from NE on write slots that nothing reads)
+                    const bool real0 = e0 < NE && bin_of(e0 >> 6, (e0 & 63) >> 4) < a.M;
+                    const bool real1 = has1 && bin_of(e1 >> 6, (e1 & 63) >> 4) < a.M;
+                    const unsigned vok = __all((!real0 || range_v_ok(s0)) && (!real1 || range_v_ok(s1))) ? 1u : 0u;
+                    if (lane == 0) s_vok[half][w] = vok;
+                }
                 if (KL) {
                     rL[e0] = xL[e0] / (s0 < a.eps ? a.eps : s0);
                     if (has1) rL[e1] = xL[e1] / (s1 < a.eps ? a.eps : s1);
@@ -700,6 +742,25 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
     }
     };
 
+    if constexpr (HOIST) {
+        // tame (mu_tile_hoisted): one thread per exemplar of the member, its M bins from A2p (the values the LDS dictionary
+        // and A1p hold as well), once per launch
+        static_assert(ATHREADS == 16 * ATILES, "one thread per exemplar of the member");
+        const long j = (long)member * ATILES + (tid >> 4);
+        const int e = tid & 15, q = e >> 2, r = e & 3;
+        bool ok = a.range_hoist != 0 && a.M > 0 && a.M <= 16 * MT && 16 * j + e < a.N && d0 >= 0.0 && d0 <= RANGE_SUM_HI &&
+                  lo <= RANGE_LO_MAX;
+        if (ok) {
+            double cs = 0.0;
+            for (int b = 0; b < a.M; ++b) {
+                const double x = A2p[((j * MT + (b >> 4)) * 2 + (r >> 1)) * 128 + (16 * q + (b & 15)) * 2 + (r & 1)];
+                ok = ok && x >= 0.0;             // (a NaN fails here, an infinity at the sum)
+                cs += x;
+            }
+            ok = ok && cs >= RANGE_SUM_LO && cs <= RANGE_SUM_HI;
+        }
+        tame = __builtin_amdgcn_readfirstlane(__syncthreads_and(ok)) != 0;
+    }
     if constexpr (S::LDS_DICT) {
         if (LONE ? a.M == 4 * MSTEPS - 3 : (a.M > 0 && a.M < PR)) {
             // the member's 32 tiles from A2p (A2p[j][u][r/2][l][r&1] = A[16 u + (l&15)][16 j + 4 (l>>4) + r]), once per launch

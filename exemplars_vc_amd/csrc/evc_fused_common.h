@@ -38,7 +38,11 @@ struct FusedArgs {
     // cooperative launch (k_fused_res, few frame tiles): coop_c workgroups share one 16-frame tile, each owning
     // NT / coop_c exemplar tiles; they exchange their V' partials through coop_buf once per iteration
     int coop_c;              // 1 = off
-    double* coop_buf;        // [2][TT][coop_c][E]
+    // k_fused_all / k_fused_lone with 1, 2, 4 or 8 members, Frobenius: 1 = the update's range test is decided once per sweep
+    // (mu_tile_hoisted), 0 = per unit as everywhere else (EVC_FLAG_NO_RANGE_HOIST).  (It sits in what was padding behind
+    // coop_c: the kernels' argument block keeps its size and every other field its offset.)
+    int range_hoist;
+    double* coop_buf;       // [2][TT][coop_c][E]
     int* coop_cnt;           // [TT] arrival counters, zero at launch
     int* coop_abort;         // set when a wait timed out: the launch's results are void
     int groups;              // k_fused_all: groups of coop_c workgroups walking the frame tiles (set by the launcher)
@@ -189,6 +193,55 @@ __device__ __forceinline__ void mu_tile_guarded(HT& h, const f64x4& p, const f64
             dn = (mode == EVC_EPS_CLAMP && !(dn > eps)) ? eps : dn;         // deComP
             q[r] = p[r] / dn;
             __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h[r] = h[r] * q[r];
+}
+
+// mu_tile_guarded with the range test decided once per sweep (k_fused_all / k_fused_lone with 1, 2, 4 or 8 members,
+// Frobenius).  `safe` is a scalar: with it a unit runs the fast quotients and branches over the test; without it the
+// unit is mu_tile_guarded, word for word.  The fast quotients are the same instructions on the same values either way,
+// so H is bit for bit what the per-unit test gives.
+//
+// Why `safe` is exact.  safe = tame && flagged, where
+//   tame (per member, once per launch): no padding exemplar; every dictionary entry of its 512 exemplars finite and
+//     >= 0; every column sum over the M bins in [2^-100, 2^100]; d0 = l1 (+ pymf's eps) in [0, 2^100]; and
+//     fast_lo(mode, eps) <= the high word of 2^-201 (RANGE_LO_MAX: a large CLAMP eps is not tame);
+//   flagged (per sweep, by the threads that write the combined V' into vL): every element of V of a bin < M has its high
+//     word in [RANGE_V_LO, RANGE_V_HI), that is a value in [2^-100, 2^100) - negative values, zeros, denormals,
+//     infinities and NaNs fail by construction (elements of bins >= M are exact zeros and multiply zeros).
+// Then for every (exemplar e, frame f) of the member's tiles d - d0 = sum_b A[b, e] V[b, f] is a sum of M <= 32 terms that
+// are all >= 0: nothing cancels, and the exact sum lies in [colsum 2^-100, colsum 2^100], inside [2^-200, 2^200].  The
+// chain (an FMA for the lone bin, 4-bin MFMA steps) rounds at most 33 times and the column sum that was tested at most 31
+// times, each by a factor within 1 -+ 2^-53: the computed d lies in [2^-200 (1 - 2^-46), 2^200 (1 + 2^-46) + 2^100], which
+// is inside [2^-201, 2^202) and so far inside the fast range [lo, 2^250) for every lo <= RANGE_LO_MAX.  (The binade
+// between 2^-201 and 2^-200 is that rounding's: a bound of 2^-200 on lo would let a d one ulp below 2^-200 through.)
+constexpr unsigned RANGE_V_LO = 0x39B00000u;        // high word of 2^-100
+constexpr unsigned RANGE_V_HI = 0x46300000u;        // high word of 2^100
+constexpr unsigned RANGE_LO_MAX = 0x33600000u;      // high word of 2^-201
+constexpr double RANGE_SUM_LO = 0x1p-100, RANGE_SUM_HI = 0x1p100;      // column sums and (upper end) d0
+__device__ __forceinline__ bool range_v_ok(double x) { return hi_word(x) - RANGE_V_LO < RANGE_V_HI - RANGE_V_LO; }
+template <class HT>
+__device__ __forceinline__ void mu_tile_hoisted(HT& h, const f64x4& p, const f64x4& dacc, int mode, double eps, unsigned lo,
+                                                bool safe) {
+    double rc[4], q[4];
+    batch_rcp(dacc, rc);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) q[r] = p[r] * rc[r];
+    if (__builtin_expect(!safe, 0)) {
+        const unsigned span = FAST_HI_WORD > lo ? FAST_HI_WORD - lo : 0u;
+        const unsigned worst = max(max(hi_word(dacc[0]) - lo, hi_word(dacc[1]) - lo),
+                                   max(hi_word(dacc[2]) - lo, hi_word(dacc[3]) - lo));
+        if (__builtin_expect(!__all(worst < span), 0)) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                double dn = dacc[r];
+                dn = (mode == EVC_EPS_ZERO_REPLACE && dn == 0.0) ? eps : dn;   // sklearn _nmf.py:620
+                dn = (mode == EVC_EPS_CLAMP && !(dn > eps)) ? eps : dn;         // deComP
+                q[r] = p[r] / dn;
+                __builtin_amdgcn_sched_barrier(0);
+            }
         }
     }
 #pragma unroll

@@ -236,9 +236,13 @@ enum { EVC_LOSS_FROBENIUS = 0, EVC_LOSS_KL = 1 };
  *   NO_LONE_BIN      A/B and tests: M = 25 with 2, 4 or 8 members (N = 1024, 2048, 4096) runs k_fused_all's own 15-MFMA
  *                    unit instead of k_fused_lone's 14 (bin 24 folded into the denominators' start value: the same sums with
  *                    bin 24 added first, so results differ in the last bits; C2 +1.5 %, profiles/lone_bin_README.md).
- *                    evc_solve_info reports EVC_KERNEL_FUSED_ALL either way; no other shape is affected */
+ *                    evc_solve_info reports EVC_KERNEL_FUSED_ALL either way; no other shape is affected
+ *   NO_RANGE_HOIST   A/B and tests: k_fused_all / k_fused_lone with 1, 2, 4 or 8 members (N <= 4096, Frobenius) test every
+ *                    unit's denominators for the fast quotients' range, as every other kernel does, instead of deciding
+ *                    it once per sweep from bounds on V and on the member's dictionary (mu_tile_hoisted,
+ *                    evc_fused_common.h).  Results are bit for bit the same either way */
 enum { EVC_FLAG_NO_FUSED = 1, EVC_FLAG_EXACT_DIV = 2, EVC_FLAG_NO_EXCHANGE = 4, EVC_FLAG_NO_ALL_RESIDENT = 16, EVC_FLAG_PAIR_TILES = 32,
-       EVC_FLAG_NO_LONE_BIN = 64 };
+       EVC_FLAG_NO_LONE_BIN = 64, EVC_FLAG_NO_RANGE_HOIST = 128 };
 
 struct evc_solve_info;
 struct evc_dict;

@@ -1,8 +1,9 @@
 // Stand-alone timing harness for k_fused_all (diagnostic build with in-kernel s_memtime stamps).
 // Build (from the repo root):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DEVC_ALL_TIMING -o /tmp/fused_all_bench tools/ubench/fused_all_bench.hip
-// Run on the GPU box: /tmp/fused_all_bench [N=4096] [rounds=2] [iters=100] [lone=1]
+// Run on the GPU box: /tmp/fused_all_bench [N=4096] [rounds=2] [iters=100] [lone=1] [hoist=1]
 // lone = 1: k_fused_lone where fused_all_launch routes to it (M = 25; N = 1024, 2048, 4096), 0: k_fused_all everywhere.
+// hoist = 1: the update's range test decided once per sweep (FusedArgs.range_hoist), 0: in front of every unit.
 // Prints the kernel time and, for the first round, the mean length (shader cycles) of a sweep step, an
 // exchange step and the barrier wait that follows each, per half.
 #include "../../exemplars_vc_amd/csrc/evc_fused_all.hip"
@@ -22,6 +23,7 @@ int main(int argc, char** argv) {
     const int rounds = argc > 2 ? atoi(argv[2]) : 2;
     const int iters = argc > 3 ? atoi(argv[3]) : 100;
     const bool lone = argc > 4 ? atoi(argv[4]) != 0 : true;
+    const bool hoist = argc > 5 ? atoi(argv[5]) != 0 : true;
     const int M = 25, msteps = 7, mtiles = 2, msp = 8;
     const int NT = N / 16, C = NT / 32;
     int dev = 0, cus = 0;
@@ -90,6 +92,7 @@ int main(int argc, char** argv) {
     a.write_err = 0; a.skip_all_live = 0; a.force_live = 0; a.exact_div = 0; a.loss = EVC_LOSS_FROBENIUS;
     a.eps_mode = EVC_EPS_ZERO_REPLACE; a.eps = 1.1920929e-7; a.l1 = 0.0;
     a.M = M; a.spare_q = -1; a.coop_c = C; a.coop_buf = dbuf; a.coop_cnt = dcnt; a.coop_abort = dcnt + 512; a.groups = 0; a.dbg = ddbg;
+    a.range_hoist = hoist ? 1 : 0;
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     float best = 1e30f;
     for (int rep = 0; rep < 4; ++rep) {
