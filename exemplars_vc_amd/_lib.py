@@ -27,6 +27,7 @@ FLAG_NO_RANGE_HOIST = 128
 LEARN_SKLEARN, LEARN_PYMF = 0, 1
 CDL_BOTH, CDL_DICT_ONLY = 0, 1
 DCL_BOTH, DCL_DICT_ONLY = 0, 1
+CONVEX_BOTH, CONVEX_H_ONLY, CONVEX_G_ONLY = 0, 1, 2
 
 # every symbol include/evc.h declares; tests check that the library exports all of them
 SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_bytes",
@@ -45,6 +46,7 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_deconv_workspace_bytes", "evc_deconv_solve", "evc_deconv_synthesize",
            "evc_deconv_learn_workspace_bytes", "evc_deconv_learn_splits", "evc_deconv_learn",
            "evc_semi_workspace_bytes", "evc_semi_solve",
+           "evc_convex_workspace_bytes", "evc_convex_splits", "evc_convex_learn",
            "evc_prox_workspace_bytes", "evc_prox_solve",
            "evc_prox_masked_workspace_bytes", "evc_prox_masked_solve",
            "evc_prox_learn_workspace_bytes", "evc_prox_learn_block", "evc_prox_learn",
@@ -53,6 +55,7 @@ BETA_MAX_M = 528
 DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 DECONV_LEARN_MAX_R = 4096
 SEMI_MAX_M, SEMI_MAX_N = 1056, 16384
+CONVEX_MAX_M, CONVEX_MAX_T, CONVEX_MAX_R, CONVEX_MAX_S = 1056, 16384, 1024, 16
 PROX_MAX_M, PROX_MAX_N, PROX_MAX_SLOTS = 1056, 16384, 4097
 PROX_LEARN_MAX_M, PROX_LEARN_MAX_N = 1056, 4096
 PROX_MASKED_LEARN_MAX_M, PROX_MASKED_LEARN_MAX_N, PROX_MASKED_LEARN_MAX_S = 1056, 1024, 1 << 28
@@ -190,6 +193,16 @@ class SemiOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
         ("init_mode", C.c_int), ("check_every", C.c_int), ("stop_rule", C.c_int), ("reserved", C.c_int),
         ("eps", C.c_double), ("tol", C.c_double), ("init_value", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class ConvexOpts(C.Structure):
+    """Mirror of `evc_convex_opts` (include/evc.h): options of the convex-NMF learner."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
+        ("check_every", C.c_int), ("update", C.c_int), ("reserved", C.c_int),
+        ("tol", C.c_double), ("eps", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -480,6 +493,18 @@ def lib():
         C.c_int, C.c_int, C.c_int,                                          # M, R, T
         C.POINTER(C.c_int), C.c_int, C.POINTER(DeconvLearnOpts),            # utt_offsets, n_utt, opts
         C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_convex_workspace_bytes.restype = C.c_size_t
+    L.evc_convex_workspace_bytes.argtypes = [C.c_int] * 4
+    L.evc_convex_splits.restype = C.c_int
+    L.evc_convex_splits.argtypes = [C.c_int] * 2
+    L.evc_convex_learn.restype = C.c_int
+    L.evc_convex_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,   # X, G, H, W
+        C.c_int, C.c_int, C.c_int,                                          # M, R, T
+        C.POINTER(ConvexOpts), C.c_void_p, C.c_size_t,                      # opts, workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
         C.c_void_p,                                                         # stream
     ]

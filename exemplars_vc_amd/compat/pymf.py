@@ -15,6 +15,9 @@ call (evc_nmf_learn, pymf surface), W and H are updated in place and `ferr` is a
 `SNMF` is pymf's semi-NMF (pymf/snmf.py): `data` and `W` are signed, only `H` is non-negative.  `compute_w=False` is one
 native call (evc_semi_solve); the default `compute_w=True` forms W = data H^T (H H^T)^-1 on the host (snmf.py:61-64) and
 runs one GPU activation update per iteration, with the same warning.
+
+`CNMF` is pymf's convex NMF (pymf/cnmf.py): data ~ (data G) H with signed data and G, H >= 0.  `factorize` is one native
+call (evc_convex_learn) for every combination of compute_w / compute_h; the default start is pymf's k-means on the host.
 """
 from __future__ import annotations
 
@@ -22,7 +25,8 @@ import logging
 
 import numpy as np
 
-from ..solver import frame_residuals, learn_dictionary, solve_activations, solve_activations_semi, synthesize
+from ..solver import (convex_cluster_start, frame_residuals, learn_dictionary, learn_dictionary_convex, solve_activations,
+                      solve_activations_semi, synthesize)
 
 _EPS = np.finfo(float).eps
 
@@ -187,3 +191,111 @@ class SNMF(NMF):
             np.asarray(self.W, dtype=np.float64), np.asarray(self.data, dtype=np.float64),
             np.asarray(self.H, dtype=np.float64), layout="bin_major", iters=niter, eps=10 ** -9, init="given", dtype="f64",
             device=self._device, **kw)
+
+
+def kmeans_assign(data, num_bases, niter=10):
+    """pymf's Kmeans(data, num_bases).factorize(niter=10).assigned (pymf/kmeans.py, pymf/dist.py:54-127, base.py:238-270) in
+    numpy on the host: centres drawn by random.sample (the global `random` state), every sample assigned to the nearest
+    centre (Euclidean, the first of equals), centres moved to their samples' means (an empty cluster keeps its centre),
+    at most `niter` rounds, stopped by base.py's machine-epsilon test on ||data - W H||_F."""
+    import random
+    data = np.asarray(data)
+    T = data.shape[1]
+    sel = random.sample(range(T), num_bases)
+    W = data[:, np.sort(sel)]
+
+    def vq():
+        d = np.zeros((num_bases, T))
+        for a in range(num_bases):
+            d[a:a + 1, :] = np.sqrt(((data[:, :] - W[:, a:a + 1]) ** 2.0).sum(axis=0)).reshape((1, -1))
+        return np.argmin(d, axis=0)
+
+    assigned = vq()
+    ferr = np.zeros(niter)
+    for i in range(niter):
+        for k in range(num_bases):
+            idx = assigned == k
+            n = np.sum(idx)
+            if n > 0:
+                W[:, k] = np.sum(data[:, idx], axis=1) / n
+        assigned = vq()
+        H = np.zeros((num_bases, T))
+        H[assigned, range(T)] = 1.0
+        ferr[i] = np.sqrt(np.sum((data[:, :] - np.dot(W, H)) ** 2))
+        if i > 1 and np.abs(ferr[i] - ferr[i - 1]) / T < _EPS:
+            break
+    return assigned
+
+
+class CNMF(NMF):
+    """pymf's CNMF(data, num_bases): convex NMF, data ~ W H with W = data G, signed data and G, H >= 0 (pymf/cnmf.py:18-175).
+    `G` is num_samples x num_bases.  factorize() is one native call (evc_convex_learn): per iteration H, then G with the
+    new H, then the error and base.py's machine-epsilon stop; `W`, `G`, `H` and `ferr` are left as pymf leaves them."""
+
+    def __init__(self, data, num_bases=4, **kwargs):
+        NMF.__init__(self, data, num_bases, **kwargs)
+        if self._dictionary_update != "host":
+            raise ValueError("CNMF has no dictionary_update option: both factors are always updated on the device")
+
+    def _init_h(self):
+        """cnmf.py:67-92: H and G from a k-means clustering of the samples, W = data G"""
+        need_h, need_g = not hasattr(self, "H"), not hasattr(self, "G")
+        if need_g and not need_h:
+            raise AttributeError("set .G (num_samples x num_bases) along with .H: pymf builds G only from its own k-means start")
+        if need_h:
+            assign = kmeans_assign(self.data, self._num_bases, 10)
+            G0, self.H = convex_cluster_start(assign, self._num_bases)
+            if need_g:
+                self.G = G0
+        if not hasattr(self, "W"):
+            self.W = np.dot(self.data[:, :], self.G)
+
+    def _init_w(self):
+        pass
+
+    def factorize(self, niter=10, compute_w=True, compute_h=True, compute_err=True, show_progress=False):
+        if show_progress:
+            self._logger.setLevel(logging.INFO)
+        else:
+            self._logger.setLevel(logging.ERROR)
+        if not hasattr(self, "H") or not hasattr(self, "G"):
+            self._init_h()
+        data = np.asarray(self.data, dtype=np.float64)
+        G, H = np.asarray(self.G, dtype=np.float64), np.asarray(self.H, dtype=np.float64)
+        XG = np.dot(data, G)
+        if not hasattr(self, "W"):
+            self.W = XG
+        elif not compute_w and not np.allclose(np.asarray(self.W, dtype=np.float64), XG, rtol=1e-10,
+                                               atol=1e-12 * max(float(np.abs(XG).max()), 1e-300)):
+            raise NotImplementedError("factorize(compute_w=False) with a W that is not data G: pymf then measures ferr against "
+                                      "the stale W while it updates H for data G; evc_convex_learn always measures "
+                                      "||data - (data G) H||.  Set W = data G, or leave W unset")
+        self.ferr = np.zeros(niter)
+        if niter <= 0:
+            return
+        if not compute_w and not compute_h:           # nothing moves: the error repeats and base.py's test fires at i = 2
+            if compute_err:
+                err = float(np.sqrt(np.sum((data - np.dot(np.asarray(self.W, dtype=np.float64), H)) ** 2)))
+                self.ferr = np.full(min(niter, 2), err) if niter >= 3 else np.full(niter, err)
+            return
+        update = "both" if compute_w and compute_h else ("h" if compute_h else "g")
+        W, G, H, info = learn_dictionary_convex(data, G, H, layout="bin_major", iters=niter, update=update,
+                                                check_every=1 if compute_err else 0, tol=self._EPS if compute_err else 0.0,
+                                                eps=10 ** -9, dtype="f64", device=self._device, info=True)
+        if compute_w:
+            if isinstance(self.G, np.ndarray) and self.G.dtype == np.float64:
+                self.G[...] = G                  # in place, like `self.G *= ...`
+            else:
+                self.G = G
+            self.W = W
+        if compute_h:
+            self.H = H
+        if compute_err:
+            n = info["n_iter"]
+            ferr = info["err"][1:1 + n]
+            if n < niter or (n >= 3 and abs(ferr[n - 1] - ferr[n - 2]) / self._num_samples < self._EPS):
+                self.ferr = ferr[:n - 1].copy()     # cnmf.py:174: ferr = ferr[:i], i = n - 1
+            else:
+                self.ferr[:n] = ferr
+            for i, e in enumerate(self.ferr):
+                self._logger.info("FN: %s (%s/%s)" % (e, i + 1, niter))

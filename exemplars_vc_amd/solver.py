@@ -1486,6 +1486,130 @@ def compact_dictionary(A, B, R, *, iters=100, tol=0.0, layout="bin_major", prepa
     return Wa, Wb, G, info
 
 
+_CONVEX_UPDATES = {"both": _lib.CONVEX_BOTH, "h": _lib.CONVEX_H_ONLY, "g": _lib.CONVEX_G_ONLY}
+
+
+def convex_cluster_start(assign, R):
+    """pymf's convex-NMF start from cluster labels (cnmf.py:77-89), float64 numpy: G0 = (one-hot + 0.01) / cluster size
+    (T x R), H0 = one-hot + 0.2 (R x T)"""
+    assign = np.asarray(assign)
+    if assign.ndim != 1 or len(assign) < 1 or assign.min() < 0 or assign.max() >= R:
+        raise ValueError(f"assign must hold one label in 0 .. {R - 1} per exemplar")
+    T = len(assign)
+    num = np.bincount(assign, minlength=R).astype(np.float64)
+    H0 = np.zeros((R, T))
+    H0[assign, np.arange(T)] = 1.0
+    H0 += 0.2
+    G0 = np.zeros((T, R))
+    G0[np.arange(T), assign] = 1.0
+    G0 += 0.01
+    G0 /= num[assign].reshape(-1, 1)
+    return G0, H0
+
+
+def learn_dictionary_convex(X, G0, H0, *, layout, iters, update="both", check_every=1, tol=0.0, eps=1e-9, dtype=None,
+                            device=None, info=False, out_g=None, out_h=None, loop_events=None, splits=0, waves=0):
+    """Convex NMF on the GPU (evc_convex_learn; Ding, Li and Jordan, pymf's CNMF): X ~ (X G) H with X SIGNED and G, H >= 0,
+    so that the R atoms W = X G are non-negative combinations of the exemplars (the columns of X) themselves.  X and H are
+    addressed as in learn_dictionary; G is always T x R, a row per exemplar, whatever the layout.  G0 / H0: the
+    non-negative start.  update: "both", or "h" / "g" to leave the other factor untouched.  The error ||X - (X G) H||_F is
+    evaluated at the start and every `check_every` iterations; with tol > 0 the loop stops, from the third check on, when
+    |err - err_prev| / T < tol (pymf: check_every=1, tol=2.22e-16).  At most 1056 bins, 16384 exemplars and
+    min(T, 1024) atoms.
+
+    Returns (W, G, H) (numpy in -> numpy out, device tensor in -> device tensor out), W addressed like X; with info=True
+    also dict(n_iter=int, err=[1 + iters // check_every] errors (NaN where not evaluated), splits=k-ranges of the Gram
+    sweeps).  out_g / out_h: device tensors updated in place (they then hold the start, G0 / H0 are ignored when None).
+    splits / waves: tuning and tests, 1..16 k-ranges and 8, 4 or 2 wavefronts per workgroup of the sweeps.
+    No CPU fallback: without a HIP device this raises RuntimeError."""
+    if update not in _CONVEX_UPDATES:
+        raise ValueError(f"update must be one of {sorted(_CONVEX_UPDATES)}, got {update!r}")
+    lay = _LAYOUTS[layout]
+    bm = lay == _lib.BIN_MAJOR
+    g_like = G0 if G0 is not None else out_g
+    xshape, gshape = tuple(getattr(X, "shape", ())), tuple(getattr(g_like, "shape", ()))
+    if len(xshape) != 2 or len(gshape) != 2:
+        raise ValueError(f"X and G must be 2-D, got shapes {xshape} and {gshape}")
+    M, T = xshape if bm else xshape[::-1]
+    R = gshape[1]
+    if gshape[0] != T:
+        raise ValueError(f"G must have one row per exemplar: X has {T}, G has shape {gshape}")
+    if M < 1 or T < 1 or R < 1:
+        raise ValueError(f"empty convex-NMF problem M={M}, T={T}, R={R}")
+    if M > _lib.CONVEX_MAX_M or T > _lib.CONVEX_MAX_T or R > min(T, _lib.CONVEX_MAX_R):      # what the ABI answers with -3
+        raise ValueError(f"unsupported convex-NMF shape: M = {M} bins, T = {T} exemplars, R = {R} atoms; the kernel holds at "
+                         f"most {_lib.CONVEX_MAX_M} bins, {_lib.CONVEX_MAX_T} exemplars and min(T, {_lib.CONVEX_MAX_R}) atoms")
+    tdtype, dcode = _pick_dtype(dtype, X, g_like)
+    device = require_device(device)
+    torch = _torch()
+    X_d, x_np = _to_dev(X, tdtype, device)
+    G_d = _factor_start(G0, out_g, "g", tdtype, device)
+    H_d = _factor_start(H0, out_h, "h", tdtype, device)
+    if tuple(G_d.shape) != (T, R) or tuple(H_d.shape) != ((R, T) if bm else (T, R)):
+        raise ValueError(f"X {xshape}, G {tuple(G_d.shape)} and H {tuple(H_d.shape)} do not fit ({layout})")
+    W_d = torch.empty((M, R) if bm else (R, M), dtype=tdtype, device=device)
+    opts = _lib.ConvexOpts()
+    opts.iters, opts.check_every, opts.update = int(iters), int(check_every), _CONVEX_UPDATES[update]
+    opts.tol, opts.eps = float(tol), float(eps)
+    opts.reserved = (int(waves) & 0xff) << 16
+    _common_opts(opts, dcode, lay, loop_events, splits)
+    L = _lib.lib()
+    nbytes = int(L.evc_convex_workspace_bytes(M, R, T, dcode))
+    extra = int(splits) - int(L.evc_convex_splits(R, T))
+    if nbytes and extra > 0:                     # forced k-ranges beyond the plan's: their slabs of partial sums
+        nbytes += 2 * (extra + 1) * T * R * (8 if dcode == _lib.F64 else 4) + 256
+    p = types.SimpleNamespace(device=device)
+    head = (X_d.data_ptr(), _ld(X_d), G_d.data_ptr(), _ld(G_d), H_d.data_ptr(), _ld(H_d), W_d.data_ptr(), _ld(W_d), M, R, T)
+    (n_iter,), err = _learn_run(L, "evc_convex_learn", p, head, opts, nbytes,
+                                f"unsupported convex-NMF shape M={M}, T={T}, R={R}", _n_slots(iters, check_every),
+                                info or tol > 0, info)
+    res = (W_d, G_d, H_d)
+    if x_np and out_g is None and out_h is None:
+        res = tuple(_to_host(t) for t in res)
+    if info:
+        res += ({"n_iter": n_iter, "err": err, "splits": _splits_info(splits, L.evc_convex_splits, R, T)},)
+    return res
+
+
+def compact_dictionary_convex(A, B, R, *, iters=100, tol=0.0, assign=None, layout="bin_major", dtype=None, device=None):
+    """A compact parallel dictionary of SIGNED exemplars (mel-cepstra, MFCCs): the aligned source and target exemplars are
+    stacked, D = [A; B] ((Ma + Mb) x N), and factored by learn_dictionary_convex, D ~ (D G) H with G, H >= 0.  The atoms
+    [Wa; Wb] = D G = [A G; B G] are non-negative combinations of the exemplars with the SAME weights on both sides, so they
+    stay parallel whatever the sign of the features; (Wa, Wb) then stand in for (A, B) in convert_semi at (R / N)^2 of the
+    Gram sweep's cost.
+
+    The start is deterministic: exemplar t belongs to cluster assign[t] (default t * R // N: aligned exemplars are in time
+    order, neighbours are alike; or the caller's own labels, 0 .. R-1), G0 = (one-hot + 0.01) / cluster size and
+    H0 = one-hot + 0.2, pymf's construction.  The error is checked every iteration (tol: pymf's stop).  Returns
+    (Wa, Wb, G, H, info) in the caller's orientation (G is N x R); info as learn_dictionary_convex's."""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    bm = lay == _lib.BIN_MAJOR
+    ashape, bshape = tuple(getattr(A, "shape", ())), tuple(getattr(B, "shape", ()))
+    if len(ashape) != 2 or len(bshape) != 2 or ashape[1 if bm else 0] != bshape[1 if bm else 0]:
+        raise ValueError(f"A and B must be 2-D with the same number of exemplars, got shapes {ashape} and {bshape}")
+    N, R = ashape[1 if bm else 0], int(R)
+    if not 1 <= R <= N:
+        raise ValueError(f"R must be between 1 and the number of exemplars ({N}), got {R}")
+    G0, H0 = convex_cluster_start((np.arange(N) * R) // N if assign is None else np.asarray(assign, dtype=np.int64), R)
+    if assign is not None and len(assign) != N:
+        raise ValueError(f"assign must hold one label per exemplar ({N}), got {len(assign)}")
+    tdtype, _ = _pick_dtype(dtype, A, B)
+    device = require_device(device)
+    A_d, a_np = _to_dev(A, tdtype, device)
+    B_d, _ = _to_dev(B, tdtype, device)
+    D = torch.cat([A_d, B_d], dim=0 if bm else 1)
+    Ma = ashape[0 if bm else 1]
+    G_d = torch.from_numpy(G0).to(device=device, dtype=tdtype)
+    H_d = torch.from_numpy(H0 if bm else np.ascontiguousarray(H0.T)).to(device=device, dtype=tdtype)
+    W, G, H, info = learn_dictionary_convex(D, None, None, layout=layout, iters=iters, tol=tol, check_every=1, dtype=tdtype,
+                                            device=device, info=True, out_g=G_d, out_h=H_d)
+    Wa, Wb = (W[:Ma], W[Ma:]) if bm else (W[:, :Ma], W[:, Ma:])
+    if a_np:
+        return _to_host(Wa), _to_host(Wb), _to_host(G), _to_host(H), info
+    return Wa, Wb, G, H, info
+
+
 _DCL_UPDATES = {"both": _lib.DCL_BOTH, "dict": _lib.DCL_DICT_ONLY}
 
 

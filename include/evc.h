@@ -64,6 +64,10 @@
  *   evc_semi_solve  replaces pymf's SNMF(data, num_bases).factorize(compute_w=False) (pymf/snmf.py:66-85,
  *                   pymf/base.py:208-270): semi-NMF activations, signed data and dictionary, non-negative activations -
  *                   the solve for the signed mel-cepstra of the dictionary build; evc_semi_workspace_bytes sizes it
+ *   evc_convex_learn  replaces pymf's CNMF(data, num_bases).factorize() (pymf/cnmf.py:97-175): convex NMF,
+ *                   X ~ (X G) H with G, H >= 0 and signed X - the atoms are non-negative combinations of the exemplars
+ *                   themselves, which compacts a signed parallel dictionary; evc_convex_workspace_bytes sizes it,
+ *                   evc_convex_splits tells the k-ranges of its Gram sweeps
  *   evc_prox_solve  replaces deComP's lasso.solve / nnls.solve with method ista, fista, ista_pos, fista_pos
  *                   (decomp/lasso.py:97-189, 274-297, 388-415): L1-penalised activations by proximal gradient, signed or
  *                   non-negative, with exact zeros; evc_prox_workspace_bytes sizes it
@@ -1111,6 +1115,66 @@ size_t evc_semi_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
 int evc_semi_solve(const void* A, int lda, const void* X, int ldx, void* H, int ldh, int M, int N, int T,
                    const int* utt_offsets, int n_utt, const evc_semi_opts* opts, void* workspace, size_t workspace_bytes,
                    int* n_iter_out, double* err_out, evc_stream_t stream);
+
+/* Convex NMF (Ding, Li and Jordan 2010; pymf cnmf.py:97-175): X ~ (X G) H with X (M x T) SIGNED, G (T x R) and H (R x T)
+ * non-negative, so that the R atoms W = X G are non-negative combinations of the T exemplars (columns of X) themselves.
+ * With pos(m) = (|m| + m) / 2 and neg(m) = (|m| - m) / 2, formed as written, and K = X^T X (T x T, once per call), per
+ * iteration:
+ *     Np = pos(K) G;  Nn = neg(K) G                                                  (T x R each; Gram sweep 1)
+ *     update H:  Sp = G^T Np;  Sn = G^T Nn  (R x R);
+ *                Ha = Np + H^T Sn;  Hb = (Nn + H^T Sp) + eps;  H^T <- H^T * sqrt(Ha / Hb)
+ *     update G (with the new H; Np, Nn of the old G):  C = H H^T  (R x R);
+ *                Wa = pos(K) H^T + Nn C;  Wb = (neg(K) H^T + Np C) + eps;  G <- G * sqrt(Wa / Wb)      (Gram sweep 2)
+ * pymf's T x T product H^T G^T is never formed: H^T (G^T Nn) has an R x R matrix in the middle, and every term is a sum of
+ * non-negative products.  pos(K) B and neg(K) B are two sums of non-negative products of their own (never
+ * (|K| B -+ K B) / 2): exact zeros of G and H stay exact.  eps = 0 is accepted and may give 0 / 0 = NaN, as in pymf.
+ * The error, at the start and after every `check_every` iterations, is ||X - (X G) H||_F (float64 residuals, a fixed
+ * summation order); from the third evaluated error after the start on, the loop stops when |err - err_prev| / T < tol,
+ * decided on the device (pymf: check_every = 1, tol = 2.22e-16; base.py:189-206, cnmf.py:172-175; tol = 0 never stops, a
+ * NaN error compares false and runs on).  The stopping iteration's updates are kept.
+ * k_convex_sweep forms [pos(K) B, neg(K) B] for B = G and B = H^T: a workgroup of W wavefronts owns 16 W rows x 64 columns,
+ * streams K (symmetric: rows read as columns) and B over k ascending through LDS, splits every fragment of K in registers
+ * and feeds two accumulators per output on the matrix cores.  Where R is too small to fill the chip k is split into S
+ * contiguous ranges (at most 16, of at least 64 exemplars) whose partial sums go to the workspace and are added in ascending
+ * order, and where that is not enough the row blocks narrow (W = 8, 4, 2): W and S are functions of (T, R) alone
+ * (evc_convex_splits tells S), there are no float atomics, and the same call gives the same bits every time.  With S = 1 sweep 2's epilogue applies the update of G (each element is
+ * read and written by one lane, and the sweep streams H^T, never G, so G is updated where it stands).
+ *   X, H, W : addressed as in evc_nmf_learn (W is M x R); G is T x R, a row per exemplar: G[t * ldg + r], ldg >= R
+ *   G, H    : the non-negative start on entry, updated in place; nothing outside their logical elements is written
+ *   W       : NULL, or receives X G of the returned G (iters = 0: the only thing written)
+ *   M : 1 .. 1056, T : 1 .. 16384, R : 1 .. min(T, 1024) (larger: -3)
+ *   n_iter_out : host int or NULL: iterations carried out
+ *   err_out    : host, 1 + iters / check_every doubles or NULL (at most 4097 slots; more: -1): the error at the start, then at
+ *                every check (NaN where not evaluated)
+ * float32 inputs are learnt in float32; the errors are summed in float64.  The workspace holds K (round_up(T, 128)^2
+ * elements: 2 GiB at T = 16384 in float64), four T x R and two R x R arrays, the k-ranges' partial sums and the check's
+ * products: ask evc_convex_workspace_bytes (a forced S beyond evc_convex_splits needs 2 T R elements more per range).
+ * The three R x R products that contract over all of T (G^T Np, G^T Nn, H H^T) are split over k as well, into ranges that
+ * depend on (T, R) alone and are added in ascending order.
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: as evc_semi_solve. */
+enum { EVC_CONVEX_BOTH = 0, EVC_CONVEX_H_ONLY = 1, EVC_CONVEX_G_ONLY = 2 };
+typedef struct evc_convex_opts {
+    int struct_bytes;  /* sizeof(evc_convex_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int iters;         /* >= 0 */
+    int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
+    int update;        /* EVC_CONVEX_* */
+    int reserved;      /* 0; bits 8..15, tuning and tests: that many k-ranges (1 .. 16) instead of evc_convex_splits();
+                          bits 16..23, likewise: 8, 4 or 2 wavefronts (128, 64 or 32 rows) per workgroup of the sweeps;
+                          anything else: status -1 */
+    double tol;        /* >= 0 */
+    double eps;        /* >= 0, added to Hb and Wb (pymf: 1e-9) */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_convex_opts;
+/* bytes of workspace evc_convex_learn needs (0: invalid or unsupported sizes, wherever the call would return -1 or -3) */
+size_t evc_convex_workspace_bytes(int M, int R, int T, int dtype);
+/* k-ranges the Gram sweeps are split into, 1 .. 16: a function of the sizes only (0: invalid or unsupported sizes) */
+int evc_convex_splits(int R, int T);
+int evc_convex_learn(const void* X, int ldx, void* G, int ldg, void* H, int ldh, void* W, int ldw, int M, int R, int T,
+                     const evc_convex_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
+                     evc_stream_t stream);
 
 /* Sparse activations by proximal gradient (ISTA / FISTA; deComP lasso.py:97-189, 228-256, 274-297, 331-357, 388-415 and
  * math_utils/eigen.py:9-20):   min_h  1/2 ||x - A h||^2 + sum_n lambda_n h_n,   h >= 0 (EVC_PROX_POSITIVE) or h signed
