@@ -317,6 +317,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) dl[r] = __builtin_fma(al[r], vl, d0);
                 }
+                EVC_STAMP(3);                    // (stamps build: the sweep's head ends here)
                 f64x4 vn[MT];
 #pragma unroll
                 for (int u = 0; u < MT; ++u) vn[u] = f64x4{0, 0, 0, 0};
@@ -335,6 +336,8 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                     __builtin_amdgcn_sched_barrier(0);
                     if constexpr (LONE) {
                         if (k + 1 < AKT) {
+                            // (the four words waited for together: one s_waitcnt in front of the fold, not one per FMA)
+                            asm volatile("" : "+v"(al[0]), "+v"(al[1]), "+v"(al[2]), "+v"(al[3]));
 #pragma unroll
                             for (int r = 0; r < 4; ++r) dl[r] = __builtin_fma(al[r], vl, d0);
                         }
@@ -347,6 +350,12 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                     } else {
                         mu_tile_guarded(h[k], p[k], d, mode, eps, lo);
                     }
+                    // One vector phase per unit: the update is closed towards the V' MFMAs as well.  Left open, the
+                    // compiler sinks the last h *= q behind the first V' MFMA and the next unit's fold behind the third - two
+                    // more MFMA <-> vector switches per unit (profiles/step_chain_README.md).  Not in the reduce-scatter
+                    // instances: their step is the exchange, which shares its SIMDs with this sweep, and with the MFMAs
+                    // packed tighter C5 (32 members) ran 0.8 % slower - they keep the order the compiler chooses.
+                    if constexpr (C >= 1) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int u = 0; u < MT; ++u)
 #pragma unroll

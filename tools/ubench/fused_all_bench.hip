@@ -5,7 +5,7 @@
 // lone = 1: k_fused_lone where fused_all_launch routes to it (M = 25; N = 1024, 2048, 4096), 0: k_fused_all everywhere.
 // hoist = 1: the update's range test decided once per sweep (FusedArgs.range_hoist), 0: in front of every unit.
 // Prints the kernel time and, for the first round, the mean length (shader cycles) of a sweep step, an
-// exchange step and the barrier wait that follows each, per half.
+// exchange step and the barrier wait that follows each, and of the sweep's head (stamp 3), per half.
 #include "../../exemplars_vc_amd/csrc/evc_fused_all.hip"
 
 #include <cstdio>
@@ -114,15 +114,17 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(dbg.data(), ddbg, ndbg * 8, hipMemcpyDeviceToHost));
     const int NS = 2 * iters + 1;
     for (int half = 0; half < 2; ++half) {
-        double sw = 0, ex = 0, bs = 0, be = 0; long ns = 0, ne = 0;
+        double sw = 0, ex = 0, bs = 0, be = 0, hd = 0; long ns = 0, ne = 0;
         for (int b = 0; b < pairs * C; ++b)
             for (int st = 2; st < NS - 2; ++st) {
                 const long long* d = &dbg[(((size_t)b * 2 + half) * NS + st) * 4];
                 const bool mine = (st & 1) == half;
-                if (mine) { sw += d[1] - d[0]; bs += d[2] - d[1]; ++ns; } else { ex += d[1] - d[0]; be += d[2] - d[1]; ++ne; }
+                if (mine) { sw += d[1] - d[0]; bs += d[2] - d[1]; hd += d[3] - d[0]; ++ns; } else { ex += d[1] - d[0]; be += d[2] - d[1]; ++ne; }
             }
         printf("half %d: sweep %.0f cyc (+barrier wait %.0f)   exchange %.0f cyc (+barrier wait %.0f)\n", half,
                sw / ns, bs / ns, ex / ne, be / ne);
+        // stamp 3 stands in front of the sweep's first unit: the head is what lies between the step's start and it
+        printf("half %d: sweep's head (step start to the first unit) %.0f cyc\n", half, hd / ns);
     }
     // the step boundary: from behind the barrier (stamp 2) to the next step's stamp 0 (the s_fail test and the loop's branch)
     for (int half = 0; half < 2; ++half) {
