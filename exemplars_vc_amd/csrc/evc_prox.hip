@@ -24,7 +24,8 @@
 // Every output's sum runs over k = 0 .. N - 1 in one fixed MFMA order: no split over k, no float atomics, no exchange between
 // workgroups, no residency assumption.  A column of the accumulators only ever sees its own column of W: a batch gives
 // bitwise the per-utterance results and a NaN stays in its frame's column.
-// k_prox_state, k_prox_start, k_prox_finish and k_prox_check live in evc_prox_kernels.h, which evc_prox_masked.hip includes too.
+// k_prox_start, k_prox_finish and k_prox_check live in evc_prox_kernels.h, which evc_prox_masked.hip includes too, with the host
+// frame of a call (prox_solve_frame): here are the preparation and the sweep it is given.
 #include "evc_prox_kernels.h"
 
 namespace evc {
@@ -223,37 +224,18 @@ int prox_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
     const ProxWs w = carve_prox(ws, N, T_, n_utt, o.dtype);
     if (w.bytes > ws_bytes) return ST_WORKSPACE;
     const bool fm = o.layout == EVC_FRAME_MAJOR;
-    const int n_slots = prox_slots(o.iters, o.check_every);
     const int NP = round_up(N, PROX_BN);
     const long as_n = fm ? lda : 1, as_m = fm ? 1 : lda, xs_t = fm ? ldx : 1, xs_m = fm ? 1 : ldx;
     const long hs_t = fm ? ldh : 1, hs_n = fm ? 1 : ldh;
 
-    const int whole[2] = {0, T_};
-    HIP_TRY(hipMemcpyAsync(w.offs, utt_offsets ? utt_offsets : whole, sizeof(int) * ((size_t)n_utt + 1), hipMemcpyHostToDevice,
-                           s));
-    long n_state = (long)n_utt * n_slots;
-    if (n_state < T_) n_state = T_;
-    if (n_state < n_utt) n_state = n_utt;
-    hipLaunchKernelGGL(k_prox_state, dim3(prox_blocks_of(n_state)), dim3(256), 0, s, w.offs, n_utt, T_, n_slots, w.stop, w.trace,
-                       w.frame_utt);
-    HIP_TRY(hipGetLastError());
-
-    const unsigned nb = prox_blocks_of((long)N * T_);
-    if (T_ > 0 && o.iters == 0) {               // the start stays as it is: nothing is scaled
-        if (o.init_mode == EVC_INIT_CONST) {
-            hipLaunchKernelGGL(k_prox_finish<T>, dim3(nb), dim3(256), 0, s, H, hs_t, hs_n, (const T*)nullptr, N, T_, fm ? 1 : 0, 1,
-                               (T)o.init_value);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    if (T_ > 0 && o.iters > 0) {
-        T* G = reinterpret_cast<T*>(w.G);
-        T* P = reinterpret_cast<T*>(w.P);
-        T* Wb[2] = {reinterpret_cast<T*>(w.W[0]), reinterpret_cast<T*>(w.W[1])};
-        T* thr = reinterpret_cast<T*>(w.thr);
-        T* tolv = reinterpret_cast<T*>(w.tolv);
-        T* d = reinterpret_cast<T*>(w.d);
-        T* lip = reinterpret_cast<T*>(w.lip);
+    T* G = reinterpret_cast<T*>(w.G);
+    T* P = reinterpret_cast<T*>(w.P);
+    T* Wb[2] = {reinterpret_cast<T*>(w.W[0]), reinterpret_cast<T*>(w.W[1])};
+    T* thr = reinterpret_cast<T*>(w.thr);
+    T* tolv = reinterpret_cast<T*>(w.tolv);
+    T* d = reinterpret_cast<T*>(w.d);
+    T* lip = reinterpret_cast<T*>(w.lip);
+    auto prepare = [&]() -> int {
         HIP_TRY(hipMemsetAsync(G, 0, (size_t)NP * NP * sizeof(T), s));
         HIP_TRY(gemm_strided<T>(A, as_n, as_m, A, as_n, as_m, G, NP, 1, N, N, M, s));
         HIP_TRY(gemm_strided<T>(A, as_n, as_m, X, xs_t, xs_m, P, T_, 1, N, T_, M, s));
@@ -265,54 +247,26 @@ int prox_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_prox_lip<T>, dim3(1), dim3(256), 0, s, lip, N, (T)o.lipschitz, thr);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_prox_start<T>, dim3(nb), dim3(256), 0, s, P, H, hs_t, hs_n, Wb[0], (const T*)d, N, T_, fm ? 1 : 0,
-                           o.normalize, o.init_mode == EVC_INIT_GIVEN ? 1 : 0, (T)o.init_value);
-        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_prox_start<T>, dim3(prox_blocks_of((long)N * T_)), dim3(256), 0, s, P, H, hs_t, hs_n, Wb[0],
+                           (const T*)d, N, T_, fm ? 1 : 0, o.normalize, o.init_mode == EVC_INIT_GIVEN ? 1 : 0, (T)o.init_value);
+        return (int)hipGetLastError();
+    };
 
-        if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
-        ProxArgs<T> a;
-        a.G = G; a.P = P; a.X = H; a.xs_t = hs_t; a.xs_n = hs_n; a.thr = thr; a.tolv = tolv; a.s = lip;
-        a.frame_utt = w.frame_utt; a.stop = w.stop;
-        a.N = N; a.NP = NP; a.T_ = T_; a.signed_mode = o.mode == EVC_PROX_SIGNED ? 1 : 0;
-        const int W = prox_waves(N, T_);
-        const int row_blocks = (N + 16 * W - 1) / (16 * W);
-        const dim3 grid((unsigned)((T_ + PROX_BT - 1) / PROX_BT), (unsigned)row_blocks);
-        ProxMomentum mom(o.momentum);
-        for (int i = 0; i < o.iters; ++i) {
-            const bool check = o.check_every > 0 && i % o.check_every == 0;
-            a.Win = Wb[i & 1]; a.Wout = Wb[(i + 1) & 1];
-            a.partials = check ? w.partials : nullptr;
-            a.c = (T)mom.next(i);
-            if (W == 8) hipLaunchKernelGGL((k_prox_sweep<T, 8>), grid, dim3(512), 0, s, a);
-            else hipLaunchKernelGGL((k_prox_sweep<T, 4>), grid, dim3(256), 0, s, a);
-            HIP_TRY(hipGetLastError());
-            if (check) {
-                hipLaunchKernelGGL(k_prox_check, dim3(n_utt), dim3(256), 0, s, (const double*)w.partials, row_blocks, T_,
-                                   (const int*)w.offs, w.stop, w.trace, n_slots, i / o.check_every, i + 1, o.stop_rule);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-        if (o.normalize) {
-            hipLaunchKernelGGL(k_prox_finish<T>, dim3(nb), dim3(256), 0, s, H, hs_t, hs_n, (const T*)d, N, T_, fm ? 1 : 0, 0, T(0));
-            HIP_TRY(hipGetLastError());
-        }
-    } else {
-        if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
-        if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    }
-
-    if (!n_iter_out && !(change_out && n_slots > 0)) return 0;
-    int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
-    if (!ni_h) return (int)hipErrorOutOfMemory;
-    hipError_t e = hipMemcpyAsync(ni_h, w.stop, sizeof(int) * n_utt, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && change_out && n_slots > 0)
-        e = hipMemcpyAsync(change_out, w.trace, sizeof(double) * n_utt * n_slots, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    for (int u = 0; e == hipSuccess && n_iter_out && u < n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : o.iters;
-    free(ni_h);
-    HIP_TRY(e);
-    return 0;
+    ProxArgs<T> a;
+    a.G = G; a.P = P; a.X = H; a.xs_t = hs_t; a.xs_n = hs_n; a.thr = thr; a.tolv = tolv; a.s = lip;
+    a.frame_utt = w.frame_utt; a.stop = w.stop;
+    a.N = N; a.NP = NP; a.T_ = T_; a.signed_mode = o.mode == EVC_PROX_SIGNED ? 1 : 0;
+    const int W = prox_waves(N, T_);
+    const int row_blocks = (N + 16 * W - 1) / (16 * W);
+    const dim3 grid((unsigned)((T_ + PROX_BT - 1) / PROX_BT), (unsigned)row_blocks);
+    auto sweep = [&](int, const T* Win, T* Wout, double* partials, T c) -> int {
+        a.Win = Win; a.Wout = Wout; a.partials = partials; a.c = c;
+        if (W == 8) hipLaunchKernelGGL((k_prox_sweep<T, 8>), grid, dim3(512), 0, s, a);
+        else hipLaunchKernelGGL((k_prox_sweep<T, 4>), grid, dim3(256), 0, s, a);
+        return (int)hipGetLastError();
+    };
+    return prox_solve_frame<T>(o, w, Wb, (const T*)d, row_blocks, H, hs_t, hs_n, fm ? 1 : 0, N, T_, utt_offsets, n_utt,
+                               n_iter_out, change_out, s, prepare, sweep);
 }
 
 }  // namespace

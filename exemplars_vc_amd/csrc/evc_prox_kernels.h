@@ -1,10 +1,12 @@
-// evc_prox_kernels.h - the small kernels the two proximal-gradient drivers share: the per-call state,
-// the start, the finish and the per-utterance check of the stop statistic, with the helpers of their arithmetic.  Two
-// translation units include this file, evc_prox.hip (evc_prox_solve) and evc_prox_masked.hip (evc_prox_masked_solve), each into
-// an unnamed namespace of its own: both get the same device code from the same text.  The sweeps themselves stay with their
-// drivers.
+// evc_prox_kernels.h - the small kernels the two proximal-gradient drivers share: the start, the
+// finish and the per-utterance check of the stop statistic, with the helpers of their arithmetic (the per-call state is
+// evc_solve_state.h's, which evc_semi.hip includes too) - and prox_solve_frame, the host frame of a call around the driver's
+// own preparation and sweep.  Two translation units include this file, evc_prox.hip (evc_prox_solve) and
+// evc_prox_masked.hip (evc_prox_masked_solve), each into an unnamed namespace of its own: both get the same device code from
+// the same text.  The sweeps themselves stay with their drivers.
 #pragma once
 #include "evc_prox_plan.h"
+#include "evc_solve_state.h"
 
 namespace evc {
 
@@ -20,22 +22,6 @@ __device__ __forceinline__ double psqrt(double v) { return sqrt(v); }
 __device__ __forceinline__ float psqrt(float v) { return sqrtf(v); }
 // numpy's maximum: a NaN on either side wins
 __device__ __forceinline__ double nanmax(double a, double b) { return a != a ? a : (b != b ? b : (a > b ? a : b)); }
-
-// stop = 0, trace = NaN, frame_utt[t] = the utterance of frame t (the largest u with offs[u] <= t)
-__global__ void k_prox_state(const int* __restrict__ offs, int n_utt, int T_, int n_slots, int* stop, double* trace,
-                             int* frame_utt) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_utt) stop[i] = 0;
-    if (i < (long)n_utt * n_slots) trace[i] = __builtin_nan("");
-    if (i < T_) {
-        int lo = 0, hi = n_utt - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (offs[mid] <= i) lo = mid; else hi = mid - 1;
-        }
-        frame_utt[i] = lo;
-    }
-}
 
 // over the N x T_ elements: P_n <- P_n / d_n (P == NULL: the caller's P is already in the scaled dictionary);  X_0 = (H | value) d_n,
 // left in H and copied to W_0 (normalize == 0: no arithmetic)
@@ -93,6 +79,39 @@ __global__ __launch_bounds__(256) void k_prox_check(const double* __restrict__ p
 }
 
 unsigned prox_blocks_of(long n) { return (unsigned)((n + 255) / 256); }
+
+// What a call of either driver does around its own part, in launch order: the state head; without iterations the constant
+// start, if asked for (a given start stays as it is: nothing is scaled); with frames and iterations prepare() - the driver's
+// once-per-call work, which ends with k_prox_start leaving X_0 in H and Wb[0] - then prox_loop over the driver's sweep with
+// k_prox_check as its check, and the division of H by d under `normalize`; the read-back.  t: the tail of the driver's
+// workspace; row_blocks: the row blocks of the sweep that writes t.partials; H(t, n) at t hs_t + n hs_n, n_fast: n is its
+// contiguous direction.
+template <typename T, typename Opts, typename Prepare, typename Sweep>
+int prox_solve_frame(const Opts& o, const ProxTail& t, T* const Wb[2], const T* d, int row_blocks, T* H, long hs_t, long hs_n,
+                     int n_fast, int N, int T_, const int* utt_offsets, int n_utt, int* n_iter_out, double* change_out,
+                     hipStream_t s, Prepare prepare, Sweep sweep) {
+    const int n_slots = prox_slots(o.iters, o.check_every);
+    HIP_TRY(solve_state_head(utt_offsets, n_utt, T_, n_slots, t.offs, t.stop, t.trace, t.frame_utt, s));
+    const unsigned nb = prox_blocks_of((long)N * T_);
+    if (T_ > 0 && o.iters == 0 && o.init_mode == EVC_INIT_CONST) {
+        hipLaunchKernelGGL(k_prox_finish<T>, dim3(nb), dim3(256), 0, s, H, hs_t, hs_n, (const T*)nullptr, N, T_, n_fast, 1,
+                           (T)o.init_value);
+        HIP_TRY(hipGetLastError());
+    }
+    const bool live = T_ > 0 && o.iters > 0;
+    if (live) HIP_TRY(prepare());
+    auto check = [&](int slot, int applied) -> int {
+        hipLaunchKernelGGL(k_prox_check, dim3(n_utt), dim3(256), 0, s, (const double*)t.partials, row_blocks, T_,
+                           (const int*)t.offs, t.stop, t.trace, n_slots, slot, applied, o.stop_rule);
+        return (int)hipGetLastError();
+    };
+    HIP_TRY(prox_loop<T>(o, live, Wb, t.partials, s, sweep, check));
+    if (live && o.normalize) {
+        hipLaunchKernelGGL(k_prox_finish<T>, dim3(nb), dim3(256), 0, s, H, hs_t, hs_n, d, N, T_, n_fast, 0, T(0));
+        HIP_TRY(hipGetLastError());
+    }
+    return solve_read_back(t.stop, t.trace, n_utt, n_slots, o.iters, n_iter_out, change_out, s);
+}
 
 }  // namespace
 

@@ -215,11 +215,8 @@ int prox_learn(const T* X, int ldx, T* D, int ldd, T* H, int ldh, T* C, int ldc,
     const int ldz = fm ? R : bs;
     const int NB = plearn_block(M, o.dtype), n_blocks = (N + NB - 1) / NB;
     const size_t lds = ((size_t)NB * M + (size_t)NB * NB + (size_t)PLEARN_ROWS * NB) * sizeof(T);
-    const evc_prox_opts po = plearn_lasso_opts(o);
-    const long total = (long)o.epochs * nbat;
+    const evc_prox_opts po = plearn_lasso_opts<evc_prox_opts>(o);
     const bool lasso = !(o.reserved & PLEARN_NO_LASSO), stats = !(o.reserved & PLEARN_NO_STATS), sweep = !(o.reserved & PLEARN_NO_SWEEP);
-    const bool reads = sweep && (o.tol > 0.0 || trace_out);
-    if (trace_out) for (long i = 0; i < total; ++i) trace_out[i] = __builtin_nan("");
 
     if (!o.resume) {
         hipLaunchKernelGGL(k_plearn_unit<T>, dim3(N), dim3(PLEARN_THREADS), 0, s, D, ds_n, ds_m, M);
@@ -227,69 +224,49 @@ int prox_learn(const T* X, int ldx, T* D, int ldd, T* H, int ldh, T* C, int ldc,
         HIP_TRY(hipMemset2DAsync(C, sizeof(T) * (size_t)ldc, 0, sizeof(T) * (size_t)R, (size_t)N, s));
         *count_io = 0;
     }
-    long long count = *count_io;
-    long n_steps = 0;
-    int n_epochs = o.epochs;
-    bool stopped = false;
-    if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
-    for (int e = 0; e < o.epochs && !stopped; ++e) {
-        if (order && nbat > 0)      // from pageable memory: HIP has copied the bytes by the time the call returns
-            HIP_TRY(hipMemcpyAsync(w.ord, order + (size_t)e * T_, sizeof(int) * (size_t)T_, hipMemcpyHostToDevice, s));
-        const int* ord = order ? w.ord : nullptr;
-        for (int b = 0; b < nbat && !stopped; ++b) {
-            const int t0 = b * bs;
-            hipLaunchKernelGGL(k_plearn_gather<T>, dim3(plearn_blocks_of((long)bs * R)), dim3(256), 0, s, X, xs_t, xs_m,
-                               (const T*)H, hs_t, hs_n, Z, zs_t, zs_r, ord, t0, bs, N, M, fm ? 1 : 0);
-            HIP_TRY(hipGetLastError());
-            if (lasso)
-                HIP_TRY(evc_prox_solve(D, ldd, Zx, ldz, Z, ldz, M, N, bs, nullptr, 1, &po, w.prox_ws, w.prox_bytes, nullptr,
-                                       nullptr, reinterpret_cast<evc_stream_t>(s)));
-            hipLaunchKernelGGL(k_plearn_scatter<T>, dim3(plearn_blocks_of((long)bs * N)), dim3(256), 0, s, H, hs_t, hs_n,
-                               (const T*)Z, zs_t, zs_r, ord, t0, bs, N, fm ? 1 : 0);
-            HIP_TRY(hipGetLastError());
+    auto stage_order = [&](int e) -> int { return plearn_stage_order(order, e, T_, w.ord, s); };
+    auto step = [&](const int* ord, int t0, double forget) -> int {
+        hipLaunchKernelGGL(k_plearn_gather<T>, dim3(plearn_blocks_of((long)bs * R)), dim3(256), 0, s, X, xs_t, xs_m,
+                           (const T*)H, hs_t, hs_n, Z, zs_t, zs_r, ord, t0, bs, N, M, fm ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        if (lasso)
+            HIP_TRY(evc_prox_solve(D, ldd, Zx, ldz, Z, ldz, M, N, bs, nullptr, 1, &po, w.prox_ws, w.prox_bytes, nullptr,
+                                   nullptr, reinterpret_cast<evc_stream_t>(s)));
+        hipLaunchKernelGGL(k_plearn_scatter<T>, dim3(plearn_blocks_of((long)bs * N)), dim3(256), 0, s, H, hs_t, hs_n,
+                           (const T*)Z, zs_t, zs_r, ord, t0, bs, N, fm ? 1 : 0);
+        HIP_TRY(hipGetLastError());
 
-            const T beta = (T)plearn_beta(count, bs);
-            if (stats) {
-                hipLaunchKernelGGL(k_plearn_stats<T>, dim3((R + PLS_B - 1) / PLS_B, (N + PLS_B - 1) / PLS_B), dim3(256), 0, s,
-                                   (const T*)Z, zs_t, zs_r, bs, N, M, beta, C, (long)ldc);
-                HIP_TRY(hipGetLastError());
-            }
-
-            if (sweep) {
-                // Rm <- S D^T, then Q - that
-                HIP_TRY(gemm_strided<T>(C, ldc, 1, D, ds_m, ds_n, Rm, M, 1, N, M, N, s));
-                hipLaunchKernelGGL(k_plearn_resid<T>, dim3(plearn_blocks_of((long)N * M)), dim3(256), 0, s, (const T*)C, (long)ldc,
-                                   (const T*)D, ds_n, ds_m, Rm, Dw, N, M, fm ? 1 : 0);
-                HIP_TRY(hipGetLastError());
-                for (int k0 = 0; k0 < N; k0 += NB) {
-                    const int nbk = N - k0 < NB ? N - k0 : NB;
-                    const int behind = N - k0 - nbk;
-                    const int tiles = (behind + PLEARN_ROWS - 1) / PLEARN_ROWS;
-                    hipLaunchKernelGGL(k_plearn_block<T>, dim3(tiles > 0 ? tiles : 1), dim3(PLEARN_THREADS), lds, s, (const T*)C,
-                                       (long)ldc, Rm, (const T*)Dw, D, ds_n, ds_m, N, M, NB, k0, nbk, (T)1e-15, w.shares);
-                    HIP_TRY(hipGetLastError());
-                }
-            }
-            ++count;
-            ++n_steps;
-            if (!reads) continue;
-            hipLaunchKernelGGL(k_plearn_stat, dim3(1), dim3(64), 0, s, (const double*)w.shares, n_blocks, w.stat);
+        const T beta = (T)forget;
+        if (stats) {
+            hipLaunchKernelGGL(k_plearn_stats<T>, dim3((R + PLS_B - 1) / PLS_B, (N + PLS_B - 1) / PLS_B), dim3(256), 0, s,
+                               (const T*)Z, zs_t, zs_r, bs, N, M, beta, C, (long)ldc);
             HIP_TRY(hipGetLastError());
-            double stat;
-            HIP_TRY(hipMemcpyAsync(&stat, w.stat, sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (trace_out) trace_out[n_steps - 1] = stat;
-            if (stat < o.tol) {
-                stopped = true;
-                n_epochs = e + 1;
+        }
+
+        if (sweep) {
+            // Rm <- S D^T, then Q - that
+            HIP_TRY(gemm_strided<T>(C, ldc, 1, D, ds_m, ds_n, Rm, M, 1, N, M, N, s));
+            hipLaunchKernelGGL(k_plearn_resid<T>, dim3(plearn_blocks_of((long)N * M)), dim3(256), 0, s, (const T*)C, (long)ldc,
+                               (const T*)D, ds_n, ds_m, Rm, Dw, N, M, fm ? 1 : 0);
+            HIP_TRY(hipGetLastError());
+            for (int k0 = 0; k0 < N; k0 += NB) {
+                const int nbk = N - k0 < NB ? N - k0 : NB;
+                const int behind = N - k0 - nbk;
+                const int tiles = (behind + PLEARN_ROWS - 1) / PLEARN_ROWS;
+                hipLaunchKernelGGL(k_plearn_block<T>, dim3(tiles > 0 ? tiles : 1), dim3(PLEARN_THREADS), lds, s, (const T*)C,
+                                   (long)ldc, Rm, (const T*)Dw, D, ds_n, ds_m, N, M, NB, k0, nbk, (T)1e-15, w.shares);
+                HIP_TRY(hipGetLastError());
             }
         }
-    }
-    if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    *count_io = count;
-    if (n_steps_out) *n_steps_out = (int)n_steps;
-    if (n_epochs_out) *n_epochs_out = n_epochs;
-    return ST_OK;
+        return ST_OK;
+    };
+    auto read_stat = [&](double* stat) -> int {
+        hipLaunchKernelGGL(k_plearn_stat, dim3(1), dim3(64), 0, s, (const double*)w.shares, n_blocks, w.stat);
+        HIP_TRY(hipGetLastError());
+        return plearn_fetch_stat(w.stat, stat, s);
+    };
+    return plearn_loop(o, nbat, sweep, order ? w.ord : nullptr, count_io, n_epochs_out, n_steps_out, trace_out, s, stage_order,
+                       step, read_stat);
 }
 
 }  // namespace

@@ -72,6 +72,18 @@ __global__ __launch_bounds__(256) void k_plearn_scatter(T* __restrict__ H, long 
 
 unsigned plearn_blocks_of(long n) { return (unsigned)((n + 255) / 256); }
 
+// what both drivers hand plearn_loop (evc_prox_learn_plan.h) as stage_order: row e of the caller's order[epochs][T_] to `ord`
+// (from pageable memory: HIP has copied the bytes by the time the call returns) ...
+int plearn_stage_order(const int* order, int e, int T_, int* ord, hipStream_t s) {
+    return (int)hipMemcpyAsync(ord, order + (size_t)e * T_, sizeof(int) * (size_t)T_, hipMemcpyHostToDevice, s);
+}
+
+// ... and the end of their read_stat: the statistic their own kernel has just left in `stat`, waited for
+int plearn_fetch_stat(const double* stat, double* out, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(out, stat, sizeof(double), hipMemcpyDeviceToHost, s));
+    return (int)hipStreamSynchronize(s);
+}
+
 }  // namespace
 
 }  // namespace evc

@@ -380,43 +380,24 @@ int prox_masked_solve(const T* A, int lda, const T* X, int ldx, const T* mask, i
     const ProxMaskedWs w = carve_prox_masked(ws, M, N, T_, n_utt, o.dtype);
     if (w.bytes > ws_bytes) return ST_WORKSPACE;
     const bool fm = o.layout == EVC_FRAME_MAJOR;
-    const int n_slots = prox_slots(o.iters, o.check_every);
     const int NK = pm_nk(N), MP = pm_mp(M), MK = pm_mk(M), NP = pm_np(N);
     const long as_n = fm ? lda : 1, as_m = fm ? 1 : lda, xs_t = fm ? ldx : 1, xs_m = fm ? 1 : ldx;
     const long ms_t = fm ? ldm : 1, ms_m = fm ? 1 : ldm, hs_t = fm ? ldh : 1, hs_n = fm ? 1 : ldh;
 
-    const int whole[2] = {0, T_};
-    HIP_TRY(hipMemcpyAsync(w.offs, utt_offsets ? utt_offsets : whole, sizeof(int) * ((size_t)n_utt + 1), hipMemcpyHostToDevice,
-                           s));
-    long n_state = (long)n_utt * n_slots;
-    if (n_state < T_) n_state = T_;
-    if (n_state < n_utt) n_state = n_utt;
-    hipLaunchKernelGGL(k_prox_state, dim3(prox_blocks_of(n_state)), dim3(256), 0, s, w.offs, n_utt, T_, n_slots, w.stop, w.trace,
-                       w.frame_utt);
-    HIP_TRY(hipGetLastError());
-
-    const unsigned nb = prox_blocks_of((long)N * T_);
-    if (T_ > 0 && o.iters == 0) {               // the start stays as it is: nothing is scaled
-        if (o.init_mode == EVC_INIT_CONST) {
-            hipLaunchKernelGGL(k_prox_finish<T>, dim3(nb), dim3(256), 0, s, H, hs_t, hs_n, (const T*)nullptr, N, T_, fm ? 1 : 0, 1,
-                               (T)o.init_value);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    if (T_ > 0 && o.iters > 0) {
-        T* Dn = reinterpret_cast<T*>(w.Dn);
-        T* Dm = reinterpret_cast<T*>(w.Dm);
-        T* P = reinterpret_cast<T*>(w.P);
-        T* Wb[2] = {reinterpret_cast<T*>(w.W[0]), reinterpret_cast<T*>(w.W[1])};
-        T* R = reinterpret_cast<T*>(w.R);
-        T* Xm = reinterpret_cast<T*>(w.Xm);
-        T* lam = reinterpret_cast<T*>(w.lam);
-        T* tolv = reinterpret_cast<T*>(w.tolv);
-        T* d = reinterpret_cast<T*>(w.d);
-        T* colsum = reinterpret_cast<T*>(w.colsum);
-        T* wbar = reinterpret_cast<T*>(w.wbar);
-        T* sv = reinterpret_cast<T*>(w.s);
-        T* cf = reinterpret_cast<T*>(w.cf);
+    T* Dn = reinterpret_cast<T*>(w.Dn);
+    T* Dm = reinterpret_cast<T*>(w.Dm);
+    T* P = reinterpret_cast<T*>(w.P);
+    T* Wb[2] = {reinterpret_cast<T*>(w.W[0]), reinterpret_cast<T*>(w.W[1])};
+    T* R = reinterpret_cast<T*>(w.R);
+    T* Xm = reinterpret_cast<T*>(w.Xm);
+    T* lam = reinterpret_cast<T*>(w.lam);
+    T* tolv = reinterpret_cast<T*>(w.tolv);
+    T* d = reinterpret_cast<T*>(w.d);
+    T* colsum = reinterpret_cast<T*>(w.colsum);
+    T* wbar = reinterpret_cast<T*>(w.wbar);
+    T* sv = reinterpret_cast<T*>(w.s);
+    T* cf = reinterpret_cast<T*>(w.cf);
+    auto prepare = [&]() -> int {
         HIP_TRY(hipMemsetAsync(Dn, 0, (size_t)NK * MP * sizeof(T), s));
         HIP_TRY(hipMemsetAsync(Dm, 0, (size_t)MK * NP * sizeof(T), s));
         hipLaunchKernelGGL(k_pm_norm<T>, dim3(prox_blocks_of(N)), dim3(256), 0, s, A, as_n, as_m, M, N, o.normalize, (T)o.alpha,
@@ -440,62 +421,34 @@ int prox_masked_solve(const T* A, int lda, const T* X, int ldx, const T* mask, i
         hipLaunchKernelGGL(k_pm_lip<T>, dim3(n_utt), dim3(256), 0, s, (const T*)colsum, N, mask ? 1 : 0, (T)o.lipschitz, sv);
         HIP_TRY(hipGetLastError());
         HIP_TRY(gemm_strided<T>(Dm, 1, NP, Xm, 1, T_, P, T_, 1, N, T_, M, s));
-        hipLaunchKernelGGL(k_prox_start<T>, dim3(nb), dim3(256), 0, s, (T*)nullptr, H, hs_t, hs_n, Wb[0], (const T*)d, N, T_, fm ? 1 : 0,
-                           o.normalize, o.init_mode == EVC_INIT_GIVEN ? 1 : 0, (T)o.init_value);
+        hipLaunchKernelGGL(k_prox_start<T>, dim3(prox_blocks_of((long)N * T_)), dim3(256), 0, s, (T*)nullptr, H, hs_t, hs_n, Wb[0],
+                           (const T*)d, N, T_, fm ? 1 : 0, o.normalize, o.init_mode == EVC_INIT_GIVEN ? 1 : 0, (T)o.init_value);
+        return (int)hipGetLastError();
+    };
+
+    PmResidArgs<T> ra;
+    ra.Dn = Dn; ra.R = R; ra.mask = mask; ra.ms_t = ms_t; ra.ms_m = ms_m; ra.frame_utt = w.frame_utt; ra.stop = w.stop;
+    ra.M = M; ra.MP = MP; ra.N = N; ra.T_ = T_;
+    PmBackArgs<T> ba;
+    ba.Dm = Dm; ba.R = R; ba.P = P; ba.X = H; ba.xs_t = hs_t; ba.xs_n = hs_n; ba.lam = lam; ba.cf = cf; ba.tolv = tolv;
+    ba.s = sv; ba.frame_utt = w.frame_utt; ba.stop = w.stop;
+    ba.M = M; ba.N = N; ba.NP = NP; ba.T_ = T_; ba.signed_mode = o.mode == EVC_PROX_SIGNED ? 1 : 0;
+    const int Wr = pm_resid_waves(M, T_), Wk = pm_back_waves(N, T_);
+    const unsigned frame_blocks = (unsigned)((T_ + PROX_BT - 1) / PROX_BT);
+    const int row_blocks = (N + 16 * Wk - 1) / (16 * Wk);
+    const dim3 rgrid(frame_blocks, (unsigned)((M + 16 * Wr - 1) / (16 * Wr))), bgrid(frame_blocks, (unsigned)row_blocks);
+    auto sweep = [&](int, const T* Win, T* Wout, double* partials, T c) -> int {
+        ra.Win = ba.Win = Win;
+        ba.Wout = Wout; ba.partials = partials; ba.c = c;
+        if (Wr == 8) hipLaunchKernelGGL((k_prox_resid<T, 8>), rgrid, dim3(512), 0, s, ra);
+        else hipLaunchKernelGGL((k_prox_resid<T, 4>), rgrid, dim3(256), 0, s, ra);
         HIP_TRY(hipGetLastError());
-
-        if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
-        PmResidArgs<T> ra;
-        ra.Dn = Dn; ra.R = R; ra.mask = mask; ra.ms_t = ms_t; ra.ms_m = ms_m; ra.frame_utt = w.frame_utt; ra.stop = w.stop;
-        ra.M = M; ra.MP = MP; ra.N = N; ra.T_ = T_;
-        PmBackArgs<T> ba;
-        ba.Dm = Dm; ba.R = R; ba.P = P; ba.X = H; ba.xs_t = hs_t; ba.xs_n = hs_n; ba.lam = lam; ba.cf = cf; ba.tolv = tolv;
-        ba.s = sv; ba.frame_utt = w.frame_utt; ba.stop = w.stop;
-        ba.M = M; ba.N = N; ba.NP = NP; ba.T_ = T_; ba.signed_mode = o.mode == EVC_PROX_SIGNED ? 1 : 0;
-        const int Wr = pm_resid_waves(M, T_), Wk = pm_back_waves(N, T_);
-        const unsigned frame_blocks = (unsigned)((T_ + PROX_BT - 1) / PROX_BT);
-        const int row_blocks = (N + 16 * Wk - 1) / (16 * Wk);
-        const dim3 rgrid(frame_blocks, (unsigned)((M + 16 * Wr - 1) / (16 * Wr))), bgrid(frame_blocks, (unsigned)row_blocks);
-        ProxMomentum mom(o.momentum);
-        for (int i = 0; i < o.iters; ++i) {
-            const bool check = o.check_every > 0 && i % o.check_every == 0;
-            ra.Win = ba.Win = Wb[i & 1];
-            ba.Wout = Wb[(i + 1) & 1];
-            ba.partials = check ? w.partials : nullptr;
-            ba.c = (T)mom.next(i);
-            if (Wr == 8) hipLaunchKernelGGL((k_prox_resid<T, 8>), rgrid, dim3(512), 0, s, ra);
-            else hipLaunchKernelGGL((k_prox_resid<T, 4>), rgrid, dim3(256), 0, s, ra);
-            HIP_TRY(hipGetLastError());
-            if (Wk == 8) hipLaunchKernelGGL((k_prox_back<T, 8>), bgrid, dim3(512), 0, s, ba);
-            else hipLaunchKernelGGL((k_prox_back<T, 4>), bgrid, dim3(256), 0, s, ba);
-            HIP_TRY(hipGetLastError());
-            if (check) {
-                hipLaunchKernelGGL(k_prox_check, dim3(n_utt), dim3(256), 0, s, (const double*)w.partials, row_blocks, T_,
-                                   (const int*)w.offs, w.stop, w.trace, n_slots, i / o.check_every, i + 1, o.stop_rule);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-        if (o.normalize) {
-            hipLaunchKernelGGL(k_prox_finish<T>, dim3(nb), dim3(256), 0, s, H, hs_t, hs_n, (const T*)d, N, T_, fm ? 1 : 0, 0, T(0));
-            HIP_TRY(hipGetLastError());
-        }
-    } else {
-        if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
-        if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    }
-
-    if (!n_iter_out && !(change_out && n_slots > 0)) return 0;
-    int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
-    if (!ni_h) return (int)hipErrorOutOfMemory;
-    hipError_t e = hipMemcpyAsync(ni_h, w.stop, sizeof(int) * n_utt, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && change_out && n_slots > 0)
-        e = hipMemcpyAsync(change_out, w.trace, sizeof(double) * n_utt * n_slots, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    for (int u = 0; e == hipSuccess && n_iter_out && u < n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : o.iters;
-    free(ni_h);
-    HIP_TRY(e);
-    return 0;
+        if (Wk == 8) hipLaunchKernelGGL((k_prox_back<T, 8>), bgrid, dim3(512), 0, s, ba);
+        else hipLaunchKernelGGL((k_prox_back<T, 4>), bgrid, dim3(256), 0, s, ba);
+        return (int)hipGetLastError();
+    };
+    return prox_solve_frame<T>(o, w, Wb, (const T*)d, row_blocks, H, hs_t, hs_n, fm ? 1 : 0, N, T_, utt_offsets, n_utt,
+                               n_iter_out, change_out, s, prepare, sweep);
 }
 
 }  // namespace

@@ -256,11 +256,8 @@ int prox_masked_learn(const T* X, int ldx, const T* W, int ldm, T* D, int ldd, T
     T* Zw = Z + (long)(N + M) * zs_r;                    // the batch's mask inside Z
     const int ldz = fm ? R : bs;
     const evc_prox_masked_opts po = pmlearn_lasso_opts(o);
-    const long total = (long)o.epochs * nbat;
     const bool lasso = !(o.reserved & PMLEARN_NO_LASSO), stats = !(o.reserved & PMLEARN_NO_STATS);
     const bool atoms = !(o.reserved & PMLEARN_NO_ATOMS);
-    const bool reads = atoms && (o.tol > 0.0 || trace_out);
-    if (trace_out) for (long i = 0; i < total; ++i) trace_out[i] = __builtin_nan("");
 
     if (!o.resume) {
         hipLaunchKernelGGL(k_plearn_unit<T>, dim3(N), dim3(PLEARN_THREADS), 0, s, D, ds_n, ds_m, M);
@@ -269,71 +266,51 @@ int prox_masked_learn(const T* X, int ldx, const T* W, int ldm, T* D, int ldd, T
         HIP_TRY(hipMemset2DAsync(Q, sizeof(T) * (size_t)ld_q, 0, sizeof(T) * (size_t)M, (size_t)N, s));
         *count_io = 0;
     }
-    if (total > 0) {
+    if ((long)o.epochs * nbat > 0) {
         hipLaunchKernelGGL(k_pmlearn_dcopy<T>, dim3(plearn_blocks_of((long)N * M)), dim3(256), 0, s, (const T*)D, ds_n, ds_m, Dt, N,
                            M, fm ? 1 : 0);
         HIP_TRY(hipGetLastError());
         // without the statistics (measurement only) G and the diagonals are never written: they read as zero
         if (!stats) HIP_TRY(hipMemsetAsync(w.G, 0, (size_t)(w.Dt - w.G), s));       // G and diag lie next to each other
     }
-    long long count = *count_io;
-    long n_steps = 0;
-    int n_epochs = o.epochs;
-    bool stopped = false;
-    if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
-    for (int e = 0; e < o.epochs && !stopped; ++e) {
-        if (order && nbat > 0)      // from pageable memory: HIP has copied the bytes by the time the call returns
-            HIP_TRY(hipMemcpyAsync(w.ord, order + (size_t)e * T_, sizeof(int) * (size_t)T_, hipMemcpyHostToDevice, s));
-        const int* ord = order ? w.ord : nullptr;
-        for (int b = 0; b < nbat && !stopped; ++b) {
-            const int t0 = b * bs;
-            hipLaunchKernelGGL(k_plearn_gather<T>, dim3(plearn_blocks_of((long)bs * (N + M))), dim3(256), 0, s, X, xs_t, xs_m,
-                               (const T*)H, hs_t, hs_n, Z, zs_t, zs_r, ord, t0, bs, N, M, fm ? 1 : 0);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_plearn_gather<T>, dim3(plearn_blocks_of((long)bs * M)), dim3(256), 0, s, W, ws_t, ws_m,
-                               (const T*)nullptr, 0L, 0L, Zw, zs_t, zs_r, ord, t0, bs, 0, M, fm ? 1 : 0);
-            HIP_TRY(hipGetLastError());
-            if (lasso)
-                HIP_TRY(evc_prox_masked_solve(D, ldd, Zx, ldz, Zw, ldz, Z, ldz, M, N, bs, nullptr, 1, &po, w.prox_ws, w.prox_bytes,
-                                              nullptr, nullptr, reinterpret_cast<evc_stream_t>(s)));
-            hipLaunchKernelGGL(k_plearn_scatter<T>, dim3(plearn_blocks_of((long)bs * N)), dim3(256), 0, s, H, hs_t, hs_n,
-                               (const T*)Z, zs_t, zs_r, ord, t0, bs, N, fm ? 1 : 0);
-            HIP_TRY(hipGetLastError());
+    auto stage_order = [&](int e) -> int { return plearn_stage_order(order, e, T_, w.ord, s); };
+    auto step = [&](const int* ord, int t0, double forget) -> int {
+        hipLaunchKernelGGL(k_plearn_gather<T>, dim3(plearn_blocks_of((long)bs * (N + M))), dim3(256), 0, s, X, xs_t, xs_m,
+                           (const T*)H, hs_t, hs_n, Z, zs_t, zs_r, ord, t0, bs, N, M, fm ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_plearn_gather<T>, dim3(plearn_blocks_of((long)bs * M)), dim3(256), 0, s, W, ws_t, ws_m,
+                           (const T*)nullptr, 0L, 0L, Zw, zs_t, zs_r, ord, t0, bs, 0, M, fm ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        if (lasso)
+            HIP_TRY(evc_prox_masked_solve(D, ldd, Zx, ldz, Zw, ldz, Z, ldz, M, N, bs, nullptr, 1, &po, w.prox_ws, w.prox_bytes,
+                                          nullptr, nullptr, reinterpret_cast<evc_stream_t>(s)));
+        hipLaunchKernelGGL(k_plearn_scatter<T>, dim3(plearn_blocks_of((long)bs * N)), dim3(256), 0, s, H, hs_t, hs_n,
+                           (const T*)Z, zs_t, zs_r, ord, t0, bs, N, fm ? 1 : 0);
+        HIP_TRY(hipGetLastError());
 
-            const T beta = (T)plearn_beta(count, bs);
-            if (stats) {
-                hipLaunchKernelGGL(k_pmlearn_stats<T>, dim3((N + PML_B - 1) / PML_B, M), dim3(256), 0, s, (const T*)Z, zs_t, zs_r,
-                                   bs, N, N + M, beta, S, (long)ld_s, (const T*)Dt, G, M, diag);
-                HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(k_pmlearn_q<T>, dim3(plearn_blocks_of((long)N * M)), dim3(256), 0, s, (const T*)Z, zs_t, zs_r, bs,
-                                   N, M, beta, Q, (long)ld_q);
-                HIP_TRY(hipGetLastError());
-            }
-            if (atoms) {
-                hipLaunchKernelGGL(k_pmlearn_atoms<T>, dim3(N), dim3(PLEARN_THREADS), 0, s, (const T*)Q, (long)ld_q, (const T*)G,
-                                   (const T*)diag, D, ds_n, ds_m, Dt, N, M, (T)1e-15, w.shares);
-                HIP_TRY(hipGetLastError());
-            }
-            ++count;
-            ++n_steps;
-            if (!reads) continue;
-            hipLaunchKernelGGL(k_pmlearn_stat, dim3(1), dim3(PLEARN_THREADS), 0, s, (const double*)w.shares, N, w.stat);
+        const T beta = (T)forget;
+        if (stats) {
+            hipLaunchKernelGGL(k_pmlearn_stats<T>, dim3((N + PML_B - 1) / PML_B, M), dim3(256), 0, s, (const T*)Z, zs_t, zs_r,
+                               bs, N, N + M, beta, S, (long)ld_s, (const T*)Dt, G, M, diag);
             HIP_TRY(hipGetLastError());
-            double stat;
-            HIP_TRY(hipMemcpyAsync(&stat, w.stat, sizeof(double), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (trace_out) trace_out[n_steps - 1] = stat;
-            if (stat < o.tol) {
-                stopped = true;
-                n_epochs = e + 1;
-            }
+            hipLaunchKernelGGL(k_pmlearn_q<T>, dim3(plearn_blocks_of((long)N * M)), dim3(256), 0, s, (const T*)Z, zs_t, zs_r, bs,
+                               N, M, beta, Q, (long)ld_q);
+            HIP_TRY(hipGetLastError());
         }
-    }
-    if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
-    *count_io = count;
-    if (n_steps_out) *n_steps_out = (int)n_steps;
-    if (n_epochs_out) *n_epochs_out = n_epochs;
-    return ST_OK;
+        if (atoms) {
+            hipLaunchKernelGGL(k_pmlearn_atoms<T>, dim3(N), dim3(PLEARN_THREADS), 0, s, (const T*)Q, (long)ld_q, (const T*)G,
+                               (const T*)diag, D, ds_n, ds_m, Dt, N, M, (T)1e-15, w.shares);
+            HIP_TRY(hipGetLastError());
+        }
+        return ST_OK;
+    };
+    auto read_stat = [&](double* stat) -> int {
+        hipLaunchKernelGGL(k_pmlearn_stat, dim3(1), dim3(PLEARN_THREADS), 0, s, (const double*)w.shares, N, w.stat);
+        HIP_TRY(hipGetLastError());
+        return plearn_fetch_stat(w.stat, stat, s);
+    };
+    return plearn_loop(o, nbat, atoms, order ? w.ord : nullptr, count_io, n_epochs_out, n_steps_out, trace_out, s, stage_order,
+                       step, read_stat);
 }
 
 }  // namespace

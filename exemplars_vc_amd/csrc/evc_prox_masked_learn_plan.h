@@ -21,16 +21,12 @@ inline bool pmlearn_too_large(int M, int N) {
     return M > PMLEARN_MAX_M || N > PMLEARN_MAX_N || (long)M * N * N > PMLEARN_MAX_S;
 }
 
-struct PMLearnWs {
+struct PMLearnWs : PLearnTail {
     char* Z;            // the batch, gathered: [bs][N + 2 M] (frame-major) or [N + 2 M][bs] (bin-major): H_F, X_F, then W_F
     char* G;            // [N][M] elements: G[k][m] = sum_j S_m[k][j] D_old[j][m]
     char* diag;         // [M][N] elements: S_m[k][k]
     char* Dt;           // [M][N] elements: the dictionary, a bin per row (what k_pmlearn_stats reads along j)
-    double* shares;     // [N]: an atom's max |dD|
-    double* stat;       // [1]
-    int* ord;           // [T]: the epoch's row of `order`
-    char* prox_ws;      // evc_prox_masked_solve's workspace for a batch
-    size_t prox_bytes, bytes;
+    size_t bytes;       // (PLearnTail: a share per atom; the lasso's workspace is evc_prox_masked_solve's)
 };
 constexpr int PMLEARN_WS_ARRAYS = 8;
 
@@ -43,11 +39,7 @@ inline PMLearnWs carve_pmlearn(void* ws, int M, int N, int T_, int bs, int dtype
     w.G = c.take<char>((size_t)N * M * es);
     w.diag = c.take<char>((size_t)N * M * es);
     w.Dt = c.take<char>((size_t)N * M * es);
-    w.shares = c.take<double>((size_t)N);
-    w.stat = c.take<double>(1);
-    w.ord = c.take<int>((size_t)T_);
-    w.prox_bytes = prox_masked_workspace_bytes(M, N, bs, 1, dtype);
-    w.prox_ws = c.take<char>(w.prox_bytes);
+    static_cast<PLearnTail&>(w) = carve_plearn_tail(c, (size_t)N, T_, prox_masked_workspace_bytes(M, N, bs, 1, dtype));
     w.bytes = c.bytes();
     return w;
 }
@@ -60,12 +52,8 @@ inline size_t prox_masked_learn_workspace_bytes(int M, int N, int T_, int batch_
 
 // the options of a step's lasso: evc_prox_masked_solve on the gathered batch as one utterance, deComP's step
 inline evc_prox_masked_opts pmlearn_lasso_opts(const evc_prox_masked_learn_opts& o) {
-    evc_prox_masked_opts p;
-    memset(&p, 0, sizeof(p));
-    p.struct_bytes = (int)sizeof(evc_prox_masked_opts);
-    p.dtype = o.dtype; p.layout = o.layout; p.iters = o.lasso_iters; p.mode = o.mode; p.momentum = o.momentum;
-    p.normalize = 1; p.check_every = o.lasso_check_every; p.stop_rule = EVC_STOP_DECOMP; p.init_mode = EVC_INIT_GIVEN;
-    p.lip_weights = EVC_PROX_LIP_MEAN; p.alpha = o.alpha; p.tol = o.lasso_tol;
+    evc_prox_masked_opts p = plearn_lasso_opts<evc_prox_masked_opts>(o);
+    p.lip_weights = EVC_PROX_LIP_MEAN;
     return p;
 }
 
@@ -77,20 +65,11 @@ inline int pmlearn_args_check(const void* X, int ldx, const void* mask, int ldm,
                               const void* workspace, size_t workspace_bytes) {
     if (!opts || opts->struct_bytes != (int)sizeof(evc_prox_masked_learn_opts)) return ST_BADARG;
     const evc_prox_masked_learn_opts& o = *opts;
-    if (M < 1 || N < 1 || T < 1 || (o.dtype != EVC_F64 && o.dtype != EVC_F32)) return ST_BADARG;
-    if (o.layout != EVC_FRAME_MAJOR && o.layout != EVC_BIN_MAJOR) return ST_BADARG;
+    if (M < 1 || N < 1 || T < 1 || !plearn_opts_ok(o, T)) return ST_BADARG;
     if (!X || !mask || !D || !H || !stats_s || !stats_q || !count_io || !workspace) return ST_BADARG;
     if (bad_ld(o.layout, ldx, T, M) || bad_ld(o.layout, ldm, T, M) || bad_ld(o.layout, ldd, N, M) || bad_ld(o.layout, ldh, T, N))
         return ST_BADARG;
     if (ld_s < N || ld_q < M) return ST_BADARG;
-    if (o.batch_size < 1 || o.batch_size > T || o.epochs < 0 || (o.resume != 0 && o.resume != 1)) return ST_BADARG;
-    if (o.lasso_iters < 0 || o.lasso_check_every < 0 || (o.reserved & ~7) != 0 || o.reserved2 != 0) return ST_BADARG;
-    if (o.mode != EVC_PROX_POSITIVE && o.mode != EVC_PROX_SIGNED) return ST_BADARG;
-    if (o.momentum != EVC_PROX_ISTA && o.momentum != EVC_PROX_FISTA && o.momentum != EVC_PROX_NESTEROV) return ST_BADARG;
-    if (!(o.alpha >= 0.0) || !(o.alpha - o.alpha == 0.0) || !(o.tol >= 0.0) || !(o.tol - o.tol == 0.0)) return ST_BADARG;
-    if (!(o.lasso_tol >= 0.0) || !(o.lasso_tol - o.lasso_tol == 0.0)) return ST_BADARG;
-    if (prox_slots(o.lasso_iters, o.lasso_check_every) > PROX_MAX_SLOTS) return ST_BADARG;
-    if ((long)o.epochs * (T / o.batch_size) > 0x7fffffffL) return ST_BADARG;        // n_steps_out is an int
     if (o.resume && *count_io < 0) return ST_BADARG;
     HIP_TRY(plearn_order_check(order, o.epochs, T));
     if (pmlearn_too_large(M, N)) return ST_UNSUPPORTED;

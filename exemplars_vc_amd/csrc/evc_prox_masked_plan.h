@@ -22,7 +22,7 @@ inline int pm_np(int N) { return round_up(N, PROX_BN); }
 inline int pm_resid_waves(int M, int T_) { return prox_waves(M, T_); }
 inline int pm_back_waves(int N, int T_) { return prox_waves(N, T_); }
 
-struct ProxMaskedWs {
+struct ProxMaskedWs : ProxTail {
     char* Dn;           // [pm_nk(N)][pm_mp(M)] elements: A / d, exemplar-major, zero in the padding
     char* Dm;           // [pm_mk(M)][pm_np(N)] elements: A / d, bin-major, zero in the padding
     char* P;            // [N][T] elements: A^T (mask . X) in the scaled dictionary
@@ -36,17 +36,12 @@ struct ProxMaskedWs {
     char* wbar;         // [n_utt][M] elements: the per-bin weights of the bound
     char* s;            // [n_utt] elements: 1 / L_u
     char* cf;           // [T] elements: cnt_t = sum_m mask_tm | 1 (normalize == 0)
-    double* partials;   // [pm_np(N) / 64][T]: max over a row block of |X_new - X_old| - tol_n, per frame
-    int* frame_utt;     // [T]
-    int* offs;          // [n_utt + 1]
-    int* stop;          // [n_utt]: 0 running, else the updates applied when the utterance stopped
-    double* trace;      // [n_utt][PROX_MAX_SLOTS]
     size_t bytes;
 };
 constexpr int PROX_MASKED_WS_ARRAYS = 19;
 
 // [Dn | Dm | P | W0 | W1 | R | Xm | lam | tol | d | colsum | wbar | s | cf | partials | frame_utt | offs | stop | trace], each
-// 256-byte aligned (ws == NULL: sizes only).  Nothing is N x N: the bound is formed in panels of 16 rows that live in registers.
+// 256-byte aligned (ws == NULL: sizes only); the last five are carve_prox_tail's (pm_np(N) is evc_prox_solve's NP).  Nothing is N x N: the bound is formed in panels of 16 rows that live in registers.
 inline ProxMaskedWs carve_prox_masked(void* ws, int M, int N, int T_, int n_utt, int dtype) {
     ProxMaskedWs w;
     Carver c = Carver::rounded(ws);
@@ -66,11 +61,7 @@ inline ProxMaskedWs carve_prox_masked(void* ws, int M, int N, int T_, int n_utt,
     w.wbar = c.take<char>((size_t)n_utt * M * es);
     w.s = c.take<char>((size_t)n_utt * es);
     w.cf = c.take<char>((size_t)T_ * es);
-    w.partials = c.take<double>((size_t)pm_np(N) / 64 * (size_t)T_);
-    w.frame_utt = c.take<int>((size_t)T_);
-    w.offs = c.take<int>((size_t)n_utt + 1);
-    w.stop = c.take<int>((size_t)n_utt);
-    w.trace = c.take<double>((size_t)n_utt * PROX_MAX_SLOTS);
+    static_cast<ProxTail&>(w) = carve_prox_tail(c, N, T_, n_utt);
     w.bytes = c.bytes();
     return w;
 }
@@ -90,17 +81,9 @@ inline int prox_masked_args_check(const void* A, int lda, const void* X, int ldx
     const evc_prox_masked_opts& o = *opts;
     HIP_TRY(solve_args_ok(M, N, T, n_utt, o.dtype, o.layout, A, workspace, lda, ldx, ldh, utt_offsets));
     if (mask && bad_ld(o.layout, ldm, T, M)) return ST_BADARG;
-    if (o.iters < 0 || o.check_every < 0 || o.reserved != 0 || o.reserved2 != 0 || o.reserved3 != 0) return ST_BADARG;
-    if (o.mode != EVC_PROX_POSITIVE && o.mode != EVC_PROX_SIGNED) return ST_BADARG;
-    if (o.momentum != EVC_PROX_ISTA && o.momentum != EVC_PROX_FISTA && o.momentum != EVC_PROX_NESTEROV) return ST_BADARG;
-    if (o.normalize != 0 && o.normalize != 1) return ST_BADARG;
-    if (o.init_mode != EVC_INIT_GIVEN && o.init_mode != EVC_INIT_CONST) return ST_BADARG;
-    if (o.stop_rule != EVC_STOP_NONE && o.stop_rule != EVC_STOP_DECOMP) return ST_BADARG;
+    if (!prox_opts_ok(o) || o.reserved3 != 0) return ST_BADARG;
     if (o.lip_weights != EVC_PROX_LIP_MEAN && o.lip_weights != EVC_PROX_LIP_MAX) return ST_BADARG;
-    if (!(o.alpha >= 0.0) || !(o.alpha - o.alpha == 0.0) || !(o.tol >= 0.0) || !(o.tol - o.tol == 0.0)) return ST_BADARG;
-    if (!(o.lipschitz >= 0.0) || !(o.lipschitz - o.lipschitz == 0.0) || !(o.init_value - o.init_value == 0.0)) return ST_BADARG;
     if (T > 0 && (!X || !H)) return ST_BADARG;                             // no frames: X, mask and H are never touched
-    if (prox_slots(o.iters, o.check_every) > PROX_MAX_SLOTS) return ST_BADARG;
     if (M > PROX_MAX_M || N > PROX_MAX_N) return ST_UNSUPPORTED;
     if (workspace_bytes < prox_masked_workspace_bytes(M, N, T, n_utt, o.dtype)) return ST_WORKSPACE;
     return ST_OK;

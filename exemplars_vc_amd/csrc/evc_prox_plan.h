@@ -1,6 +1,8 @@
-// evc_prox_plan.h - what evc_prox_solve decides on the host before its launches: the limits, the argument checks in the order
-// of their statuses, the workspace carving and the momentum schedule.  No device code: tests/prox_host_main.hip, a program of
-// its own, includes it and runs it under the host sanitizers (tests/test_prox_host.py).
+// evc_prox_plan.h - what evc_prox_solve decides on the host before and between its launches: the limits, the argument checks
+// in the order of their statuses, the workspace carving, the momentum schedule and the iteration loop.  What
+// evc_prox_masked_solve decides alike is here once: prox_opts_ok, carve_prox_tail, prox_loop.  No device
+// code: tests/prox_host_main.hip, a program of its own, includes it and runs it under the host sanitizers
+// (tests/test_prox_host.py).
 #pragma once
 #include "evc_internal.h"
 
@@ -47,7 +49,47 @@ struct ProxMomentum {
     }
 };
 
-struct ProxWs {
+// The iteration loop of the two proximal-gradient drivers, between its two events (recorded also when nothing is `live`: no
+// frames or no iterations).  Iteration i reads Wb[i & 1] and writes the other; the checks run at i = 0, check_every,
+// 2 check_every, ...  sweep(i, Win, Wout, partials, c) enqueues the driver's update with the momentum coefficient c_i, and
+// leaves the shares of the stop statistic in `partials` on a check iteration, where it is not NULL; check(slot, applied) then
+// enqueues k_prox_check after applied = i + 1 updates.  Apart from the events every device action is the callables'.
+template <typename T, typename Opts, typename Sweep, typename Check>
+int prox_loop(const Opts& o, bool live, T* const Wb[2], double* partials, hipStream_t s, Sweep sweep, Check check) {
+    if (o.ev_loop_start) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_start), s));
+    if (live) {
+        ProxMomentum mom(o.momentum);
+        for (int i = 0; i < o.iters; ++i) {
+            const bool checked = o.check_every > 0 && i % o.check_every == 0;
+            HIP_TRY(sweep(i, (const T*)Wb[i & 1], Wb[(i + 1) & 1], checked ? partials : nullptr, (T)mom.next(i)));
+            if (checked) HIP_TRY(check(i / o.check_every, i + 1));
+        }
+    }
+    if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
+    return ST_OK;
+}
+
+// the last five arrays of both drivers' workspaces
+struct ProxTail {
+    double* partials;   // [NP / 64][T], NP = round_up(N, PROX_BN): max over a row block of |X_new - X_old| - tol_n, per frame
+    int* frame_utt;     // [T]
+    int* offs;          // [n_utt + 1]
+    int* stop;          // [n_utt]: 0 running, else the updates applied when the utterance stopped
+    double* trace;      // [n_utt][PROX_MAX_SLOTS]
+};
+
+// [partials | frame_utt | offs | stop | trace] behind what `c` has given out so far
+inline ProxTail carve_prox_tail(Carver& c, int N, int T_, int n_utt) {
+    ProxTail t;
+    t.partials = c.take<double>((size_t)round_up(N, PROX_BN) / 64 * (size_t)T_);
+    t.frame_utt = c.take<int>((size_t)T_);
+    t.offs = c.take<int>((size_t)n_utt + 1);
+    t.stop = c.take<int>((size_t)n_utt);
+    t.trace = c.take<double>((size_t)n_utt * PROX_MAX_SLOTS);
+    return t;
+}
+
+struct ProxWs : ProxTail {
     char* G;            // [NP][NP] elements, NP = round_up(N, PROX_BN): A^T A (scaled), zero in the padding
     char* P;            // [N][T] elements: A^T X (scaled)
     char* W[2];         // [N][T] elements each: the extrapolated point, read from one and written to the other
@@ -55,11 +97,6 @@ struct ProxWs {
     char* tolv;         // [N] elements: tol_n
     char* d;            // [N] elements: sqrt(G_nn), or 1
     char* lip;          // [1 + N] elements: s = 1 / L, then the Gershgorin column sums
-    double* partials;   // [NP / 64][T]: max over a row block of |X_new - X_old| - tol_n, per frame
-    int* frame_utt;     // [T]
-    int* offs;          // [n_utt + 1]
-    int* stop;          // [n_utt]: 0 running, else the updates applied when the utterance stopped
-    double* trace;      // [n_utt][PROX_MAX_SLOTS]
     size_t bytes;
 };
 
@@ -78,11 +115,7 @@ inline ProxWs carve_prox(void* ws, int N, int T_, int n_utt, int dtype) {
     w.tolv = c.take<char>((size_t)N * es);
     w.d = c.take<char>((size_t)N * es);
     w.lip = c.take<char>(((size_t)N + 1) * es);
-    w.partials = c.take<double>(NP / 64 * (size_t)T_);
-    w.frame_utt = c.take<int>((size_t)T_);
-    w.offs = c.take<int>((size_t)n_utt + 1);
-    w.stop = c.take<int>((size_t)n_utt);
-    w.trace = c.take<double>((size_t)n_utt * PROX_MAX_SLOTS);
+    static_cast<ProxTail&>(w) = carve_prox_tail(c, N, T_, n_utt);
     w.bytes = c.bytes();
     return w;
 }
@@ -93,6 +126,19 @@ inline size_t prox_workspace_bytes(int M, int N, int T_, int n_utt, int dtype) {
     return carve_prox(nullptr, N, T_, n_utt, dtype).bytes + 256;
 }
 
+// the option ranges evc_prox_opts and evc_prox_masked_opts share, field for field: true, or false for ST_BADARG
+template <typename Opts> bool prox_opts_ok(const Opts& o) {
+    if (o.iters < 0 || o.check_every < 0 || o.reserved != 0 || o.reserved2 != 0) return false;
+    if (o.mode != EVC_PROX_POSITIVE && o.mode != EVC_PROX_SIGNED) return false;
+    if (o.momentum != EVC_PROX_ISTA && o.momentum != EVC_PROX_FISTA && o.momentum != EVC_PROX_NESTEROV) return false;
+    if (o.normalize != 0 && o.normalize != 1) return false;
+    if (o.init_mode != EVC_INIT_GIVEN && o.init_mode != EVC_INIT_CONST) return false;
+    if (o.stop_rule != EVC_STOP_NONE && o.stop_rule != EVC_STOP_DECOMP) return false;
+    if (!(o.alpha >= 0.0) || !(o.alpha - o.alpha == 0.0) || !(o.tol >= 0.0) || !(o.tol - o.tol == 0.0)) return false;
+    if (!(o.lipschitz >= 0.0) || !(o.lipschitz - o.lipschitz == 0.0) || !(o.init_value - o.init_value == 0.0)) return false;
+    return prox_slots(o.iters, o.check_every) <= PROX_MAX_SLOTS;
+}
+
 // evc_prox_solve's argument checks, in the order of its statuses: ST_BADARG, ST_UNSUPPORTED, ST_WORKSPACE before any device work
 inline int prox_args_check(const void* A, int lda, const void* X, int ldx, const void* H, int ldh, int M, int N, int T,
                            const int* utt_offsets, int n_utt, const evc_prox_opts* opts, const void* workspace,
@@ -100,16 +146,8 @@ inline int prox_args_check(const void* A, int lda, const void* X, int ldx, const
     if (!opts || opts->struct_bytes != (int)sizeof(evc_prox_opts)) return ST_BADARG;
     const evc_prox_opts& o = *opts;
     HIP_TRY(solve_args_ok(M, N, T, n_utt, o.dtype, o.layout, A, workspace, lda, ldx, ldh, utt_offsets));
-    if (o.iters < 0 || o.check_every < 0 || o.reserved != 0 || o.reserved2 != 0) return ST_BADARG;
-    if (o.mode != EVC_PROX_POSITIVE && o.mode != EVC_PROX_SIGNED) return ST_BADARG;
-    if (o.momentum != EVC_PROX_ISTA && o.momentum != EVC_PROX_FISTA && o.momentum != EVC_PROX_NESTEROV) return ST_BADARG;
-    if (o.normalize != 0 && o.normalize != 1) return ST_BADARG;
-    if (o.init_mode != EVC_INIT_GIVEN && o.init_mode != EVC_INIT_CONST) return ST_BADARG;
-    if (o.stop_rule != EVC_STOP_NONE && o.stop_rule != EVC_STOP_DECOMP) return ST_BADARG;
-    if (!(o.alpha >= 0.0) || !(o.alpha - o.alpha == 0.0) || !(o.tol >= 0.0) || !(o.tol - o.tol == 0.0)) return ST_BADARG;
-    if (!(o.lipschitz >= 0.0) || !(o.lipschitz - o.lipschitz == 0.0) || !(o.init_value - o.init_value == 0.0)) return ST_BADARG;
+    if (!prox_opts_ok(o)) return ST_BADARG;
     if (T > 0 && (!X || !H)) return ST_BADARG;                             // no frames: X and H are never touched
-    if (prox_slots(o.iters, o.check_every) > PROX_MAX_SLOTS) return ST_BADARG;
     if (M > PROX_MAX_M || N > PROX_MAX_N) return ST_UNSUPPORTED;
     if (workspace_bytes < prox_workspace_bytes(M, N, T, n_utt, o.dtype)) return ST_WORKSPACE;
     return ST_OK;

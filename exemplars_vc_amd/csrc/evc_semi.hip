@@ -24,7 +24,9 @@
 //
 // The error: V = A H by the strided contraction, k_semi_err leaves every frame's squared residual (float64), k_semi_check
 // sums an utterance's in a fixed order, records the square root and applies pymf's stop rule on the device.
+// The per-utterance state, its head and the read-back are evc_solve_state.h's, shared with the proximal-gradient solves.
 #include "evc_semi_plan.h"
+#include "evc_solve_state.h"
 
 namespace evc {
 
@@ -164,22 +166,6 @@ __global__ __launch_bounds__(64 * SEMI_MAX_WAVES) void k_semi_sweep(SemiArgs<T> 
     }
 }
 
-// stop = 0, trace = NaN, frame_utt[t] = the utterance of frame t (the largest u with offs[u] <= t)
-__global__ void k_semi_state(const int* __restrict__ offs, int n_utt, int T_, int n_slots, int* stop, double* trace,
-                             int* frame_utt) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_utt) stop[i] = 0;
-    if (i < (long)n_utt * n_slots) trace[i] = __builtin_nan("");
-    if (i < T_) {
-        int lo = 0, hi = n_utt - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (offs[mid] <= i) lo = mid; else hi = mid - 1;
-        }
-        frame_utt[i] = lo;
-    }
-}
-
 // dst(t, n) = src ? src(t, n) : value over the N x T_ elements, each side with its own strides
 template <typename T>
 __global__ void k_semi_copy(const T* __restrict__ src, long ss_t, long ss_n, T* __restrict__ dst, long ds_t, long ds_n, int N,
@@ -253,14 +239,7 @@ int semi_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
     const int NP = round_up(N, SEMI_BN);
     const long as_n = fm ? lda : 1, as_m = fm ? 1 : lda, xs_t = fm ? ldx : 1, xs_m = fm ? 1 : ldx;
 
-    const int whole[2] = {0, T_};
-    HIP_TRY(hipMemcpyAsync(w.offs, utt_offsets ? utt_offsets : whole, sizeof(int) * ((size_t)n_utt + 1), hipMemcpyHostToDevice,
-                           s));
-    long n_state = (long)n_utt * n_slots;
-    if (n_state < T_) n_state = T_;
-    hipLaunchKernelGGL(k_semi_state, dim3(blocks_of(n_state)), dim3(256), 0, s, w.offs, n_utt, T_, n_slots, w.stop, w.trace,
-                       w.frame_utt);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(solve_state_head(utt_offsets, n_utt, T_, n_slots, w.offs, w.stop, w.trace, w.frame_utt, s));
 
     if (T_ > 0) {
         T* G = reinterpret_cast<T*>(w.G);
@@ -317,17 +296,7 @@ int semi_solve(const T* A, int lda, const T* X, int ldx, T* H, int ldh, int M, i
         if (o.ev_loop_stop) HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(o.ev_loop_stop), s));
     }
 
-    if (!n_iter_out && !err_out) return 0;
-    int* ni_h = static_cast<int*>(malloc(sizeof(int) * n_utt));
-    if (!ni_h) return (int)hipErrorOutOfMemory;
-    hipError_t e = hipMemcpyAsync(ni_h, w.stop, sizeof(int) * n_utt, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && err_out)
-        e = hipMemcpyAsync(err_out, w.trace, sizeof(double) * n_utt * n_slots, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    for (int u = 0; e == hipSuccess && n_iter_out && u < n_utt; ++u) n_iter_out[u] = ni_h[u] ? ni_h[u] : o.iters;
-    free(ni_h);
-    HIP_TRY(e);
-    return 0;
+    return solve_read_back(w.stop, w.trace, n_utt, n_slots, o.iters, n_iter_out, err_out, s);
 }
 
 }  // namespace

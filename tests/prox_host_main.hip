@@ -6,6 +6,7 @@
 //   waves <N T> <W>         prox_waves: the wavefronts per workgroup of k_prox_sweep, around its two thresholds
 //   slots <iters check_every> <n>   prox_slots
 //   mom <kind> <c_0 .. c_7>         ProxMomentum, 17 significant digits
+//   loop <case> sweeps <n> checks <the iterations checked> c <c_0 ..>     prox_loop driven by fake callables: no device
 #include "../exemplars_vc_amd/csrc/evc_prox_plan.h"
 
 #include <cstdio>
@@ -113,7 +114,49 @@ static void args_lines() {
     { auto o = opts(); o.reserved = 2; run("reserved_before_limits", o, 25, PROX_MAX_N + 1, 70, 16); }
 }
 
+// prox_loop with both events NULL makes no HIP call of its own: the callables below only record.  What only this program can
+// see is checked here (the ping-pong of the two buffers, `partials` handed on at a check and NULL elsewhere, the check right
+// behind its sweep with slot i / check_every after i + 1 updates); the printed line is checked by tests/test_prox_host.py.
+template <typename Opts> static void loop_line(const char* name, int iters, int check_every, int momentum, bool live) {
+    Opts o{};
+    o.iters = iters; o.check_every = check_every; o.momentum = momentum;
+    double w0 = 0, w1 = 0, shares = 0;
+    double* Wb[2] = {&w0, &w1};
+    std::vector<int> checked;
+    std::vector<double> cs;
+    int last = -1;
+    bool ok = true;
+    auto sweep = [&](int i, const double* Win, double* Wout, double* partials, double c) -> int {
+        const bool due = check_every > 0 && i % check_every == 0;
+        ok = ok && i == last + 1 && Win == Wb[i & 1] && Wout == Wb[(i + 1) & 1] && partials == (due ? &shares : nullptr);
+        last = i;
+        cs.push_back(c);
+        return ST_OK;
+    };
+    auto check = [&](int slot, int applied) -> int {
+        ok = ok && applied == last + 1 && slot * check_every == last;
+        checked.push_back(last);
+        return ST_OK;
+    };
+    const int st = prox_loop<double>(o, live, Wb, &shares, nullptr, sweep, check);
+    if (st != ST_OK || !ok || (int)cs.size() != (live ? iters : 0)) {
+        printf("loop %s BAD\n", name);
+        exit(5);
+    }
+    printf("loop %s sweeps %zu checks", name, cs.size());
+    for (int i : checked) printf(" %d", i);
+    printf(" c");
+    for (double c : cs) printf(" %.17g", c);
+    printf("\n");
+}
+
 int main() {
+    loop_line<evc_prox_opts>("fista_7_every_3", 7, 3, EVC_PROX_FISTA, true);
+    loop_line<evc_prox_opts>("nesterov_5_every_1", 5, 1, EVC_PROX_NESTEROV, true);
+    loop_line<evc_prox_opts>("ista_4_no_checks", 4, 0, EVC_PROX_ISTA, true);
+    loop_line<evc_prox_masked_opts>("masked_fista_10_every_10", 10, 10, EVC_PROX_FISTA, true);
+    loop_line<evc_prox_masked_opts>("masked_fista_11_every_10", 11, 10, EVC_PROX_FISTA, true);
+    loop_line<evc_prox_opts>("nothing_live", 5, 1, EVC_PROX_FISTA, false);
     for (size_t shift : {size_t(0), size_t(8)}) {
         carve_line(25, 64, 32, 1, EVC_F64, shift);
         carve_line(25, 17, 70, 4, EVC_F32, shift);

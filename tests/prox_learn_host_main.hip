@@ -6,6 +6,8 @@
 //   block <M> <esize> <nb>   plearn_block, with the LDS bytes of k_plearn_block at that width
 //   beta <count> <bs> <beta> plearn_beta, 17 significant digits
 //   order <case> <status>    plearn_order_check
+//   loop <case> n_epochs <e> n_steps <n> count <count_io afterwards> staged <epochs whose order row was staged> reads <calls
+//        of read_stat> t0 <the steps' first frames> trace <trace_out>      plearn_loop driven by fake callables: no device
 #include "../exemplars_vc_amd/csrc/evc_prox_learn_plan.h"
 
 #include <cstdio>
@@ -147,7 +149,53 @@ static void order_lines() {
     printf("order args_twice %d\n", plearn_args_check(p, 3, p, 3, p, 4, p, 7, &count, twice, 3, 4, T_, &o, p, 16));
 }
 
+// plearn_loop with both events NULL makes no HIP call of its own: the callables below only record.  The statistic of the
+// k-th read (1, 2, ...) is 1 + 1 / k, but 0 at read `stop_at`.  What only this program can see is checked here (the order
+// pointer handed on, beta = plearn_beta of the running count to the bit, the element behind the trace untouched); the
+// printed line is checked by tests/test_prox_learn_host.py.
+static void loop_line(const char* name, int epochs, int nbat, int bs, double tol, bool has_stat, bool with_order, bool with_trace,
+                      long long count0, int stop_at) {
+    evc_prox_learn_opts o{};
+    o.epochs = epochs; o.batch_size = bs; o.tol = tol;
+    static const int device_row = 0;            // stands for the staged row: never dereferenced
+    const int* ord = with_order ? &device_row : nullptr;
+    const long total = (long)epochs * nbat;
+    std::vector<double> trace((size_t)total + 1, -5.0);
+    std::vector<int> staged, t0s;
+    long long count = count0;
+    int n_epochs = -1, n_steps = -1, reads = 0;
+    bool ok = true;
+    auto stage_order = [&](int e) -> int { staged.push_back(e); return ST_OK; };
+    auto step = [&](const int* got, int t0, double beta) -> int {
+        ok = ok && got == ord && beta == plearn_beta(count0 + (long long)t0s.size(), bs);
+        t0s.push_back(t0);
+        return ST_OK;
+    };
+    auto read_stat = [&](double* stat) -> int { ++reads; *stat = reads == stop_at ? 0.0 : 1.0 + 1.0 / reads; return ST_OK; };
+    const int st = plearn_loop(o, nbat, has_stat, ord, &count, &n_epochs, &n_steps, with_trace ? trace.data() : nullptr, nullptr,
+                               stage_order, step, read_stat);
+    if (st != ST_OK || !ok || trace[(size_t)total] != -5.0) {
+        printf("loop %s BAD\n", name);
+        exit(5);
+    }
+    printf("loop %s n_epochs %d n_steps %d count %lld staged", name, n_epochs, n_steps, count);
+    for (int e : staged) printf(" %d", e);
+    printf(" reads %d t0", reads);
+    for (int t : t0s) printf(" %d", t);
+    printf(" trace");
+    for (long i = 0; with_trace && i < total; ++i) printf(" %.17g", trace[(size_t)i]);
+    printf("\n");
+}
+
 int main() {
+    loop_line("stop_at_step_2_of_epoch_1", 4, 3, 8, 0.5, true, true, true, 0, 5);
+    loop_line("tol_0_with_a_trace", 2, 2, 8, 0.0, true, false, true, 0, 3);
+    loop_line("no_trace_no_tol", 2, 3, 8, 0.0, true, true, false, 0, 0);
+    loop_line("tol_without_a_trace", 3, 2, 8, 0.5, true, false, false, 0, 2);
+    loop_line("no_statistic", 2, 2, 8, 0.5, false, true, true, 0, 1);
+    loop_line("epochs_0", 0, 3, 8, 0.5, true, true, true, 4, 0);
+    loop_line("nbat_0", 3, 0, 8, 0.5, true, true, true, 4, 0);
+    loop_line("resumed_count", 1, 2, 32, 0.0, true, true, true, 7, 0);
     const int shapes[][4] = {{25, 17, 70, 32}, {1, 1, 1, 1}, {201, 96, 150, 64}, {50, 4096, 2048, 1024}, {1056, 4096, 4096, 4096},
                              {402, 1024, 1030, 1024}};
     for (const auto& sh : shapes)

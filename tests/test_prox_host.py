@@ -388,6 +388,25 @@ def test_host_carving_and_argument_checks(program):
         assert moms[kind] == pr.schedule(name, 8), name
 
 
+def test_the_iteration_loop_with_fake_callables(program):
+    """prox_loop (csrc/evc_prox_plan.h), driven without a device: the checks at 0, k, 2k, ... < iters, the coefficients the
+    sweep is handed against the restatement's schedule to the bit (the ping-pong and the hand-over of `partials` are
+    checked in the program)"""
+    loops = {}
+    for ln in program[0]:
+        if ln.startswith("loop "):
+            w = ln.split()
+            loops[w[1]] = (int(w[3]), [int(v) for v in w[5:w.index("c")]], [float(v) for v in w[w.index("c") + 1:]])
+    want = {"fista_7_every_3": (7, 3, "fista"), "nesterov_5_every_1": (5, 1, "nesterov"), "ista_4_no_checks": (4, 0, "ista"),
+            "masked_fista_10_every_10": (10, 10, "fista"), "masked_fista_11_every_10": (11, 10, "fista")}
+    assert sorted(loops) == sorted(list(want) + ["nothing_live"])
+    for name, (iters, every, momentum) in want.items():
+        sweeps, checked, cs = loops[name]
+        assert sweeps == iters and checked == (list(range(0, iters, every)) if every else []), name
+        assert len(checked) == pr.n_slots(iters, every) and cs == pr.schedule(momentum, iters), name
+    assert loops["nothing_live"] == (0, [], [])                     # no frames or no iterations: the two events only
+
+
 def test_the_host_program_runs_clean_under_the_sanitizers(program):
     """a stand-alone program: address + undefined-behaviour sanitizers on the host code, nothing preloaded anywhere"""
     assert _program_lines(program[1], True) == program[0]

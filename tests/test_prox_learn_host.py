@@ -296,6 +296,42 @@ def test_host_carving_and_argument_checks(program):
                           args_good=-2, args_twice=-1)
 
 
+def test_the_epoch_loop_with_fake_callables(program):
+    """plearn_loop (csrc/evc_prox_learn_plan.h), driven without a device: epochs x batches of 8 frames (the last case: 32),
+    the k-th statistic read is 1 + 1 / k, or 0 where the case says so"""
+    nan = float("nan")
+    loops = {}
+    for ln in program[0]:
+        if ln.startswith("loop "):
+            w = ln.split()
+            cut = {k: w.index(k) for k in ("staged", "reads", "t0", "trace")}
+            loops[w[1]] = dict(n_epochs=int(w[3]), n_steps=int(w[5]), count=int(w[7]),
+                               staged=[int(v) for v in w[cut["staged"] + 1:cut["reads"]]], reads=int(w[cut["reads"] + 1]),
+                               t0=[int(v) for v in w[cut["t0"] + 1:cut["trace"]]], trace=[float(v) for v in w[cut["trace"] + 1:]])
+    stat = lambda k: 1.0 + 1.0 / k       # noqa: E731
+    want = {
+        # 4 epochs of 3 steps, tol 0.5, the 5th statistic is 0: the stop at step 1 of epoch 1, NaN after it
+        "stop_at_step_2_of_epoch_1": dict(n_epochs=2, n_steps=5, count=5, staged=[0, 1], reads=5, t0=[0, 8, 16, 0, 8],
+                                          trace=[stat(1), stat(2), stat(3), stat(4), 0.0] + [nan] * 7),
+        # tol = 0 never stops, not even on a statistic of 0; no order: nothing staged
+        "tol_0_with_a_trace": dict(n_epochs=2, n_steps=4, count=4, staged=[], reads=4, t0=[0, 8, 0, 8],
+                                   trace=[stat(1), stat(2), 0.0, stat(4)]),
+        # nobody reads the statistic: read_stat, the only synchronisation of a step, is never called
+        "no_trace_no_tol": dict(n_epochs=2, n_steps=6, count=6, staged=[0, 1], reads=0, t0=[0, 8, 16] * 2, trace=[]),
+        "tol_without_a_trace": dict(n_epochs=1, n_steps=2, count=2, staged=[], reads=2, t0=[0, 8], trace=[]),
+        # a step that leaves no statistic (measurement only): nothing is read whatever tol and the trace ask for
+        "no_statistic": dict(n_epochs=2, n_steps=4, count=4, staged=[0, 1], reads=0, t0=[0, 8, 0, 8], trace=[nan] * 4),
+        "epochs_0": dict(n_epochs=0, n_steps=0, count=4, staged=[], reads=0, t0=[], trace=[]),
+        "nbat_0": dict(n_epochs=3, n_steps=0, count=4, staged=[], reads=0, t0=[], trace=[]),
+        # count_io = 7 on entry: the forgetting factors of steps 7 and 8 (checked in the program), 9 on return
+        "resumed_count": dict(n_epochs=1, n_steps=2, count=9, staged=[0], reads=2, t0=[0, 32], trace=[stat(1), stat(2)]),
+    }
+    assert sorted(loops) == sorted(want)
+    for name, w in want.items():
+        got = loops[name]
+        assert np.array_equal(got.pop("trace"), w.pop("trace"), equal_nan=True) and got == w, name
+
+
 def test_the_host_program_runs_clean_under_the_sanitizers(program):
     """a stand-alone program: address + undefined-behaviour sanitizers on the host code, nothing preloaded anywhere"""
     assert _program_lines(program[1], True) == program[0]

@@ -1,6 +1,6 @@
 """Prints the digests a digest test pins: runs the CASES of tests/test_gpu_learn_digests.py (dictionary-learning calls on
 fixtures of tests/golden) or of the test module named on the command line (tests/test_gpu_solve_digests.py: the
-fixed-dictionary solves) on the library in place, or on the one EVC_LIB names, and prints `"case": "sha256",` lines ready
+fixed-dictionary solves; tests/test_gpu_prox_digests.py: the sparse family and the semi-NMF solve) on the library in place, or on the one EVC_LIB names, and prints `"case": "sha256",` lines ready
 for that module's PARENT_DIGESTS.  Every case runs twice; one whose two runs differ is named in a comment line instead
 and must not be pinned.  Run it on the commit whose results are to be pinned; needs a HIP device.
 
