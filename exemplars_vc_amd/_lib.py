@@ -50,8 +50,12 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_prox_workspace_bytes", "evc_prox_solve",
            "evc_prox_masked_workspace_bytes", "evc_prox_masked_solve",
            "evc_prox_learn_workspace_bytes", "evc_prox_learn_block", "evc_prox_learn",
-           "evc_prox_masked_learn_workspace_bytes", "evc_prox_masked_learn")
+           "evc_prox_masked_learn_workspace_bytes", "evc_prox_masked_learn",
+           "evc_mu_masked_workspace_bytes", "evc_mu_masked_solve",
+           "evc_mu_masked_learn_workspace_bytes", "evc_mu_masked_learn_splits", "evc_mu_masked_learn")
 BETA_MAX_M = 528
+MU_MASKED_MAX_M, MU_MASKED_MAX_SLOTS = 528, 4097
+MU_MASKED_LEARN_MAX_R = 4096
 DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 DECONV_LEARN_MAX_R = 4096
 SEMI_MAX_M, SEMI_MAX_N = 1056, 16384
@@ -244,6 +248,26 @@ class ProxLearnOpts(C.Structure):
 class ProxMaskedLearnOpts(C.Structure):
     """Mirror of `evc_prox_masked_learn_opts` (include/evc.h): `evc_prox_learn_opts`' fields for the learning with a mask."""
     _fields_ = list(ProxLearnOpts._fields_)
+
+
+class MuMaskedOpts(C.Structure):
+    """Mirror of `evc_mu_masked_opts` (include/evc.h): options of the multiplicative-update solve with missing data."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("loss", C.c_int), ("iters", C.c_int),
+        ("init_mode", C.c_int), ("check_every", C.c_int), ("stop_rule", C.c_int), ("reserved", C.c_int), ("reserved2", C.c_int),
+        ("tol", C.c_double), ("init_value", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class MuMaskedLearnOpts(C.Structure):
+    """Mirror of `evc_mu_masked_learn_opts` (include/evc.h): options of the multiplicative-update learning with missing data."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("loss", C.c_int), ("iters", C.c_int),
+        ("check_every", C.c_int), ("reserved", C.c_int), ("reserved2", C.c_int),
+        ("tol", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
 
 
 class Dict(C.Structure):
@@ -564,6 +588,29 @@ def lib():
         C.c_int, C.c_int, C.c_int, C.POINTER(ProxMaskedLearnOpts),          # M, N, T, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),      # n_epochs_out, n_steps_out, trace_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_mu_masked_workspace_bytes.restype = C.c_size_t
+    L.evc_mu_masked_workspace_bytes.argtypes = [C.c_int] * 5
+    L.evc_mu_masked_solve.restype = C.c_int
+    L.evc_mu_masked_solve.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # A, X, mask, H
+        C.c_int, C.c_int, C.c_int,                                          # M, N, T
+        C.POINTER(C.c_int), C.c_int, C.POINTER(MuMaskedOpts),               # utt_offsets, n_utt, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_mu_masked_learn_workspace_bytes.restype = C.c_size_t
+    L.evc_mu_masked_learn_workspace_bytes.argtypes = [C.c_int] * 4
+    L.evc_mu_masked_learn_splits.restype = C.c_int
+    L.evc_mu_masked_learn_splits.argtypes = [C.c_int] * 3
+    L.evc_mu_masked_learn.restype = C.c_int
+    L.evc_mu_masked_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, mask, W, H
+        C.c_int, C.c_int, C.c_int, C.POINTER(MuMaskedLearnOpts),            # M, R, T, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, stat_out
         C.c_void_p,                                                         # stream
     ]
     _lib = L

@@ -24,6 +24,10 @@ deComP's online sparse dictionary learning (decomp/dictionary_learning.py) as on
 (it, D, x) with D in deComP's orientation, atoms as rows.  Its lasso half is one of the four methods above, which must be
 named: deComP's default there, 'cd', is not mirrored.  Its `mask` is refused here with NotImplementedError;
 exemplars_vc_amd.learn_dictionary_sparse(mask=..., seed=...) runs deComP's masked learning natively (evc_prox_masked_learn).
+
+`nmf.solve(y, D, x=None, tol=1e-3, minibatch=None, maxiter=1000, method='mu', likelihood='l2', mask=None)` mirrors deComP's
+batch NMF by multiplicative updates (decomp/nmf.py, nmf_methods/batch_mu.py) as one native call (evc_mu_masked_learn) and
+returns (it, D, x).  Only the batch method is mirrored: `minibatch` and every method but 'mu' raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -140,6 +144,66 @@ def _dictionary_learning_solve(y, D, alpha, x=None, tol=1.0e-3, minibatch=None, 
     return (info["n_epochs"] if stopped else maxiter), np.asarray(Dn), np.asarray(H)
 
 
+def _nmf_solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='mu', likelihood='l2', mask=None,
+               random_seed=None, device=None, **kwargs):
+    """deComP's nmf.solve -> (it, D, x): y is [n_samples, n_channels], D [n_features, n_channels] (atoms as rows), x
+    [n_samples, n_features] (None: ones), mask like y.  One native call (evc_mu_masked_learn) of at most maxiter - 1
+    iterations (deComP's loop is `range(1, maxiter)`), the statistic max |D - D_new| checked after every one; `it` is the
+    iteration (from 1) at which it fell below tol, else maxiter.  Negative y (likelihood 'kl'), D or x: AssertionError;
+    mismatched shapes, dimensions or dtypes: ValueError (deComP's ShapeMismatchError, DimInvalidError and DtypeMismatchError
+    are ValueErrors); `minibatch`, a method other than 'mu', options of the mini-batch methods, complex input:
+    NotImplementedError."""
+    from ..solver import learn_dictionary_masked
+    y, D = np.asarray(y), np.asarray(D)
+    x = np.ones((y.shape[0], D.shape[0]), dtype=y.dtype) if x is None else np.asarray(x)
+    mask = None if mask is None else np.asarray(mask)
+    arrays = [("y", y), ("D", D), ("x", x)] + ([] if mask is None else [("mask", mask)])
+    for name, a in arrays:                       # deComP: assert_dtypes
+        if name != "mask" and a.dtype.kind == 'c':
+            raise NotImplementedError("compat.decomp: complex input is not mirrored")
+        if a.dtype != y.dtype:
+            raise ValueError('Data type should be all identical, y: {0:s} and {1:s}: {2:s}'.format(str(y.dtype), name, str(a.dtype)))
+        if a.dtype.kind != 'f':
+            raise ValueError('Data type should be one of f, but given {0:s} for {1:s}'.format(str(a.dtype), name))
+    for name, a in arrays[:3]:                   # deComP: assert_ndim
+        if a.ndim != 2:
+            raise ValueError('Dimension of {0:s} should be 2 but given {1:d}'.format(name, a.ndim))
+    if x.shape[-1:] != D.shape[:1]:              # deComP: assert_shapes
+        raise ValueError('x.shape[-1:] == D.shape[:1] should be satisfied. Given: x.shape = {0:s} and D.shape = {1:s}'.format(
+            str(x.shape), str(D.shape)))
+    if y.shape[-1] != D.shape[-1]:
+        raise ValueError('y.shape[[-1]] == D.shape[[-1]] should be satisfied. Given: y.shape = {0:s} and D.shape = {1:s}'.format(
+            str(y.shape), str(D.shape)))
+    if mask is not None and mask.shape != y.shape:
+        raise ValueError('Shapes of y and mask should be identical. Given y: {0:s} and mask: {1:s}'.format(
+            str(y.shape), str(mask.shape)))
+    if x.shape[0] != y.shape[0]:
+        raise ValueError("x has shape %s, expected %s" % (x.shape, (y.shape[0], D.shape[0])))
+    assert (D >= 0.0).all() and (x >= 0.0).all()             # deComP: assert_nonnegative
+    if likelihood == 'kl':
+        assert (y >= 0.0).all()
+    if likelihood not in ('l2', 'kl'):
+        raise NotImplementedError("compat.decomp: likelihood '%s' is not mirrored (l2 and kl are)" % likelihood)
+    if minibatch is not None:
+        raise NotImplementedError("compat.decomp: the mini-batch NMF methods are not mirrored (minibatch must be None)")
+    if method != 'mu':
+        raise NotImplementedError('Batch-NMF with {} algorithm is not yet implemented.'.format(method))
+    if kwargs:
+        raise NotImplementedError("compat.decomp: unknown options %s" % sorted(kwargs))
+    dtype = np.float32 if y.dtype == np.float32 else np.float64
+    if mask is not None:
+        assert (mask >= 0.0).all()               # a negative weight: evc_mu_masked_learn does not look for it
+    maxiter = int(maxiter)
+    Dn, H, info = learn_dictionary_masked(np.ascontiguousarray(y, dtype=dtype), np.ascontiguousarray(D, dtype=dtype),
+                                          np.ascontiguousarray(x, dtype=dtype),
+                                          None if mask is None else np.ascontiguousarray(mask, dtype=dtype),
+                                          loss={"l2": "frobenius", "kl": "kl"}[likelihood], layout="frame_major",
+                                          iters=max(maxiter - 1, 0), check_every=1, tol=float(tol),
+                                          dtype="f64" if dtype == np.float64 else "f32", device=device, info=True)
+    return (info["n_iter"] if info["stopped"] else maxiter), np.asarray(Dn), np.asarray(H)
+
+
+nmf = types.SimpleNamespace(solve=_nmf_solve, BATCH_METHODS=['mu'])
 lasso = types.SimpleNamespace(solve=_lasso_solve, AVAILABLE_METHODS=AVAILABLE_METHODS,
                               AVAILABLE_NNLS_METHODS=AVAILABLE_NNLS_METHODS)
 nnls = types.SimpleNamespace(solve=_nnls_solve)

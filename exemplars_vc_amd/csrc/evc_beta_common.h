@@ -91,6 +91,63 @@ template <typename T> struct BetaCtx {
     int utt0;               // first utterance of a call that runs over a range (evc_online_learn_fresh: one batch); else 0
 };
 
+// ----- device pieces of the factored sweep, shared by k_beta_sweep / k_beta_err (evc_beta.hip) and k_mum_sweep / k_mum_err
+// (evc_mu_masked.hip); Args: BetaArgs<T> or MumArgs<T> (the fields H, hs_t, hs_n, Ap1, N, NP, MP) -----
+template <typename T> struct Vec4;
+template <> struct Vec4<double> { typedef f64x4 type; };
+template <> struct Vec4<float> { typedef f32x4 type; };
+
+// Vs[bin][frame] = (A H)[bin][frame] for the tile's 16 frame slots (0 in the padding); ends with a barrier
+template <typename T, typename Args>
+__device__ __forceinline__ void beta_form_v(const Args& a, const int4 tl, T* __restrict__ Vs) {
+    typedef typename Mma<T>::acc_t acc_t;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int f = lane & 15, g = lane >> 4;
+    const bool fvalid = f < tl.z;
+    const T* Hf = a.H + (long)(tl.y + (fvalid ? f : 0)) * a.hs_t;
+    const int NC = a.NP / 16, MT = a.MP / 16;
+#pragma unroll 1
+    for (int t0 = 0; t0 < MT; t0 += BT_GT) {
+        acc_t acc[BT_GT];
+#pragma unroll
+        for (int j = 0; j < BT_GT; ++j) acc[j] = acc_t{0, 0, 0, 0};
+#pragma unroll 1
+        for (int c = wave; c < NC; c += BT_WAVES) {
+            const int n0 = c * 16 + g * 4;
+            T h[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {          // clamped address, then select
+                const int n = n0 + s;
+                const T v = Hf[(long)(n < a.N ? n : a.N - 1) * a.hs_n];
+                h[s] = (fvalid && n < a.N) ? v : T(0);
+            }
+            const T* Ab = a.Ap1 + (long)n0 * a.MP + t0 * 16 + f;
+#pragma unroll
+            for (int j = 0; j < BT_GT; ++j)
+                if (t0 + j < MT) {
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) acc[j] = Mma<T>::mma(Ab[(long)s * a.MP + j * 16], h[s], acc[j]);
+                }
+        }
+        // the four partial sums, added in wavefront order
+#pragma unroll 1
+        for (int w = 0; w < BT_WAVES; ++w) {
+            if (wave == w) {
+#pragma unroll
+                for (int j = 0; j < BT_GT; ++j)
+                    if (t0 + j < MT) {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int idx = ((t0 + j) * 16 + Mma<T>::row(lane, r)) * BT_F + f;
+                            Vs[idx] = w ? Vs[idx] + acc[j][r] : acc[j][r];
+                        }
+                    }
+            }
+            __syncthreads();
+        }
+    }
+}
+
 // gamma of the multiplicative update (sklearn _nmf.py:780-785)
 inline double beta_gamma(double beta) { return beta < 1.0 ? 1.0 / (2.0 - beta) : beta > 2.0 ? 1.0 / (beta - 1.0) : 1.0; }
 

@@ -732,6 +732,100 @@ def convert_prox(A, B, X, H0=None, *, layout="bin_major", dtype=None, device=Non
     return (Y, H, inf) if info else (Y, H)
 
 
+def _mu_masked_shapes(A, X, lay):
+    """the sizes (M, N) of a masked multiplicative-update call from the operands' shapes alone, checked against each other and
+    against the kernel's limit - before the device is asked for"""
+    ashape, xshape = tuple(getattr(A, "shape", ())), tuple(getattr(X, "shape", ()))
+    if len(ashape) != 2 or len(xshape) != 2:
+        raise ValueError(f"A and X must be 2-D, got shapes {ashape} and {xshape}")
+    M, N = ashape if lay == _lib.BIN_MAJOR else ashape[::-1]
+    M2 = xshape[0 if lay == _lib.BIN_MAJOR else 1]
+    if M2 != M:
+        raise ValueError(f"A and X disagree on the number of bins: {M} vs {M2}")
+    if M < 1 or N < 1:
+        raise ValueError(f"empty masked multiplicative-update problem M={M}, N={N}")
+    if M > _lib.MU_MASKED_MAX_M:                              # what the ABI answers with -3
+        raise ValueError(f"unsupported masked multiplicative-update shape: M = {M} bins, the kernel holds at most "
+                         f"{_lib.MU_MASKED_MAX_M}")
+    return M, N
+
+
+def solve_activations_masked(A, X, mask=None, H0=None, *, loss="frobenius", iters=100, check_every=0, tol=0.0,
+                             stop_rule=None, init=None, init_value=1.0, layout="bin_major",
+                             utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False,
+                             loop_events=None):
+    """Multiplicative updates of the activations with missing data, the dictionary fixed (the activation half of deComP's
+    nmf.solve(method='mu', likelihood='l2' | 'kl', mask=...)), on the GPU (evc_mu_masked_solve).  mask: finite weights >= 0 of
+    X's shape, one per bin of every frame, a zero marks a missing bin; None is the unmasked update.  loss: "frobenius"
+    (deComP's 'l2') or "kl".  Per update h <- h * max(Num, 0) / max(Den, 1e-15) with Num | Den = A^T (mask x) | A^T (mask (A h))
+    (frobenius) or A^T ((mask x) / (A h + 1e-15)) | A^T mask (kl).  A frame whose mask is all zero gets h = 0.  init: "given"
+    (H0) or "const" (init_value; deComP starts at ones); default "given" with H0, else "const".  stop_rule "sklearn" (the
+    default when tol > 0 and check_every > 0): per utterance, every `check_every` iterations, stop when (err_prev - err) /
+    err_at_start < tol, with err the masked sqrt-divergence of the loss.  At most 528 bins.
+
+    Returns the activations in the caller's orientation (numpy in -> numpy out, device tensor in -> device tensor out);
+    with info=True also dict(n_iter=int array per utterance, err=[n_utt, 1 + iters // check_every] array (NaN where not
+    evaluated), kernel="k_mum_sweep", launches=int).  No CPU fallback: without a HIP device this raises RuntimeError."""
+    lay = _LAYOUTS[layout]
+    if loss not in _LOSSES:
+        raise ValueError("loss must be 'frobenius' or 'kl'")
+    iters, check_every, tol = int(iters), int(check_every), float(tol)
+    if stop_rule is None:
+        stop_rule = "sklearn" if (tol > 0.0 and check_every > 0) else "none"
+    if stop_rule not in ("none", "sklearn"):
+        raise ValueError("stop_rule must be 'none' or 'sklearn'")
+    if not (tol >= 0.0 and np.isfinite(tol)):
+        raise ValueError("tol must be finite and >= 0")
+    n_slots = _n_slots(iters, check_every)
+    if iters < 0 or check_every < 0 or n_slots > _lib.MU_MASKED_MAX_SLOTS:
+        raise ValueError(f"iters and check_every must be >= 0 with at most {_lib.MU_MASKED_MAX_SLOTS} error slots")
+    if init is None:
+        init = "given" if H0 is not None else "const"
+    if init not in ("given", "const"):
+        raise ValueError("init must be 'given' or 'const'")
+    _mu_masked_shapes(A, X, lay)
+    if mask is not None:
+        _prox_mask_ok(mask, X)
+    _pick_dtype(dtype, X, A)
+    device = require_device(device)
+    L = _lib.lib()
+    p = _operands(A, X, H0, init, layout, dtype, device, utt_offsets)
+    opts = _lib.MuMaskedOpts()
+    opts.loss, opts.iters, opts.init_mode = _LOSSES[loss], iters, _INITS[p.init]
+    opts.check_every, opts.stop_rule = check_every, _STOPS[stop_rule]
+    opts.tol, opts.init_value = tol, float(init_value)
+    _common_opts(opts, p.dcode, lay, loop_events)
+    mask_d = None if mask is None else _to_dev(mask, p.tdtype, device)[0]
+    mid = (None, 0) if mask_d is None else (mask_d.data_ptr(), _ld(mask_d))
+    ws_bytes = int(L.evc_mu_masked_workspace_bytes(p.M, p.N, p.T, p.n_utt, p.dcode))
+    return _solve_fixed(L, "evc_mu_masked_solve", device, p, (p.A_d.data_ptr(), _ld(p.A_d)), opts, ws_bytes, ("err", n_slots),
+                        info, mid=mid, kernel="k_mum_sweep",
+                        launches=iters + 2 * n_slots * (check_every > 0) if p.T > 0 else 0)
+
+
+def convert_masked(A, B, X, mask=None, H0=None, *, layout="bin_major", dtype=None, device=None, info=False, **kw):
+    """solve_activations_masked on the source side (A, X, mask) followed by synthesize with the dictionary B on the same
+    activations: returns (Y, H) with Y = B H, with info=True (Y, H, info).  With B = A, Y imputes the missing bins of X.
+    Keywords as for solve_activations_masked."""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    _, N = _mu_masked_shapes(A, X, lay)
+    bshape = tuple(getattr(B, "shape", ()))
+    if len(bshape) != 2 or bshape[1 if lay == _lib.BIN_MAJOR else 0] != N:
+        raise ValueError(f"A and B disagree on the number of exemplars: {N} vs shape {bshape}")
+    if mask is not None:
+        _prox_mask_ok(mask, X)
+    tdtype, _ = _pick_dtype(dtype, X, A)
+    device = require_device(device)
+    x_np = not isinstance(X, torch.Tensor)
+    X_d, _ = _to_dev(X, tdtype, device)
+    out = solve_activations_masked(A, X_d, mask, H0, layout=layout, dtype=tdtype, device=device, info=info, **kw)
+    H_d, inf = out if info else (out, None)
+    Y_d = synthesize(B, H_d, layout=layout, dtype=tdtype, device=device)
+    Y, H = (_to_host(Y_d), _to_host(H_d)) if x_np else (Y_d, H_d)
+    return (Y, H, inf) if info else (Y, H)
+
+
 def transform_online(W, X, *, beta=2.0, layout, max_iter=200, tol=1e-4, l1=0.0, l2=0.0, H0=None, init=None,
                      utt_offsets: Optional[Sequence[int]] = None, dtype=None, device=None, info=False, init_value=0.0,
                      out=None, loop_events=None):
@@ -1052,6 +1146,52 @@ def learn_dictionary(X, W0, H0, *, layout, iters, surface="sklearn", check_every
                                 info or tol > 0, info)
     return _learn_result(p, out_w, out_h, {"n_iter": n_iter, "err": err,
                                            "splits": _splits_info(splits, L.evc_learn_splits, M, R, T)} if info else None)
+
+
+def learn_dictionary_masked(X, W0, H0, mask=None, *, loss="frobenius", layout, iters, check_every=1, tol=0.0, dtype=None,
+                            device=None, info=False, out_w=None, out_h=None, loop_events=None, splits=0):
+    """deComP's batch NMF with missing data, X ~ W H with unit-norm atoms (nmf.solve(method='mu', likelihood='l2' | 'kl',
+    mask=...)), on the GPU (evc_mu_masked_learn).  W is addressed like the dictionary A of solve_activations, H like its
+    activations, both start at W0 / H0; mask: finite weights >= 0 of X's shape (None: the unmasked nmf.solve).  W0's atoms are
+    divided by their norms first; then per iteration H by one update of solve_activations_masked's kernel, W by the same
+    update, every atom divided by its norm, and the statistic max |W_before - W_after|: with tol > 0 the call stops after the
+    iteration whose statistic is < tol (checked every `check_every` iterations; deComP: 1).  At most 528 bins and 4096 atoms.
+
+    Returns (W, H) as learn_dictionary does; with info=True also dict(n_iter=int, stat=[1 + iters // check_every] statistics
+    (NaN in slot 0 and where not evaluated), stopped=bool, splits=frame ranges of the dictionary half's sums).  out_w / out_h,
+    loop_events, splits: as learn_dictionary's.  No CPU fallback: without a HIP device this raises RuntimeError."""
+    if loss not in _LOSSES:
+        raise ValueError("loss must be 'frobenius' or 'kl'")
+    tol = float(tol)
+    if not (tol >= 0.0 and np.isfinite(tol)):
+        raise ValueError("tol must be finite and >= 0")
+    xshape = tuple(getattr(X, "shape", ()))
+    if len(xshape) == 2 and xshape[0 if _LAYOUTS[layout] == _lib.BIN_MAJOR else 1] > _lib.MU_MASKED_MAX_M:   # the ABI's -3
+        raise ValueError(f"unsupported masked multiplicative-update shape: M = "
+                         f"{xshape[0 if _LAYOUTS[layout] == _lib.BIN_MAJOR else 1]} bins, the kernel holds at most "
+                         f"{_lib.MU_MASKED_MAX_M}")
+    if mask is not None:
+        _prox_mask_ok(mask, X)
+    opts = _lib.MuMaskedLearnOpts()
+    opts.loss, opts.iters, opts.check_every, opts.tol = _LOSSES[loss], int(iters), int(check_every), tol
+    p = _learn_operands(X, W0, H0, out_w, out_h, layout, dtype, device)
+    L = _lib.lib()
+    _common_opts(opts, p.dcode, p.lay, loop_events, splits)
+    M, R, T = p.M, p.R, p.T
+    mask_d = None if mask is None else _to_dev(mask, p.tdtype, p.device)[0]
+    head = (p.X_d.data_ptr(), _ld(p.X_d), None if mask_d is None else mask_d.data_ptr(), 0 if mask_d is None else _ld(mask_d),
+            p.W_d.data_ptr(), _ld(p.W_d), p.H_d.data_ptr(), _ld(p.H_d), M, R, T)
+    (n_iter,), stat = _learn_run(L, "evc_mu_masked_learn", p, head, opts,
+                                 int(L.evc_mu_masked_learn_workspace_bytes(M, R, T, p.dcode)),
+                                 f"unsupported masked multiplicative-update learning shape M={M}, R={R}, T={T} "
+                                 f"(M <= {_lib.MU_MASKED_MAX_M}, R <= {_lib.MU_MASKED_LEARN_MAX_R})",
+                                 _n_slots(iters, check_every), info or tol > 0, info)
+    if not info:
+        return _learn_result(p, out_w, out_h, None)
+    slot = n_iter // int(check_every) if check_every > 0 and n_iter % max(int(check_every), 1) == 0 else 0
+    stopped = bool(tol > 0 and slot > 0 and stat[slot] < tol)
+    return _learn_result(p, out_w, out_h, {"n_iter": n_iter, "stat": stat, "stopped": stopped,
+                                           "splits": _splits_info(splits, L.evc_mu_masked_learn_splits, M, R, T)})
 
 
 _BETA_ROUTES = {None: 0, "fused": 1, "unfused": 2}

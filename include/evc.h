@@ -81,6 +81,14 @@
  *   evc_prox_masked_learn  the same learning with deComP's `mask` (dictionary_learning.py:171-231): evc_prox_masked_solve's
  *                   lasso, one Gram statistic per bin and a Jacobi update of all atoms from the old dictionary;
  *                   evc_prox_masked_learn_workspace_bytes sizes it
+ *   evc_mu_masked_solve  replaces the activation half of deComP's nmf.solve(method='mu', likelihood='l2' | 'kl', mask=...)
+ *                   (decomp/nmf_methods/grads.py:77-84, 108-115, 143-150): multiplicative updates with a weight per bin of
+ *                   every frame (missing data), the dictionary fixed, on a factored sweep with the weights applied between
+ *                   its two contractions; a NULL mask is the unmasked update; evc_mu_masked_workspace_bytes sizes it
+ *   evc_mu_masked_learn  replaces deComP's nmf.solve(method='mu', likelihood='l2' | 'kl', mask=...) itself (decomp/nmf.py:16-80,
+ *                   nmf_methods/batch_mu.py, utils/normalize.py): batch NMF with a weight per entry and unit-norm atoms - per
+ *                   iteration evc_mu_masked_solve's update, the same update of the dictionary and its normalisation;
+ *                   evc_mu_masked_learn_workspace_bytes and evc_mu_masked_learn_splits size and describe it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -1430,6 +1438,98 @@ int evc_prox_masked_learn(const void* X, int ldx, const void* mask, int ldm, voi
                           int ld_s, void* stats_q, int ld_q, long long* count_io, const int* order, int M, int N, int T,
                           const evc_prox_masked_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_epochs_out,
                           int* n_steps_out, double* trace_out, evc_stream_t stream);
+
+/* Multiplicative updates of the activations with a weight per bin of every frame (missing data), the dictionary fixed:
+ * deComP's Likelihood.update_x (decomp/nmf_methods/grads.py), the activation half of nmf.solve(method='mu', likelihood='l2' |
+ * 'kl', mask=...), mirrored and not corrected.  `mask` has X's dtype, layout and shape (M x T) with its own leading dimension
+ * ldm; NULL means every weight is 1 and no mask is read (deComP's unmasked update).  With J = 1e-15 (deComP's _JITTER, in
+ * both element types), per iteration and frame:
+ *     EVC_LOSS_FROBENIUS (l2):  V = A h;      Num = A^T (mask . x);          Den = A^T (mask . V)
+ *     EVC_LOSS_KL (kl):         V = A h + J;  Num = A^T ((mask . x) / V);    Den = A^T mask
+ *     h <- (h * max(Num, 0)) / max(Den, J)        (the product first, then the quotient; a NaN passes both maxima, as numpy's)
+ * A frame whose mask is all zero gets h = 0 after one update.  Negative weights are not looked for.
+ * deComP has no fixed-dictionary surface, so the error and the stop rule are this library's own: the error of utterance u,
+ * at the start and after every `check_every` iterations, is the masked form of sklearn's _beta_divergence(square_root=True),
+ *     l2:  sqrt(sum mask (X - V)^2)           kl:  sqrt(2 max(sum mask (X log(X / V) - X + V), 0)),  terms with X = 0: mask V
+ * over the utterance's frames, with V = A h (kl: + J), and EVC_STOP_SKLEARN stops an utterance at a check when
+ * (err_prev - err) / err_at_start < tol; its frames are frozen while the others go on.  A NaN error never stops.
+ * One kernel launch per iteration (k_mum_sweep) on k_beta_sweep's geometry: a workgroup owns 16 frames of one utterance,
+ * forms V = A H on the matrix cores, turns it into Q1 | Q2 in LDS (l2: mask . X | mask . V; kl: (mask . X) / V | mask) and forms
+ * Num | Den per exemplar tile; mask . X and mask are packed once per call.  The error is summed in float64 for both types, per utterance in a fixed order (no float atomics): the same
+ * call gives bitwise the same output every time, a batch of utterances gives bitwise the activations of one call per
+ * utterance, a NULL mask the bits of a mask of ones, and a NaN in a frame of X stays in that frame's column.
+ *   M      : 1 .. 528 bins (larger: -3);  any N >= 1, T >= 0 (an utterance may be empty);  iters = 0 leaves the start in H
+ *   layout, utt_offsets, n_utt, n_iter_out, err_out : as for evc_beta_solve (at most 4097 error slots per utterance: -1)
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: as evc_beta_solve, case (8). */
+typedef struct evc_mu_masked_opts {
+    int struct_bytes;  /* sizeof(evc_mu_masked_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int loss;          /* EVC_LOSS_FROBENIUS (deComP: 'l2') | EVC_LOSS_KL ('kl') */
+    int iters;         /* number of multiplicative updates (>= 0) */
+    int init_mode;     /* EVC_INIT_GIVEN | EVC_INIT_CONST */
+    int check_every;   /* 0: the error is never evaluated; k > 0: at the start and every k iterations */
+    int stop_rule;     /* EVC_STOP_NONE | EVC_STOP_SKLEARN */
+    int reserved;      /* 0 */
+    int reserved2;     /* 0 */
+    double tol;        /* >= 0: threshold of stop_rule */
+    double init_value; /* EVC_INIT_CONST */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_mu_masked_opts;
+/* bytes of workspace evc_mu_masked_solve needs (0: invalid or unsupported arguments, M > 528 among them) */
+size_t evc_mu_masked_workspace_bytes(int M, int N, int T, int n_utt, int dtype);
+int evc_mu_masked_solve(const void* A, int lda, const void* X, int ldx, const void* mask, int ldm, void* H, int ldh, int M,
+                        int N, int T, const int* utt_offsets, int n_utt, const evc_mu_masked_opts* opts, void* workspace,
+                        size_t workspace_bytes, int* n_iter_out, double* err_out, evc_stream_t stream);
+
+/* Multiplicative updates of BOTH factors with a weight per entry (missing data), X ~ W H with unit-norm atoms: deComP's
+ * nmf.solve(y, D, x, tol, maxiter=iters + 1, method='mu', likelihood='l2' | 'kl', mask=mask) (decomp/nmf.py,
+ * nmf_methods/batch_mu.py, nmf_methods/grads.py, utils/normalize.py), mirrored and not corrected.  X is M x T, W is M x R (atoms
+ * as columns; deComP's D is its transpose), H is R x T (deComP's x is its transpose), mask as in evc_mu_masked_solve (NULL:
+ * deComP's unmasked nmf.solve); layouts and leading dimensions as in evc_nmf_learn.  W and H hold the start on entry and are
+ * updated in place.  On entry every atom of W is divided by its Euclidean norm (nmf.solve does).  Then per iteration:
+ *   activations  one update of evc_mu_masked_solve on the current W (the same kernel; its packed dictionary images are
+ *                rebuilt from W every iteration): with iters = 1 the activations are bitwise those of
+ *                evc_mu_masked_solve(iters = 1, EVC_INIT_GIVEN) on the normalised start
+ *   dictionary   with the new H and J = 1e-15:   l2: Num = (mask . X) H^T,              Den = (mask . (W H)) H^T
+ *                                                kl: Num = ((mask . X) / (W H + J)) H^T,  Den = mask H^T
+ *                W <- (W * max(Num, 0)) / max(Den, J); then every atom is divided by its Euclidean norm (a zero atom becomes
+ *                NaN, as in numpy)
+ *   statistic    max |W_before - W_after| over all entries (both normalised)
+ * With check_every > 0 and (tol > 0 or stat_out) the host reads the statistic after every check_every-th iteration and, with
+ * tol > 0, stops when it is < tol (deComP: check_every = 1; a NaN statistic never stops); *n_iter_out is the number of
+ * iterations run.  deComP's loop is `for it in range(1, maxiter)`: it runs at most maxiter - 1 iterations and returns `it` when it
+ * stops, else maxiter.
+ * The dictionary half runs on evc_beta_learn's unfused route: V^T = H^T W^T by the generic contraction, k_mum_dict_q forms the
+ * two left operands, the split contraction of evc_nmf_learn sums them against H over S = evc_mu_masked_learn_splits(M, R, T)
+ * contiguous frame ranges, and k_mum_dict_apply - one workgroup per atom - adds the S slabs in the order 0 .. S-1, updates,
+ * normalises and compares.  Every reduction runs in an order fixed by the sizes and S: no float atomics, the same call gives
+ * the same bits every time.
+ *   M : 1 .. 528, R : 1 .. 4096 (larger: -3);  T >= 1
+ *   stat_out : host, 1 + iters / check_every doubles or NULL: NaN in slot 0 (there is no statistic at the start), then the
+ *              statistic at every check that was evaluated (NaN where not); at most 4097 slots (more: -1)
+ * Status -1 / -3 / -2 are returned before any device work.  Host synchronisation: as evc_beta_learn, case (9). */
+typedef struct evc_mu_masked_learn_opts {
+    int struct_bytes;  /* sizeof(evc_mu_masked_learn_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int loss;          /* EVC_LOSS_FROBENIUS (deComP: 'l2') | EVC_LOSS_KL ('kl') */
+    int iters;         /* maximum number of iterations (>= 0; deComP: maxiter - 1) */
+    int check_every;   /* 0: the statistic is never read; k > 0: after every k-th iteration (deComP: 1) */
+    int reserved;      /* 0; tests and tuning: bits 8..15 force the number of frame ranges S (1 .. 64) */
+    int reserved2;     /* 0 */
+    double tol;        /* >= 0: the call stops when the statistic is < tol; 0: never */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the iteration loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_mu_masked_learn_opts;
+/* bytes of workspace evc_mu_masked_learn needs (0: invalid or unsupported arguments, M > 528 and R > 4096 among them) */
+size_t evc_mu_masked_learn_workspace_bytes(int M, int R, int T, int dtype);
+/* the frame ranges S the dictionary half sums over when none is forced (0: invalid or unsupported sizes) */
+int evc_mu_masked_learn_splits(int M, int R, int T);
+int evc_mu_masked_learn(const void* X, int ldx, const void* mask, int ldm, void* W, int ldw, void* H, int ldh, int M, int R,
+                        int T, const evc_mu_masked_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
+                        double* stat_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
