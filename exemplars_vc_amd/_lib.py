@@ -24,6 +24,7 @@ PROX_LIP_MEAN, PROX_LIP_MAX = 0, 1
 LOSS_FROBENIUS, LOSS_KL = 0, 1
 FLAG_NO_FUSED, FLAG_EXACT_DIV, FLAG_NO_EXCHANGE, FLAG_NO_ALL_RESIDENT, FLAG_PAIR_TILES, FLAG_NO_LONE_BIN = 1, 2, 4, 16, 32, 64
 FLAG_NO_RANGE_HOIST = 128
+FLAG_NO_QUAD_ROWS = 1 << 20
 LEARN_SKLEARN, LEARN_PYMF = 0, 1
 CDL_BOTH, CDL_DICT_ONLY = 0, 1
 DCL_BOTH, DCL_DICT_ONLY = 0, 1

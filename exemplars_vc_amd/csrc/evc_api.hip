@@ -257,7 +257,8 @@ int fused_launches(const SolveCall& c, const Workspace<double>& w, const Dims& d
         ++inf->launches;
         HIP_TRY(fused_iterate(w.fl, fb, r, w.u, d.N, d.T_, n, first, check ? 1 : 0, w.err2, o.eps_mode, o.eps, o.l1,
                               o.stop_rule == EVC_STOP_NONE ? 1 : 0, o.loss, s, last ? &lt : nullptr,
-                              !(o.reserved & EVC_FLAG_NO_LONE_BIN), !(o.reserved & EVC_FLAG_NO_RANGE_HOIST)));
+                              !(o.reserved & EVC_FLAG_NO_LONE_BIN), !(o.reserved & EVC_FLAG_NO_RANGE_HOIST),
+                              !(o.reserved & EVC_FLAG_NO_QUAD_ROWS)));
         first = 0;
         done += n;
         if (check)

@@ -534,7 +534,7 @@ static FusedArgs fused_args(const FusedLayout& f, const double* A1p, const doubl
 hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const FusedRoute& r, const UttState& u, int N,
                          int T_, int iters, int first, int write_err, double* err2, int eps_mode, double eps, double l1,
                          int all_live_known, int loss, hipStream_t s, const FusedLaunchTail* tail, bool lone_bin,
-                         bool range_hoist) {
+                         bool range_hoist, bool quad_rows) {
     FusedArgs a = fused_args(f, b.A1p, b.A2p, b.Xp, b.Hp, b.Vp, u, N, T_, iters, first);
     a.err2 = err2; a.write_err = write_err;
     a.loss = loss; a.exact_div = r.exact_div;
@@ -567,7 +567,7 @@ hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const Fuse
             }
         }
         a.range_hoist = (!xy && range_hoist) ? 1 : 0;
-        e = xy ? fused_xy_launch(f.msteps, a, r.n_cus, s) : fused_all_launch(f.msteps, a, r.n_cus, s, lone_bin);
+        e = xy ? fused_xy_launch(f.msteps, a, r.n_cus, s) : fused_all_launch(f.msteps, a, r.n_cus, s, lone_bin, quad_rows);
         a.range_hoist = 0;
         a.coop_c = 1;            // the general kernel behind it takes no part in any exchange
         a.first = 0; a.init_const = 0; a.Hx = nullptr; a.Yslab = nullptr; a.skip_hp = 0;

@@ -123,23 +123,30 @@ struct AllShape {
 #define EVC_STAMP(i)
 #endif
 
-// The kernel's text is evc_fused_all_body.inc, compiled twice.  EVC_ALL_LONE 0: k_fused_all<MSTEPS, C, KL>, every shape.
+// The kernel's text is evc_fused_all_body.inc, compiled three times.  EVC_ALL_LONE 0: k_fused_all<MSTEPS, C, KL>, every shape.
 // EVC_ALL_LONE 1: k_fused_lone<MSTEPS, C>, the same algorithm for M == 4 MSTEPS - 3 (Frobenius, dictionary in LDS, direct
 // exchange), where the last k-step of D = A_j^T V holds ONE real bin and three zero slots: that bin goes into the
 // accumulator's start value as a rank-1 update (four v_fma_f64 per lane) and the D chain is one MFMA shorter - 14 MFMAs per
 // unit at M = 25 instead of 15.  A kernel of its own, not a branch or a template parameter of k_fused_all: that kernel's
 // instances keep their names and their code, instruction for instruction (DESIGN.md 5.1a cont.).
+// EVC_ALL_LONE 2: k_fused_quad<MSTEPS, C>, k_fused_lone with bins 16 .. 24 of V' on twelve v_mfma_f64_4x4x4_4b_f64 per unit
+// instead of a second 16-row tile of four v_mfma_f64_16x16x4_f64 - again a kernel of its own, for the same reason.
 #define EVC_ALL_LONE 0
 #include "evc_fused_all_body.inc"
 #undef EVC_ALL_LONE
 #define EVC_ALL_LONE 1
 #include "evc_fused_all_body.inc"
 #undef EVC_ALL_LONE
+#define EVC_ALL_LONE 2
+#include "evc_fused_all_body.inc"
+#undef EVC_ALL_LONE
 
-template <int MSTEPS, int C, bool KL, bool LONE = false>
+// LONE: 0 k_fused_all, 1 k_fused_lone, 2 k_fused_quad
+template <int MSTEPS, int C, bool KL, int LONE = 0>
 static hipError_t launch_all(FusedArgs a, int n_cus, hipStream_t s) {
     void (*kernel)(FusedArgs);
-    if constexpr (LONE) kernel = k_fused_lone<MSTEPS, C>;
+    if constexpr (LONE == 2) kernel = k_fused_quad<MSTEPS, C>;
+    else if constexpr (LONE == 1) kernel = k_fused_lone<MSTEPS, C>;
     else kernel = k_fused_all<MSTEPS, C, KL>;
     int occ = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, ATHREADS, 0);
@@ -174,15 +181,17 @@ static hipError_t launch_all(FusedArgs a, int n_cus, hipStream_t s) {
 }
 
 template <int MSTEPS, bool KL>
-static hipError_t pick_c(const FusedArgs& a, int n_cus, hipStream_t s, bool lone_bin) {
+static hipError_t pick_c(const FusedArgs& a, int n_cus, hipStream_t s, bool lone_bin, bool quad_rows) {
     // M = 25 with 2, 4 or 8 members: the 14-MFMA unit of k_fused_lone (C2 +1.5 %, profiles/lone_bin_README.md; lone_bin
     // false: EVC_FLAG_NO_LONE_BIN).  (Instantiated for 7 k-steps only: 25 is the one narrow width in use; with 16 members
     // and more the exchange is the longer half of a step, and M 26 .. 28 have no lone bin.)
+    // The same shapes, quad_rows (false: EVC_FLAG_NO_QUAD_ROWS): k_fused_quad, whose bins 16 .. 24 of V' run on 4x4x4 MFMAs
+    // (profiles/quad_rows_README.md).
     if constexpr (MSTEPS == 7 && !KL)
         if (lone_bin && a.M == 4 * MSTEPS - 3) switch (a.NT / ATILES) {
-            case 2: return launch_all<MSTEPS, 2, KL, true>(a, n_cus, s);
-            case 4: return launch_all<MSTEPS, 4, KL, true>(a, n_cus, s);
-            case 8: return launch_all<MSTEPS, 8, KL, true>(a, n_cus, s);
+            case 2: return quad_rows ? launch_all<MSTEPS, 2, KL, 2>(a, n_cus, s) : launch_all<MSTEPS, 2, KL, 1>(a, n_cus, s);
+            case 4: return quad_rows ? launch_all<MSTEPS, 4, KL, 2>(a, n_cus, s) : launch_all<MSTEPS, 4, KL, 1>(a, n_cus, s);
+            case 8: return quad_rows ? launch_all<MSTEPS, 8, KL, 2>(a, n_cus, s) : launch_all<MSTEPS, 8, KL, 1>(a, n_cus, s);
             default: break;
         }
     switch (a.NT / ATILES) {
@@ -220,17 +229,17 @@ int fused_all_members(int NT, int N, int eps_mode, int exact_div, int loss) {
     return (c >= 1 && c <= ALL_MAX_MEMBERS) ? c : 0;
 }
 
-hipError_t fused_all_launch(int msteps, const FusedArgs& a, int n_cus, hipStream_t s, bool lone_bin) {
+hipError_t fused_all_launch(int msteps, const FusedArgs& a, int n_cus, hipStream_t s, bool lone_bin, bool quad_rows) {
     if (a.NT % ATILES || !a.coop_buf || !a.coop_abort) return hipErrorInvalidValue;
     switch (msteps) {
-        case 1: return a.loss == EVC_LOSS_KL ? pick_c<1, true>(a, n_cus, s, lone_bin) : pick_c<1, false>(a, n_cus, s, lone_bin);
-        case 2: return a.loss == EVC_LOSS_KL ? pick_c<2, true>(a, n_cus, s, lone_bin) : pick_c<2, false>(a, n_cus, s, lone_bin);
-        case 3: return a.loss == EVC_LOSS_KL ? pick_c<3, true>(a, n_cus, s, lone_bin) : pick_c<3, false>(a, n_cus, s, lone_bin);
-        case 4: return a.loss == EVC_LOSS_KL ? pick_c<4, true>(a, n_cus, s, lone_bin) : pick_c<4, false>(a, n_cus, s, lone_bin);
-        case 5: return a.loss == EVC_LOSS_KL ? pick_c<5, true>(a, n_cus, s, lone_bin) : pick_c<5, false>(a, n_cus, s, lone_bin);
-        case 6: return a.loss == EVC_LOSS_KL ? pick_c<6, true>(a, n_cus, s, lone_bin) : pick_c<6, false>(a, n_cus, s, lone_bin);
-        case 7: return a.loss == EVC_LOSS_KL ? pick_c<7, true>(a, n_cus, s, lone_bin) : pick_c<7, false>(a, n_cus, s, lone_bin);
-        case 8: return a.loss == EVC_LOSS_KL ? pick_c<8, true>(a, n_cus, s, lone_bin) : pick_c<8, false>(a, n_cus, s, lone_bin);
+        case 1: return a.loss == EVC_LOSS_KL ? pick_c<1, true>(a, n_cus, s, lone_bin, quad_rows) : pick_c<1, false>(a, n_cus, s, lone_bin, quad_rows);
+        case 2: return a.loss == EVC_LOSS_KL ? pick_c<2, true>(a, n_cus, s, lone_bin, quad_rows) : pick_c<2, false>(a, n_cus, s, lone_bin, quad_rows);
+        case 3: return a.loss == EVC_LOSS_KL ? pick_c<3, true>(a, n_cus, s, lone_bin, quad_rows) : pick_c<3, false>(a, n_cus, s, lone_bin, quad_rows);
+        case 4: return a.loss == EVC_LOSS_KL ? pick_c<4, true>(a, n_cus, s, lone_bin, quad_rows) : pick_c<4, false>(a, n_cus, s, lone_bin, quad_rows);
+        case 5: return a.loss == EVC_LOSS_KL ? pick_c<5, true>(a, n_cus, s, lone_bin, quad_rows) : pick_c<5, false>(a, n_cus, s, lone_bin, quad_rows);
+        case 6: return a.loss == EVC_LOSS_KL ? pick_c<6, true>(a, n_cus, s, lone_bin, quad_rows) : pick_c<6, false>(a, n_cus, s, lone_bin, quad_rows);
+        case 7: return a.loss == EVC_LOSS_KL ? pick_c<7, true>(a, n_cus, s, lone_bin, quad_rows) : pick_c<7, false>(a, n_cus, s, lone_bin, quad_rows);
+        case 8: return a.loss == EVC_LOSS_KL ? pick_c<8, true>(a, n_cus, s, lone_bin, quad_rows) : pick_c<8, false>(a, n_cus, s, lone_bin, quad_rows);
         default: return hipErrorInvalidValue;
     }
 }

@@ -1,4 +1,5 @@
-// The text of k_fused_all and of k_fused_lone (evc_fused_all.hip includes this file once for each, EVC_ALL_LONE 0 / 1).
+// The text of k_fused_all, k_fused_lone and k_fused_quad (evc_fused_all.hip includes this file once for each, EVC_ALL_LONE
+// 0 / 1 / 2).
 // LONE (k_fused_lone only, M == 4 MSTEPS - 3): the last k-step of D = A_j^T V and of P = A_j^T X would multiply one real
 // bin, BL = M - 1, and three zero slots.  It is not issued: the bin enters the accumulator's start value instead,
 //   d[r] = fma(A[BL, e_r], V[BL, f], d0)   and   p[r] = A[BL, e_r] X[BL, f]        (e_r: the lane's four exemplars, f: its frame)
@@ -7,18 +8,36 @@
 // The four FMAs of a unit stand in the update of the unit before it (see the sweep), not in front of its own D chain.
 // V' keeps all its MFMAs (the bins from 16 on need the second row tile), and so do the exchange, the tile end and the Y pass.
 //
+// QUAD (k_fused_quad only: k_fused_lone but for the sweep's V' part): the second row tile of V' holds M - 16 = 9 real bins and
+// 7 rows of zeros.  Its four v_mfma_f64_16x16x4_f64 per unit are replaced by twelve v_mfma_f64_4x4x4_4b_f64, whose rows come
+// in fours: NQ = 3 bin blocks (16 .. 19, 20 .. 23, 24 and three zero slots) x 4 exemplar registers.  The instruction
+// computes four independent 4 x 4 x 4 products; with A[i][k] of block b in lane i + 4 b + 16 k, B[k][j] in lane
+// j + 4 b + 16 k and D[i][j] in lane j + 4 b + 16 i (tools/ubench/mfma64_quad.hip, profiles/quad_rows_ubench.txt) the
+// contraction runs over the lane groups as in the 16x16x4 form, so h[k][r] is the B operand as it stands, the blocks are the
+// frame groups f >> 2, and lane l of accumulator beta holds V'[16 + 4 beta + (l >> 4)][frame l & 15]: element l of k-step image
+// 4 + beta of the B-operand order, the slot the second tile's accumulator register beta filled.  A has to be the same in all
+// four blocks.  The f64 form ignores cbsz / abid (the same record), so the fragment is READ replicated: aq[beta][r], lane l:
+// A[min(16 + 4 beta + (l & 3), M)][exemplar 4 (l >> 4) + r], lanes l, l + 4, l + 8, l + 12 sharing an address - twelve
+// ds_read_b64 per unit in place of four, issued behind the update, where its temporaries are dead.
+//
 // KL: the generalised Kullback-Leibler update (sklearn _nmf.py:557-606 with update_H=False): A1p then holds the
 // dictionary divided by its column sums, the sweep's B operand is R = X / max(V, eps) instead of V, the update is
 // h <- h * (A~_j^T R) - no numerator tiles, no division in the sweep - and R is formed where V is combined.
 #if EVC_ALL_LONE
 template <int MSTEPS, int C>
+#if EVC_ALL_LONE == 2
+__global__ __launch_bounds__(ATHREADS, 2) void k_fused_quad(FusedArgs a) {
+    constexpr bool QUAD = true;
+#else
 __global__ __launch_bounds__(ATHREADS, 2) void k_fused_lone(FusedArgs a) {
+    constexpr bool QUAD = false;
+#endif
     constexpr bool KL = false, LONE = true;
     static_assert(MSTEPS > 4 && C > 1 && AllShape<MSTEPS, C, false>::LDS_DICT, "two bin tiles, the dictionary in LDS, direct exchange");
 #else
 template <int MSTEPS, int C, bool KL>
 __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
-    constexpr bool LONE = false;
+    constexpr bool LONE = false, QUAD = false;
 #endif
     using S = AllShape<MSTEPS, C, KL>;
     constexpr int DS = LONE ? MSTEPS - 1 : MSTEPS;   // k-steps of the D and P chains
@@ -90,6 +109,12 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
     const double* const dB = s_dict + rowB + (lane & 15);
     const double* const dBL = s_dict + rowB + min(lane & 15, a.M - 16 * (MT - 1));
     const double* const dL = s_dict + rowB + BL;      // LONE: bin BL of the lane's four exemplars (16-lane broadcasts)
+    // QUAD: bins 16 (MT - 1) + 4 beta + (lane & 3) of the lane group's exemplars, beta in the immediate; the last block (bin BL
+    // and the row's zero slot M, never the next row) has a base of its own
+    constexpr int MTL = QUAD ? MT - 1 : MT;           // bin tiles of V' on 16x16x4 MFMAs
+    constexpr int NQ = QUAD ? MSTEPS - 4 * MTL : 0;   // bin blocks of four on 4x4x4 MFMAs
+    const double* const dQ = s_dict + rowB + 16 * MTL + (lane & 3);
+    const double* const dQL = s_dict + rowB + min(BL + (lane & 3), a.M);
     // `lds`: std::true_type - fragments from s_dict, std::false_type - buffer loads from A1p / A2p.  (The compiler would
     // pair reads off one address into ds_read2_b64: 8 LDS cycles for 16-lane groups, where this layout is 2-way
     // conflicted, against 2 x 2 for two ds_read_b64 - an empty asm with a memory clobber between the reads keeps them apart.)
@@ -130,7 +155,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
     auto load_a2 = [&](double (&a2)[MT][4], int k, auto lds) {
         if constexpr (decltype(lds)::value) {
 #pragma unroll
-            for (int u = 0; u < MT; ++u)
+            for (int u = 0; u < MTL; ++u)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     a2[u][r] = (u == MT - 1 ? dBL : dB)[k * TPD + r * PR + 16 * u];
@@ -149,6 +174,15 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 const f64x2 v = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(r2, ul16 + (u * 2 + (r >> 1)) * 1024, so, 0));
                 a2[u][r] = v[0];
                 a2[u][r + 1] = v[1];
+            }
+    };
+    auto load_aq = [&](double (&aq)[NQ > 0 ? NQ : 1][4], int k) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int b = 0; b < NQ; ++b) {
+                aq[b][r] = b < NQ - 1 ? dQ[k * TPD + r * PR + 4 * b] : dQL[k * TPD + r * PR];
+                LDS_NO_PAIR();
             }
     };
 
@@ -321,6 +355,7 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                 f64x4 vn[MT];
 #pragma unroll
                 for (int u = 0; u < MT; ++u) vn[u] = f64x4{0, 0, 0, 0};
+                double vq[NQ > 0 ? NQ : 1] = {};     // QUAD: V' of the bin blocks 16 MTL + 4 beta ..
 #pragma unroll
                 for (int k = 0; k < AKT; ++k) {
                     __builtin_amdgcn_sched_barrier(0);
@@ -356,16 +391,30 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
                     // instances: their step is the exchange, which shares its SIMDs with this sweep, and with the MFMAs
                     // packed tighter C5 (32 members) ran 0.8 % slower - they keep the order the compiler chooses.
                     if constexpr (C >= 1) __builtin_amdgcn_sched_barrier(0);
+                    [[maybe_unused]] double aq[NQ > 0 ? NQ : 1][4];
+                    if constexpr (QUAD) load_aq(aq, k);
 #pragma unroll
-                    for (int u = 0; u < MT; ++u)
+                    for (int u = 0; u < MTL; ++u)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) vn[u] = Mma<double>::mma(a2[u][r], h[k][r], vn[u]);
+                    if constexpr (QUAD) {
+                        // r-major, rotating over the blocks: an accumulator comes round every third instruction
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int b = 0; b < NQ; ++b)
+                                vq[b] = __builtin_amdgcn_mfma_f64_4x4x4f64(aq[b][r], h[k][r], vq[b], 0, 0, 0);
+                    }
                 }
 #pragma unroll
-                for (int u = 0; u < MT; ++u)
+                for (int u = 0; u < MTL; ++u)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (u * 4 + r < MSTEPS) red[w * RSTR + (u * 4 + r) * 64 + lane] = vn[u][r];
+                if constexpr (QUAD) {
+#pragma unroll
+                    for (int b = 0; b < NQ; ++b) red[w * RSTR + (4 * MTL + b) * 64 + lane] = vq[b];
+                }
             } else if (C > 1 && valid && !mine && step > 0) {
                 // ---------------- exchange, 2 / 4 / 8 members, on 16-byte words (round 7).  Thread th < NE / 2 owns the
                 // elements 2 th and 2 th + 1: one ds_read_b128 per wavefront's partial, ONE 16-byte sc1 store, and per fetch

@@ -251,7 +251,8 @@ __device__ __forceinline__ void mu_tile_hoisted(HT& h, const f64x4& p, const f64
 hipError_t fused_res_launch(int msteps, const FusedArgs& a, hipStream_t s);
 // evc_fused_all.hip: every activation and numerator tile register-resident, NT / 32 workgroups per frame tile
 // lone_bin: M = 25 with 2, 4 or 8 members runs k_fused_lone; false (EVC_FLAG_NO_LONE_BIN): k_fused_all as everywhere else
-hipError_t fused_all_launch(int msteps, const FusedArgs& a, int n_cus, hipStream_t s, bool lone_bin = true);
+// quad_rows: those shapes run k_fused_quad (bins 16 .. 24 of V' on 4x4x4 MFMAs); false (EVC_FLAG_NO_QUAD_ROWS): k_fused_lone
+hipError_t fused_all_launch(int msteps, const FusedArgs& a, int n_cus, hipStream_t s, bool lone_bin = true, bool quad_rows = true);
 // evc_fused_xy.hip: the same with two frame tiles per member and the exchange inside the sweeps, NT / 16 workgroups per pair
 hipError_t fused_xy_launch(int msteps, const FusedArgs& a, int n_cus, hipStream_t s);
 

@@ -367,11 +367,12 @@ hipError_t fused_unpack_y(const FusedLayout& fB, const double* Yp, int members, 
 // `iters` updates in one launch.  first: V is built from H by a pre-pass (else carried over in
 // Vp from the previous launch); write_err: per-frame squared residuals of the final H -> err2.
 // lone_bin: k_fused_all at M = 25 runs as k_fused_lone where fused_all_launch has an instance (false: EVC_FLAG_NO_LONE_BIN).
+// quad_rows: k_fused_lone's shapes run as k_fused_quad (false: EVC_FLAG_NO_QUAD_ROWS).
 // range_hoist: k_fused_all / k_fused_lone decide the update's range test once per sweep (false: EVC_FLAG_NO_RANGE_HOIST).
 hipError_t fused_iterate(const FusedLayout& f, const FusedBuffers& b, const FusedRoute& r, const UttState& u, int N,
                          int T_, int iters, int first, int write_err, double* err2, int eps_mode, double eps, double l1,
                          int all_live_known, int loss, hipStream_t s, const FusedLaunchTail* tail, bool lone_bin = true,
-                         bool range_hoist = true);
+                         bool range_hoist = true, bool quad_rows = true);
 
 // ----- evc_wide.hip -----
 // Fused FACTORED kernel for wide spectra (32 < M <= 208 bins, float32): k_fused_wide, a task queue over

@@ -365,7 +365,8 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
            stop_rule="none", tol=0.0, utt_offsets: Optional[Sequence[int]] = None,
            dtype=None, device=None, info=False, out=None, loop_events=None,
            fused=True, fused_c=0, fused_w=0, want_h=True, out_y=None, loss="frobenius", exact_div=False,
-           cooperative=True, all_resident=True, pair_tiles=False, lone_bin=True, range_hoist=True, _fake_coop_timeout=False,
+           cooperative=True, all_resident=True, pair_tiles=False, lone_bin=True, range_hoist=True, quad_rows=True,
+           _fake_coop_timeout=False,
            solve_info=None):
     torch = _torch()
     device = require_device(device)
@@ -408,13 +409,15 @@ def _solve(A, X, H0, B, *, layout="bin_major", iters=100, eps_mode="add", eps=No
     # (pair_tiles=True: the experimental k_fused_xy instead of k_fused_all), NO_LONE_BIN (lone_bin=False: M = 25 with 2, 4
     # or 8 members on k_fused_all's own 15-MFMA unit, not k_fused_lone's 14 - A/B and tests), NO_RANGE_HOIST
     # (range_hoist=False: k_fused_all / k_fused_lone test every unit's denominators instead of once per sweep - A/B and
-    # tests, bitwise the same result); bits
+    # tests, bitwise the same result), NO_QUAD_ROWS (quad_rows=False: k_fused_lone's shapes on that kernel, not on
+    # k_fused_quad, whose bins 16 .. 24 of V' run on 4x4x4 MFMAs - A/B and tests); bits
     # 8..15 = 1 or 2 force the general streamed kernel with that many frame tiles per workgroup (tuning; on the wide
     # float32 path: exemplar ranges per frame group), bits 16..19 = wavefronts per workgroup of k_fused_wide (4 / 8)
     opts.reserved = ((0 if fused else _lib.FLAG_NO_FUSED) | (_lib.FLAG_EXACT_DIV if exact_div else 0)
                      | (0 if cooperative else _lib.FLAG_NO_EXCHANGE)
                      | (0 if all_resident else _lib.FLAG_NO_ALL_RESIDENT) | (_lib.FLAG_PAIR_TILES if pair_tiles else 0)
                      | (0 if lone_bin else _lib.FLAG_NO_LONE_BIN) | (0 if range_hoist else _lib.FLAG_NO_RANGE_HOIST)
+                     | (0 if quad_rows else _lib.FLAG_NO_QUAD_ROWS)
                      | ((int(fused_c) & 0xff) << 8)
                      | ((int(fused_w) & 0xf) << 16))
     if _fake_coop_timeout is not False and _fake_coop_timeout is not None:

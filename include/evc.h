@@ -252,9 +252,13 @@ enum { EVC_LOSS_FROBENIUS = 0, EVC_LOSS_KL = 1 };
  *   NO_RANGE_HOIST   A/B and tests: k_fused_all / k_fused_lone with 1, 2, 4 or 8 members (N <= 4096, Frobenius) test every
  *                    unit's denominators for the fast quotients' range, as every other kernel does, instead of deciding
  *                    it once per sweep from bounds on V and on the member's dictionary (mu_tile_hoisted,
- *                    evc_fused_common.h).  Results are bit for bit the same either way */
+ *                    evc_fused_common.h).  Results are bit for bit the same either way
+ *   NO_QUAD_ROWS     A/B and tests: the shapes of k_fused_lone (M = 25; 2, 4 or 8 members) run that kernel, not k_fused_quad,
+ *                    which computes bins 16 .. 24 of V' with twelve v_mfma_f64_4x4x4_4b_f64 per unit instead of a second
+ *                    16-row tile (9 real rows) of four v_mfma_f64_16x16x4_f64 (profiles/quad_rows_README.md).  The same
+ *                    products grouped the same way; evc_solve_info reports EVC_KERNEL_FUSED_ALL either way */
 enum { EVC_FLAG_NO_FUSED = 1, EVC_FLAG_EXACT_DIV = 2, EVC_FLAG_NO_EXCHANGE = 4, EVC_FLAG_NO_ALL_RESIDENT = 16, EVC_FLAG_PAIR_TILES = 32,
-       EVC_FLAG_NO_LONE_BIN = 64, EVC_FLAG_NO_RANGE_HOIST = 128 };
+       EVC_FLAG_NO_LONE_BIN = 64, EVC_FLAG_NO_RANGE_HOIST = 128, EVC_FLAG_NO_QUAD_ROWS = 1 << 20 };
 
 struct evc_solve_info;
 struct evc_dict;

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Are the instances of k_fused_all and k_fused_lone in two `hipcc -S` outputs of evc_fused_all.hip the same, instruction
-for instruction?
+"""Are the instances of k_fused_all, k_fused_lone and k_fused_quad in two `hipcc -S` outputs of evc_fused_all.hip the
+same, instruction for instruction?
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 --offload-device-only -S exemplars_vc_amd/csrc/evc_fused_all.hip -o new.s
     python tools/fused_all_isa_diff.py parent.s new.s
@@ -19,7 +19,7 @@ import collections
 import re
 import sys
 
-NAME = re.compile(r"^(_ZN3evc1[12]k_fused_(?:allILi\dELin?\d+ELb[01]E|loneILi\dELi\d+E)EEvNS_9FusedArgsE):", re.M)
+NAME = re.compile(r"^(_ZN3evc1[12]k_fused_(?:allILi\dELin?\d+ELb[01]E|(?:lone|quad)ILi\dELi\d+E)EEvNS_9FusedArgsE):", re.M)
 FOLLOWS_ORDER = re.compile(r"^\s*(s_waitcnt|s_nop)\b")
 
 

@@ -1,8 +1,9 @@
 // Stand-alone timing harness for k_fused_all (diagnostic build with in-kernel s_memtime stamps).
 // Build (from the repo root):
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DEVC_ALL_TIMING -o /tmp/fused_all_bench tools/ubench/fused_all_bench.hip
-// Run on the GPU box: /tmp/fused_all_bench [N=4096] [rounds=2] [iters=100] [lone=1] [hoist=1]
+// Run on the GPU box: /tmp/fused_all_bench [N=4096] [rounds=2] [iters=100] [lone=1] [hoist=1] [quad=1]
 // lone = 1: k_fused_lone where fused_all_launch routes to it (M = 25; N = 1024, 2048, 4096), 0: k_fused_all everywhere.
+// quad = 1 (with lone = 1): k_fused_quad - bins 16 .. 24 of V' on 4x4x4 MFMAs - instead of k_fused_lone.
 // hoist = 1: the update's range test decided once per sweep (FusedArgs.range_hoist), 0: in front of every unit.
 // Prints the kernel time and, for the first round, the mean length (shader cycles) of a sweep step, an
 // exchange step and the barrier wait that follows each, and of the sweep's head (stamp 3), per half.
@@ -24,6 +25,7 @@ int main(int argc, char** argv) {
     const int iters = argc > 3 ? atoi(argv[3]) : 100;
     const bool lone = argc > 4 ? atoi(argv[4]) != 0 : true;
     const bool hoist = argc > 5 ? atoi(argv[5]) != 0 : true;
+    const bool quad = argc > 6 ? atoi(argv[6]) != 0 : true;
     const int M = 25, msteps = 7, mtiles = 2, msp = 8;
     const int NT = N / 16, C = NT / 32;
     int dev = 0, cus = 0;
@@ -31,7 +33,7 @@ int main(int argc, char** argv) {
     CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const int pairs = cus / C, groups = 2 * pairs;
     const int TT = groups * rounds, T = TT * 16;
-    printf("N=%d NT=%d C=%d cus=%d groups=%d TT=%d iters=%d lone=%d\n", N, NT, C, cus, groups, TT, iters, (int)lone);
+    printf("N=%d NT=%d C=%d cus=%d groups=%d TT=%d iters=%d lone=%d quad=%d\n", N, NT, C, cus, groups, TT, iters, (int)lone, (int)quad);
     // a consistent NMF problem: positive dictionary with unit columns, X = A H* (sparse H*), H0 constant
     std::vector<double> A((size_t)M * N), X((size_t)M * T);
     srand(1);
@@ -99,7 +101,7 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(dH, Hp.data(), Hp.size() * 8, hipMemcpyHostToDevice));
         CK(hipMemcpy(dV, Vp.data(), Vp.size() * 8, hipMemcpyHostToDevice));
         CK(hipEventRecord(e0, 0));
-        CK(fused_all_launch(msteps, a, cus, 0, lone));
+        CK(fused_all_launch(msteps, a, cus, 0, lone, quad));
         CK(hipEventRecord(e1, 0));
         CK(hipDeviceSynchronize());
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
