@@ -53,10 +53,13 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_prox_learn_workspace_bytes", "evc_prox_learn_block", "evc_prox_learn",
            "evc_prox_masked_learn_workspace_bytes", "evc_prox_masked_learn",
            "evc_mu_masked_workspace_bytes", "evc_mu_masked_solve",
-           "evc_mu_masked_learn_workspace_bytes", "evc_mu_masked_learn_splits", "evc_mu_masked_learn")
+           "evc_mu_masked_learn_workspace_bytes", "evc_mu_masked_learn_splits", "evc_mu_masked_learn",
+           "evc_mu_stoch_learn_workspace_bytes", "evc_mu_stoch_learn_route", "evc_mu_stoch_learn_splits", "evc_mu_stoch_learn")
 BETA_MAX_M = 528
 MU_MASKED_MAX_M, MU_MASKED_MAX_SLOTS = 528, 4097
 MU_MASKED_LEARN_MAX_R = 4096
+STOCH_ASG, STOCH_ASAG, STOCH_GSAG, STOCH_SVRMU = 0, 1, 2, 3
+MU_STOCH_MAX_R, MU_STOCH_FUSED_MAX_R = 4096, 256
 DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 DECONV_LEARN_MAX_R = 4096
 SEMI_MAX_M, SEMI_MAX_N = 1056, 16384
@@ -267,6 +270,17 @@ class MuMaskedLearnOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("loss", C.c_int), ("iters", C.c_int),
         ("check_every", C.c_int), ("reserved", C.c_int), ("reserved2", C.c_int),
         ("tol", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class MuStochOpts(C.Structure):
+    """Mirror of `evc_mu_stoch_opts` (include/evc.h): options of the mini-batch multiplicative-update learning."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("loss", C.c_int), ("method", C.c_int),
+        ("batch_size", C.c_int), ("epochs", C.c_int), ("inner_iters", C.c_int), ("order_rows", C.c_int), ("route", C.c_int),
+        ("reserved", C.c_int), ("reserved2", C.c_int),
+        ("forget_rate", C.c_double), ("alpha", C.c_double), ("tol", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -612,6 +626,21 @@ def lib():
         C.c_int, C.c_int, C.c_int, C.POINTER(MuMaskedLearnOpts),            # M, R, T, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, stat_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_mu_stoch_learn_workspace_bytes.restype = C.c_size_t
+    L.evc_mu_stoch_learn_workspace_bytes.argtypes = [C.c_int] * 6
+    L.evc_mu_stoch_learn_route.restype = C.c_int
+    L.evc_mu_stoch_learn_route.argtypes = [C.c_int] * 2
+    L.evc_mu_stoch_learn_splits.restype = C.c_int
+    L.evc_mu_stoch_learn_splits.argtypes = [C.c_int] * 4
+    L.evc_mu_stoch_learn.restype = C.c_int
+    L.evc_mu_stoch_learn.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,      # X, mask, W, H
+        C.POINTER(C.c_int),                                                 # order
+        C.c_int, C.c_int, C.c_int, C.POINTER(MuStochOpts),                  # M, R, T, opts
+        C.c_void_p, C.c_size_t,                                             # workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),      # n_epochs_out, n_steps_out, trace_out
         C.c_void_p,                                                         # stream
     ]
     _lib = L

@@ -27,7 +27,10 @@ exemplars_vc_amd.learn_dictionary_sparse(mask=..., seed=...) runs deComP's maske
 
 `nmf.solve(y, D, x=None, tol=1e-3, minibatch=None, maxiter=1000, method='mu', likelihood='l2', mask=None)` mirrors deComP's
 batch NMF by multiplicative updates (decomp/nmf.py, nmf_methods/batch_mu.py) as one native call (evc_mu_masked_learn) and
-returns (it, D, x).  Only the batch method is mirrored: `minibatch` and every method but 'mu' raise NotImplementedError.
+returns (it, D, x); with `minibatch=bs` and method 'asg-mu', 'gsg-mu', 'asag-mu', 'gsag-mu', 'svrmu' or 'svrmu-acc' it mirrors deComP's
+mini-batch NMF (nmf_methods/serizel.py, nmf_methods/kasai.py) as one native call (evc_mu_stoch_learn), with their options
+forget_rate / alpha, beta.  As in deComP, `minibatch` with 'mu' and a mini-batch method without `minibatch` raise
+NotImplementedError.
 """
 from __future__ import annotations
 
@@ -151,8 +154,8 @@ def _nmf_solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='m
     iterations (deComP's loop is `range(1, maxiter)`), the statistic max |D - D_new| checked after every one; `it` is the
     iteration (from 1) at which it fell below tol, else maxiter.  Negative y (likelihood 'kl'), D or x: AssertionError;
     mismatched shapes, dimensions or dtypes: ValueError (deComP's ShapeMismatchError, DimInvalidError and DtypeMismatchError
-    are ValueErrors); `minibatch`, a method other than 'mu', options of the mini-batch methods, complex input:
-    NotImplementedError."""
+    are ValueErrors); `minibatch` with 'mu', a mini-batch method without `minibatch`, unknown options, complex input:
+    NotImplementedError.  With `minibatch`: _nmf_solve_minibatch."""
     from ..solver import learn_dictionary_masked
     y, D = np.asarray(y), np.asarray(D)
     x = np.ones((y.shape[0], D.shape[0]), dtype=y.dtype) if x is None else np.asarray(x)
@@ -184,16 +187,20 @@ def _nmf_solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='m
         assert (y >= 0.0).all()
     if likelihood not in ('l2', 'kl'):
         raise NotImplementedError("compat.decomp: likelihood '%s' is not mirrored (l2 and kl are)" % likelihood)
-    if minibatch is not None:
-        raise NotImplementedError("compat.decomp: the mini-batch NMF methods are not mirrored (minibatch must be None)")
-    if method != 'mu':
+    if minibatch is None and method != 'mu':
         raise NotImplementedError('Batch-NMF with {} algorithm is not yet implemented.'.format(method))
-    if kwargs:
-        raise NotImplementedError("compat.decomp: unknown options %s" % sorted(kwargs))
+    if minibatch is not None and method not in MINIBATCH_METHODS:      # 'mu' among them, as in deComP
+        raise NotImplementedError('NMF with {} algorithm is not yet implemented.'.format(method))
+    allowed = () if minibatch is None else ('alpha', 'beta') if method in ('svrmu', 'svrmu-acc') else ('forget_rate',)
+    if any(k not in allowed for k in kwargs):
+        raise NotImplementedError("compat.decomp: unknown options %s" % sorted(k for k in kwargs if k not in allowed))
     dtype = np.float32 if y.dtype == np.float32 else np.float64
     if mask is not None:
-        assert (mask >= 0.0).all()               # a negative weight: evc_mu_masked_learn does not look for it
+        assert (mask >= 0.0).all()               # a negative weight: the native calls do not look for it
     maxiter = int(maxiter)
+    if minibatch is not None:
+        return _nmf_solve_minibatch(y, D, x, mask, float(tol), int(minibatch), maxiter, method, likelihood, random_seed, dtype,
+                                    device, kwargs)
     Dn, H, info = learn_dictionary_masked(np.ascontiguousarray(y, dtype=dtype), np.ascontiguousarray(D, dtype=dtype),
                                           np.ascontiguousarray(x, dtype=dtype),
                                           None if mask is None else np.ascontiguousarray(mask, dtype=dtype),
@@ -203,7 +210,39 @@ def _nmf_solve(y, D, x=None, tol=1.0e-3, minibatch=None, maxiter=1000, method='m
     return (info["n_iter"] if info["stopped"] else maxiter), np.asarray(Dn), np.asarray(H)
 
 
-nmf = types.SimpleNamespace(solve=_nmf_solve, BATCH_METHODS=['mu'])
+MINIBATCH_METHODS = ['asg-mu', 'gsg-mu', 'asag-mu', 'gsag-mu', 'svrmu', 'svrmu-acc']
+_STOCH_NATIVE = {'asg-mu': 'asg', 'gsg-mu': 'asg', 'asag-mu': 'asag', 'gsag-mu': 'gsag', 'svrmu': 'svrmu', 'svrmu-acc': 'svrmu'}
+
+
+def _nmf_solve_minibatch(y, D, x, mask, tol, minibatch, maxiter, method, likelihood, random_seed, dtype, device, kwargs):
+    """nmf.solve's mini-batch half -> (it, D, x): one native call (evc_mu_stoch_learn) of maxiter - 1 epochs over
+    int(n_samples / minibatch) batches each.  The frames go in the order deComP shuffles them with `random_seed`: Serizel's
+    four methods reshuffle cumulatively every epoch, Kasai's two shuffle once.  'gsg-mu' runs 'asg-mu' (deComP's dispatch);
+    'svrmu-acc' is 'svrmu' with int(max(beta F (3 K + 2 N) / (3 F N + 2 K), 1)) activation updates per step.  `it` is the
+    epoch (from 1) of the update that stopped the loop, else maxiter."""
+    from ..solver import decomp_frame_order, learn_dictionary_stochastic
+    T, (F, K) = y.shape[0], D.shape
+    if T < minibatch:                            # deComP: MinibatchBase.__init__
+        raise ValueError('Minibatch size should be smaller than the total size. Given {} < {}'.format(T, minibatch))
+    kasai = method in ('svrmu', 'svrmu-acc')
+    inner = 1
+    if method == 'svrmu-acc':
+        inner = int(np.maximum(float(kwargs.get('beta', 0.5)) * F * (3 * K + 2 * T) / (3 * F * T + 2 * K), 1.0))
+    epochs = max(maxiter - 1, 0)
+    order = decomp_frame_order(T, 1 if kasai else epochs, random_seed)   # None: unseeded, as deComP
+    Dn, H, info = learn_dictionary_stochastic(np.ascontiguousarray(y, dtype=dtype), np.ascontiguousarray(D, dtype=dtype),
+                                              np.ascontiguousarray(x, dtype=dtype),
+                                              None if mask is None else np.ascontiguousarray(mask, dtype=dtype),
+                                              method=_STOCH_NATIVE[method], loss={"l2": "frobenius", "kl": "kl"}[likelihood],
+                                              layout="frame_major", batch_size=minibatch, epochs=epochs, tol=tol,
+                                              forget_rate=float(kwargs.get('forget_rate', 0.5)),
+                                              alpha=float(kwargs.get('alpha', 1.0)), inner_iters=inner,
+                                              order=order if epochs > 0 else None,
+                                              dtype="f64" if dtype == np.float64 else "f32", device=device, info=True)
+    return (info["n_epochs"] if info["stopped"] else maxiter), np.asarray(Dn), np.asarray(H)
+
+
+nmf = types.SimpleNamespace(solve=_nmf_solve, BATCH_METHODS=['mu'], MINIBATCH_METHODS=MINIBATCH_METHODS)
 lasso = types.SimpleNamespace(solve=_lasso_solve, AVAILABLE_METHODS=AVAILABLE_METHODS,
                               AVAILABLE_NNLS_METHODS=AVAILABLE_NNLS_METHODS)
 nnls = types.SimpleNamespace(solve=_nnls_solve)

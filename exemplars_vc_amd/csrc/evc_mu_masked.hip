@@ -23,8 +23,7 @@
 //
 // k_mum_err forms V the same way and leaves every frame's share of the error (float64); k_mum_check sums an utterance's
 // shares in a fixed order, records the error and applies the family's stop rule on the device, as k_beta_check does.
-#include "evc_beta_common.h"
-#include "evc_mu_masked_plan.h"
+#include "evc_mu_masked_common.h"
 #include "evc_solve_state.h"
 
 namespace evc {
@@ -32,23 +31,6 @@ namespace evc {
 static_assert(MUM_F == BT_F && MUM_MAX_M == BETA_MAX_M && MUM_MAX_SLOTS == BETA_MAX_SLOTS, "evc_mu_masked_plan.h restates evc_beta_common.h");
 
 namespace {
-
-template <typename T> struct MumArgs {
-    const T* Ap1;           // [NP][MP] exemplars as rows, bins contiguous, zero-padded
-    const T* Ap3;           // [NP][MP] the same with the bins of every chunk of 16 permuted: slot 4 g + s = bin 4 s + g
-    const T* Xp;            // [n_tiles][MP][16] frames of a tile, zero-padded
-    const T* XMp;           // [n_tiles][MP][16] mask . X
-    const T* Mp;            // [n_tiles][MP][16] mask
-    T* H;
-    long hs_t, hs_n;        // H(n, t) = H[t * hs_t + n * hs_n]
-    const int4* tiles;      // {utterance, first frame, frames, -}
-    const int* stop;        // [n_utt] 0: running; else the iteration the utterance stopped at
-    double* errf;           // [n_tiles * 16] per-frame share of the error
-    int M, MP, N, NP;
-};
-
-// (max(v, lo) as numpy's maximum: a NaN passes)
-template <typename T> __device__ __forceinline__ T max_nan(T v, T lo) { return !(v <= lo) ? v : lo; }
 
 template <typename T, int LOSS>
 __global__ __launch_bounds__(BT_THREADS) void k_mum_sweep(MumArgs<T> a) {
@@ -221,6 +203,9 @@ unsigned mum_blocks(long n) { return (unsigned)((n + 255) / 256); }
 template <typename T> size_t mum_sweep_lds(int MP) { return (size_t)2 * MP * BT_F * sizeof(T); }
 template <typename T> size_t mum_err_lds(int MP) { return (size_t)MP * BT_F * sizeof(T) + 256 * sizeof(double); }
 
+}  // namespace
+
+// ----- the host steps evc_mu_stoch_learn shares (evc_mu_masked_common.h) -----
 template <typename T> int mum_sweep(const MumArgs<T>& a, int loss, int n_tiles, hipStream_t s) {
     if (loss == EVC_LOSS_KL)
         hipLaunchKernelGGL((k_mum_sweep<T, EVC_LOSS_KL>), dim3(n_tiles), dim3(BT_THREADS), mum_sweep_lds<T>(a.MP), s, a);
@@ -229,12 +214,25 @@ template <typename T> int mum_sweep(const MumArgs<T>& a, int loss, int n_tiles, 
     return (int)hipGetLastError();
 }
 
-// one call's activation half: the kernel arguments, the carved workspace and the tile count
-template <typename T> struct MumCtx {
-    MumArgs<T> a;
-    MumWs w;
-    int n_tiles, n_utt, n_slots, fm;
-};
+// the attribute is per function and process-wide: always the limit of MUM_MAX_M (see beta_begin)
+template <typename T> int mum_sweep_prepare() {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mum_sweep<T, EVC_LOSS_FROBENIUS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)mum_sweep_lds<T>(MUM_MAX_M)));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mum_sweep<T, EVC_LOSS_KL>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)mum_sweep_lds<T>(MUM_MAX_M)));
+    return 0;
+}
+
+// the two dictionary images are k_beta_sweep's: packed by its host step (A addressed as in evc_beta_solve)
+template <typename T> int mum_pack_dict(const MumCtx<T>& c, const T* A, int lda, hipStream_t s) {
+    BetaCtx<T> bc{};
+    bc.n_tiles = c.n_tiles; bc.fm = c.fm;
+    bc.a.M = c.a.M; bc.a.MP = c.a.MP; bc.a.N = c.a.N; bc.a.NP = c.a.NP;
+    bc.w.Ap1 = reinterpret_cast<T*>(c.w.Ap1); bc.w.Ap3 = reinterpret_cast<T*>(c.w.Ap3);
+    return beta_pack_dict<T>(bc, A, lda, s);
+}
+
+namespace {
 
 // carves the workspace, stages the tile table, clears the stop state and the trace, packs X | mask . X | mask and fills the
 // kernel arguments; returns 0, -2 or a hipError_t
@@ -258,26 +256,13 @@ int mum_begin(MumCtx<T>& c, const T* X, int ldx, const T* mask, int ldm, T* H, i
     a.tiles = w.tiles; a.stop = w.stop; a.errf = w.errf;
     a.M = M; a.MP = MP; a.N = N; a.NP = NP;
     if (c.n_tiles == 0) return 0;
-    // the attribute is per function and process-wide: always the limit of MUM_MAX_M (see beta_begin)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mum_sweep<T, EVC_LOSS_FROBENIUS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)mum_sweep_lds<T>(MUM_MAX_M)));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mum_sweep<T, EVC_LOSS_KL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)mum_sweep_lds<T>(MUM_MAX_M)));
+    HIP_TRY(mum_sweep_prepare<T>());
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_mum_err<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)mum_err_lds<T>(MUM_MAX_M)));
     hipLaunchKernelGGL(k_mum_pack<T>, dim3(mum_blocks((long)c.n_tiles * MP * BT_F)), dim3(256), 0, s, X, ldx, mask, ldm,
                        fm ? 1 : 0, M, MP, (const int4*)w.tiles, c.n_tiles, reinterpret_cast<T*>(w.Xp),
                        reinterpret_cast<T*>(w.XMp), reinterpret_cast<T*>(w.Mp));
     return (int)hipGetLastError();
-}
-
-// the two dictionary images are k_beta_sweep's: packed by its host step (A addressed as in evc_beta_solve)
-template <typename T> int mum_pack_dict(const MumCtx<T>& c, const T* A, int lda, hipStream_t s) {
-    BetaCtx<T> bc{};
-    bc.n_tiles = c.n_tiles; bc.fm = c.fm;
-    bc.a.M = c.a.M; bc.a.MP = c.a.MP; bc.a.N = c.a.N; bc.a.NP = c.a.NP;
-    bc.w.Ap1 = reinterpret_cast<T*>(c.w.Ap1); bc.w.Ap3 = reinterpret_cast<T*>(c.w.Ap3);
-    return beta_pack_dict<T>(bc, A, lda, s);
 }
 
 // check number `chk` (0: the start): every utterance's error into its trace slot, then the stop rule on the device
@@ -352,8 +337,22 @@ __global__ __launch_bounds__(256) void k_mum_dict_q(const T* __restrict__ X, int
     Q2t[gid] = q2;
 }
 
-// (numpy's max: a NaN passes)
-__device__ __forceinline__ double max_pass_nan(double a, double b) { return a != a ? a : b != b ? b : a > b ? a : b; }
+}  // namespace
+
+template <typename T>
+int mum_dict_q(int loss, const T* X, int ldx, const T* mask, int ldm, int fm, const T* Vt, T* Q1t, T* Q2t, int ldq, int M, int T_,
+               long rows, hipStream_t s) {
+    const long n = rows * ldq;
+    if (loss == EVC_LOSS_KL)
+        hipLaunchKernelGGL((k_mum_dict_q<T, EVC_LOSS_KL>), dim3(mum_blocks(n)), dim3(256), 0, s, X, ldx, mask, ldm, fm, Vt, Q1t, Q2t,
+                           ldq, M, T_, rows);
+    else
+        hipLaunchKernelGGL((k_mum_dict_q<T, EVC_LOSS_FROBENIUS>), dim3(mum_blocks(n)), dim3(256), 0, s, X, ldx, mask, ldm, fm, Vt,
+                           Q1t, Q2t, ldq, M, T_, rows);
+    return (int)hipGetLastError();
+}
+
+namespace {
 
 constexpr int MDA_PER = (MUM_MAX_M + 255) / 256;      // bins per thread of k_mum_dict_apply
 
@@ -462,14 +461,7 @@ int mum_learn(const void* X_, int ldx, const void* mask_, int ldm, void* W_, int
         HIP_TRY(copy2d<T>(W, ldw, M, R, fm ? 1 : 0, Am, d.Np, d.Mj, d.Np, 0, s));
         HIP_TRY(copy2d<T>(H, ldh, T_, R, fm ? 0 : 1, Ht, d.Np, d.Tp, d.Np, 0, s));
         HIP_TRY(gemm_nt<T>(Ht, d.Np, Am, d.Np, Vt, d.Mj, d.Tp, d.Mj, d.Np, s, nullptr, 0, nullptr, d.Mk));
-        const long n = (long)d.Tp * d.Mj;
-        if (o.loss == EVC_LOSS_KL)
-            hipLaunchKernelGGL((k_mum_dict_q<T, EVC_LOSS_KL>), dim3(mum_blocks(n)), dim3(256), 0, s, X, ldx, mask, ldm, fm ? 1 : 0,
-                               (const T*)Vt, Q1t, Q2t, d.Mj, M, T_, (long)d.Tp);
-        else
-            hipLaunchKernelGGL((k_mum_dict_q<T, EVC_LOSS_FROBENIUS>), dim3(mum_blocks(n)), dim3(256), 0, s, X, ldx, mask, ldm,
-                               fm ? 1 : 0, (const T*)Vt, Q1t, Q2t, d.Mj, M, T_, (long)d.Tp);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(mum_dict_q<T>(o.loss, X, ldx, mask, ldm, fm ? 1 : 0, (const T*)Vt, Q1t, Q2t, d.Mj, M, T_, (long)d.Tp, s));
         HIP_TRY(dict_grad<T>(Q1t, d.Mj, Q2t, d.Mj, Ht, d.Np, M, T_, S, part, s));
         return apply(1);
     };
@@ -492,6 +484,14 @@ int mum_learn(const void* X_, int ldx, const void* mask_, int ldm, void* W_, int
 }
 
 }  // namespace
+
+#define MUM_STEP_INSTANTIATE(T)                                                                                          \
+    template int mum_sweep_prepare<T>();                                                                                 \
+    template int mum_pack_dict<T>(const MumCtx<T>&, const T*, int, hipStream_t);                                         \
+    template int mum_sweep<T>(const MumArgs<T>&, int, int, hipStream_t);                                                 \
+    template int mum_dict_q<T>(int, const T*, int, const T*, int, int, const T*, T*, T*, int, int, int, long, hipStream_t);
+MUM_STEP_INSTANTIATE(double)
+MUM_STEP_INSTANTIATE(float)
 
 }  // namespace evc
 

@@ -1341,6 +1341,100 @@ def decomp_frame_order(T, epochs, seed):
     return rows
 
 
+_STOCH_METHODS = {"asg": _lib.STOCH_ASG, "asag": _lib.STOCH_ASAG, "gsag": _lib.STOCH_GSAG, "svrmu": _lib.STOCH_SVRMU}
+
+
+def learn_dictionary_stochastic(X, W0, H0, mask=None, *, method, loss="frobenius", layout, batch_size, epochs, tol=0.0,
+                                forget_rate=0.5, alpha=1.0, inner_iters=1, order=None, seed=None, route=None, dtype=None,
+                                device=None, info=False, out_w=None, out_h=None, loop_events=None):
+    """deComP's mini-batch NMF, X ~ W H with unit-norm atoms (nmf.solve(minibatch=batch_size, method='asg-mu' | 'asag-mu' |
+    'gsag-mu' | 'svrmu' | 'svrmu-acc', likelihood='l2' | 'kl', mask=...)), on the GPU (evc_mu_stoch_learn).  W and H are
+    addressed and start as learn_dictionary_masked's; mask: finite weights >= 0 of X's shape (None: no mask).  method: "asg"
+    (W from every batch's own gradients; deComP's 'gsg-mu' runs the same code), "asag" (gradients averaged with
+    forget_rate, W every step), "gsag" (the same average, W once per epoch), "svrmu" (Kasai's variance-reduced update with
+    step alpha; inner_iters > 1 activation updates per step is deComP's 'svrmu-acc').  An epoch takes floor(T / batch_size)
+    batches of batch_size frames in the order of its row of `order` ((epochs, T) or (1, T) ints, every row a permutation;
+    None: as the frames lie); seed (when order is None) builds the rows as deComP does with random_seed=seed: one row per
+    epoch (decomp_frame_order), for "svrmu" one row for all epochs.  The call stops at the first update with
+    max |W - W_new| < tol and then keeps the old W, as deComP does (tol = 0: never).  At most 528 bins and 4096 atoms.
+
+    Returns (W, H) as learn_dictionary does; with info=True also dict(n_epochs=the epoch (from 1) of the stopping update, else
+    epochs, n_steps=steps carried out, stat=[epochs * (T // batch_size); gsag: epochs] max |W - W_new| of every update (NaN
+    after the stop), stopped=bool, route="fused" | "unfused", splits=frame ranges of a batch's gradient sums).  route: tests
+    and tuning, "fused" (R <= 256) or "unfused" instead of the library's choice.  info=False with tol=0 enqueues without
+    waiting.  No CPU fallback: without a HIP device this raises RuntimeError."""
+    if method not in _STOCH_METHODS:
+        raise ValueError(f"method must be one of {sorted(_STOCH_METHODS)}, got {method!r}")
+    if loss not in _LOSSES:
+        raise ValueError("loss must be 'frobenius' or 'kl'")
+    if route not in _BETA_ROUTES:
+        raise ValueError(f"route must be None, 'fused' or 'unfused', got {route!r}")
+    tol, forget_rate, alpha = float(tol), float(forget_rate), float(alpha)
+    if not (tol >= 0.0 and np.isfinite(tol)):
+        raise ValueError("tol must be finite and >= 0")
+    if not 0.0 < forget_rate <= 1.0:
+        raise ValueError(f"forget_rate must lie in (0, 1], got {forget_rate!r}")
+    if not np.isfinite(alpha):
+        raise ValueError("alpha must be finite")
+    batch_size, epochs, inner_iters = int(batch_size), int(epochs), int(inner_iters)
+    lay = _LAYOUTS[layout]
+    xshape = tuple(getattr(X, "shape", ()))
+    if len(xshape) != 2:
+        raise ValueError(f"expected a 2-D matrix, got shape {xshape}")
+    bm = lay == _lib.BIN_MAJOR
+    T, M0 = int(xshape[1 if bm else 0]), int(xshape[0 if bm else 1])
+    if M0 > _lib.MU_MASKED_MAX_M:                                          # the ABI's -3
+        raise ValueError(f"unsupported mini-batch multiplicative-update shape: M = {M0} bins, the kernel holds at most "
+                         f"{_lib.MU_MASKED_MAX_M}")
+    if not 1 <= batch_size <= T:
+        raise ValueError(f"batch_size must be between 1 and the number of frames ({T}), got {batch_size}")
+    if epochs < 0:
+        raise ValueError("epochs must be >= 0")
+    if inner_iters < 1 or (inner_iters != 1 and method != "svrmu"):
+        raise ValueError("inner_iters must be >= 1, and 1 unless method='svrmu'")
+    if order is None and seed is not None:
+        order = decomp_frame_order(T, 1 if method == "svrmu" else epochs, seed)
+    if order is not None:
+        order = np.ascontiguousarray(order, dtype=np.int32)
+        rows = order.shape[0] if order.ndim == 2 else -1
+        if order.ndim != 2 or order.shape[1] != T or rows not in (1, epochs) or \
+                not np.array_equal(np.sort(order, axis=1), np.broadcast_to(np.arange(T), (rows, T))):
+            raise ValueError(f"order must hold 1 or {epochs} rows, each a permutation of the {T} frames")
+        if rows == 0:
+            order = None
+    if mask is not None:
+        _prox_mask_ok(mask, X)
+    opts = _lib.MuStochOpts()
+    opts.loss, opts.method, opts.batch_size, opts.epochs = _LOSSES[loss], _STOCH_METHODS[method], batch_size, epochs
+    opts.inner_iters, opts.order_rows, opts.route = inner_iters, 0 if order is None else int(order.shape[0]), _BETA_ROUTES[route]
+    opts.forget_rate, opts.alpha, opts.tol = forget_rate, alpha, tol
+    p = _learn_operands(X, W0, H0, out_w, out_h, layout, dtype, device)
+    L = _lib.lib()
+    _common_opts(opts, p.dcode, p.lay, loop_events)
+    M, R = p.M, p.R
+    if route == "fused" and R > _lib.MU_STOCH_FUSED_MAX_R:
+        raise ValueError(f"the fused route holds at most {_lib.MU_STOCH_FUSED_MAX_R} atoms, got R={R}")
+    mask_d = None if mask is None else _to_dev(mask, p.tdtype, p.device)[0]
+    order_p = None if order is None else order.ctypes.data_as(C.POINTER(C.c_int))
+    head = (p.X_d.data_ptr(), _ld(p.X_d), None if mask_d is None else mask_d.data_ptr(), 0 if mask_d is None else _ld(mask_d),
+            p.W_d.data_ptr(), _ld(p.W_d), p.H_d.data_ptr(), _ld(p.H_d), order_p, M, R, T)
+    n_loop = T // batch_size
+    n_upd = epochs if method == "gsag" else epochs * n_loop
+    (n_epochs, n_steps), stat = _learn_run(L, "evc_mu_stoch_learn", p, head, opts,
+                                           int(L.evc_mu_stoch_learn_workspace_bytes(M, R, T, batch_size, opts.method, p.dcode)),
+                                           f"unsupported mini-batch multiplicative-update shape M={M}, R={R}, T={T} "
+                                           f"(M <= {_lib.MU_MASKED_MAX_M}, R <= {_lib.MU_STOCH_MAX_R})",
+                                           (n_upd,), info or tol > 0, info, n_counts=2)
+    if not info:
+        return _learn_result(p, out_w, out_h, None)
+    done = -(-n_steps // n_loop) if method == "gsag" else n_steps
+    stopped = bool(tol > 0 and done > 0 and n_steps % (n_loop if method == "gsag" else 1) == 0 and stat[done - 1] < tol)
+    rcode = _BETA_ROUTES[route]
+    return _learn_result(p, out_w, out_h, {"n_epochs": n_epochs, "n_steps": n_steps, "stat": stat, "stopped": stopped,
+                                           "route": ("fused", "unfused")[int(L.evc_mu_stoch_learn_route(R, rcode)) - 1],
+                                           "splits": int(L.evc_mu_stoch_learn_splits(M, R, batch_size, rcode))})
+
+
 def learn_dictionary_sparse(X, D0, H0=None, *, alpha, layout, batch_size, epochs, tol=0.0, lasso_iters=10, lasso_tol=1e-5,
                             positive=True, momentum="fista", order=None, seed=None, state=None, dtype=None, device=None,
                             info=False, out_w=None, out_h=None, loop_events=None, lasso_check_every=10, skip=(), mask=None):

@@ -89,6 +89,11 @@
  *                   nmf_methods/batch_mu.py, utils/normalize.py): batch NMF with a weight per entry and unit-norm atoms - per
  *                   iteration evc_mu_masked_solve's update, the same update of the dictionary and its normalisation;
  *                   evc_mu_masked_learn_workspace_bytes and evc_mu_masked_learn_splits size and describe it
+ *   evc_mu_stoch_learn  replaces deComP's nmf.solve(minibatch=bs, method='asg-mu' | 'gsg-mu' | 'asag-mu' | 'gsag-mu' | 'svrmu' |
+ *                   'svrmu-acc') (nmf_methods/serizel.py, nmf_methods/kasai.py): mini-batch NMF - per step evc_mu_masked_solve's
+ *                   update on the batch's frames, a fused masked dictionary gradient and the method's dictionary update, the
+ *                   stop decided on the device; evc_mu_stoch_learn_workspace_bytes, evc_mu_stoch_learn_route and
+ *                   evc_mu_stoch_learn_splits size and describe it
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -1534,6 +1539,71 @@ int evc_mu_masked_learn_splits(int M, int R, int T);
 int evc_mu_masked_learn(const void* X, int ldx, const void* mask, int ldm, void* W, int ldw, void* H, int ldh, int M, int R,
                         int T, const evc_mu_masked_learn_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out,
                         double* stat_out, evc_stream_t stream);
+
+/* deComP's mini-batch NMF, X ~ W H with unit-norm atoms: nmf.solve(y, D, x, tol, minibatch=batch_size, maxiter=epochs + 1,
+ * method='asg-mu' | 'gsg-mu' | 'asag-mu' | 'gsag-mu' | 'svrmu' | 'svrmu-acc', likelihood='l2' | 'kl', mask=mask)
+ * (decomp/nmf.py, nmf_methods/serizel.py, nmf_methods/kasai.py, nmf_methods/grads.py, utils/data.py, utils/normalize.py),
+ * mirrored and not corrected.  X, mask, W, H, layouts and leading dimensions as in evc_mu_masked_learn; W and H hold the start
+ * on entry and are updated in place.  On entry every atom of W is divided by its Euclidean norm.  An epoch has n_loop =
+ * floor(T / batch_size) steps; step b takes the frames F = order[e][b bs .. (b + 1) bs), the last T mod bs frames of the row
+ * are not touched in that epoch.  Per step, with J = 1e-15:
+ *   activations  inner_iters updates of evc_mu_masked_solve (the same kernel) on X[:, F], mask[:, F], H[:, F] with the current W
+ *   gradients    from the new H_F:  l2: g+ = (mask . X_F) H_F^T,              g- = (mask . (W H_F)) H_F^T
+ *                                   kl: g+ = ((mask . X_F) / (W H_F + J)) H_F^T,  g- = mask H_F^T
+ *   dictionary   EVC_STOCH_ASG   ('asg-mu'; deComP sends 'gsg-mu' here too):  W_new = (W max(g+, 0)) / max(g-, J), every step
+ *                EVC_STOCH_ASAG  a+- <- (1 - rho) a+- + rho g+- (zero at every epoch's start), W_new from a+-, every step
+ *                EVC_STOCH_GSAG  the same accumulation every step, W_new from a+- once, after the epoch's last step
+ *                EVC_STOCH_SVRMU at every epoch's start, without an activation update, full+- = (sum_b g+-_b) / n_loop in
+ *                                step order;  per step P = g+ + prev-[b] + full+,  Q = g- + prev+[b] + full- (the crossed
+ *                                signs are deComP's),  W_new = max(W ((1 - alpha) + alpha P / max(Q, J)), 0),  then
+ *                                prev+-[b] <- g+-;  prev starts at zero and lives for the whole call
+ *                every operation in the order written, none contracted; then every atom of W_new is divided by its
+ *                Euclidean norm (a zero atom becomes NaN, as in numpy)
+ *   stop         stat = max |W - W_new|;  stat < tol ends the call and W KEEPS THE OLD VALUE (deComP returns D, not D_new), H
+ *                keeps this step's update, the frames of later steps are untouched;  a NaN statistic never stops;  otherwise
+ *                W <- W_new
+ * The dictionary half has two routes (opts.route: 0 the library's choice, fused up to R = 256; 1 fused, R <= 256 or -3; 2 unfused):
+ * fused, k_mus_dict_grad recomputes W H_F on the matrix cores, applies mask and loss in registers and contracts against H_F in
+ * one launch; unfused, evc_mu_masked_learn's kernels.  Both leave S slabs of partial sums over contiguous frame ranges of the
+ * batch (S a function of M, R, batch_size and the route only), added in the order 0 .. S-1.  The stop is decided on the device:
+ * the launches enqueued after it return at once, and the host reads the stop word once per epoch (only when tol > 0).  No
+ * float atomics, no exchange between workgroups: the same call gives the same bits every time.
+ *   M : 1 .. 528, R : 1 .. 4096 (larger: -3);  1 <= batch_size <= T;  svrmu keeps 2 n_loop M R elements (over 2^40 bytes: -3)
+ *   order        : host int[order_rows][T], every row a permutation of 0 .. T-1 (else -1); NULL with order_rows = 0: the
+ *                  frames as they lie; order_rows = 1: every epoch takes the same row (svrmu); else order_rows = epochs
+ *   n_epochs_out : host int or NULL: the epoch (from 1) of the update that stopped the call, else `epochs`
+ *   n_steps_out  : host int or NULL: the steps carried out (the stopping one included)
+ *   trace_out    : host, one double per dictionary update (epochs * n_loop; gsag: epochs) or NULL: its statistic, NaN after
+ *                  the stop
+ * Status -1 / -3 / -2 are returned before any device work.  With tol = 0 and all three outputs NULL the call only enqueues. */
+enum { EVC_STOCH_ASG = 0, EVC_STOCH_ASAG = 1, EVC_STOCH_GSAG = 2, EVC_STOCH_SVRMU = 3 };
+typedef struct evc_mu_stoch_opts {
+    int struct_bytes;  /* sizeof(evc_mu_stoch_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int loss;          /* EVC_LOSS_FROBENIUS (deComP: 'l2') | EVC_LOSS_KL ('kl') */
+    int method;        /* EVC_STOCH_* */
+    int batch_size;    /* frames per step (deComP: minibatch) */
+    int epochs;        /* >= 0 (deComP: maxiter - 1) */
+    int inner_iters;   /* >= 1 activation updates per step; must be 1 unless EVC_STOCH_SVRMU (deComP's svrmu-acc) */
+    int order_rows;    /* 0 (order == NULL) | 1 | epochs */
+    int route;         /* 0: the library's choice; 1: fused; 2: unfused */
+    int reserved;      /* 0 */
+    int reserved2;     /* 0 */
+    double forget_rate;   /* rho of asag / gsag, 0 < rho <= 1 (deComP: 0.5) */
+    double alpha;         /* svrmu's step (deComP: 1.0) */
+    double tol;           /* >= 0: the call stops when the statistic is < tol; 0: never */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the epoch loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_mu_stoch_opts;
+/* bytes of workspace evc_mu_stoch_learn needs (0: invalid or unsupported arguments) */
+size_t evc_mu_stoch_learn_workspace_bytes(int M, int R, int T, int batch_size, int method, int dtype);
+/* the route (1 fused, 2 unfused) and the frame ranges S the dictionary half takes for `route` (0: invalid or unsupported) */
+int evc_mu_stoch_learn_route(int R, int route);
+int evc_mu_stoch_learn_splits(int M, int R, int batch_size, int route);
+int evc_mu_stoch_learn(const void* X, int ldx, const void* mask, int ldm, void* W, int ldw, void* H, int ldh, const int* order,
+                       int M, int R, int T, const evc_mu_stoch_opts* opts, void* workspace, size_t workspace_bytes,
+                       int* n_epochs_out, int* n_steps_out, double* trace_out, evc_stream_t stream);
 
 #ifdef __cplusplus
 }
