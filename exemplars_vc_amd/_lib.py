@@ -302,13 +302,23 @@ class SolveInfo(C.Structure):
     ]
 
 
+# block codes of evc_solve_info.variant for k_gemm_nt / k_gemm2 (include/evc.h): frames x rows, None: no such product
+GEMM_BLOCKS = {0: None, 1: (64, 64), 2: (64, 128), 3: (128, 64), 4: (128, 128), 5: (128, 128)}
+
+
 def decode_variant(kernel: int, v: int):
     """evc_solve_info.variant as a dict (None for the kernels that report none): schedule and template instance of the
-    task-queue kernels.  k_fused_wide: k_fused_wide<mt, w, tagged>; k_fused_wide64: k_fused_wide64<tpw>.  k_fused_all:
+    task-queue kernels.  k_gemm_nt / k_gemm2: the block (frames, rows) of the update contraction, of V = H Am^T with its
+    k-split count and of the numerator P (None where a solve forms none), and whether a block is k_gemm2's deep-slab
+    shape (diagnostic builds).  k_fused_wide: k_fused_wide<mt, w, tagged>; k_fused_wide64: k_fused_wide64<tpw>.  k_fused_all:
     set when its last launch formed Y itself (evc_nmf_convert), with whether that launch still stored the packed
     activations; None for every other solve on that kernel."""
     if kernel == 5 and v:      # k_fused_all: what the end of a frame tile did in the last launch
         return {"y_in_kernel": bool(v & 1), "packed_h_stored": bool(v & 2)}
+    if kernel in (1, 2) and v:      # the contraction kernels: block (frames, rows) of each product, k-splits of V = H Am^T
+        blk = lambda c: GEMM_BLOCKS[c & 15]
+        return {"update": blk(v), "v": blk(v >> 4), "v_splits": (v >> 8) & 63, "p": blk(v >> 16),
+                "deep": any(((v >> b) & 15) == 5 for b in (0, 4, 16))}
     if kernel not in (6, 7):
         return None
     d = {"static": bool(v & 1), "reduce": bool(v & 2), "tagged": bool(v & 4)}

@@ -488,14 +488,18 @@ int solve_gemm(const SolveCall& c, const evc_solve_opts& o, const Route& r, evc_
     // ---- numerator (and Gram matrix) ----
     const bool gram = (algo == EVC_ALGO_GRAM || algo == EVC_ALGO_LITERAL);
     if (gram) HIP_TRY(gemm_nt<T>(w.At, d.Mk, w.At, d.Mk, w.G, d.Np, d.Np, d.Np, d.Mk, s));
-    if (!kl) HIP_TRY(gemm_nt<T>(w.Xt, d.Mk, w.At, d.Mk, w.Pt, d.Np, d.Tp, d.Np, d.Mk, s));
+    // what the launchers chose (evc_gemm_plan.h), for evc_solve_info.variant: the numerator, V = H Am^T in the loop, the update
+    GemmPlan plan_p{}, plan_v{}, plan_u{};
+    if (!kl) HIP_TRY(gemm_nt<T>(w.Xt, d.Mk, w.At, d.Mk, w.Pt, d.Np, d.Tp, d.Np, d.Mk, s, nullptr, 0, nullptr, 0, nullptr, &plan_p));
 
     T* Hc = w.H0;       // current activations
     T* Hn = w.H1;       // ping-pong partner (GRAM only)
     bool v_valid = false;
 
     auto residual_check = [&](int c) -> int {
-        if (!v_valid) HIP_TRY(gemm_nt<T>(Hc, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, w.Vsplit, w.vsplit_elems, nullptr, d.Mk));
+        // (the V of a check serves the next iteration of FACTORED / KL: reported as the loop's; GRAM / LITERAL report none)
+        if (!v_valid) HIP_TRY(gemm_nt<T>(Hc, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, w.Vsplit, w.vsplit_elems, nullptr, d.Mk,
+                                         nullptr, gram ? nullptr : &plan_v));
         v_valid = true;
         if (kl) HIP_TRY(frame_err_kl<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, o.eps, w.err2, s));
         else HIP_TRY(frame_err2<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, T_, w.err2, s));
@@ -526,22 +530,23 @@ int solve_gemm(const SolveCall& c, const evc_solve_opts& o, const Route& r, evc_
         }
         if (gram) {
             ep.Hin = Hc;                  // H' = mu(H, P, H G^T)   (G symmetric)
-            HIP_TRY(gemm_nt_mu<T>(Hc, d.Np, w.G, d.Np, Hn, d.Tp, d.Np, d.Np, ep, s));
+            HIP_TRY(gemm_nt_mu<T>(Hc, d.Np, w.G, d.Np, Hn, d.Tp, d.Np, d.Np, ep, s, &plan_u));
             T* tmp = Hc; Hc = Hn; Hn = tmp;
         } else {
-            if (!v_valid) HIP_TRY(gemm_nt<T>(Hc, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, w.Vsplit, w.vsplit_elems, nullptr, d.Mk, gate));
+            if (!v_valid) HIP_TRY(gemm_nt<T>(Hc, d.Np, w.Am, d.Np, w.Vt, d.Mj, d.Tp, d.Mj, d.Np, s, w.Vsplit, w.vsplit_elems, nullptr, d.Mk, gate, &plan_v));
             ep.Hin = Hc;
             if (kl) {                     // H' = H (.) (X (/) max(V, eps)) (A / colsum)   sklearn _nmf.py:556-606
                 HIP_TRY(kl_ratio<T>(w.Xt, d.Mk, w.Vt, d.Mj, M, d.Tp, o.eps, w.Rt, d.Mk, s));
-                HIP_TRY(gemm_nt_mu<T>(w.Rt, d.Mk, w.Akl, d.Mk, Hc, d.Tp, d.Np, d.Mk, ep, s));
+                HIP_TRY(gemm_nt_mu<T>(w.Rt, d.Mk, w.Akl, d.Mk, Hc, d.Tp, d.Np, d.Mk, ep, s, &plan_u));
             } else {                      // H' = mu(H, P, V At^T), V = H Am^T ; in place
-                HIP_TRY(gemm_nt_mu<T>(w.Vt, d.Mj, w.At, d.Mk, Hc, d.Tp, d.Np, d.Mk, ep, s));
+                HIP_TRY(gemm_nt_mu<T>(w.Vt, d.Mj, w.At, d.Mk, Hc, d.Tp, d.Np, d.Mk, ep, s, &plan_u));
             }
         }
         v_valid = false;
         if (o.check_every > 0 && it % o.check_every == 0) HIP_TRY(residual_check(it / o.check_every));
     }
 
+    inf->variant = gemm_variant(plan_u, plan_v, plan_p);
     if (o.ev_loop_stop) HIP_TRY(hipEventRecord((hipEvent_t)o.ev_loop_stop, s));
     if (H) HIP_TRY(copy2d<T>(Hc, d.Np, d.T_, d.N, 0, H, ldh, d.T_, d.N, fm ? 0 : 1, s));
     if (y) HIP_TRY(synth_rows<T>(Hc, d.Np, *y, d.N, d.T_, fm, s));

@@ -21,7 +21,7 @@
 
 namespace evc {
 
-constexpr int KS = 16;  // k-slab depth staged per barrier
+constexpr int KS = GEMM_KS;  // k-slab depth staged per barrier
 constexpr int NT_EPI_KL = 100, NT_EPI_STORE = 101;      // epilogue bodies besides the four eps modes
 
 template <typename T, int E> struct VecOf { typedef T type __attribute__((ext_vector_type(E))); };
@@ -220,68 +220,42 @@ hipError_t sum_slabs(const T* part, long slab, int splits, T* C, hipStream_t s, 
     return hipGetLastError();
 }
 
-// Which generation of the contraction kernel serves a call: k_gemm2 for float32 (77 against 65 Tflop/s on the
-// STFT flow); float64 stays on k_gemm_nt, which k_gemm2 does not beat (its 64-cycle MFMAs hide what k_gemm2
-// removes).  Diagnostic builds (-DEVC_DIAG_GEMM_V1 / -DEVC_DIAG_GEMM2_F64) force one or the other for A/B timing;
-// the shipped library reads nothing from the environment.
-template <typename T> static bool use_gemm2() {
-#if defined(EVC_DIAG_GEMM_V1)
-    return false;
-#elif defined(EVC_DIAG_GEMM2_F64)
-    return true;
-#else
-    return sizeof(T) == 4;
-#endif
+// Which generation of the contraction kernel serves a call: plan_use_gemm2 (evc_gemm_plan.h)
+template <typename T> static bool use_gemm2() { return plan_use_gemm2((int)sizeof(T)); }
+
+static int device_cus_or_256() {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+        cus = 256;
+    return cus;
 }
 
+// Block shape and split count come from plan_gemm_nt / plan_gemm_nt_mu (evc_gemm_plan.h); the instances below are the
+// ones those plans can name.
 template <typename T>
 hipError_t gemm_nt(const T* L, int ldl, const T* R, int ldr, T* C, int ldc, int I, int J, int Kd,
-                   hipStream_t s, T* scratch, size_t scratch_elems, int* splits_out, int j_valid, const int* gate) {
+                   hipStream_t s, T* scratch, size_t scratch_elems, int* splits_out, int j_valid, const int* gate,
+                   GemmPlan* plan_out) {
     if (splits_out) *splits_out = 0;
+    if (plan_out) *plan_out = GemmPlan{0, 0, 0, -1, 1};
     if (I <= 0 || J <= 0) return hipSuccess;
     if (use_gemm2<T>() && gemm2_ok<T>(L, ldl, R, ldr, C, ldc, I, J, Kd)) {
         int dev = 0, cus = 0;
         if (scratch && (hipGetDevice(&dev) != hipSuccess ||
                         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess))
             cus = 0;
-        return gemm2<T>(L, ldl, R, ldr, C, ldc, I, J, Kd, s, scratch, scratch_elems, splits_out, cus, j_valid, gate);
+        return gemm2<T>(L, ldl, R, ldr, C, ldc, I, J, Kd, s, scratch, scratch_elems, splits_out, cus, j_valid, gate, plan_out);
     }
     if (I % 64 || J % 64 || Kd % KS || Kd <= 0) return hipErrorInvalidValue;
     MuEpilogue<T> ep{};
     ep.gate = gate;
-    // few output tiles (one utterance): 64x64 tiles put 2-4x more workgroups on the 256 CUs, and a long
-    // contraction is additionally split over blockIdx.z into slabs of partial products (summed in order)
-    const long blocks = (long)(I / 64) * (J / 64);
-    if ((long)((I + 127) / 128) * (J / 64) < 256) {
-        int splits = 1;
+    const int cus = plan_nt_wants_cus(I, J, ldc, scratch != nullptr) ? device_cus_or_256() : 256;
+    const GemmPlan pl = plan_gemm_nt(I, J, Kd, ldc, cus, scratch != nullptr, scratch_elems);
+    if (plan_out) *plan_out = pl;
+    if (plan_nt_few_tiles(I, J)) {
+        const int splits = pl.splits;
         const long slab = (long)I * ldc;
-        if (scratch && ldc == J) {
-            // The split (<= 8, not necessarily a divisor of the k-slabs) that is expected to finish first: a CU works
-            // on up to four of these workgroups at once, one wavefront of each per SIMD, so a launch lasts about
-            // (most workgroups on one CU) x (one workgroup's work ~ 1 / split), a little longer when few workgroups
-            // share a CU (their latencies are less well covered: 0.6 / 0.8 / 0.9 / 0.95 of the matrix rate for 1..4).
-            // C3's V = H Am^T (99 tiles): 7 ranges put at most 3 workgroups on a CU where 8 put 4 on some.  Every
-            // workgroup keeps a worthwhile chunk (512 deep for long contractions, 64 for short ones such as the
-            // 400-point DFTs of Griffin-Lim, whose 84 tiles would otherwise run 25 slabs each on a third of the CUs).
-            int dev = 0, cus = 0;
-            if (hipGetDevice(&dev) != hipSuccess ||
-                hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-                cus = 256;
-            static const double eff[5] = {1.0, 0.6, 0.8, 0.9, 0.95};
-            const int nslabs = Kd / KS, chunk = Kd >= 1024 ? 512 : 64;
-            double best = 1e30;
-            for (int sp = 1; sp <= 8 && Kd >= 1024; ++sp) {
-                if (blocks * sp > 4L * cus || (sp > 1 && (nslabs / sp) * KS < chunk) || (size_t)sp * slab > scratch_elems) continue;
-                const long per_cu = (blocks * sp + cus - 1) / cus;
-                const double cost = (double)per_cu / sp / eff[per_cu];
-                if (cost < best - 1e-9) { best = cost; splits = sp; }
-            }
-            // short contractions (measured on Griffin-Lim's: 12.7 ms per 300 iterations with the rule above against
-            // 11.2): the largest split that divides the k-slabs evenly
-            for (int sp = 2; sp <= 8 && Kd < 1024; ++sp)
-                if (nslabs % sp == 0 && blocks * sp <= 1024 && Kd / sp >= chunk && (size_t)sp * slab <= scratch_elems)
-                    splits = sp;
-        }
         if (splits == 1) return launch_nt<T, 64, 64, 32, 32, false>(L, ldl, R, ldr, C, ldc, I, J, Kd, ep, s, 1, 0, j_valid);
         hipError_t e = launch_nt<T, 64, 64, 32, 32, false>(L, ldl, R, ldr, scratch, ldc, I, J, Kd, ep, s, splits, slab, j_valid);
         if (e != hipSuccess) return e;
@@ -293,28 +267,26 @@ hipError_t gemm_nt(const T* L, int ldl, const T* R, int ldr, T* C, int ldc, int 
                            slab, C, gate);
         return hipGetLastError();
     }
-    if (I % 128) {      // short batches are padded to 64 frames only: 64-row blocks
-        if (J % 128 == 0) return launch_nt<T, 64, 128, 32, 32, false>(L, ldl, R, ldr, C, ldc, I, J, Kd, ep, s, 1, 0, j_valid);
+    if (pl.bf == 64) {      // short batches are padded to 64 frames only: 64-row blocks
+        if (pl.br == 128) return launch_nt<T, 64, 128, 32, 32, false>(L, ldl, R, ldr, C, ldc, I, J, Kd, ep, s, 1, 0, j_valid);
         return launch_nt<T, 64, 64, 32, 32, false>(L, ldl, R, ldr, C, ldc, I, J, Kd, ep, s, 1, 0, j_valid);
     }
-    if (J % 128 == 0) return launch_nt<T, 128, 128, 64, 32, false>(L, ldl, R, ldr, C, ldc, I, J, Kd, ep, s, 1, 0, j_valid);
+    if (pl.br == 128) return launch_nt<T, 128, 128, 64, 32, false>(L, ldl, R, ldr, C, ldc, I, J, Kd, ep, s, 1, 0, j_valid);
     return launch_nt<T, 128, 64, 32, 32, false>(L, ldl, R, ldr, C, ldc, I, J, Kd, ep, s, 1, 0, j_valid);
 }
 
 template <typename T>
 hipError_t gemm_nt_mu(const T* L, int ldl, const T* R, int ldr, T* Hout, int I, int J, int Kd,
-                      const MuEpilogue<T>& ep, hipStream_t s) {
+                      const MuEpilogue<T>& ep, hipStream_t s, GemmPlan* plan_out) {
+    if (plan_out) *plan_out = GemmPlan{0, 0, 0, -1, 1};
     if (I <= 0 || J <= 0) return hipSuccess;
     if (use_gemm2<T>() && J % 128 == 0 && gemm2_ok<T>(L, ldl, R, ldr, Hout, ep.ldh, I, J, Kd) &&
         gemm2_ok<T>(ep.Hin, ep.ldh, ep.Hin, ep.ldh, ep.kl ? ep.Hin : ep.P, ep.ldh, I, J, Kd))
-        return gemm2_mu<T>(L, ldl, R, ldr, Hout, I, J, Kd, ep, s);
+        return gemm2_mu<T>(L, ldl, R, ldr, Hout, I, J, Kd, ep, s, plan_out);
     if (I % 64 || J % 128 || Kd % KS || Kd <= 0) return hipErrorInvalidValue;
-    // Tile quantisation for one or two utterances: 128x128 tiles run in rounds of 256 (one per CU), 64x128
-    // tiles in rounds of 512 (two per CU, half the work each; a trailing all-padding row tile leaves at
-    // once).  C3 (768 x 8192): 384 full tiles = 2 rounds against 768 half tiles = 2 half rounds.
-    const long b128 = (long)((I + 127) / 128) * (J / 128), b64 = (long)(I / 64) * (J / 128);
-    const long t128 = 2 * ((b128 + 255) / 256), t64 = (b64 + 511) / 512;     // in half-tile rounds
-    if (I % 128 || (I <= 2048 && t64 < t128))
+    const GemmPlan pl = plan_gemm_nt_mu(I, J);
+    if (plan_out) *plan_out = pl;
+    if (pl.bf == 64)
         return launch_nt<T, 64, 128, 32, 32, true>(L, ldl, R, ldr, Hout, ep.ldh, I, J, Kd, ep, s);
     return launch_nt<T, 128, 128, 64, 32, true>(L, ldl, R, ldr, Hout, ep.ldh, I, J, Kd, ep, s);
 }
@@ -489,9 +461,9 @@ hipError_t synth_skinny(const T* H, long hst, long hsn, const T* B, long bsn, lo
 }
 
 #define EVC_INST(T)                                                                                  \
-    template hipError_t gemm_nt<T>(const T*, int, const T*, int, T*, int, int, int, int, hipStream_t, T*, size_t, int*, int, const int*); \
+    template hipError_t gemm_nt<T>(const T*, int, const T*, int, T*, int, int, int, int, hipStream_t, T*, size_t, int*, int, const int*, GemmPlan*); \
     template hipError_t gemm_nt_mu<T>(const T*, int, const T*, int, T*, int, int, int,                \
-                                      const MuEpilogue<T>&, hipStream_t);                            \
+                                      const MuEpilogue<T>&, hipStream_t, GemmPlan*);                 \
     template hipError_t sum_slabs<T>(const T*, long, int, T*, hipStream_t, const int*);                          \
     template hipError_t gemm_strided<T>(const T*, long, long, const T*, long, long, T*, long, long,  \
                                         int, int, int, hipStream_t);                                  \

@@ -401,46 +401,20 @@ static hipError_t launch_shape(int shape, const T* L, int ldl, const T* R, int l
     }
 }
 
-static double round_eff(long wg, long slots) { return (double)wg / (double)(((wg + slots - 1) / slots) * slots); }
-
 // C = L R^T.  With `scratch` (and ldc == J) a short grid is split over k into slabs; see gemm_nt for splits_out.
+// Shape and split count: plan_gemm2 (evc_gemm_plan.h).
 template <typename T>
 hipError_t gemm2(const T* L, int ldl, const T* R, int ldr, T* C, int ldc, int I, int J, int Kd, hipStream_t s,
-                 T* scratch, size_t scratch_elems, int* splits_out, int n_cus, int jv, const int* gate) {
+                 T* scratch, size_t scratch_elems, int* splits_out, int n_cus, int jv, const int* gate, GemmPlan* plan_out) {
     if (splits_out) *splits_out = 0;
     MuEpilogue<T> ep{};
     ep.gate = gate;
-    if (n_cus <= 0) n_cus = 256;
-    // 64 x 128 blocks (three per CU) when R has a multiple of 128 rows and the grid fills the CUs; 64 x 64 blocks
-    // (four per CU) otherwise: a grid of less than one round runs as long as ONE workgroup does, so the smallest
-    // tile is the fastest
-#ifdef EVC_G2_PLAIN_SHAPE      // diagnostic builds: force a block shape of the plain product (0 / 1: 128 x 128)
-    const bool wide = EVC_G2_PLAIN_SHAPE != 3;
-    const int shape = EVC_G2_PLAIN_SHAPE;
-    const long blocks = shape <= 1 ? (long)(I / 128) * (J / 128) : (long)(I / 64) * (J / (wide ? 128 : 64));
-    const long slots = (long)n_cus * (shape == 0 ? 1 : (shape == 1 ? 2 : (wide ? 3 : 4)));
-#else
-    const bool wide = J % 128 == 0 && (long)(I / 64) * (J / 128) >= 3L * n_cus;
-    const int shape = wide ? 2 : 3;
-    const long blocks = (long)(I / 64) * (J / (wide ? 128 : 64));
-    // (48 KiB of LDS hold three workgroups per CU for either shape; counting four for the narrow one makes the rule
-    // split a little earlier, which measured better: STFT flow, 16 utterances, 157.8 against 155.5 kframes/s)
-    const long slots = (long)n_cus * (wide ? 3 : 4);
-#endif
-    // split-K so that the grid fills the CUs' workgroup slots in whole rounds: the smallest split whose rounds
-    // are >= 85 % full (each workgroup keeps >= 128 of k)
-    int splits = 1;
+    const GemmPlan pl = plan_gemm2(I, J, Kd, ldc, n_cus, scratch != nullptr, scratch_elems);
+    if (plan_out) *plan_out = pl;
+    const int splits = pl.splits;
     const long slab = (long)I * ldc;
-    if (scratch && ldc == J) {
-        double best = round_eff(blocks, slots);
-        for (int sp = 2; sp <= 32 && best < 0.85; ++sp) {
-            if (Kd % (sp * 16) || Kd / sp < 128 || (size_t)sp * slab > scratch_elems) continue;
-            const double eff = round_eff(blocks * sp, slots);
-            if (eff > best + 0.03) { best = eff; splits = sp; }
-        }
-    }
     T* out = splits > 1 ? scratch : C;
-    hipError_t e = launch_shape<T, false>(shape, L, ldl, R, ldr, out, ldc, I, J, Kd, ep, s, splits, slab, jv);
+    hipError_t e = launch_shape<T, false>(pl.shape, L, ldl, R, ldr, out, ldc, I, J, Kd, ep, s, splits, slab, jv);
     if (e != hipSuccess || splits == 1) return e;
     if (splits_out) {          // the caller's next kernel sums the slabs itself (scratch + z * I * ldc, z < splits)
         *splits_out = splits;
@@ -449,35 +423,24 @@ hipError_t gemm2(const T* L, int ldl, const T* R, int ldr, T* C, int ldc, int I,
     return sum_slabs<T>(scratch, slab, splits, C, s, gate);
 }
 
-// the same contraction with the multiplicative update as epilogue: Hout = mu(Hin, P, L R^T)
+// the same contraction with the multiplicative update as epilogue: Hout = mu(Hin, P, L R^T); shape: plan_gemm2_mu
 template <typename T>
 hipError_t gemm2_mu(const T* L, int ldl, const T* R, int ldr, T* Hout, int I, int J, int Kd,
-                    const MuEpilogue<T>& ep, hipStream_t s) {
-    // The epilogue moves 3 elements per output against 2 Kd flops: for short contractions (Kd of a few hundred) it is as
-    // long as the main loop, so several workgroups share a CU and one's epilogue runs beside the others' MFMAs.
-    // float32: 128 x 128 blocks, two per CU, when there are enough of them for whole rounds; else (and float64,
-    // whose accumulators need the registers) 64 x 128 blocks, three per CU.
-    // A grid of less than one round of 64 x 128 blocks takes the 64 x 64 shape (four per CU): it then runs as long
-    // as one small workgroup does.
+                    const MuEpilogue<T>& ep, hipStream_t s, GemmPlan* plan_out) {
     int dev = 0, n_cus = 256;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&n_cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cus <= 0)
         n_cus = 256;
-    const long b128 = (long)(I / 128) * (J / 128), b64 = (long)(I / 64) * (J / 128);
-#ifdef EVC_G2_MU_SHAPE
-    const int shape = EVC_G2_MU_SHAPE;       // diagnostic builds: force a block shape
-    (void)b128; (void)b64;
-#else
-    const int shape = (sizeof(T) == 4 && I % 128 == 0 && b128 >= 8L * n_cus) ? 1 : (b64 >= 3L * n_cus ? 2 : 3);
-#endif
-    return launch_shape<T, true>(shape, L, ldl, R, ldr, Hout, ep.ldh, I, J, Kd, ep, s, 1, 0);
+    const GemmPlan pl = plan_gemm2_mu(I, J, (int)sizeof(T), n_cus);
+    if (plan_out) *plan_out = pl;
+    return launch_shape<T, true>(pl.shape, L, ldl, R, ldr, Hout, ep.ldh, I, J, Kd, ep, s, 1, 0);
 }
 
 #define EVC_INST2(T)                                                                                              \
     template bool gemm2_ok<T>(const T*, int, const T*, int, const T*, int, int, int, int);                        \
     template hipError_t gemm2<T>(const T*, int, const T*, int, T*, int, int, int, int, hipStream_t, T*, size_t,  \
-                                 int*, int, int, const int*);                                                       \
-    template hipError_t gemm2_mu<T>(const T*, int, const T*, int, T*, int, int, int, const MuEpilogue<T>&, hipStream_t);
+                                 int*, int, int, const int*, GemmPlan*);                                            \
+    template hipError_t gemm2_mu<T>(const T*, int, const T*, int, T*, int, int, int, const MuEpilogue<T>&, hipStream_t, GemmPlan*);
 EVC_INST2(double)
 EVC_INST2(float)
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/evc.h"
+#include "evc_gemm_plan.h"
 
 namespace evc {
 
@@ -218,7 +219,8 @@ inline int frame_tiles_stage(int F, const int* utt_offsets, int n_utt, int T_, i
 template <typename T>
 hipError_t gemm_nt(const T* L, int ldl, const T* R, int ldr, T* C, int ldc, int I, int J, int Kd,
                    hipStream_t s, T* scratch = nullptr, size_t scratch_elems = 0, int* splits_out = nullptr,
-                   int j_valid = 0, const int* gate = nullptr);
+                   int j_valid = 0, const int* gate = nullptr, GemmPlan* plan_out = nullptr);
+// plan_out: optional; what was launched (evc_gemm_plan.h; kernel 0 when nothing was)
 // gate: optional device word; the launched kernels return at once when it is 0 (the stop rules have stopped every
 // utterance: the launches the host has still queued cost a few microseconds each instead of a contraction)
 // j_valid: rows of R from j_valid on are known to be zero (padding up to the block width); their products are skipped
@@ -227,17 +229,18 @@ hipError_t gemm_nt(const T* L, int ldl, const T* R, int ldr, T* C, int ldc, int 
 // Same contraction with the multiplicative update as epilogue: C = mu(Hin, P, L R^T).
 template <typename T>
 hipError_t gemm_nt_mu(const T* L, int ldl, const T* R, int ldr, T* Hout, int I, int J, int Kd,
-                      const MuEpilogue<T>& ep, hipStream_t s);
+                      const MuEpilogue<T>& ep, hipStream_t s, GemmPlan* plan_out = nullptr);
 // ----- evc_gemm2.hip: second-generation contraction kernel (swizzled row-major LDS, 16-byte fragment reads,
 // vector epilogue); gemm_nt / gemm_nt_mu route to it whenever shapes and alignment allow -----
 template <typename T>
 bool gemm2_ok(const T* L, int ldl, const T* R, int ldr, const T* C, int ldc, int I, int J, int Kd);
 template <typename T>
 hipError_t gemm2(const T* L, int ldl, const T* R, int ldr, T* C, int ldc, int I, int J, int Kd, hipStream_t s,
-                 T* scratch, size_t scratch_elems, int* splits_out, int n_cus, int j_valid, const int* gate = nullptr);
+                 T* scratch, size_t scratch_elems, int* splits_out, int n_cus, int j_valid, const int* gate = nullptr,
+                 GemmPlan* plan_out = nullptr);
 template <typename T>
 hipError_t gemm2_mu(const T* L, int ldl, const T* R, int ldr, T* Hout, int I, int J, int Kd,
-                    const MuEpilogue<T>& ep, hipStream_t s);
+                    const MuEpilogue<T>& ep, hipStream_t s, GemmPlan* plan_out = nullptr);
 // C = sum_z part[z * slab + .]  (fixed order)
 template <typename T>
 hipError_t sum_slabs(const T* part, long slab, int splits, T* C, hipStream_t s, const int* gate = nullptr);

@@ -340,7 +340,15 @@ typedef struct evc_solve_info {
                           bits 8..15: k_fused_wide: wavefronts per workgroup (4 | 8); k_fused_wide64: whole bin tiles per
                                       wavefront (3 | 4 | 5 | 7 | 8);
                           bits 16..23: bin tiles of 16 the instance holds (k_fused_wide: MT = 4 | 6 | 8 | 10 | 13;
-                                       k_fused_wide64: 4 x tiles per wavefront + 1) */
+                                       k_fused_wide64: 4 x tiles per wavefront + 1)
+                          The block shapes of the two contraction kernels (EVC_KERNEL_GEMM_NT, EVC_KERNEL_GEMM2; a redone
+                          solve reports the kernel it was redone on).  Block codes, frames x rows of the other operand:
+                          0 none, 1 64 x 64, 2 64 x 128, 3 128 x 64, 4 128 x 128, 5 128 x 128 with deep k-slabs (k_gemm2,
+                          diagnostic builds only):
+                          bits 0..3: the update contraction (the one whose epilogue is the multiplicative update);
+                          bits 4..7: V = H Am^T of the iteration loop (0 for GRAM and LITERAL, which form none there);
+                          bits 8..13: the number of k-ranges that product was split into (1: no split);
+                          bits 16..19: the numerator P = X A (0 under the Kullback-Leibler loss, which has none) */
 } evc_solve_info;
 
 /* A dictionary imported once.  The reference builds A and B once per run (04_align_n_nmf.py:230-246,350-361) and the

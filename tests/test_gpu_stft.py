@@ -64,3 +64,23 @@ def test_features_feed_the_solver_like_the_script():
     assert err < 5e-3, err
     d64 = features.conversion_features(y, 16000, dtype=np.complex128)
     assert d64["fs"] == 16000 and d64["stft"].dtype == np.complex128
+
+
+# geometries other than (400, 80): F % 16 != 0, hop coprime with F, no overlap, hop > F, 64-fold overlap, k-padding that
+# reads past a frame, the smallest legal size; signals of F - 1, F, F + 1 and 10 hop + 3 samples, centred and not
+STFT_GEOMETRIES = [(30, 7), (30, 30), (30, 41), (64, 1), (34, 5), (2, 1), (256, 64)]
+
+
+@pytest.mark.parametrize("center", [True, False])
+@pytest.mark.parametrize("n_fft,hop", STFT_GEOMETRIES)
+def test_stft_other_geometries(n_fft, hop, center):
+    for n in (n_fft - 1, n_fft, n_fft + 1, 10 * hop + 3):
+        y = _signal(n, n + n_fft)
+        want = o.librosa_stft(y, n_fft, hop, center).T
+        re, im = evc.stft(y, n_fft, hop, center=center)
+        assert re.shape == want.shape == im.shape, (n, re.shape, want.shape)
+        if want.size:
+            scale = np.abs(want).max()
+            err = max(np.abs(re - want.real).max(), np.abs(im - want.imag).max())
+            print(f"STFT F={n_fft} hop={hop} center={center} n={n} err={err:.3e} of {scale:.3e}")
+            assert err <= 1e-11 * scale, (n, err, scale)

@@ -55,6 +55,12 @@ def test_solve_info_variant_field_and_decoding():
         "static": True, "reduce": True, "tagged": False, "tpw": 3, "tiles": 13}
     for k in (0, 1, 2, 3, 4, 5, 8):
         assert _lib.decode_variant(k, 0) is None
+    # the contraction kernels: update 64 x 128, V 64 x 64 in 7 k-ranges, P 64 x 128; GRAM on 128 x 128 without a V product
+    assert _lib.decode_variant(1, 2 | (1 << 4) | (7 << 8) | (2 << 16)) == {
+        "update": (64, 128), "v": (64, 64), "v_splits": 7, "p": (64, 128), "deep": False}
+    assert _lib.decode_variant(2, 4 | (2 << 16)) == {
+        "update": (128, 128), "v": None, "v_splits": 0, "p": (64, 128), "deep": False}
+    assert _lib.decode_variant(2, 3 | (2 << 4) | (1 << 8))["p"] is None      # KL: no numerator
 
 
 def _nm():

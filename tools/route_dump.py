@@ -176,7 +176,9 @@ def solve_lines():
         info = res[-1]
         mats = " ".join(sha(t) for t in res[:-1])
         var = info["variant"]
-        var = "-" if var is None else ",".join("%s=%d" % (k, int(v)) for k, v in sorted(var.items()))
+        # (the contraction kernels report blocks: (frames, rows) pairs, None where a solve forms no such product)
+        fmt = lambda v: "-" if v is None else ("%dx%d" % v if isinstance(v, tuple) else "%d" % int(v))
+        var = "-" if var is None else ",".join("%s=%s" % (k, fmt(v)) for k, v in sorted(var.items()))
         out.append("solve %s : kernel=%s members=%d launches=%d redo=%d exchange=%d prepared=%d variant=%s n_iter=%s : %s" % (
             name, info["kernel"], info["members"], info["launches"], info["redo"], info["exchange"], info["prepared"], var,
             ",".join(map(str, info["n_iter"].tolist())), mats))
