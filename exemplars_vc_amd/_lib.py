@@ -29,6 +29,8 @@ LEARN_SKLEARN, LEARN_PYMF = 0, 1
 CDL_BOTH, CDL_DICT_ONLY = 0, 1
 DCL_BOTH, DCL_DICT_ONLY = 0, 1
 CONVEX_BOTH, CONVEX_H_ONLY, CONVEX_G_ONLY = 0, 1, 2
+KM_BOTH, KM_ASSIGN_ONLY = 0, 1
+KM_STOP_NONE, KM_STOP_PYMF, KM_STOP_LABELS = 0, 1, 2
 
 # every symbol include/evc.h declares; tests check that the library exports all of them
 SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_bytes",
@@ -54,7 +56,8 @@ SYMBOLS = ("evc_version", "evc_strerror", "evc_device_count", "evc_workspace_byt
            "evc_prox_masked_learn_workspace_bytes", "evc_prox_masked_learn",
            "evc_mu_masked_workspace_bytes", "evc_mu_masked_solve",
            "evc_mu_masked_learn_workspace_bytes", "evc_mu_masked_learn_splits", "evc_mu_masked_learn",
-           "evc_mu_stoch_learn_workspace_bytes", "evc_mu_stoch_learn_route", "evc_mu_stoch_learn_splits", "evc_mu_stoch_learn")
+           "evc_mu_stoch_learn_workspace_bytes", "evc_mu_stoch_learn_route", "evc_mu_stoch_learn_splits", "evc_mu_stoch_learn",
+           "evc_kmeans_workspace_bytes", "evc_kmeans_splits", "evc_kmeans")
 BETA_MAX_M = 528
 MU_MASKED_MAX_M, MU_MASKED_MAX_SLOTS = 528, 4097
 MU_MASKED_LEARN_MAX_R = 4096
@@ -64,6 +67,7 @@ DECONV_MAX_M, DECONV_MAX_TAPS, DECONV_MAX_MB = 256, 16, 1056
 DECONV_LEARN_MAX_R = 4096
 SEMI_MAX_M, SEMI_MAX_N = 1056, 16384
 CONVEX_MAX_M, CONVEX_MAX_T, CONVEX_MAX_R, CONVEX_MAX_S = 1056, 16384, 1024, 16
+KMEANS_MAX_M, KMEANS_MAX_T, KMEANS_MAX_R, KMEANS_MAX_S = 1056, 1 << 20, 4096, 16
 PROX_MAX_M, PROX_MAX_N, PROX_MAX_SLOTS = 1056, 16384, 4097
 PROX_LEARN_MAX_M, PROX_LEARN_MAX_N = 1056, 4096
 PROX_MASKED_LEARN_MAX_M, PROX_MASKED_LEARN_MAX_N, PROX_MASKED_LEARN_MAX_S = 1056, 1024, 1 << 28
@@ -211,6 +215,16 @@ class ConvexOpts(C.Structure):
         ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
         ("check_every", C.c_int), ("update", C.c_int), ("reserved", C.c_int),
         ("tol", C.c_double), ("eps", C.c_double),
+        ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
+    ]
+
+
+class KmeansOpts(C.Structure):
+    """Mirror of `evc_kmeans_opts` (include/evc.h): options of the device k-means."""
+    _fields_ = [
+        ("struct_bytes", C.c_int), ("dtype", C.c_int), ("layout", C.c_int), ("iters", C.c_int),
+        ("update", C.c_int), ("stop_rule", C.c_int), ("reserved", C.c_int),
+        ("tol", C.c_double),
         ("ev_loop_start", C.c_void_p), ("ev_loop_stop", C.c_void_p),
     ]
 
@@ -651,6 +665,18 @@ def lib():
         C.c_int, C.c_int, C.c_int, C.POINTER(MuStochOpts),                  # M, R, T, opts
         C.c_void_p, C.c_size_t,                                             # workspace
         C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),      # n_epochs_out, n_steps_out, trace_out
+        C.c_void_p,                                                         # stream
+    ]
+    L.evc_kmeans_workspace_bytes.restype = C.c_size_t
+    L.evc_kmeans_workspace_bytes.argtypes = [C.c_int] * 4
+    L.evc_kmeans_splits.restype = C.c_int
+    L.evc_kmeans_splits.argtypes = [C.c_int] * 2
+    L.evc_kmeans.restype = C.c_int
+    L.evc_kmeans.argtypes = [
+        C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,   # X, W, labels, counts
+        C.c_int, C.c_int, C.c_int,                                          # M, R, T
+        C.POINTER(KmeansOpts), C.c_void_p, C.c_size_t,                      # opts, workspace
+        C.POINTER(C.c_int), C.POINTER(C.c_double),                          # n_iter_out, err_out
         C.c_void_p,                                                         # stream
     ]
     _lib = L

@@ -17,7 +17,11 @@ native call (evc_semi_solve); the default `compute_w=True` forms W = data H^T (H
 runs one GPU activation update per iteration, with the same warning.
 
 `CNMF` is pymf's convex NMF (pymf/cnmf.py): data ~ (data G) H with signed data and G, H >= 0.  `factorize` is one native
-call (evc_convex_learn) for every combination of compute_w / compute_h; the default start is pymf's k-means on the host.
+call (evc_convex_learn) for every combination of compute_w / compute_h; the default start is pymf's k-means on the host,
+`CNMF(..., start="device")` runs the same k-means from the same random draw on the GPU (evc_kmeans).
+
+`Kmeans` is pymf's k-means (pymf/kmeans.py, "unary-convex matrix factorization"): `factorize` is one native call (evc_kmeans),
+`compute_w=False` is pymf's `vq` against the given centres.
 """
 from __future__ import annotations
 
@@ -25,8 +29,8 @@ import logging
 
 import numpy as np
 
-from ..solver import (convex_cluster_start, frame_residuals, learn_dictionary, learn_dictionary_convex, solve_activations,
-                      solve_activations_semi, synthesize)
+from ..solver import (convex_cluster_start, frame_residuals, kmeans, learn_dictionary, learn_dictionary_convex,
+                      solve_activations, solve_activations_semi, synthesize)
 
 _EPS = np.finfo(float).eps
 
@@ -227,6 +231,64 @@ def kmeans_assign(data, num_bases, niter=10):
     return assigned
 
 
+class Kmeans(NMF):
+    """pymf's Kmeans(data, num_bases): data ~ W H with H one-hot and every column of W the mean of its samples (pymf/kmeans.py:14-83
+    on base.py:208-270).  factorize() is one native call (evc_kmeans): the centres drawn by random.sample (the global `random`
+    state, sorted) unless .W is set, one assignment, then per round the means, the assignment and ||data - W H||_F with
+    base.py's machine-epsilon stop.  `W`, `H` (one-hot float64), `assigned` and `ferr` are left as pymf leaves them;
+    compute_w=False assigns against the given .W (pymf's vq).  The assignment always starts from the current .W: an .H set by
+    hand is not read."""
+
+    def __init__(self, data, num_bases=4, **kwargs):
+        NMF.__init__(self, data, num_bases, **kwargs)
+        if self._dictionary_update != "host":
+            raise ValueError("Kmeans has no dictionary_update option: centres and labels are always updated on the device")
+
+    def _init_w(self):
+        """kmeans.py:62-67: some random data samples, their indices sorted"""
+        import random
+        sel = random.sample(range(self._num_samples), self._num_bases)
+        self.W = np.asarray(self.data)[:, np.sort(sel)]
+
+    def _init_h(self):
+        self.factorize(niter=0, compute_w=False, compute_err=False)
+
+    def factorize(self, niter=100, show_progress=False, compute_w=True, compute_h=True, compute_err=True):
+        if show_progress:
+            self._logger.setLevel(logging.INFO)
+        else:
+            self._logger.setLevel(logging.ERROR)
+        if not compute_h:
+            raise NotImplementedError("Kmeans.factorize(compute_h=False): the assignment is the factorisation; only "
+                                      "compute_w=False (vq against fixed centres) is offered besides the default")
+        if not hasattr(self, "W"):
+            if not compute_w:
+                raise AttributeError("set .W (data_dimension x num_bases) before factorize(compute_w=False)")
+            self._init_w()
+        data = np.asarray(self.data, dtype=np.float64)
+        W, assigned, info = kmeans(data, np.asarray(self.W, dtype=np.float64), layout="bin_major", iters=max(int(niter), 0),
+                                   stop="pymf" if compute_err else "none", tol=self._EPS, update="both" if compute_w else "assign",
+                                   dtype="f64", device=self._device, info=True)
+        if compute_w:
+            if isinstance(self.W, np.ndarray) and self.W.dtype == np.float64:
+                self.W[...] = W                  # in place, like `self.W[:, i] = ...`
+            else:
+                self.W = W
+        self.assigned = assigned.astype(np.int64)
+        self.H = np.zeros((self._num_bases, self._num_samples))
+        self.H[self.assigned, np.arange(self._num_samples)] = 1.0
+        if compute_err:
+            self.ferr = np.zeros(max(int(niter), 0))
+            n = info["n_iter"]
+            ferr = info["err"][1:1 + n]
+            if n < niter or (n >= 3 and abs(ferr[n - 1] - ferr[n - 2]) / self._num_samples < self._EPS):
+                self.ferr = ferr[:n - 1].copy()     # base.py:268: ferr = ferr[:i], i = n - 1
+            else:
+                self.ferr[:n] = ferr
+            for i, e in enumerate(self.ferr):
+                self._logger.info("FN: %s (%s/%s)" % (e, i + 1, niter))
+
+
 class CNMF(NMF):
     """pymf's CNMF(data, num_bases): convex NMF, data ~ W H with W = data G, signed data and G, H >= 0 (pymf/cnmf.py:18-175).
     `G` is num_samples x num_bases.  factorize() is one native call (evc_convex_learn): per iteration H, then G with the
@@ -236,6 +298,18 @@ class CNMF(NMF):
         NMF.__init__(self, data, num_bases, **kwargs)
         if self._dictionary_update != "host":
             raise ValueError("CNMF has no dictionary_update option: both factors are always updated on the device")
+        self._start = kwargs.get("start", "host")
+        if self._start not in ("host", "device"):
+            raise ValueError("start must be 'host' or 'device'")
+
+    def _kmeans_start(self):
+        """the labels of pymf's Kmeans(data, num_bases).factorize(niter=10): on the host in numpy, or (start="device") the
+        same random.sample draw and evc_kmeans"""
+        if self._start == "host":
+            return kmeans_assign(self.data, self._num_bases, 10)
+        mdl = Kmeans(self.data, self._num_bases, device=self._device)
+        mdl.factorize(niter=10)
+        return mdl.assigned
 
     def _init_h(self):
         """cnmf.py:67-92: H and G from a k-means clustering of the samples, W = data G"""
@@ -243,7 +317,7 @@ class CNMF(NMF):
         if need_g and not need_h:
             raise AttributeError("set .G (num_samples x num_bases) along with .H: pymf builds G only from its own k-means start")
         if need_h:
-            assign = kmeans_assign(self.data, self._num_bases, 10)
+            assign = self._kmeans_start()
             G0, self.H = convex_cluster_start(assign, self._num_bases)
             if need_g:
                 self.G = G0

@@ -14,8 +14,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OBJ = os.path.join(HERE, "_build")
 LIB = os.path.join(PKG, "libevc_hip.so")
-SOURCES = ["evc_gemm.hip", "evc_gemm2.hip", "evc_aux.hip", "evc_fused.hip", "evc_fused_res.hip", "evc_fused_all.hip", "evc_fused_xy.hip", "evc_wide.hip", "evc_wide64.hip", "evc_gl.hip", "evc_dtw.hip", "evc_cd.hip", "evc_learn.hip", "evc_mfcc.hip", "evc_beta.hip", "evc_beta_learn.hip", "evc_online.hip", "evc_transform.hip", "evc_deconv.hip", "evc_deconv_learn.hip", "evc_semi.hip", "evc_convex.hip", "evc_prox.hip", "evc_prox_masked.hip", "evc_prox_learn.hip", "evc_prox_masked_learn.hip", "evc_mu_masked.hip", "evc_mu_stoch.hip", "evc_api.hip"]
-HEADERS = ["evc_internal.h", "evc_gemm_plan.h", "evc_solve_plan.h", "evc_fused_common.h", "evc_beta_common.h", "evc_online_plan.h", "evc_transform_plan.h", "evc_deconv_plan.h", "evc_deconv_kernels.h", "evc_deconv_learn_plan.h", "evc_semi_plan.h", "evc_solve_state.h", "evc_convex_plan.h", "evc_prox_plan.h", "evc_prox_kernels.h", "evc_prox_masked_plan.h", "evc_prox_learn_plan.h", "evc_prox_learn_kernels.h", "evc_prox_masked_learn_plan.h", "evc_mu_masked_plan.h", "evc_mu_masked_common.h", "evc_mu_stoch_plan.h", "evc_fused_all_body.inc", os.path.join("..", "..", "include", "evc.h")]
+SOURCES = ["evc_gemm.hip", "evc_gemm2.hip", "evc_aux.hip", "evc_fused.hip", "evc_fused_res.hip", "evc_fused_all.hip", "evc_fused_xy.hip", "evc_wide.hip", "evc_wide64.hip", "evc_gl.hip", "evc_dtw.hip", "evc_cd.hip", "evc_learn.hip", "evc_mfcc.hip", "evc_beta.hip", "evc_beta_learn.hip", "evc_online.hip", "evc_transform.hip", "evc_deconv.hip", "evc_deconv_learn.hip", "evc_semi.hip", "evc_convex.hip", "evc_prox.hip", "evc_prox_masked.hip", "evc_prox_learn.hip", "evc_prox_masked_learn.hip", "evc_mu_masked.hip", "evc_mu_stoch.hip", "evc_kmeans.hip", "evc_api.hip"]
+HEADERS = ["evc_internal.h", "evc_gemm_plan.h", "evc_solve_plan.h", "evc_fused_common.h", "evc_beta_common.h", "evc_online_plan.h", "evc_transform_plan.h", "evc_deconv_plan.h", "evc_deconv_kernels.h", "evc_deconv_learn_plan.h", "evc_semi_plan.h", "evc_solve_state.h", "evc_convex_plan.h", "evc_prox_plan.h", "evc_prox_kernels.h", "evc_prox_masked_plan.h", "evc_prox_learn_plan.h", "evc_prox_learn_kernels.h", "evc_prox_masked_learn_plan.h", "evc_mu_masked_plan.h", "evc_mu_masked_common.h", "evc_mu_stoch_plan.h", "evc_kmeans_plan.h", "evc_fused_all_body.inc", os.path.join("..", "..", "include", "evc.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 EXTRA_FLAGS = {}
 

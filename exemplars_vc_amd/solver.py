@@ -1808,7 +1808,8 @@ def learn_dictionary_convex(X, G0, H0, *, layout, iters, update="both", check_ev
     return res
 
 
-def compact_dictionary_convex(A, B, R, *, iters=100, tol=0.0, assign=None, layout="bin_major", dtype=None, device=None):
+def compact_dictionary_convex(A, B, R, *, iters=100, tol=0.0, assign=None, layout="bin_major", dtype=None, device=None,
+                              kmeans_iters=10):
     """A compact parallel dictionary of SIGNED exemplars (mel-cepstra, MFCCs): the aligned source and target exemplars are
     stacked, D = [A; B] ((Ma + Mb) x N), and factored by learn_dictionary_convex, D ~ (D G) H with G, H >= 0.  The atoms
     [Wa; Wb] = D G = [A G; B G] are non-negative combinations of the exemplars with the SAME weights on both sides, so they
@@ -1817,7 +1818,9 @@ def compact_dictionary_convex(A, B, R, *, iters=100, tol=0.0, assign=None, layou
 
     The start is deterministic: exemplar t belongs to cluster assign[t] (default t * R // N: aligned exemplars are in time
     order, neighbours are alike; or the caller's own labels, 0 .. R-1), G0 = (one-hot + 0.01) / cluster size and
-    H0 = one-hot + 0.2, pymf's construction.  The error is checked every iteration (tol: pymf's stop).  Returns
+    H0 = one-hot + 0.2, pymf's construction.  assign="kmeans": the labels come from compact_dictionary_kmeans on the same
+    stack (at most `kmeans_iters` rounds), a clustering on the device in place of the time-order split.  The error is
+    checked every iteration (tol: pymf's stop).  Returns
     (Wa, Wb, G, H, info) in the caller's orientation (G is N x R); info as learn_dictionary_convex's."""
     torch = _torch()
     lay = _LAYOUTS[layout]
@@ -1828,6 +1831,11 @@ def compact_dictionary_convex(A, B, R, *, iters=100, tol=0.0, assign=None, layou
     N, R = ashape[1 if bm else 0], int(R)
     if not 1 <= R <= N:
         raise ValueError(f"R must be between 1 and the number of exemplars ({N}), got {R}")
+    if isinstance(assign, str):
+        if assign != "kmeans":
+            raise ValueError(f"assign must be None, 'kmeans' or one label per exemplar, got {assign!r}")
+        lab = compact_dictionary_kmeans(A, B, R, iters=kmeans_iters, layout=layout, dtype=dtype, device=device)[2]
+        assign = lab.cpu().numpy() if isinstance(lab, torch.Tensor) else lab
     G0, H0 = convex_cluster_start((np.arange(N) * R) // N if assign is None else np.asarray(assign, dtype=np.int64), R)
     if assign is not None and len(assign) != N:
         raise ValueError(f"assign must hold one label per exemplar ({N}), got {len(assign)}")
@@ -1845,6 +1853,120 @@ def compact_dictionary_convex(A, B, R, *, iters=100, tol=0.0, assign=None, layou
     if a_np:
         return _to_host(Wa), _to_host(Wb), _to_host(G), _to_host(H), info
     return Wa, Wb, G, H, info
+
+
+_KM_UPDATES = {"both": _lib.KM_BOTH, "assign": _lib.KM_ASSIGN_ONLY}
+_KM_STOPS = {"none": _lib.KM_STOP_NONE, "pymf": _lib.KM_STOP_PYMF, "labels": _lib.KM_STOP_LABELS}
+
+
+def kmeans(X, W0, *, layout, iters=10, stop="pymf", tol=None, update="both", dtype=None, device=None, info=False, splits=0,
+           loop_events=None, redecide=False):
+    """k-means on the GPU (evc_kmeans; pymf's Kmeans): the columns of X (signed allowed) are clustered around the R centres
+    W0, addressed like learn_dictionary_convex's X and W.  One assignment with the start centres comes first; each of `iters`
+    rounds then moves every centre to the mean of its members (update="assign": the centres stay; an empty cluster keeps its
+    centre), assigns again and evaluates ||X - W[:, labels]||_F.  labels[t] is the smallest index among the nearest centres
+    (Euclidean), decided as the direct form sum_m (x_m - w_m)^2 decides it.  stop: "pymf" (from the third round on,
+    |err - err_prev| / T < tol, tol = 2.22e-16 unless given), "labels" (a round changed no label) or "none".  At most 1056
+    bins, 2^20 samples and min(T, 4096) centres.
+
+    Returns (W, labels) (numpy in -> numpy out, device tensor in -> device tensor out; labels int32); with info=True also
+    dict(n_iter=rounds carried out, err=[1 + iters] errors (the first after the start's assignment; NaN where not evaluated),
+    counts=members per centre, splits=centre ranges of the assignment).  splits / redecide: tuning and tests, 1..16 centre
+    ranges, and every sample through the direct-form re-decision.
+    No CPU fallback: without a HIP device this raises RuntimeError."""
+    if update not in _KM_UPDATES:
+        raise ValueError(f"update must be one of {sorted(_KM_UPDATES)}, got {update!r}")
+    if stop not in _KM_STOPS:
+        raise ValueError(f"stop must be one of {sorted(_KM_STOPS)}, got {stop!r}")
+    lay = _LAYOUTS[layout]
+    bm = lay == _lib.BIN_MAJOR
+    xshape, wshape = tuple(getattr(X, "shape", ())), tuple(getattr(W0, "shape", ()))
+    if len(xshape) != 2 or len(wshape) != 2:
+        raise ValueError(f"X and W must be 2-D, got shapes {xshape} and {wshape}")
+    M, T = xshape if bm else xshape[::-1]
+    M2, R = wshape if bm else wshape[::-1]
+    if M2 != M:
+        raise ValueError(f"X {xshape} and W {wshape} do not fit ({layout})")
+    if M < 1 or T < 1 or R < 1:
+        raise ValueError(f"empty k-means problem M={M}, T={T}, R={R}")
+    if int(iters) < 0 or int(iters) > 4096:
+        raise ValueError(f"iters must be between 0 and 4096, got {iters}")
+    r_max = min(T, _lib.KMEANS_MAX_R) if update == "both" else _lib.KMEANS_MAX_R        # the assignment alone: any codebook
+    if M > _lib.KMEANS_MAX_M or T > _lib.KMEANS_MAX_T or R > r_max:      # what the ABI answers with -3
+        raise ValueError(f"unsupported k-means shape: M = {M} bins, T = {T} samples, R = {R} centres; the kernel holds at "
+                         f"most {_lib.KMEANS_MAX_M} bins, {_lib.KMEANS_MAX_T} samples and min(T, {_lib.KMEANS_MAX_R}) centres")
+    tdtype, dcode = _pick_dtype(dtype, X, W0)
+    device = require_device(device)
+    torch = _torch()
+    X_d, x_np = _to_dev(X, tdtype, device)
+    W_d = _factor_start(W0, None, "w", tdtype, device)
+    labels = torch.empty(T, dtype=torch.int32, device=device)
+    counts = torch.empty(R, dtype=torch.int32, device=device) if info else None
+    opts = _lib.KmeansOpts()
+    opts.iters, opts.update, opts.stop_rule = int(iters), _KM_UPDATES[update], _KM_STOPS[stop]
+    opts.tol = float(np.finfo(float).eps if stop == "pymf" else 0.0) if tol is None else float(tol)
+    opts.reserved = 1 if redecide else 0
+    _common_opts(opts, dcode, lay, loop_events, splits)
+    L = _lib.lib()
+    nbytes = int(L.evc_kmeans_workspace_bytes(M, R, T, dcode))
+    extra = int(splits) - int(L.evc_kmeans_splits(R, T))
+    if nbytes and extra > 0:                     # forced centre ranges beyond the plan's: their slabs of partial results
+        nbytes += (extra + 1) * (T * (2 * (8 if dcode == _lib.F64 else 4) + 4) + 3 * 256)
+    p = types.SimpleNamespace(device=device)
+    head = (X_d.data_ptr(), _ld(X_d), W_d.data_ptr(), _ld(W_d), labels.data_ptr(), counts.data_ptr() if info else None, M, R, T)
+    (n_iter,), err = _learn_run(L, "evc_kmeans", p, head, opts, nbytes, f"unsupported k-means shape M={M}, T={T}, R={R}",
+                                1 + int(iters), info, info)
+    res = (_to_host(W_d), _to_host(labels)) if x_np else (W_d, labels)
+    if info:
+        res += ({"n_iter": n_iter, "err": err, "counts": _to_host(counts) if x_np else counts,
+                 "splits": _splits_info(splits, L.evc_kmeans_splits, R, T)},)
+    return res
+
+
+def vq(W, X, *, layout, dtype=None, device=None, splits=0, redecide=False):
+    """The nearest centre of every column of X among the columns of W (pymf dist.py's vq(W, X), Euclidean, the first of
+    equals): kmeans' assignment alone.  Returns the int32 labels, numpy for numpy operands."""
+    return kmeans(X, W, layout=layout, iters=0, stop="none", update="assign", dtype=dtype, device=device, splits=splits,
+                  redecide=redecide)[1]
+
+
+def compact_dictionary_kmeans(A, B, R, *, iters=10, stop="labels", init="spread", layout="bin_major", dtype=None, device=None):
+    """A compact parallel dictionary by vector quantisation: the aligned source and target exemplars are stacked,
+    D = [A; B] ((Ma + Mb) x N) as in compact_dictionary_convex, and clustered by kmeans; the two halves of the R centroids are
+    the parallel codebook (centroids of non-negative spectra are non-negative, so convert takes them as they stand).  The
+    start centres are the exemplars at ((2 i + 1) N) // (2 R) (init="spread": aligned exemplars are in time order), or at
+    the caller's R indices.  Returns (Wa, Wb, labels, info) in the caller's orientation; info as kmeans'."""
+    torch = _torch()
+    lay = _LAYOUTS[layout]
+    bm = lay == _lib.BIN_MAJOR
+    ashape, bshape = tuple(getattr(A, "shape", ())), tuple(getattr(B, "shape", ()))
+    if len(ashape) != 2 or len(bshape) != 2 or ashape[1 if bm else 0] != bshape[1 if bm else 0]:
+        raise ValueError(f"A and B must be 2-D with the same number of exemplars, got shapes {ashape} and {bshape}")
+    N, R = ashape[1 if bm else 0], int(R)
+    if not 1 <= R <= N:
+        raise ValueError(f"R must be between 1 and the number of exemplars ({N}), got {R}")
+    if isinstance(init, str):
+        if init != "spread":
+            raise ValueError(f"init must be 'spread' or R exemplar indices, got {init!r}")
+        pick = ((2 * np.arange(R, dtype=np.int64) + 1) * N) // (2 * R)
+    else:
+        pick = np.asarray(init, dtype=np.int64)
+        if pick.shape != (R,) or pick.min() < 0 or pick.max() >= N:
+            raise ValueError(f"init must hold {R} exemplar indices in 0 .. {N - 1}")
+    tdtype, _ = _pick_dtype(dtype, A, B)
+    device = require_device(device)
+    A_d, a_np = _to_dev(A, tdtype, device)
+    B_d, _ = _to_dev(B, tdtype, device)
+    D = torch.cat([A_d, B_d], dim=0 if bm else 1)
+    Ma = ashape[0 if bm else 1]
+    idx = torch.from_numpy(pick).to(device)
+    W0 = (D[:, idx] if bm else D[idx, :]).contiguous()
+    W, labels, info = kmeans(D, W0, layout=layout, iters=iters, stop=stop, dtype=tdtype, device=device, info=True)
+    Wa, Wb = (W[:Ma], W[Ma:]) if bm else (W[:, :Ma], W[:, Ma:])
+    if a_np:
+        info["counts"] = _to_host(info["counts"])
+        return _to_host(Wa), _to_host(Wb), _to_host(labels), info
+    return Wa, Wb, labels, info
 
 
 _DCL_UPDATES = {"both": _lib.DCL_BOTH, "dict": _lib.DCL_DICT_ONLY}

@@ -94,6 +94,10 @@
  *                   update on the batch's frames, a fused masked dictionary gradient and the method's dictionary update, the
  *                   stop decided on the device; evc_mu_stoch_learn_workspace_bytes, evc_mu_stoch_learn_route and
  *                   evc_mu_stoch_learn_splits size and describe it
+ *   evc_kmeans      replaces pymf's Kmeans(data, num_bases).factorize() (pymf/kmeans.py:57-83, pymf/dist.py:54-127): k-means
+ *                   on the device - the assignment on the matrix cores with the argmin fused into its epilogue, deterministic
+ *                   means, the stop decided on the device; CNMF's default start and a vector-quantised parallel codebook;
+ *                   evc_kmeans_workspace_bytes sizes it, evc_kmeans_splits tells the centre ranges of its assignment
  *
  * Conventions
  *   Math (BASELINE.json north_star): X is M x T (bins x frames), A is M x N (source
@@ -1612,6 +1616,58 @@ int evc_mu_stoch_learn_splits(int M, int R, int batch_size, int route);
 int evc_mu_stoch_learn(const void* X, int ldx, const void* mask, int ldm, void* W, int ldw, void* H, int ldh, const int* order,
                        int M, int R, int T, const evc_mu_stoch_opts* opts, void* workspace, size_t workspace_bytes,
                        int* n_epochs_out, int* n_steps_out, double* trace_out, evc_stream_t stream);
+
+/* k-means (pymf kmeans.py:57-83 with base.py:238-270 and dist.py:54-60, 104-127): X (M x T, signed allowed) is clustered
+ * around R centres W (M x R).  One assignment with the start centres comes first; each of `iters` rounds then moves every
+ * centre to the mean of its members (unless EVC_KM_ASSIGN_ONLY; an empty cluster keeps its centre), assigns again and
+ * evaluates err = ||X - W[:, labels]||_F.
+ *   Assignment: labels[t] is the smallest r that minimises the Euclidean distance between column t of X and column r of W,
+ *   as the direct form sum_m (x_m - w_m)^2 in the working type decides it.  k_km_assign forms the expanded scores
+ *   ||w_r||^2 - 2 w_r^T x_t on the matrix cores (v_mfma_*_16x16x4), a workgroup owning 64 samples and walking the centres in
+ *   tiles of 32, and keeps the best and the second-best score of every sample in registers: the R x T scores never reach
+ *   memory.  Every sample whose two scores lie closer than g_t = 4 (M + 4) u (||x_t||^2 + max_r ||w_r||^2), u the unit
+ *   round-off of the working type, is decided again by the direct form over all R centres (k_km_refine).  The comparison is
+ *   lexicographic on (score, index): identical centres give identical scores and the lower index wins, whatever the order
+ *   of tiles and centre ranges.  Where T alone gives fewer workgroups than the chip has compute units the centres are
+ *   split into evc_kmeans_splits(R, T) ranges, merged in ascending order by a second kernel.
+ *   Centres: members are summed in ascending sample order, in the working type; no float atomics, the same call gives the
+ *   same bits every time.  Error: sum_t ||x_t - w_labels[t]||^2 in the direct form, float64, a fixed order - unchanged
+ *   labels and centres give bit-identical consecutive errors, which is what pymf's machine-epsilon stop relies on.
+ *   Stop, decided on the device: EVC_KM_STOP_PYMF from the third round on when |err_i - err_{i-1}| / T < tol (pymf:
+ *   2.22e-16); EVC_KM_STOP_LABELS when a round changed no label.  The stopping round's centres and labels are kept.
+ *   X, W    : addressed as in evc_convex_learn's X and W, under both layouts; W holds the start centres on entry and the
+ *             final ones on return; nothing outside the logical elements of any buffer is written
+ *   labels  : T device int32 or NULL;  counts : R device int32 or NULL (members per centre under the returned labels)
+ *   M : 1 .. 1056, T : 1 .. 2^20, R : 1 .. min(T, 4096) (larger: -3; the workspace query then answers 0).  The assignment
+ *   alone (EVC_KM_ASSIGN_ONLY) also takes a codebook of more centres than samples, R : 1 .. 4096 (pymf's doctest assigns one
+ *   sample to two centres); the two queries answer for it
+ *   n_iter_out : host int or NULL: rounds carried out
+ *   err_out    : host, 1 + iters doubles or NULL (at most 4097 slots; more: -1): the error after the first assignment, then
+ *                after every round (NaN where not evaluated)
+ * float32 inputs are clustered in float32; the error is summed in float64.  Status -1 / -3 / -2 are returned before any
+ * device work.  Host synchronisation: as evc_convex_learn. */
+enum { EVC_KM_BOTH = 0, EVC_KM_ASSIGN_ONLY = 1 };
+enum { EVC_KM_STOP_NONE = 0, EVC_KM_STOP_PYMF = 1, EVC_KM_STOP_LABELS = 2 };
+typedef struct evc_kmeans_opts {
+    int struct_bytes;  /* sizeof(evc_kmeans_opts) */
+    int dtype;         /* EVC_F64 | EVC_F32 */
+    int layout;        /* EVC_FRAME_MAJOR | EVC_BIN_MAJOR */
+    int iters;         /* >= 0 rounds after the first assignment */
+    int update;        /* EVC_KM_BOTH | EVC_KM_ASSIGN_ONLY */
+    int stop_rule;     /* EVC_KM_STOP_* */
+    int reserved;      /* 0; bits 8..15, tuning and tests: that many centre ranges (1 .. 16) instead of evc_kmeans_splits();
+                          bit 0, likewise: every sample goes through the direct-form re-decision; anything else: status -1 */
+    double tol;        /* >= 0 (EVC_KM_STOP_PYMF) */
+    void* ev_loop_start;  /* optional hipEvent_t pair recorded around the launches of the round loop, as in */
+    void* ev_loop_stop;   /* evc_solve_opts; NULL = not recorded */
+} evc_kmeans_opts;
+/* bytes of workspace evc_kmeans needs (0: invalid or unsupported sizes, wherever the call would return -1 or -3) */
+size_t evc_kmeans_workspace_bytes(int M, int R, int T, int dtype);
+/* centre ranges the assignment is split into, 1 .. 16: a function of the sizes only (0: invalid or unsupported sizes) */
+int evc_kmeans_splits(int R, int T);
+int evc_kmeans(const void* X, int ldx, void* W, int ldw, int* labels, int* counts, int M, int R, int T,
+               const evc_kmeans_opts* opts, void* workspace, size_t workspace_bytes, int* n_iter_out, double* err_out,
+               evc_stream_t stream);
 
 #ifdef __cplusplus
 }
