@@ -39,7 +39,12 @@
 // Which exchange (pick_c; template C > 0: that many members, C <= 0: member count at run time):
 //   direct (C = 2, 4, 8; 8 only where the dictionary is in LDS): every member fetches every peer's partial,
 //     16-byte words, one memory round trip.  Each wavefront first watches one word per peer, so that the bulk fetch
-//     normally succeeds at once.
+//     normally succeeds at once.  k_fused_all and k_fused_lone skip the load of the member's own slot and take that pair
+//     from registers; k_fused_quad loads all C slots, its own included (a word it stored earlier in the same exchange:
+//     stale, it carries the other epoch and is fetched again like a peer's) - eight loads for seven, and in exchange no
+//     slot is zeroed or copied first, nothing branches on the member index, and the tag test is one chain per value of
+//     the wave-uniform epoch: 75 vector instructions per exchange at 8 members instead of 138, beside the other half's
+//     sweep on the same SIMDs (DESIGN.md 5.1a cont., profiles/lean_exchange_README.md).
 //   reduce-scatter, whole slices (C == 0: 8 members at M 26 .. 28, and 16, 32, 64): fetching every peer's partial
 //     would cost (C - 1) x 3.5 KB per member and exchange, so member m sums slice m of all partials and publishes it,
 //     and everybody fetches the summed slices: two memory round trips, 7 KB fetched per member whatever C is.  Whole
@@ -67,6 +72,7 @@ constexpr int ALL_STAGGER_PER_ITER = 11000;    // shader cycles of one iteration
 // 10.4 k (profiles/r04_fused_all_stamps_prio_and_11_tiles.txt).  The exchanging wavefront goes first: its instructions
 // are few, the sweep beside it does not notice.  Both exchanges then take 10.9 k and a C2 step 11.8 k cycles, not 12.6 k.
 constexpr int ALL_EXCH_PRIO = 3;
+typedef unsigned all_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned all_u32x4 __attribute__((ext_vector_type(4)));
 typedef long long all_i64x2 __attribute__((ext_vector_type(2)));
 

@@ -213,6 +213,15 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
         rs_src1 = src(th + AW * 64);
         rs_src2 = src(th + 2 * AW * 64);
     }
+    // QUAD, the same in every exchange of the launch and kept as lane masks: the lanes that watch a peer's word (lane m <->
+    // member m), and the lanes whose pair of elements lies in a real bin (both elements lie in one lane group of one k-step;
+    // bins >= M hold exact zeros)
+    unsigned long long xq_peers = 0, xq_real = 0;
+    if constexpr (QUAD) {
+        xq_peers = __builtin_amdgcn_ballot_w64(lane < C && lane != member);
+        xq_real = __builtin_amdgcn_ballot_w64(th < NE / 2 && bin_of((2 * th) >> 6, ((2 * th) & 63) >> 4) < a.M);
+        asm volatile("" : "+s"(xq_peers), "+s"(xq_real));
+    }
     if (tid == 0) s_fail = 0;
     if (tid < 2) s_hb[tid] = 0;
 
@@ -415,6 +424,95 @@ __global__ __launch_bounds__(ATHREADS, 2) void k_fused_all(FusedArgs a) {
 #pragma unroll
                     for (int b = 0; b < NQ; ++b) red[w * RSTR + (4 * MTL + b) * 64 + lane] = vq[b];
                 }
+            } else if (QUAD && valid && !mine && step > 0) {
+                // ---------------- k_fused_quad's exchange: the protocol of the next branch - buffers, offsets, 16-byte words,
+                // one epoch bit per 8-byte half, watch phase, bounded polls, s_fail, the sums' orders - with the vector
+                // instructions that the result does not need taken out (an f64 MFMA and a vector instruction of one SIMD do
+                // not overlap: every one of them is time of the sweep beside it; profiles/lean_exchange_README.md):
+                //  * every fetch round loads ALL C slots, the thread's own included.  The thread stored that word earlier in
+                //    this exchange; a stale one carries the other epoch and is fetched again like a peer's, so nothing new
+                //    rests on ordering.  No slot is zeroed or filled from registers first and nothing branches on `member`;
+                //  * the epoch is wave-uniform, so the tag test is one chain per epoch value, two low words per three-input
+                //    instruction: the OR of the words (epoch 0) or of their complements (epoch 1), then one test of bit 0.
+                //    Each 8-byte half is still checked by itself;
+                //  * the words are tagged and tested as 32-bit halves, the watched word comes through the exchange's buffer
+                //    resource (its lane offset is the same in every exchange), and "every lane" is a test of the mask.
+                constexpr int CQ = C > 0 ? C : 1;
+                __builtin_amdgcn_s_setprio(ALL_EXCH_PRIO);
+                const bool act = th < NE / 2;
+                const int ep = act ? 2 * th : 0;
+                unsigned vok = 1u;                  // (a wavefront that moves nothing vouches for nothing)
+                if (w * 64 < NE / 2) {
+                    f64x2 pv[AW], sm = {0.0, 0.0};
+#pragma unroll
+                    for (int ww = 0; ww < AW; ++ww) pv[ww] = *reinterpret_cast<const f64x2*>(red + ww * RSTR + ep);
+                    static_assert(AW == 4, "the four partials are named one by one");
+                    asm volatile("" : "+v"(pv[0]), "+v"(pv[1]), "+v"(pv[2]), "+v"(pv[3]));
+#pragma unroll
+                    for (int ww = 0; ww < AW; ++ww) sm += pv[ww];
+                    unsigned tag = (seq >> 1) & 1;               // a buffer is reused every second exchange
+                    all_u32x4 pw = __builtin_bit_cast(all_u32x4, sm);
+                    pw[0] = (pw[0] & ~1u) | tag;
+                    pw[2] = (pw[2] & ~1u) | tag;
+                    const int xo = __builtin_amdgcn_readfirstlane((int)(((seq & 1) * (unsigned)a.groups + (unsigned)g) * (unsigned)(C * 4096)));
+                    if (act) __builtin_amdgcn_raw_buffer_store_b128(pw, rx, ep * 8, xo + member * 4096, 16);
+                    bool ok = true;
+                    unsigned polls = 0;
+                    // watch one word per peer (lane m <-> member m), as below
+                    const int wo = (lane < C ? lane : 0) * 4096 + (NE - 1) * 8;
+                    for (;;) {
+                        asm volatile("" ::: "memory");      // (the builtin load is not volatile: it stays in the loop)
+                        all_u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(rx, wo, xo, 16);
+                        asm volatile("" : "+v"(b));         // (the 8-byte word as the peer stored it, not its low half alone)
+                        if ((__builtin_amdgcn_ballot_w64(((b[0] ^ tag) & 1) != 0) & xq_peers) == 0) break;
+                        if (all_polls_out(polls, a.coop_abort)) {
+                            ok = false;
+                            break;
+                        }
+                        __builtin_amdgcn_s_sleep(2);
+                    }
+                    // (no fetch round - a launch being voided, a thread without a pair: any value will do, at no instruction)
+                    all_i64x2 b[CQ];
+#pragma unroll
+                    for (int m = 0; m < CQ; ++m) asm volatile("" : "=v"(b[m]));
+                    unsigned rounds = 0;
+                    while (__builtin_expect(ok && act, 1)) {        // (runs at least once: laid out in line)
+                        asm volatile("" ::: "memory");      // (the builtin load is not volatile: it stays in the loop)
+#pragma unroll
+                        for (int m = 0; m < CQ; ++m)
+                            b[m] = __builtin_bit_cast(all_i64x2, __builtin_amdgcn_raw_buffer_load_b128(rx, ep * 8, xo + m * 4096, 16));
+                        unsigned stale = 0;
+                        if (tag) {
+#pragma unroll
+                            for (int m = 0; m < CQ; ++m) stale |= ~(unsigned)b[m][0] | ~(unsigned)b[m][1];
+                        } else {
+#pragma unroll
+                            for (int m = 0; m < CQ; ++m) stale |= (unsigned)b[m][0] | (unsigned)b[m][1];
+                        }
+                        if ((stale & 1) == 0) break;
+                        // (the threads still fetching have all counted the same rounds)
+                        unsigned r = __builtin_amdgcn_readfirstlane(rounds);
+                        const bool out = all_polls_out(r, a.coop_abort);
+                        rounds = r;
+                        if (out) {
+                            ok = false;
+                            break;
+                        }
+                        __builtin_amdgcn_s_sleep(2);
+                    }
+                    f64x2 v2 = {0.0, 0.0};
+#pragma unroll
+                    for (int m = 0; m < CQ; ++m) {                // member order: identical on every member
+                        v2[0] += __longlong_as_double(b[m][0] & ~1LL);
+                        v2[1] += __longlong_as_double(b[m][1] & ~1LL);
+                    }
+                    if (!ok) s_fail = 1;
+                    vok = (__builtin_amdgcn_ballot_w64(!(range_v_ok(v2[0]) && range_v_ok(v2[1]))) & xq_real) == 0 ? 1u : 0u;
+                    if (act) *reinterpret_cast<f64x2*>(vL + ep) = v2;
+                }
+                if (lane == 0) s_vok[half][w] = vok;
+                ++seq;
+                __builtin_amdgcn_s_setprio(0);
             } else if (C > 1 && valid && !mine && step > 0) {
                 // ---------------- exchange, 2 / 4 / 8 members, on 16-byte words (round 7).  Thread th < NE / 2 owns the
                 // elements 2 th and 2 th + 1: one ds_read_b128 per wavefront's partial, ONE 16-byte sc1 store, and per fetch
